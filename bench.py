@@ -1,21 +1,27 @@
 #!/usr/bin/env python3
 """Headline benchmark: DominantSparseSymeig forward + backward on a TFIM-shaped sparse operator.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong] [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W untimed and K timed steps, writes the outputs of the last timed step if --dump-outputs is
+given, and prints the line.  Everything measured or checked beside the timed steps -- live PMC passes, per-kernel events
+and the roofline, the option extras, the config-3 / config-4 / sweep / operand figures, the one-GPU anchors, the CPU
+baseline, the N > 1 extra points and scaling decomposition, and the N = 1 supervisor that re-measures in a fresh
+process -- runs only with --full.
 
 One "step" = one pass of the hot path over synthetic inputs already resident in HBM, through the reference API:
     forward   symeig.DominantSparseSymeig.apply(g, k, dim, device)      (Lanczos, k vectors, full reorth)
     backward  torch.autograd.grad(E0 + psi.t, g)                         (projected CG adjoint solve + hook)
 
 Workloads (what the K timed steps run, i.e. what `value` / `ms_per_step` are quoted on)
-    N = 1 (default)   BASELINE.json configs[1]: TFIM L=20 (n = 2^20), k = 200, fp64, g = 1.0.  The same run then times,
-                      OUTSIDE the K steps, the two one-GPU anchors of the multi-GPU curves (config.one_gpu_anchors):
-                      L = 28, k = 100 (strong) and 2^25 rows, k = 200 (weak).
+    N = 1 (default)   BASELINE.json configs[1]: TFIM L=20 (n = 2^20), k = 200, fp64, g = 1.0.  With --full the same run
+                      then times, OUTSIDE the K steps, the two one-GPU anchors of the multi-GPU curves
+                      (config.one_gpu_anchors): L = 28, k = 100 (strong) and 2^25 rows, k = 200 (weak).
     N > 1 (default)   STRONG scaling, north_star's curve: TFIM L=28 (n = 2^28) row-partitioned over the N GPUs with
                       k = 100 at every N (the largest k whose basis, 215 GB, fits the one 288 GB GPU of the anchor).
-                      After the timed steps the WEAK point (2^25 rows per GPU, k = 200; N = 8 is BASELINE configs[4]:
-                      L = 28 with 53.7 GB of basis + 13.4 GB bf16 shadow per GPU) is timed too and reported as
-                      config.weak_scaling_point.
+                      With --full, after the timed steps the WEAK point (2^25 rows per GPU, k = 200; N = 8 is
+                      BASELINE configs[4]: L = 28 with 53.7 GB of basis + 13.4 GB bf16 shadow per GPU) is timed too and
+                      reported as config.weak_scaling_point.
     --scaling weak|strong   time only that one point.
     --gpus N without a launcher starts its own N worker processes (python -m torch.distributed.run) BEFORE any GPU
     call and relays rank 0's JSON line; under torchrun (WORLD_SIZE set) it is a worker.
@@ -1008,6 +1014,36 @@ class Problem:
             torch.cuda.empty_cache()
 
 
+DUMP_PSI_MAX = 1 << 22           # psi entries written in full up to this length (32 MB of float64), else a sample of as many
+DUMP_SAMPLE_SEED = SEED + 99
+
+
+def dump_outputs(path, prob, E0, gl):
+    """--dump-outputs DIR: what the last timed step returned to its caller, as float64 .npy files -- E0.npy, dloss_dg.npy and
+    psi.npy (the eigenvector in global row order; above DUMP_PSI_MAX rows the entries at a fixed, seeded set of DUMP_PSI_MAX
+    indices, ascending).  Row-partitioned runs gather the slabs' entries to rank 0 (every rank calls this: collective)."""
+    psi = prob.last["psi"]
+    n, nloc = prob.n, prob.nloc
+    lo = prob.rank * nloc if prob.partitioned else 0
+    if n <= DUMP_PSI_MAX:
+        part = psi.double().cpu().numpy()
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, DUMP_PSI_MAX, replace=False))
+        mine = idx[(idx >= lo) & (idx < lo + nloc)] - lo
+        part = psi[torch.from_numpy(mine).to(psi.device)].double().cpu().numpy()
+    parts = [part]
+    if prob.partitioned and prob.world > 1:
+        import torch.distributed as dist
+        parts = [None] * prob.world
+        dist.all_gather_object(parts, part)
+    if prob.rank != 0:
+        return
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "E0.npy"), np.asarray([float(E0.item())], dtype=np.float64))
+    np.save(os.path.join(path, "dloss_dg.npy"), gl.detach().double().reshape(-1).cpu().numpy())
+    np.save(os.path.join(path, "psi.npy"), np.concatenate(parts).astype(np.float64))
+
+
 def rank_evidence(ctx):
     """what proves the collectives span N distinct GPUs: every rank's device, gathered to rank 0"""
     import torch.distributed as dist
@@ -1097,11 +1133,23 @@ def parse_args():
                          "line -- with the N ranks SHARING GPU 0 and the collectives over gloo staged through the host "
                          "(RCCL refuses two ranks on one device), at toy sizes.  It is how a one-GPU box executes the "
                          "P = 2 / 4 / 8 geometry end to end; the line is labelled as a rehearsal.")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy "
+                         "(float64): E0, dloss_dg and psi -- all of psi up to 2^22 entries, else a fixed, seeded sample of "
+                         "2^22 of its entries in ascending index order")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the timed steps (live PMC passes, kernel events and "
+                         "roofline, option extras, config-3 / config-4 / sweep / operand figures, one-GPU anchors, CPU "
+                         "baseline, N > 1 extra points and scaling decomposition, N = 1 supervisor); --anchors-only "
+                         "implies it")
     args = ap.parse_args()
     if args.anchors_only:
+        args.full = True
         args.steps = args.steps or 1
         args.warmup = 1 if args.warmup is None else args.warmup
         args.no_cpu_baseline = args.no_extras = args.no_live_pmc = args.no_kernel_events = True
+    if not args.full:
+        args.no_cpu_baseline = args.no_extras = args.no_live_pmc = args.no_kernel_events = args.no_anchors = True
     return args
 
 
@@ -1344,7 +1392,8 @@ def extra_point(ctx, L, k, shadow, steps, warmup, scaling):
 def multi_gpu_extras(args, ctx, pt, prob, anchors):
     """default schedule of N > 1, after the timed strong point (shadow: auto = on from two GPUs): the SAME point with the
     all-fp64 correction pass, the shadow-matched k, and the weak point.  Returns (strong_fp64, strong_matched, weak)."""
-    if not pt.default_schedule or os.environ.get("DSEA_BENCH_REDUCED", "") == "1":      # (fallback stages: timed point only)
+    # (without --full, and in the fallback stages: timed point only)
+    if not args.full or not pt.default_schedule or os.environ.get("DSEA_BENCH_REDUCED", "") == "1":
         return None, None, None
     prob.release()
     Ls = pt.L
@@ -1551,11 +1600,11 @@ def _supervise_one_gpu(args):
     of round 6 as an abort with "HW Exception ... GPU Hang" and an EMPTY stdout -- cause not found, not reproduced in 14 further
     runs, docs/design/12-round6.md 12.8) or stalls, a fresh child measures again without the parts that are not the number
     (live PMC passes, extras).  The line then says so (config.supervisor).  This process never touches the GPU.  Not used under a
-    profiler (its preloaded library has initialised the GPU here: no child processes then), for N > 1 (tools/bench_watchdog.py
-    supervises those), for the CPU dry run / host-staged rehearsal, or with DSEA_BENCH_NO_WATCHDOG=1."""
+    profiler (its preloaded library has initialised the GPU here: no child processes then), without --full, for N > 1
+    (tools/bench_watchdog.py supervises those), for the CPU dry run / host-staged rehearsal, or with DSEA_BENCH_NO_WATCHDOG=1."""
     import signal
     import subprocess
-    if args.gpus != 1 or os.environ.get("WORLD_SIZE") is not None or args.dry_run_cpu or args.host_staged:
+    if not args.full or args.gpus != 1 or os.environ.get("WORLD_SIZE") is not None or args.dry_run_cpu or args.host_staged:
         return
     if os.environ.get("DSEA_BENCH_SUPERVISED", "") == "1" or os.environ.get("DSEA_BENCH_NO_WATCHDOG", "") == "1" or \
             os.environ.get("DSEA_BENCH_CHILD", "") == "1":
@@ -1619,6 +1668,8 @@ def main():
     if args.rpl and not dry:
         engine.Workspace.get(pt.nloc, k, ctx.dev).set_rows_per_lane(args.rpl)
     dt, E0, gl = prob.measure(pt.steps, pt.warmup)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, prob, E0, gl)
     if os.environ.get("DSEA_BENCH_INJECT_ABORT", "") == "1" and os.environ.get("DSEA_BENCH_SUPERVISED", "") == "1" and \
             not args.no_extras:
         os.abort()       # TEST HOOK (tests/test_gpu_bench_contract.py): what a GPU hang does to the measuring process -- SIGABRT, no line
@@ -1651,9 +1702,9 @@ def main():
                            commit=_commit(), collectives=ctx.evidence, provisional=True)})
 
     # ---- beside the timed point: N > 1 default schedule / N = 1 anchors
-    anchors_in, anchors_src = load_anchors(args) if world > 1 else ({}, None)
+    anchors_in, anchors_src = load_anchors(args) if (world > 1 and args.full) else ({}, None)
     decomposition = None
-    if world > 1:
+    if world > 1 and args.full:
         # what bounds this line: collectives on the run's own communicators, exposed exchange per step / iteration,
         # SURVEY 8e's model beside the measurement (tools/bench_multi.py; outside the timed region, collective)
         sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -1707,7 +1758,9 @@ def main():
             if ctx.staged:
                 cfg["collectives"]["note"] = "rehearsal: all ranks share GPU 0 (distinct_devices = 1 is expected)"
         if world > 1:
-            cfg["one_gpu_anchor"] = _speedups(pt, ms_per_step, prob_shadow, strong_fp64, strong_matched, anchors_in, anchors_src)
+            if args.full:
+                cfg["one_gpu_anchor"] = _speedups(pt, ms_per_step, prob_shadow, strong_fp64, strong_matched, anchors_in,
+                                                  anchors_src)
             if strong_fp64 is not None:
                 cfg["strong_point_fp64_basis"] = strong_fp64
             if strong_matched is not None:
@@ -1721,7 +1774,8 @@ def main():
                 a_fp64 = anchor_ms(anchors_in, "strong_L28_k%d" % STRONG_K, False) if (not pt.explicit and not pt.toy) else None
                 decomposition["model"]["strong_point_fp64_basis"] = bench_multi.model_entry(
                     a_fp64, strong_fp64["ms_per_step"], world, decomposition["communication_ms_per_step"])
-            cfg["scaling_decomposition"] = decomposition
+            if args.full:
+                cfg["scaling_decomposition"] = decomposition
         if world == 1 and not ctx.partitioned_path:
             cfg["multi_gpu_schedule"] = (
                 "bench.py --gpus N (N > 1) times the STRONG point TFIM L=28, k=%d over N GPUs as value/ms_per_step (shadow "
@@ -1742,7 +1796,7 @@ def main():
                 pmc = json.load(open(tpath))
             except Exception:  # noqa: BLE001
                 pmc = None
-        if not ctx.partitioned_path and L == 20 and k == 200 and args.operator == "matrix-free":
+        if args.full and not ctx.partitioned_path and L == 20 and k == 200 and args.operator == "matrix-free":
             # the traffic model against the counters: bytes that crossed the HBM interface in a profiled run of this step
             if pmc and pmc.get("_total_hbm_bytes_per_step"):
                 real = float(pmc["_total_hbm_bytes_per_step"])

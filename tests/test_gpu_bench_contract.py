@@ -28,7 +28,7 @@ def _run(extra):
 
 
 def test_bench_line_single_gpu():
-    d = _run([])
+    d = _run(["--full"])
     assert REQUIRED <= set(d) and d["n_gpus"] == 1 and d["dtype"] == "f64" and d["vs_baseline"] is None
     assert d["value"] > 0 and d["ms_per_step"] > 0 and "workload" in d["config"]
     assert abs(d["config"]["E0_per_site"] - d["config"]["E0_per_site_closed_form"]) < 1e-9
@@ -50,7 +50,7 @@ def test_bench_one_gpu_supervisor_relays_the_line_and_survives_a_dead_measuring_
     round 6 did: SIGABRT, empty stdout) is replaced by a fresh one that measures without the live PMC passes and the extras, and
     the line says so."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--L-local", "14", "--k", "48", "--steps", "2", "--warmup", "1",
-           "--no-cpu-baseline", "--no-anchors"]
+           "--full", "--no-cpu-baseline", "--no-anchors"]
     env = {k: v for k, v in os.environ.items() if k != "DSEA_BENCH_NO_WATCHDOG"}
     ok = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert ok.returncode == 0, ok.stderr[-2000:]
@@ -67,17 +67,37 @@ def test_bench_one_gpu_supervisor_relays_the_line_and_survives_a_dead_measuring_
     assert "attempt 1" in bad.stderr
 
 
+def test_plain_line_and_dumped_outputs(tmp_path):
+    """without --full the line carries the timed point only (nothing measured beside it); --dump-outputs writes what the last
+    timed step returned -- E0, dloss/dg, the eigenvector -- as float64, and a second run with the same arguments writes the same"""
+    import numpy as np
+    dumps = []
+    for run in (1, 2):
+        out = tmp_path / ("run%d" % run)
+        d = _run(["--dump-outputs", str(out)])
+        assert REQUIRED <= set(d) and d["steps"] == 2 and d["warmup"] == 1 and d["ms_per_step"] > 0
+        assert "roofline" not in d and "cpu_baseline" not in d
+        assert not {"config3", "config4", "measured_ceilings", "ms_per_step_fp64_basis", "one_gpu_anchors"} & set(d["config"])
+        got = {name: np.load(str(out / (name + ".npy"))) for name in ("E0", "dloss_dg", "psi")}
+        assert all(v.dtype == np.float64 for v in got.values()) and got["psi"].shape == (1 << 14,)
+        assert abs(got["E0"][0] / 14 - d["config"]["E0_per_site"]) < 1e-12 and got["dloss_dg"][0] == d["config"]["dloss_dg"]
+        assert abs(np.linalg.norm(got["psi"]) - 1.0) < 1e-10
+        dumps.append(got)
+    for name in ("E0", "dloss_dg", "psi"):
+        np.testing.assert_allclose(dumps[1][name], dumps[0][name], rtol=0, atol=1e-12)
+
+
 def test_bench_line_cpu_baseline_forms():
-    d = _run(["--cpu-threads", "4", "--no-extras"])
+    d = _run(["--full", "--cpu-threads", "4", "--no-extras"])
     assert "FULL workload" in d["cpu_baseline"]["sample"] and "config3" not in d["config"]
     assert d["cpu_baseline"]["runs"][0]["threads"] == 4
-    d = _run(["--cpu-sample", "--no-extras"])
+    d = _run(["--full", "--cpu-sample", "--no-extras"])
     assert "capped" in d["cpu_baseline"]["sample"]
 
 
 def test_bench_line_carries_honest_extras():
     """the all-fp64-basis step time next to the headline, and the config-3 figures driver-timed"""
-    d = _run(["--no-cpu-baseline"])
+    d = _run(["--full", "--no-cpu-baseline"])
     assert d["config"]["ms_per_step_fp64_basis"] > 0 and d["config"]["bf16_shadow_of_basis"] is True
     c3 = d["config"]["config3"]
     assert c3["cg_iterations"] == 1000 and c3["cg_us_per_iteration"] > 0 and c3["lanczos_k300_ms"] > 0
@@ -112,7 +132,7 @@ def test_headline_line_measures_its_pmc_traffic_live():
     """The default N = 1 workload (BASELINE configs[1]) measures roofline.traffic in the run itself: two rocprofv3 --pmc
     child passes (FETCH_SIZE, WRITE_SIZE, separate, --kernel-trace only) started before the process touches the GPU.
     The dominant kernel's HBM traffic equals its algorithmic bytes to a few per cent (no wasted re-reads)."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline",
            "--no-extras", "--no-anchors"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -146,7 +166,7 @@ def test_bench_multi_gpu_branch_rehearsal_on_hip_kernels(world):
     # N = 8 (eight processes time-slicing one GPU: 82 s with the full schedule) runs the timed strong point only -- the extras
     # beside it (fp64 / shadow-matched / weak points, scaling decomposition) are the same code at N = 2 and N = 4
     reduced = world >= 8
-    d = _bench(["--gpus", str(world), "--host-staged", "--steps", "2", "--warmup", "1"],
+    d = _bench(["--gpus", str(world), "--host-staged", "--steps", "2", "--warmup", "1", "--full"],
                env={"DSEA_BENCH_REDUCED": "1"} if reduced else None)
     assert d["metric"].startswith("REHEARSAL") and d["n_gpus"] == world and d["scaling"] == "strong"
     assert "roofline" not in d or d["roofline"]["frac"] <= 1.0
@@ -219,7 +239,7 @@ def test_bench_watchdog_on_the_rccl_branch_rehearsal(inject, stage, driver):
     env = {"DSEA_RCCL_LIB": FAKE_RCCL, "DSEA_BENCH_STALL_S": "8", "DSEA_BENCH_STARTUP_S": "300"}
     if inject:
         env["DSEA_BENCH_INJECT_HANG"] = inject
-    d = _bench(["--gpus", "2", "--host-staged", "--steps", "2", "--warmup", "1"], env=env)
+    d = _bench(["--gpus", "2", "--host-staged", "--steps", "2", "--warmup", "1", "--full"], env=env)
     cfg = d["config"]
     assert cfg["fallback_stage"] == stage, cfg["watchdog"]
     assert cfg["partitioned_driver"].startswith(driver), cfg["partitioned_driver"]

@@ -327,7 +327,7 @@ def test_bench_multi_rank_control_flow_dry_run(world, launcher, explicit):
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    tail = [os.path.join(root, "bench.py"), "--gpus", str(world), "--steps", "2", "--warmup", "1", "--dry-run-cpu"]
+    tail = [os.path.join(root, "bench.py"), "--gpus", str(world), "--steps", "2", "--warmup", "1", "--dry-run-cpu", "--full"]
     if explicit:
         tail += ["--L", "10", "--k", "60"]
     if launcher == "self":
@@ -455,7 +455,8 @@ def test_bench_watchdog_walks_the_fallback_ladder(inject, stage):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(DSEA_BENCH_INJECT_HANG=inject, DSEA_BENCH_STALL_S="6", DSEA_BENCH_STARTUP_S="120")
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--dry-run-cpu"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--dry-run-cpu",
+           "--full"]
     if inject != "extras":
         cmd += ["--L", "10", "--k", "60"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=root)

@@ -7,7 +7,7 @@
 # profiles/ by hand, named r<round>_*).  Recipes with arguments take them as recipe:arg1:arg2 (":" separated).
 #
 #   tests[:k-expr]      pytest -m gpu (optionally -k <expr>)             smoke          __graft_entry__.smoke()
-#   bench               default bench.py line                            benchq         bench without baseline / anchors / pmc
+#   bench               bench.py --full line                             benchq         bench without baseline / anchors / pmc
 #   stats               rocprofv3 --kernel-trace --stats of 3 headline steps -> kernel_stats.csv
 #   pmc                 FETCH_SIZE / WRITE_SIZE passes (separate) -> pmc_traffic.json via tools/pmc_traffic.py
 #   callable            kernel traces of tools/bench_generic.py (native / lambda / gather-table operand) through tools/trace_gaps.py
@@ -29,7 +29,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 1
 export TMPDIR=/tmp
 TAG=${TAG:-ev}
 O=gpurun_out/$TAG; mkdir -p "$O"
-Q="--no-cpu-baseline --no-extras --no-anchors --no-live-pmc"
+Q="--full --no-cpu-baseline --no-extras --no-anchors --no-live-pmc"
 
 line() { tail -1 "$1" | cut -c1-${2:-400}; }
 stats_of() {  # stats_of <outname> <bench args...>: rocprofv3 kernel stats of a bench invocation -> $O/<outname>.csv
@@ -59,7 +59,7 @@ for spec in "$@"; do
       else timeout 3000 python -m pytest tests -m gpu -q --durations=8 > "$O/pytest.log" 2>&1; fi
       echo "pytest rc=$?"; tail -15 "$O/pytest.log" | cut -c1-250 ;;
     smoke) python -c "import __graft_entry__ as g; g.smoke()" > "$O/smoke.log" 2>&1; echo "smoke rc=$?"; tail -2 "$O/smoke.log" ;;
-    bench) python bench.py > "$O/bench.json" 2> "$O/bench.err"; echo "bench rc=$?"; line "$O/bench.json" 600 ;;
+    bench) python bench.py --full > "$O/bench.json" 2> "$O/bench.err"; echo "bench rc=$?"; line "$O/bench.json" 600 ;;
     benchq) python bench.py $Q > "$O/benchq.json" 2> "$O/benchq.err"; echo "rc=$?"; line "$O/benchq.json" ;;
     stats) stats_of kernel_stats --steps 3 --warmup 1 $Q ;;
     pmc)
@@ -89,7 +89,7 @@ for spec in "$@"; do
       stats_of kernel_stats_$a1 --operator $a1 --steps 3 --warmup 1 $Q ;;
     libdriver)
       LL=${a1:-20}
-      python bench.py --force-partitioned --L-local $LL --no-cpu-baseline --no-extras > "$O/libdriver_2p$LL.json" 2> "$O/libdriver_2p$LL.err"; echo "rc=$?"; line "$O/libdriver_2p$LL.json" 500
+      python bench.py --force-partitioned --L-local $LL --full --no-cpu-baseline --no-extras > "$O/libdriver_2p$LL.json" 2> "$O/libdriver_2p$LL.err"; echo "rc=$?"; line "$O/libdriver_2p$LL.json" 500
       stats_of libdriver_2p${LL}_kernel_stats --force-partitioned --L-local $LL --steps 1 --warmup 1 --no-cpu-baseline --no-extras --no-kernel-events ;;
     ldprof)
       LL=${a1:-20}; NS=3; [ "$LL" -ge 24 ] && NS=1
@@ -117,14 +117,14 @@ PY
       python bench.py --anchors-only > "$O/anchors.json" 2> "$O/anchors.err"; echo "anchors rc=$?"; line "$O/anchors.json" 1200 ;;
     rehearsal)
       for n in 2 4 8; do
-        timeout 900 python bench.py --gpus $n --host-staged --steps 2 --warmup 1 > "$O/rehearsal_n$n.json" 2> "$O/rehearsal_n$n.err"; echo "rehearsal N=$n rc=$?"; line "$O/rehearsal_n$n.json" 700
+        timeout 900 python bench.py --gpus $n --host-staged --steps 2 --warmup 1 --full > "$O/rehearsal_n$n.json" 2> "$O/rehearsal_n$n.err"; echo "rehearsal N=$n rc=$?"; line "$O/rehearsal_n$n.json" 700
       done ;;
     rehearsal_rccl)   # the same rehearsal with the LIBRARY'S OWN RCCL calls executing over the stand-in of tests/fake_rccl
       for n in 2 4 8; do
-        DSEA_RCCL_LIB=$PWD/tests/fake_rccl/libfake_rccl.so timeout 900 python bench.py --gpus $n --host-staged --steps 2 --warmup 1 > "$O/rehearsal_rccl_n$n.json" 2> "$O/rehearsal_rccl_n$n.err"; echo "rehearsal (stand-in RCCL) N=$n rc=$?"; line "$O/rehearsal_rccl_n$n.json" 300
+        DSEA_RCCL_LIB=$PWD/tests/fake_rccl/libfake_rccl.so timeout 900 python bench.py --gpus $n --host-staged --steps 2 --warmup 1 --full > "$O/rehearsal_rccl_n$n.json" 2> "$O/rehearsal_rccl_n$n.err"; echo "rehearsal (stand-in RCCL) N=$n rc=$?"; line "$O/rehearsal_rccl_n$n.json" 300
       done ;;
     watchdog)         # watchdog:exchange / watchdog:allreduce -- a hang injected INSIDE the stand-in RCCL, N = 2
-      DSEA_BENCH_INJECT_HANG=$a1 DSEA_BENCH_STALL_S=${a2:-20} DSEA_RCCL_LIB=$PWD/tests/fake_rccl/libfake_rccl.so timeout 900 python bench.py --gpus 2 --host-staged --steps 2 --warmup 1 > "$O/watchdog_$a1.json" 2> "$O/watchdog_$a1.err"; echo "watchdog $a1 rc=$?"
+      DSEA_BENCH_INJECT_HANG=$a1 DSEA_BENCH_STALL_S=${a2:-20} DSEA_RCCL_LIB=$PWD/tests/fake_rccl/libfake_rccl.so timeout 900 python bench.py --gpus 2 --host-staged --steps 2 --warmup 1 --full > "$O/watchdog_$a1.json" 2> "$O/watchdog_$a1.err"; echo "watchdog $a1 rc=$?"
       tail -1 "$O/watchdog_$a1.json" | python3 -c 'import json,sys; d=json.loads(sys.stdin.read()); c=d["config"]; print("stage", c["fallback_stage"], "|", c["fallback_stage_is"], "|", c["fallback_reason"], "|", c.get("partitioned_driver"))' ;;
     fuzzpart)
       for s in ${a1//,/ }; do python tools/fuzz_partitioned.py --cases ${a2:-30} --seed $s 2>&1 | grep -v "amdgpu\|Gloo" > "$O/fuzz_partitioned_seed$s.txt"; tail -1 "$O/fuzz_partitioned_seed$s.txt"; done ;;
