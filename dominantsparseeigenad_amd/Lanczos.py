@@ -17,6 +17,7 @@ global RNG advances exactly as in the reference).
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 
 from . import engine
@@ -177,3 +178,84 @@ def symeigLanczos(A, k, device=torch.device("cpu"), extreme="both", *, sparse=Fa
             vec = torch.matmul(Q[:, :s.shape[0]], torch.from_numpy(s).to(Q.dtype))
         out += [torch.tensor(val, dtype=dtype, device=alphas.device), vec.to(dtype)]
     return tuple(out)
+
+
+class LowestInfo:
+    """Diagnostics of the last ``lowestLanczos`` call: ``ritz_residuals`` = ||A psi_j - lambda_j psi_j|| (nev floats, one
+    mat-vec per pair), ``next_eigval`` = the Ritz value lambda_nev (the first level not requested; the adjoint solves are
+    well posed while lambda_{nev-1} < lambda_nev), ``bottoms`` = |s_{m-1,j}| of the tridiagonal's eigenvectors."""
+    ritz_residuals = None
+    next_eigval = float("nan")
+    bottoms = None
+
+
+last_lowest = LowestInfo()
+
+# relative gap below which two of the nev + 1 lowest Ritz values count as one degenerate level
+DEGENERACY_TOL = 1e-8
+
+
+def _refuse_partitioned(A, sparse):
+    part = engine.native_of(A) if sparse else None
+    if part is not None and getattr(part, "partitioned", False):
+        raise NotImplementedError("the lowest-nev eigenpairs are not implemented for row-partitioned operators "
+                                  "(PartitionedTFIMOperator / PartitionedCSROperator)")
+
+
+def lowestLanczos(A, k, nev, device=torch.device("cpu"), *, sparse=False, dim=None, q0=None, reorth=None):
+    """The nev lowest eigenpairs from one k-step Lanczos run (an extension the reference lacks;
+    docs/design/13-lowest-eigenpairs.md).  Returns (eigvals (nev,), eigvectors (n, nev)); on the GPU ``eigvectors`` is the
+    transposed view of a (nev, ldpsi) buffer.
+
+    Same ``_lanczos_core`` (same draws, same ``WARM_START`` handling) as ``symeigLanczos``: with nev = 1, lambda_0 and psi_0
+    are bit-identical to ``symeigLanczos(..., extreme="min")`` under the same seed.  ``reorth``: "full" (default),
+    "partial" or "twice" as in ``symeigLanczos``; "none" keeps no basis to combine and raises NotImplementedError.
+    A RuntimeWarning is issued when two of the nev + 1 lowest Ritz values are degenerate (relative gap < DEGENERACY_TOL):
+    the eigenvector adjoints are ill-defined there, and one-vector Lanczos cannot resolve an exactly degenerate level."""
+    nev = int(nev)
+    if not 1 <= nev <= 8:
+        raise ValueError("nev must be in 1 ... 8 (DSEA_MAX_NEV), got %d" % nev)
+    reorth = REORTH_DEFAULT if reorth is None else reorth
+    if reorth == "none":
+        raise NotImplementedError("reorth='none' (basis-free Lanczos) keeps no basis to combine into nev > 0 Ritz vectors")
+    if reorth not in ("full", "twice", "partial"):
+        raise ValueError("reorth must be 'full', 'twice', 'partial' or 'none'")
+    _refuse_partitioned(A, sparse)
+    if reorth != "full":
+        if torch.device(device).type != "cuda":
+            raise NotImplementedError("reorth=%r runs on the GPU" % reorth)
+        if reorth == "twice":
+            with engine.reorth_options(passes=2):
+                return lowestLanczos(A, k, nev, device, sparse=sparse, dim=dim, q0=q0, reorth="full")
+        cur = engine.partial_reorth()
+        with engine.reorth_options(partial=0.0 if cur is None else cur):
+            return lowestLanczos(A, k, nev, device, sparse=sparse, dim=dim, q0=q0, reorth="full")
+    if k < nev + 1:
+        raise ValueError("lowest %d eigenpairs need k >= nev + 1 = %d Lanczos vectors, got k = %d" % (nev, nev + 1, k))
+    where, Q, ldq, n, alphas, betas, dtype = _lanczos_core(A, k, device, sparse, dim, q0, arena=True)
+    vals, S, bottoms = engine.tridiag_lowest(alphas, betas, nev)
+    scale = float(np.abs(vals).max())
+    gaps = np.diff(vals)
+    bad = np.where(gaps < DEGENERACY_TOL * scale)[0]
+    if bad.size:
+        import warnings
+        i = int(bad[0])
+        warnings.warn("lowestLanczos: Ritz values %d and %d are degenerate (%.17g, %.17g): the eigenvector adjoints are "
+                      "ill-defined there, and single-vector Lanczos cannot resolve an exactly degenerate level"
+                      % (i, i + 1, vals[i], vals[i + 1]), RuntimeWarning)
+    if where == "cuda":
+        Y = engine.ritz_block(Q, ldq, n, S, Q.device)
+        vecs = Y[:, :n].T
+    else:
+        # column by column, with the matmul symeigLanczos makes (a (k, nev) product may take another BLAS kernel)
+        vecs = torch.stack([torch.matmul(Q[:, :S.shape[1]], torch.from_numpy(S[j]).to(Q.dtype)) for j in range(nev)],
+                           dim=1)
+    eigvals = torch.tensor(vals[:nev], dtype=torch.float64, device=alphas.device).to(dtype)
+    vecs = vecs.to(dtype)
+    _, _, amap = _resolve(A, device, sparse, dim)
+    res = []
+    for j in range(nev):
+        v = vecs[:, j].contiguous()
+        res.append(float(torch.norm(amap(v) - eigvals[j] * v)))
+    last_lowest.ritz_residuals, last_lowest.next_eigval, last_lowest.bottoms = res, float(vals[nev]), bottoms
+    return eigvals, vecs

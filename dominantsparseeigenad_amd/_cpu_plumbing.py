@@ -58,3 +58,38 @@ def cg_host(apply_A, b, x0, eps, cap, info):
             step = torch.matmul(r, r) / torch.matmul(Ad, d)
     info.iters, info.resnorm, info.converged = it, rn, rn < eps
     return x
+
+
+def cg_host_deflated(apply_A, b, x0, Psi, eps, cap, info):
+    """The deflated CG of include/dsea.h dsea_cg_run_deflated on host tensors: (A - shift) y = P b on range(P), P = I - Psi
+    Psi^T (Psi (n, m)); ``apply_A`` applies A - shift.  The residual is re-projected every iteration, the stop is decided on
+    the projected residual and accepted only after the recomputed true residual ||P(b - (A - shift) x)|| < eps."""
+    def proj(v):
+        return v - torch.matmul(Psi, torch.matmul(Psi.T, v))
+
+    def restart(x):
+        x = proj(x)
+        r = proj(b - apply_A(x))
+        return x, r, torch.norm(r).item()
+
+    x, r, rn = restart(x0)
+    d = r
+    it = 0
+    while rn >= eps and it < cap:
+        it += 1
+        Ad = apply_A(d)
+        step = torch.matmul(r, r) / torch.matmul(d, Ad)
+        x = x + step * d
+        r_new = proj(r - step * Ad)
+        rn = torch.norm(r_new).item()
+        if rn < eps:
+            x, r, rn = restart(x)
+            d = r
+            continue
+        ratio = torch.matmul(r_new, r_new) / torch.matmul(r, r)
+        r = r_new
+        d = r + ratio * d
+    if rn >= eps:
+        x = proj(x)
+    info.iters, info.resnorm, info.converged = it, rn, rn < eps
+    return x

@@ -25,6 +25,7 @@ ERR_COMM = -9
 ERR_PREMISE = -10
 ERR_SECOND_PASS = -11
 ERR_UNSUPPORTED = -6
+MAX_NEV = 8            # DSEA_MAX_NEV
 COMM_ID_BYTES = 128
 TUNE_TFIM_TILE_LOG2, TUNE_CSR_GROUP, TUNE_SELL_UNROLL, TUNE_SELL_XCD_MAP, TUNE_SELL_NT = 1, 2, 3, 4, 5
 TUNE_SELL_MAX_WIDTH = 6
@@ -165,6 +166,16 @@ _SIGNATURES = {
     "dsea_lanczos_status": (c_int, [c_void_p, POINTER(c_int), c_void_p]),
     "dsea_cg_run": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_int64,
                             c_int, POINTER(c_int64), POINTER(c_double), c_void_p]),
+    "dsea_ritz_combine_block": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_int64, c_int, c_void_p,
+                                        c_int64, c_void_p]),
+    "dsea_block_project_out": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64,
+                                       c_void_p]),
+    "dsea_cg_run_deflated": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p,
+                                     c_double, c_int64, c_int, POINTER(c_int64), POINTER(c_double), c_void_p]),
+    "dsea_cg_deflated_init": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p,
+                                      c_void_p, c_void_p, c_double, c_int64, c_void_p]),
+    "dsea_cg_deflated_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int,
+                                      c_void_p, c_double, c_int64, c_int64, c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

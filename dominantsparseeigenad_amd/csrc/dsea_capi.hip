@@ -124,7 +124,8 @@ TileGeom Workspace::geom(int64_t n_rows) const {
 
 extern "C" {
 
-int dsea_version(void) { return 140; }   // 140: fp64-MFMA transfer mat-vec on packed operands, optimistic Arnoldi second pass
+int dsea_version(void) { return 141; }   // 141: lowest-nev eigenpairs (block Ritz combine, block projection, deflated CG)
+                                          // 140: fp64-MFMA transfer mat-vec on packed operands, optimistic Arnoldi second pass
 
 const char* dsea_error_string(int status) {
   switch (status) {
@@ -1582,6 +1583,129 @@ int dsea_cg_run(dsea_op_t op, dsea_ws_t ws, const double* shift, const double* b
   int rc = check_launch();
   if (rc != DSEA_OK) return rc;
   return host_state[DSEA_CG_DONE] != 0.0 ? DSEA_OK : DSEA_ERR_NOT_CONVERGED;
+}
+
+
+// ---------------------------------------------------------------------------- lowest-nev eigenpairs
+int dsea_ritz_combine_block(dsea_ws_t ws, const double* Q, int64_t ldq, int64_t n, int k, const double* S, int64_t lds,
+                            int m, double* Y, int64_t ldy, void* stream) {
+  REQUIRE(ws && Q && S && Y && n >= 1 && k >= 1 && ldq >= n && lds >= k && ldy >= n, DSEA_ERR_ARG);
+  REQUIRE(m >= 1 && m <= DSEA_MAX_NEV, DSEA_ERR_ARG);
+  REQUIRE(aligned16(Q) && aligned16(Y) && (ldq % 2 == 0) && (ldy % 2 == 0), DSEA_ERR_ALIGN);
+  TileGeom g = ws->w.geom(n);
+  launch_ritz_block(g, Q, ldq, n, k, S, lds, m, Y, ldy, static_cast<hipStream_t>(stream));
+  return check_launch();
+}
+
+int dsea_block_project_out(dsea_ws_t ws, const double* v, const double* Psi, int64_t ldpsi, int m, double* out,
+                           double* coef_out, int64_t n, void* stream) {
+  REQUIRE(ws && v && Psi && out && n >= 1 && ldpsi >= n, DSEA_ERR_ARG);
+  REQUIRE(m >= 1 && m <= DSEA_MAX_NEV && ws->w.kmax + 1 >= m && ws->w.n >= n, DSEA_ERR_ARG);
+  REQUIRE(aligned16(v) && aligned16(Psi) && aligned16(out) && (ldpsi % 2 == 0), DSEA_ERR_ALIGN);
+  launch_block_project(v, Psi, ldpsi, m, out, coef_out, n, ws->w.partials, DSEA_MAX_WAVE_TILES,
+                       static_cast<hipStream_t>(stream));
+  return check_launch();
+}
+
+namespace {
+// the deflated CG's buffers: Psi^T r partials in rows 0..m-1 of the partial-sum area, d.A'd partials in aux[0..],
+// ||P r||^2 partials in aux[MAX_WAVE_TILES..]
+inline bool dfl_args_ok(dsea_ws_t ws, int m) { return ws && m >= 1 && m <= DSEA_MAX_NEV && ws->w.kmax >= m + 1; }
+
+void dfl_step(Workspace& w, double* x, double* r, double* d, double* Ad, const double* state, int parity, double eps,
+              const double* dP, int nd, const double* Psi, int64_t ldpsi, int m, int64_t n, hipStream_t st) {
+  double* rP = w.aux + DSEA_MAX_WAVE_TILES;
+  const double* done = state + DSEA_CG_DONE;
+  const int nu = launch_dfl_update(x, r, d, Ad, state, parity, dP, nd, Psi, ldpsi, m, n, w.partials, DSEA_MAX_WAVE_TILES, st);
+  const int nr = launch_dfl_reproject(r, Psi, ldpsi, m, w.partials, nu, DSEA_MAX_WAVE_TILES, rP, done, n, st);
+  launch_cg_direction_fused(r, d, const_cast<double*>(state), parity, rP, nr, eps, n, st);
+}
+}  // namespace
+
+int dsea_cg_deflated_init(dsea_ws_t ws, const double* b, const double* x, const double* Ax, const double* shift,
+                          const double* Psi, int64_t ldpsi, int m, double* r, double* d, double* state, double eps,
+                          int64_t n, void* stream) {
+  REQUIRE(dfl_args_ok(ws, m) && b && x && Ax && Psi && r && d && state && n >= 1 && ldpsi >= n && ws->w.n >= n,
+          DSEA_ERR_ARG);
+  REQUIRE(aligned16(b) && aligned16(x) && aligned16(Ax) && aligned16(Psi) && aligned16(r) && aligned16(d) &&
+              (ldpsi % 2 == 0), DSEA_ERR_ALIGN);
+  Workspace& w = ws->w;
+  launch_dfl_restart(b, Ax, x, shift, Psi, ldpsi, m, r, d, state, eps, 0, n, w.partials, DSEA_MAX_WAVE_TILES,
+                     w.aux + DSEA_MAX_WAVE_TILES, static_cast<hipStream_t>(stream));
+  return check_launch();
+}
+
+int dsea_cg_deflated_step(dsea_ws_t ws, double* x, double* r, double* d, double* Ad, const double* shift,
+                          const double* Psi, int64_t ldpsi, int m, double* state, double eps, int64_t iteration,
+                          int64_t n, void* stream) {
+  REQUIRE(dfl_args_ok(ws, m) && x && r && d && Ad && Psi && state && n >= 1 && ldpsi >= n && iteration >= 0 &&
+              ws->w.n >= n, DSEA_ERR_ARG);
+  REQUIRE(aligned16(x) && aligned16(r) && aligned16(d) && aligned16(Ad) && aligned16(Psi) && (ldpsi % 2 == 0),
+          DSEA_ERR_ALIGN);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  Workspace& w = ws->w;
+  const int nd = launch_shift_dot_partials(d, Ad, shift, state + DSEA_CG_DONE, n, w.aux, st);   // (A - shift) d, d.A'd
+  dfl_step(w, x, r, d, Ad, state, (int)(iteration & 1), eps, w.aux, nd, Psi, ldpsi, m, n, st);
+  return check_launch();
+}
+
+int dsea_cg_run_deflated(dsea_op_t op, dsea_ws_t ws, const double* shift, const double* b, double* x, const double* Psi,
+                         int64_t ldpsi, int m, double* state, double eps, int64_t maxiter, int poll_every,
+                         int64_t* iters_out, double* resnorm_out, void* stream) {
+  REQUIRE(op && dfl_args_ok(ws, m) && b && x && Psi && state && maxiter >= 0, DSEA_ERR_ARG);
+  const int64_t n = op->d.n;
+  REQUIRE(ws->w.n >= n && ldpsi >= n, DSEA_ERR_ARG);
+  REQUIRE(aligned16(b) && aligned16(x) && aligned16(Psi) && (ldpsi % 2 == 0), DSEA_ERR_ALIGN);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  Workspace& w = ws->w;
+  double* r = w.vec[1];
+  double* d = w.vec[2];
+  double* Ad = w.vec[3];
+  double* dP = w.aux;
+  double* rP = w.aux + DSEA_MAX_WAVE_TILES;
+  const double* done = state + DSEA_CG_DONE;
+  if (poll_every <= 0) poll_every = 16;
+  w.last_cg_form = DSEA_CG_FORM_STREAMING;
+
+  double hs[DSEA_CG_STATE_LEN];
+  auto read_state = [&]() -> bool {
+    return hipMemcpyAsync(hs, state, sizeof(hs), hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
+  };
+  // x <- P x ; r = P(b - A'x) ; d = r ; the stop flag on ||r||  (the entry, and the check of every stop the recurrence makes)
+  auto restart = [&](int keep) -> int {
+    launch_block_project(x, Psi, ldpsi, m, x, nullptr, n, w.partials, DSEA_MAX_WAVE_TILES, st);
+    if (launch_spmv(op->d, x, Ad, shift, nullptr, nullptr, st) < 0) return DSEA_ERR_UNSUPPORTED;
+    launch_dfl_restart(b, Ad, x, nullptr, Psi, ldpsi, m, r, d, state, eps, keep, n, w.partials, DSEA_MAX_WAVE_TILES, rP, st);
+    return read_state() ? DSEA_OK : DSEA_ERR_HIP;
+  };
+  int rc = restart(0);
+  int64_t issued = 0, local = 0;
+  while (rc == DSEA_OK && hs[DSEA_CG_DONE] == 0.0 && issued < maxiter) {
+    const int64_t chunk = (maxiter - issued) < poll_every ? (maxiter - issued) : poll_every;
+    for (int64_t it = 0; it < chunk; ++it, ++local) {
+      const int nd = launch_spmv(op->d, d, Ad, shift, done, dP, st);                  // A'd, d.A'd partials
+      if (nd < 0) return DSEA_ERR_UNSUPPORTED;
+      dfl_step(w, x, r, d, Ad, state, (int)(local & 1), eps, dP, nd, Psi, ldpsi, m, n, st);
+    }
+    issued += chunk;
+    if (!read_state()) rc = DSEA_ERR_HIP;
+    else if (hs[DSEA_CG_DONE] != 0.0) {   // the recurrence says converged: accept only on the recomputed true residual
+      rc = restart(1);
+      local = 0;
+    }
+  }
+  if (rc == DSEA_OK && hs[DSEA_CG_DONE] == 0.0)   // maxiter: leave x in range(P) all the same
+    launch_block_project(x, Psi, ldpsi, m, x, nullptr, n, w.partials, DSEA_MAX_WAVE_TILES, st);
+  if (rc == DSEA_ERR_HIP) {
+    g_last_hip = (int)hipGetLastError();
+    return rc;
+  }
+  if (rc != DSEA_OK) return rc;
+  if (iters_out) *iters_out = (int64_t)hs[DSEA_CG_ITERS];
+  if (resnorm_out) *resnorm_out = hs[DSEA_CG_RESNORM];
+  rc = check_launch();
+  if (rc != DSEA_OK) return rc;
+  return hs[DSEA_CG_DONE] != 0.0 ? DSEA_OK : DSEA_ERR_NOT_CONVERGED;
 }
 
 }  // extern "C"

@@ -238,6 +238,19 @@ void launch_plz_finish_form(double* r, const double* y, const double* pair, doub
                             double* alpha_out, double* beta_out, double* r_copy, int64_t n, hipStream_t st);
 void launch_finalize_pair(const double* PA, int na, double* outA, const double* PB, int nb, double* outB,
                           const double* skipB, hipStream_t st);
+// dsea_deflated.hip (lowest-nev eigenpairs)
+void launch_ritz_block(const TileGeom& g, const double* Q, int64_t ldq, int64_t n, int k, const double* S, int64_t lds,
+                       int m, double* Y, int64_t ldy, hipStream_t st);
+void launch_block_project(const double* v, const double* Psi, int64_t ldpsi, int m, double* out, double* coef_out,
+                          int64_t n, double* P, int pstride, hipStream_t st);
+void launch_dfl_restart(const double* b, const double* Ax, const double* x, const double* shift, const double* Psi,
+                        int64_t ldpsi, int m, double* r, double* d, double* state, double eps, int keep_iters, int64_t n,
+                        double* P, int pstride, double* rP, hipStream_t st);
+int launch_dfl_update(double* x, double* r, const double* d, const double* Ad, const double* state, int parity,
+                      const double* dP, int dCount, const double* Psi, int64_t ldpsi, int m, int64_t n, double* P,
+                      int pstride, hipStream_t st);
+int launch_dfl_reproject(double* r, const double* Psi, int64_t ldpsi, int m, const double* P, int count, int pstride,
+                         double* rP, const double* done, int64_t n, hipStream_t st);
 // dsea_krylov.hip
 bool blas_available();
 int blas_apply(const OpDesc& op, const double* x, double* y, hipStream_t st);

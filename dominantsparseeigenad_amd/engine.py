@@ -848,3 +848,136 @@ def project_out(v, a):
     check(lib.dsea_project_out(ws.handle, _ptr(v), _ptr(a), _ptr(out), None, n, _stream(v.device)),
           "dsea_project_out")
     return out
+
+
+# --------------------------------------------------------------------------- lowest-nev eigenpairs
+def tridiag_lowest(alphas, betas, nev, break_at=None):
+    """The nev + 1 lowest eigenvalues of the k x k tridiagonal T and the coefficient vectors of the nev lowest
+    (docs/design/13-lowest-eigenpairs.md).  Same breakdown cut as ``tridiag_extreme``, and every index is its own
+    ``eigh_tridiagonal(..., select_range=(i, i))`` call as there, so index 0 is bit-identical to ``tridiag_extreme``'s.
+
+    Returns (vals (nev + 1,) numpy, S (nev, m) numpy with m <= k the dimension used, bottom (nev,) numpy) where
+    bottom[j] = |s_{m-1, j}|: times the next Lanczos beta it is the classical residual estimate of pair j."""
+    from scipy.linalg import eigh_tridiagonal
+
+    nev = int(nev)
+    d = alphas.detach().cpu().numpy()
+    k = d.shape[0]
+    if nev < 1 or k < nev + 1:
+        raise ValueError("lowest %d eigenpairs need k >= nev + 1 = %d Lanczos vectors, got k = %d" % (nev, nev + 1, k))
+    # the cut of tridiag_extreme (a warning is issued there); its pair for "min" is index 0 of the same leading block
+    first = tridiag_extreme(alphas, betas, "min", break_at)
+    m = first[0][1].shape[0]
+    if m < nev + 1:
+        raise ValueError("the Krylov space broke down at dimension %d < nev + 1 = %d: the %d lowest levels are not "
+                         "resolved from this start vector" % (m, nev + 1, nev))
+    e = betas.detach().cpu().numpy()
+    vals = np.empty(nev + 1)
+    S = np.empty((nev, m))
+    vals[0], S[0] = first[0][0], first[0][1]
+    for i in range(1, nev + 1):
+        w, v = eigh_tridiagonal(d[:m], e[:m - 1], select="i", select_range=(i, i))
+        vals[i] = float(w[0])
+        if i < nev:
+            S[i] = v[:, 0]
+    return vals, S, np.abs(S[:, m - 1])
+
+
+def ritz_block(Q, ldq, n, S_host, device):
+    """Y[j] = sum_i S[j, i] Q[i] for the nev rows of S in one pass over the basis (dsea_ritz_combine_block).
+    Returns the (nev, ldy) buffer; row j is bit-identical to ``ritz_vector(Q, ldq, n, k, S[j])``."""
+    lib = _lib.load()
+    S = torch.from_numpy(np.ascontiguousarray(S_host, dtype=np.float64)).to(device)
+    m, k = int(S.shape[0]), int(S.shape[1])
+    ws = Workspace.get(n, k, device)
+    ldy = round_up(n, 2)
+    Y = torch.empty((m, ldy), dtype=F64, device=device)
+    check(lib.dsea_ritz_combine_block(ws.handle, _ptr(Q), ldq, n, k, _ptr(S), k, m, _ptr(Y), ldy, _stream(device)),
+          "dsea_ritz_combine_block")
+    return Y
+
+
+def block_project_out(v, Psi, ldpsi, m, coef=None):
+    """v - Psi (Psi^T v) on the device (dsea_block_project_out); Psi is an (m, ldpsi) buffer"""
+    lib = _lib.load()
+    n = v.numel()
+    v = as_vector(v, n)
+    ws = Workspace.get(n, max(8, int(m) + 1), v.device)
+    out = torch.empty(n, dtype=F64, device=v.device)
+    check(lib.dsea_block_project_out(ws.handle, _ptr(v), _ptr(Psi), int(ldpsi), int(m), _ptr(out), _ptr(coef), n,
+                                     _stream(v.device)), "dsea_block_project_out")
+    return out
+
+
+def cg_deflated(b, x0, Psi, ldpsi, m, *, native=None, callable_A=None, shift=None, eps=1e-7, maxiter=None,
+                poll_every=16):
+    """CG for (A - shift I) y = P b on range(P), P = I - Psi Psi^T (Psi an (m, ldpsi) device buffer).  Native operands run
+    dsea_cg_run_deflated; a callable runs dsea_cg_deflated_init / _step around the caller's mat-vec, with the same rule for
+    a stop: it is accepted only after the recomputed true residual is below eps.  Diagnostics in ``last_cg``."""
+    lib = _lib.load()
+    device = b.device
+    n = b.numel()
+    m = int(m)
+    b = as_vector(b, n)
+    x = as_vector(x0, n).clone()
+    cap = n if maxiter is None else int(maxiter)
+    ws = Workspace.get(n, max(8, m + 1), device)
+    st = _stream(device)
+    state = ws.state
+    shift_t = None
+    if shift is not None:
+        shift_t = shift.detach().reshape(-1)[:1].to(device=device, dtype=F64).contiguous()
+    if native is not None:
+        iters, res = c_int64(0), c_double(0.0)
+        with ws.owned_by("deflated CG (native operator)"):
+            rc = lib.dsea_cg_run_deflated(native.handle, ws.handle, _ptr(shift_t), _ptr(b), _ptr(x), _ptr(Psi), int(ldpsi),
+                                          m, _ptr(state), float(eps), cap, int(poll_every), byref(iters), byref(res), st)
+        check(rc, "dsea_cg_run_deflated", allow=(_lib.ERR_NOT_CONVERGED,))
+        last_cg.iters, last_cg.resnorm, last_cg.converged = iters.value, res.value, rc == 0
+        last_cg.form, last_cg.polls = "deflated streaming", 0
+        return x
+
+    r = torch.empty(n, dtype=F64, device=device)
+    d = torch.empty(n, dtype=F64, device=device)
+    polls, issued, total = 0, 0, 0
+
+    def restart():
+        check(lib.dsea_block_project_out(ws.handle, _ptr(x), _ptr(Psi), int(ldpsi), m, _ptr(x), None, n, st),
+              "dsea_block_project_out")
+        Ax = as_vector(callable_A(x), n)
+        if Ax.data_ptr() == x.data_ptr():
+            Ax = Ax.clone()
+        check(lib.dsea_cg_deflated_init(ws.handle, _ptr(b), _ptr(x), _ptr(Ax), _ptr(shift_t), _ptr(Psi), int(ldpsi), m,
+                                        _ptr(r), _ptr(d), _ptr(state), float(eps), n, st), "dsea_cg_deflated_init")
+        return state.cpu()
+
+    with ws.owned_by("deflated CG (callable operator)"):
+        host = restart()
+        polls += 1
+        local = 0
+        while host[_lib.CG_DONE].item() == 0.0 and issued < cap:
+            chunk = min(int(poll_every), cap - issued)
+            for _ in range(chunk):
+                Ad = as_vector(callable_A(d), n)
+                if Ad.data_ptr() == d.data_ptr() or not Ad.is_contiguous():
+                    Ad = Ad.clone()
+                check(lib.dsea_cg_deflated_step(ws.handle, _ptr(x), _ptr(r), _ptr(d), _ptr(Ad), _ptr(shift_t), _ptr(Psi),
+                                                int(ldpsi), m, _ptr(state), float(eps), local, n, st),
+                      "dsea_cg_deflated_step")
+                local += 1
+            issued += chunk
+            host = state.cpu()
+            polls += 1
+            if host[_lib.CG_DONE].item() != 0.0:      # check the stop on the true residual; restart from x if it fails
+                total += int(host[_lib.CG_ITERS].item())
+                host = restart()
+                polls += 1
+                local = 0
+        if host[_lib.CG_DONE].item() == 0.0:
+            check(lib.dsea_block_project_out(ws.handle, _ptr(x), _ptr(Psi), int(ldpsi), m, _ptr(x), None, n, st),
+                  "dsea_block_project_out")
+    last_cg.polls, last_cg.form = polls, "deflated streaming (callable operand)"
+    last_cg.iters = total + int(host[_lib.CG_ITERS].item())
+    last_cg.resnorm = float(host[_lib.CG_RESNORM].item())
+    last_cg.converged = host[_lib.CG_DONE].item() != 0.0
+    return x

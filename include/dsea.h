@@ -649,6 +649,44 @@ int dsea_cg_run(dsea_op_t op, dsea_ws_t ws, const double *shift, const double *b
                 double *state, double eps, int64_t maxiter, int poll_every, int64_t *iters_out,
                 double *resnorm_out, void *stream);
 
+/* ------------------------------------------------------------------ lowest-nev eigenpairs (docs/design/13-lowest-eigenpairs.md)
+ * Psi = the m <= DSEA_MAX_NEV requested eigenvectors, stored as the basis is: row j at Psi + j*ldpsi (ldpsi >= n, even,
+ * 16-byte aligned).  P = I - Psi Psi^T.                                                                                 */
+#define DSEA_MAX_NEV 8
+
+/* Y[j] = sum_{i<k} S[j*lds + i] Q[i] for j < m, in ONE pass over the basis.  Every column is bit-identical to
+ * dsea_ritz_combine with that column of S (same per-row summation order in the tiled and the small-n split form). */
+int dsea_ritz_combine_block(dsea_ws_t ws, const double *Q, int64_t ldq, int64_t n, int k, const double *S, int64_t lds,
+                            int m, double *Y, int64_t ldy, void *stream);
+
+/* out = v - Psi (Psi^T v) (out may be v); coef_out (nullable, device) receives the m dot products.  Two launches: the m
+ * fused dot products, then the apply.  The workspace must have been created with kmax >= m - 1.                     */
+int dsea_block_project_out(dsea_ws_t ws, const double *v, const double *Psi, int64_t ldpsi, int m, double *out,
+                           double *coef_out, int64_t n, void *stream);
+
+/* Deflated CG: (A - (*shift) I) x = P b with x in range(P), for every operand dsea_cg_run accepts (streaming form only).
+ * x (in: start vector, out: solution) is projected on entry; the residual is re-projected every iteration (its m dot
+ * products folded into the update pass) and the stop is decided on ||P r|| computed from the projected vector.  A stop is
+ * accepted only after the recomputed true residual ||P((A - shift) x - b)|| is below eps, otherwise CG restarts from x.
+ * state, iters_out, resnorm_out, poll_every and DSEA_ERR_NOT_CONVERGED as dsea_cg_run; SYNCHRONISES the stream.
+ * DSEA_ERR_ARG if m < 1, m > DSEA_MAX_NEV or the workspace was created with kmax < m + 1.                              */
+int dsea_cg_run_deflated(dsea_op_t op, dsea_ws_t ws, const double *shift, const double *b, double *x, const double *Psi,
+                         int64_t ldpsi, int m, double *state, double eps, int64_t maxiter, int poll_every,
+                         int64_t *iters_out, double *resnorm_out, void *stream);
+
+/* The same iteration around a CALLER-SUPPLIED mat-vec (the pattern of dsea_cg_init / dsea_cg_step).
+ *   dsea_cg_deflated_init: on entry x is in range(P) (dsea_block_project_out) and Ax = A x; r = P(b - (A - shift) x),
+ *       d = r, state cleared, state[RR] = ||r||^2 and the stop flag on ||r|| < eps.  Also the restart that checks a stop.
+ *   dsea_cg_deflated_step: on entry Ad = A d.  Ad -= shift d; alpha; x += alpha d; r -= alpha Ad; r = P r; the stop test on
+ *       ||r||; d = r + beta d.  `iteration` counts from 0 since the last dsea_cg_deflated_init.  No-op once DONE is set.
+ * DSEA_ERR_ARG as dsea_cg_run_deflated.                                                                                  */
+int dsea_cg_deflated_init(dsea_ws_t ws, const double *b, const double *x, const double *Ax, const double *shift,
+                          const double *Psi, int64_t ldpsi, int m, double *r, double *d, double *state, double eps,
+                          int64_t n, void *stream);
+int dsea_cg_deflated_step(dsea_ws_t ws, double *x, double *r, double *d, double *Ad, const double *shift,
+                          const double *Psi, int64_t ldpsi, int m, double *state, double eps, int64_t iteration,
+                          int64_t n, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
