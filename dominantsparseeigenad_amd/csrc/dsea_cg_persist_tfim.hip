@@ -24,19 +24,8 @@
 
 namespace dsea {
 
-namespace {
-typedef gran_u64 cgt_gu64;
-#define CGT_TIMEOUT_TICKS DSEA_GRANULE_TIMEOUT_TICKS
 #define CGT_ROWS 128
 #define CGT_MAX_G 64
-
-__device__ __forceinline__ double cgt_tfim_diag(const TfimParams& p, int64_t i, uint64_t maskL) {
-  const uint64_t gi = (uint64_t)(p.row_offset + i);
-  const uint64_t rot = ((gi << 1) | (gi >> (p.L - 1))) & maskL;
-  const int pop = __popcll(gi ^ rot);
-  return p.diag_scale * (double)(-(p.L - 2 * pop));
-}
-}  // namespace
 
 struct CgtArgs {
   TfimParams tf;
@@ -66,16 +55,16 @@ __global__ __launch_bounds__(256) void k_cg_persist_tfim(CgtArgs a) {
   const int nlocal = L < 7 ? L : 7, nfar = L - nlocal;
   const uint64_t maskL = (L >= 64) ? ~0ull : ((1ull << L) - 1ull);
   const bool v0 = row < n, v1 = row + 1 < n;
-  cgt_gu64* SA = (cgt_gu64*)a.comm;
-  cgt_gu64* SB = SA + (int64_t)2 * G;
-  cgt_gu64* SX = SB + (int64_t)2 * G * (1 + CGT_ROWS);
+  gran_u64* SA = (gran_u64*)a.comm;
+  gran_u64* SB = SA + (int64_t)2 * G;
+  gran_u64* SX = SB + (int64_t)2 * G * (1 + CGT_ROWS);
   const bool has_shift = a.shift != nullptr;
   const double sh = has_shift ? a.shift[0] : 0.0;
   const double gpar = a.tf.g_dev ? a.tf.g_dev[0] : a.tf.g_const;
   double d0 = 0.0, d1 = 0.0;
   if (wv == 0) {
-    d0 = cgt_tfim_diag(a.tf, row, maskL);
-    d1 = cgt_tfim_diag(a.tf, row + 1, maskL);
+    d0 = tfim_diag(a.tf, row, maskL);
+    d1 = tfim_diag(a.tf, row + 1, maskL);
   }
   if (tid == 0) s_b[1] = 0.0;
   __syncthreads();
@@ -105,39 +94,25 @@ __global__ __launch_bounds__(256) void k_cg_persist_tfim(CgtArgs a) {
   // all threads: gather the G slab partials published in `base` (stride `stride` granules) under `epoch` -> total in
   // every thread; with `rows_from` != null also the partner slabs' rows (granule row_off + r of slab g ^ (1 << b), slabs
   // `row_stride` granules apart) -> dst
-  auto gather = [&](cgt_gu64* base, int stride, unsigned epoch, cgt_gu64* rows_from, int row_stride, int row_off,
+  auto gather = [&](gran_u64* base, int stride, unsigned epoch, gran_u64* rows_from, int row_stride, int row_off,
                     double (*dst)[CGT_ROWS], bool& fail) -> double {
     const long long t0 = wall_clock64();
     if (wv == 1 && lane < G) {
       double v = 0.0;
-      while (!granule_try_get(base + (int64_t)lane * stride * 2, epoch, v)) {
-        __builtin_amdgcn_s_sleep(1);
-        if (wall_clock64() - t0 > CGT_TIMEOUT_TICKS) {
-          s_b[1] = 1.0;
-          break;
-        }
-      }
+      if (!granule_wait(base + (int64_t)lane * stride * 2, epoch, v, t0, DSEA_GRANULE_TIMEOUT_TICKS)) s_b[1] = 1.0;
       s_part[lane] = v;
     }
     if (rows_from && tid >= 128 && nfar > 0) {
       const int rr = tid - 128;
+      gran_u64* src[6];
+      bool on[6];
       double pv[6];
-      bool ok;
-      do {
-        ok = true;
 #pragma unroll
-        for (int b = 0; b < 6; ++b) {
-          pv[b] = 0.0;
-          if (b < nfar) ok &= granule_try_get(rows_from + ((int64_t)(g ^ (1 << b)) * row_stride + row_off + rr) * 2, epoch, pv[b]);
-        }
-        if (!ok) {
-          __builtin_amdgcn_s_sleep(1);
-          if (wall_clock64() - t0 > CGT_TIMEOUT_TICKS) {
-            s_b[1] = 1.0;
-            break;
-          }
-        }
-      } while (!ok);
+      for (int b = 0; b < 6; ++b) {
+        src[b] = rows_from + ((int64_t)(g ^ (1 << b)) * row_stride + row_off + rr) * 2;
+        on[b] = b < nfar;
+      }
+      if (!granule_wait_all(src, on, epoch, pv, t0, DSEA_GRANULE_TIMEOUT_TICKS)) s_b[1] = 1.0;
 #pragma unroll
       for (int b = 0; b < 6; ++b)
         if (b < nfar) dst[b][rr] = pv[b];
@@ -186,7 +161,7 @@ __global__ __launch_bounds__(256) void k_cg_persist_tfim(CgtArgs a) {
       acc = fma(rv.x, rv.x, acc);
       acc = fma(rv.y, rv.y, acc);
       acc = wave_sum(acc);
-      cgt_gu64* mine = SB + (int64_t)g * (1 + CGT_ROWS) * 2;
+      gran_u64* mine = SB + (int64_t)g * (1 + CGT_ROWS) * 2;
       granule_put(mine + (1 + 2 * lane) * 2, epoch, rv.x);
       granule_put(mine + (2 + 2 * lane) * 2, epoch, rv.y);
       if (lane == 0) granule_put(mine, epoch, acc);
@@ -271,16 +246,7 @@ int launch_cg_persist_tfim(const OpDesc& op, const double* shift, const double* 
   if (!cg_persist_tfim_applicable(op)) return -1;
   const int64_t n = op.n;
   const int G = (int)((n + CGT_ROWS - 1) / CGT_ROWS);
-  {
-    static thread_local int cu_dev = -1, cu_count = 0;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return -2;
-    if (dev != cu_dev) {
-      if (hipDeviceGetAttribute(&cu_count, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return -2;
-      cu_dev = dev;
-    }
-    if (G > cu_count) return -1;     // all workgroups must be resident together
-  }
+  if (const int rc = persist_resident(G)) return rc;     // (256 threads, 13.5 KB of static LDS: one per CU always fits)
   if (hipMemsetAsync(comm, 0, cg_persist_tfim_comm_bytes(n), st) != hipSuccess) return -2;
   CgtArgs a;
   a.tf = op.tfim;

@@ -49,20 +49,12 @@
 namespace dsea {
 
 namespace {
-typedef gran_u64 cgb_gu64;
 typedef unsigned int cgb_v4u __attribute__((ext_vector_type(4)));
-#define CGB_TIMEOUT_TICKS DSEA_GRANULE_TIMEOUT_TICKS
 #define CGB_T 11
 #define CGB_TILE 2048
 #define CGB_PER 4          /* row pairs per thread */
 #define CGB_SC1 16         /* aux bits of the buffer intrinsics: sc1 */
 
-__device__ __forceinline__ double cgb_tfim_diag(const TfimParams& p, int64_t i, uint64_t maskL) {
-  const uint64_t gi = (uint64_t)(p.row_offset + i);
-  const uint64_t rot = ((gi << 1) | (gi >> (p.L - 1))) & maskL;
-  const int pop = __popcll(gi ^ rot);
-  return p.diag_scale * (double)(-(p.L - 2 * pop));
-}
 __device__ __forceinline__ double2 cgb_as_d2(cgb_v4u v) {
   return make_double2(__hiloint2double((int)v.y, (int)v.x), __hiloint2double((int)v.w, (int)v.z));
 }
@@ -110,9 +102,9 @@ __global__ __launch_bounds__(256 * NVB) void k_cg_persist_tfim_big(CgbArgs a) {
   const int64_t n = (int64_t)1 << L, base = (int64_t)tile * CGB_TILE;
   const uint64_t maskL = (L >= 64) ? ~0ull : ((1ull << L) - 1ull);
   const int nctiles = a.ntiles * 4;
-  cgb_gu64* PA = (cgb_gu64*)a.comm;
-  cgb_gu64* PC = PA + (int64_t)2 * a.ntiles;
-  cgb_gu64* FL = PC + (int64_t)2 * nctiles;
+  gran_u64* PA = (gran_u64*)a.comm;
+  gran_u64* PC = PA + (int64_t)2 * a.ntiles;
+  gran_u64* FL = PC + (int64_t)2 * nctiles;
   const bool has_shift = a.shift != nullptr;
   const double sh = has_shift ? a.shift[0] : 0.0;
   const double gpar = a.tf.g_dev ? a.tf.g_dev[0] : a.tf.g_const;
@@ -178,8 +170,8 @@ __global__ __launch_bounds__(256 * NVB) void k_cg_persist_tfim_big(CgbArgs a) {
       sum.x += far[m].x;
       sum.y += far[m].y;
       double2 v;
-      v.x = __dsub_rn(__dmul_rn(xv.x, cgb_tfim_diag(a.tf, i0, maskL)), __dmul_rn(gpar, sum.x));
-      v.y = __dsub_rn(__dmul_rn(xv.y, cgb_tfim_diag(a.tf, i0 + 1, maskL)), __dmul_rn(gpar, sum.y));
+      v.x = __dsub_rn(__dmul_rn(xv.x, tfim_diag(a.tf, i0, maskL)), __dmul_rn(gpar, sum.x));
+      v.y = __dsub_rn(__dmul_rn(xv.y, tfim_diag(a.tf, i0 + 1, maskL)), __dmul_rn(gpar, sum.y));
       if (has_shift) {
         v.x = __dsub_rn(v.x, __dmul_rn(sh, xv.x));
         v.y = __dsub_rn(v.y, __dmul_rn(sh, xv.y));
@@ -201,28 +193,19 @@ __global__ __launch_bounds__(256 * NVB) void k_cg_persist_tfim_big(CgbArgs a) {
   };
   // every virtual block gathers ALL `count` partials published under `epoch` and sums them in the order of
   // sum_partials_block (two_acc) or k_finalize1 (!two_acc); the total is returned in every thread
-  auto gather = [&](cgb_gu64* src, int count, unsigned epoch, bool two_acc, bool& fail) -> double {
+  auto gather = [&](gran_u64* src, int count, unsigned epoch, bool two_acc, bool& fail) -> double {
     double v = 0.0;
     if (vb == 0) {
+      gran_u64* gp[8];
+      bool on[8];
       double pv[8];
-      const long long t0 = wall_clock64();
-      bool ok;
-      do {
-        ok = true;
 #pragma unroll
-        for (int m = 0; m < 8; ++m) {
-          pv[m] = 0.0;
-          const int b = t + 256 * m;
-          if (b < count) ok &= granule_try_get(src + 2 * (int64_t)b, epoch, pv[m]);
-        }
-        if (!ok) {
-          __builtin_amdgcn_s_sleep(1);
-          if (wall_clock64() - t0 > CGB_TIMEOUT_TICKS) {
-            sm.fail = 1.0;
-            break;
-          }
-        }
-      } while (!ok);
+      for (int m = 0; m < 8; ++m) {
+        const int b = t + 256 * m;
+        gp[m] = src + 2 * (int64_t)b;
+        on[m] = b < count;
+      }
+      if (!granule_wait_all(gp, on, epoch, pv, wall_clock64(), DSEA_GRANULE_TIMEOUT_TICKS)) sm.fail = 1.0;
       if (two_acc) {   // sum_partials_block: a0 takes b = t, t + 512, ... ; a1 takes b = t + 256, t + 768, ...
         double a0 = 0.0, a1 = 0.0;
 #pragma unroll
@@ -267,15 +250,7 @@ __global__ __launch_bounds__(256 * NVB) void k_cg_persist_tfim_big(CgbArgs a) {
   auto wait_partners = [&](unsigned epoch, bool& fail) {
     if (t < nfar) {
       const long long t0 = wall_clock64();
-      cgb_gu64* f = FL + 2 * (int64_t)(tile ^ (1 << t));
-      for (;;) {
-        if (granule_epoch(f) >= epoch) break;
-        __builtin_amdgcn_s_sleep(1);
-        if (wall_clock64() - t0 > CGB_TIMEOUT_TICKS) {
-          sm.fail = 1.0;
-          break;
-        }
-      }
+      if (!granule_wait_epoch(FL + 2 * (int64_t)(tile ^ (1 << t)), epoch, t0, DSEA_GRANULE_TIMEOUT_TICKS)) sm.fail = 1.0;
     }
     __syncthreads();
     fail = sm.fail != 0.0;
@@ -297,7 +272,7 @@ __global__ __launch_bounds__(256 * NVB) void k_cg_persist_tfim_big(CgbArgs a) {
     // see its tag and run into the time-out.  With two, the slot of epoch e is rewritten at epoch e + 2, which a workgroup
     // reaches only after ALL workgroups have published epoch e + 1, i.e. after every one of them has left the gather of e.
     auto exchange2 = [&](double v0, double v1, unsigned epoch, bool& fail, double& out0, double& out1) {
-      cgb_gu64* PE = PA + (int64_t)(epoch & 1u) * 4 * (int64_t)gridDim.x;
+      gran_u64* PE = PA + (int64_t)(epoch & 1u) * 4 * (int64_t)gridDim.x;
       v0 = wave_sum(v0);
       v1 = wave_sum(v1);
       __syncthreads();
@@ -316,17 +291,12 @@ __global__ __launch_bounds__(256 * NVB) void k_cg_persist_tfim_big(CgbArgs a) {
       if (vb == 0) {
         const int G = (int)gridDim.x;
         if (t < G) {
-          const long long t0 = wall_clock64();
-          for (;;) {
-            const bool ok0 = granule_try_get(PE + 2 * ((int64_t)t * 2), epoch, g0);
-            const bool ok1 = granule_try_get(PE + 2 * ((int64_t)t * 2 + 1), epoch, g1);
-            if (ok0 && ok1) break;
-            __builtin_amdgcn_s_sleep(1);
-            if (wall_clock64() - t0 > CGB_TIMEOUT_TICKS) {
-              sm.fail = 1.0;
-              break;
-            }
-          }
+          gran_u64* gp[2] = {PE + 2 * ((int64_t)t * 2), PE + 2 * ((int64_t)t * 2 + 1)};
+          const bool on[2] = {true, true};
+          double gv[2];
+          if (!granule_wait_all(gp, on, epoch, gv, wall_clock64(), DSEA_GRANULE_TIMEOUT_TICKS)) sm.fail = 1.0;
+          g0 = gv[0];
+          g1 = gv[1];
         }
         g0 = wave_sum(g0);
         g1 = wave_sum(g1);
@@ -541,16 +511,7 @@ int launch_cg_persist_tfim_big(const OpDesc& op, const double* shift, const doub
   const int ntiles = (int)(n / CGB_TILE);
   const int nvb = ntiles > 256 ? 2 : 1;
   const int G = ntiles / nvb;
-  {
-    static thread_local int cu_dev = -1, cu_count = 0;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return -2;
-    if (dev != cu_dev) {
-      if (hipDeviceGetAttribute(&cu_count, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return -2;
-      cu_dev = dev;
-    }
-    if (G > cu_count) return -1;     // all workgroups must be resident together: one per compute unit
-  }
+  if (const int rc = persist_resident(G)) return rc;     // (<= 512 threads, ~33 KB of static LDS: one per CU always fits)
   if (hipMemsetAsync(comm, 0, cg_persist_tfim_big_comm_bytes(n), st) != hipSuccess) return -2;
   CgbArgs a;
   a.tf = op.tfim;

@@ -196,9 +196,12 @@ __device__ __forceinline__ double sum_partials_block(const double* __restrict__ 
 // 32-bit epoch of the exchange; a reader accepts the value when both words carry the epoch it waits for.  Relaxed
 // agent-scope stores and polls, no fences, no separate flags (cdna_hip_programming.md Guideline 16, form R2); the
 // buffers are zeroed by the launcher before every launch (epoch 0 = "nothing yet").
+// Every wait of a persistent kernel goes through the bounded waits below: only this header reads a granule.
 // ------------------------------------------------------------------------------------------
 typedef __attribute__((address_space(1))) unsigned long long gran_u64;
 #define DSEA_GRANULE_TIMEOUT_TICKS 300000000ll /* 3 s of the 100 MHz wall clock: a lost peer must not hang the GPU */
+#define DSEA_GRANULE_SHORT_TIMEOUT_TICKS 30000000ll /* 0.3 s, k_lanczos_persist: a healthy step takes ~10 us, a lost peer
+                                                       must not hold up to 64 CUs for seconds before the host falls back */
 __device__ __forceinline__ void granule_put(gran_u64* g, unsigned epoch, double v) {
   const unsigned long long b = (unsigned long long)__double_as_longlong(v);
   const unsigned long long tag = (unsigned long long)epoch << 32;
@@ -217,6 +220,46 @@ __device__ __forceinline__ unsigned granule_epoch(gran_u64* g) {
   const unsigned long long hi = __hip_atomic_load(g + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   const unsigned a = (unsigned)(lo >> 32), b = (unsigned)(hi >> 32);
   return a < b ? a : b;
+}
+
+// Bounded waits.  One pass polls each granule once; a failed pass is followed by s_sleep(1) and only then by the
+// comparison of the wall clock with t0 + budget (longer back-off and sparser polls measured slower:
+// docs/design/04-kernels.md).  All return false on timeout -- a peer is lost, the caller raises its fail flag -- and
+// several waits may share one t0.
+// N granules of one epoch, polled by one thread: slots with on[m] false are not read and give 0.0.
+template <int N>
+__device__ __forceinline__ bool granule_wait_all(gran_u64* (&g)[N], const bool (&on)[N], unsigned epoch, double (&v)[N],
+                                                 long long t0, long long budget) {
+#pragma unroll
+  for (int m = 0; m < N; ++m) v[m] = 0.0;
+  bool ok;
+  do {
+    ok = true;
+#pragma unroll
+    for (int m = 0; m < N; ++m)
+      if (on[m]) ok &= granule_try_get(g[m], epoch, v[m]);
+    if (!ok) {
+      __builtin_amdgcn_s_sleep(1);
+      if (wall_clock64() - t0 > budget) break;
+    }
+  } while (!ok);
+  return ok;
+}
+__device__ __forceinline__ bool granule_wait(gran_u64* g, unsigned epoch, double& v, long long t0, long long budget) {
+  gran_u64* gs[1] = {g};
+  const bool on[1] = {true};
+  double vs[1];
+  const bool ok = granule_wait_all<1>(gs, on, epoch, vs, t0, budget);
+  v = vs[0];
+  return ok;
+}
+// until the granule carries `epoch` or a later one (its value is not read)
+__device__ __forceinline__ bool granule_wait_epoch(gran_u64* g, unsigned epoch, long long t0, long long budget) {
+  for (;;) {
+    if (granule_epoch(g) >= epoch) return true;
+    __builtin_amdgcn_s_sleep(1);
+    if (wall_clock64() - t0 > budget) return false;
+  }
 }
 
 }  // namespace dsea

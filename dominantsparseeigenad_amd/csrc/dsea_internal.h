@@ -69,6 +69,18 @@ struct Stencil3Params {
   const double* halo_lo;
   const double* halo_hi;
 };
+// the operators' row formulas, shared by the streaming and the persistent kernels (bit-compared between them)
+__device__ __forceinline__ double tfim_diag(const TfimParams& p, int64_t i, uint64_t maskL) {
+  const uint64_t gi = (uint64_t)(p.row_offset + i);
+  const uint64_t rot = ((gi << 1) | (gi >> (p.L - 1))) & maskL;
+  const int pop = __popcll(gi ^ rot);
+  return p.diag_scale * (double)(-(p.L - 2 * pop));
+}
+// 3-point stencil + diagonal (schrodinger1D.py:18-27)
+__device__ __forceinline__ double stencil_row(double coef, double Vi, double xi, double up, double dn) {
+  const double lap = __dadd_rn(__dadd_rn(__dmul_rn(-2.0, xi), up), dn);
+  return __dadd_rn(__dmul_rn(coef, lap), __dmul_rn(Vi, xi));
+}
 struct DenseParams {
   int64_t n, lda;
   const double* A;  // row-major n x n
@@ -270,6 +282,13 @@ void launch_gmres_givens(double* H, int ldh, int j, double* cs, double* sn, doub
 void launch_gmres_solve(const double* H, int ldh, int m, const double* g, const double* state, double* y,
                         hipStream_t st);
 size_t persist_comm_bytes(int64_t n);
+// Residency gate of the persistent single-launch kernels, whose workgroups wait on each other: all G must be resident
+// at once.  device_cu_count(): CUs of the current device, cached per host thread, -1 on a HIP error.  persist_resident():
+// 0 if G workgroups fit one per CU -- and, when `kernel` is given, the occupancy query admits one workgroup of `threads`
+// threads and `dyn_lds` bytes of dynamic LDS per CU --, -1 if not (the caller takes the multi-launch kernels), -2 on a
+// HIP error.
+int device_cu_count();
+int persist_resident(int G, const void* kernel = nullptr, int threads = 0, size_t dyn_lds = 0);
 int launch_cg_persist(const OpDesc& op, const double* shift, const double* b, double* x, double* state, double eps,
                       int64_t maxiter, void* comm, int ppt_override, hipStream_t st, int lose_peer = 0);
 int launch_spmv(const OpDesc& op, const double* x, double* y, const double* shift, const double* skip,

@@ -1248,13 +1248,6 @@ __global__ __launch_bounds__(256) void k_scale_store_fused(const double* __restr
   }
 }
 
-__device__ __forceinline__ double tfim_diag(const TfimParams& p, int64_t i, uint64_t maskL) {
-  const uint64_t gi = (uint64_t)(p.row_offset + i);
-  const uint64_t rot = ((gi << 1) | (gi >> (p.L - 1))) & maskL;
-  const int pop = __popcll(gi ^ rot);
-  return p.diag_scale * (double)(-(p.L - 2 * pop));
-}
-
 template <int T, bool FUSED>
 __global__ __launch_bounds__(256) void k_spmv_tfim(TfimParams p, const double* __restrict__ x,
                                                    double* __restrict__ y,
@@ -2107,15 +2100,11 @@ __global__ __launch_bounds__(256) void k_csr_sddmm(CsrParams p, const double* __
   }
 }
 
-// 3-point stencil + diagonal (schrodinger1D.py:18-27).
+// 3-point stencil + diagonal (stencil_row, schrodinger1D.py:18-27).
 // Geometry ("canonical tile"): a block of 256 threads works on tiles of 512 consecutive rows, thread t on the row
 // pair (2t, 2t+1) of the tile -- 16-byte accesses; the two outer neighbours are scalar loads (L1 hits).  With
 // one tile per block (n <= 2^21, see ew_blocks) P[tile] is the x.y partial of exactly that tile: the geometry
 // the persistent single-launch CG (k_cg_persist_stencil) reproduces bit for bit.
-__device__ __forceinline__ double stencil_row(double coef, double Vi, double xi, double up, double dn) {
-  const double lap = __dadd_rn(__dadd_rn(__dmul_rn(-2.0, xi), up), dn);
-  return __dadd_rn(__dmul_rn(coef, lap), __dmul_rn(Vi, xi));
-}
 
 template <bool FUSED>
 __global__ __launch_bounds__(256) void k_spmv_stencil3(Stencil3Params p, const double* __restrict__ x,
@@ -2299,16 +2288,6 @@ __global__ __launch_bounds__(256) void k_symv_reduce(SymDenseParams p, const dou
 // (tests/test_gpu_persistent.py) and identical on every workgroup, so all take the same exit.
 // Reference: CG.py:24-41 with A' = A - shift (CG.py:120).
 // ------------------------------------------------------------------------------------------
-typedef gran_u64 gu64;
-#define DSEA_RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
-#ifndef DSEA_PERSIST_SLEEP
-#define DSEA_PERSIST_SLEEP 1
-#endif
-#define DSEA_PERSIST_TIMEOUT_TICKS DSEA_GRANULE_TIMEOUT_TICKS
-
-__device__ __forceinline__ void put_f64(gu64* g, unsigned epoch, double v) { granule_put(g, epoch, v); }
-__device__ __forceinline__ bool try_get_f64(gu64* g, unsigned epoch, double& v) { return granule_try_get(g, epoch, v); }
-
 struct PersistArgs {
   Stencil3Params p;
   const double* shift;
@@ -2333,9 +2312,9 @@ struct PersistSm {
 // thread 256 / 320 fetch the neighbour workgroups' edge values when `edges`.  Returns the total in every thread;
 // el / er receive the edges.  `fail` is set (in every thread) if a peer did not show up in time.
 template <int NVB>
-__device__ __forceinline__ double persist_gather(gu64* base, int count, unsigned epoch, bool two_acc, gu64* edge_base,
-                                                 bool edges, int g, int G, PersistSm* sm, double& el, double& er,
-                                                 bool& fail) {
+__device__ __forceinline__ double persist_gather(gran_u64* base, int count, unsigned epoch, bool two_acc,
+                                                 gran_u64* edge_base, bool edges, int g, int G, PersistSm* sm, double& el,
+                                                 double& er, bool& fail) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const long long t0 = wall_clock64();
   // edge pollers: two lanes of waves that do not poll tile partials (NVB >= 2), else two lanes of the polling waves
@@ -2345,35 +2324,22 @@ __device__ __forceinline__ double persist_gather(gu64* base, int count, unsigned
     const int peer = left ? g - 1 : g + 1;
     double v = 0.0;
     if (peer >= 0 && peer < G) {
-      gu64* src = edge_base + (peer * 2 + (left ? 1 : 0)) * 2;
-      bool ok;
-      do {
-        ok = try_get_f64(src, epoch, v);
-        if (!ok) {
-          __builtin_amdgcn_s_sleep(DSEA_PERSIST_SLEEP);
-          if (wall_clock64() - t0 > DSEA_PERSIST_TIMEOUT_TICKS) break;
-        }
-      } while (!ok);
-      if (!ok) sm->bcast[3] = 1.0;
+      gran_u64* src = edge_base + (peer * 2 + (left ? 1 : 0)) * 2;   // left neighbour's LAST row / right one's FIRST
+      if (!granule_wait(src, epoch, v, t0, DSEA_GRANULE_TIMEOUT_TICKS)) sm->bcast[3] = 1.0;
     }
     sm->bcast[left ? 1 : 2] = v;
   }
   if (tid < 256) {
-    double pv[4] = {0.0, 0.0, 0.0, 0.0};
-    bool ok;
-    do {
-      ok = true;
+    gran_u64* src[4];
+    bool on[4];
+    double pv[4];
 #pragma unroll
-      for (int m = 0; m < 4; ++m) {
-        const int idx = tid + 256 * m;
-        if (idx < count) ok &= try_get_f64(base + 2 * idx, epoch, pv[m]);
-      }
-      if (!ok) {
-        __builtin_amdgcn_s_sleep(DSEA_PERSIST_SLEEP);
-        if (wall_clock64() - t0 > DSEA_PERSIST_TIMEOUT_TICKS) break;
-      }
-    } while (!ok);
-    if (!ok) sm->bcast[3] = 1.0;
+    for (int m = 0; m < 4; ++m) {
+      const int idx = tid + 256 * m;
+      src[m] = base + 2 * idx;
+      on[m] = idx < count;
+    }
+    if (!granule_wait_all(src, on, epoch, pv, t0, DSEA_GRANULE_TIMEOUT_TICKS)) sm->bcast[3] = 1.0;
     double acc;
     if (two_acc) {
       const double a0 = (0.0 + pv[0]) + pv[2], a1 = (0.0 + pv[1]) + pv[3];
@@ -2388,16 +2354,8 @@ __device__ __forceinline__ double persist_gather(gu64* base, int count, unsigned
     const int peer = left ? g - 1 : g + 1;
     double v = 0.0;
     if (peer >= 0 && peer < G) {
-      gu64* src = edge_base + (peer * 2 + (left ? 1 : 0)) * 2;   // left neighbour's LAST row / right one's FIRST
-      bool ok;
-      do {
-        ok = try_get_f64(src, epoch, v);
-        if (!ok) {
-          __builtin_amdgcn_s_sleep(DSEA_PERSIST_SLEEP);
-          if (wall_clock64() - t0 > DSEA_PERSIST_TIMEOUT_TICKS) break;
-        }
-      } while (!ok);
-      if (!ok) sm->bcast[3] = 1.0;
+      gran_u64* src = edge_base + (peer * 2 + (left ? 1 : 0)) * 2;   // left neighbour's LAST row / right one's FIRST
+      if (!granule_wait(src, epoch, v, t0, DSEA_GRANULE_TIMEOUT_TICKS)) sm->bcast[3] = 1.0;
     }
     sm->bcast[left ? 1 : 2] = v;
   }
@@ -2422,15 +2380,15 @@ __global__ __launch_bounds__(256 * NVB) void k_cg_persist_stencil(PersistArgs a)
   const int g = blockIdx.x, G = gridDim.x;
   if (a.lose_peer && G > 1 && g == G - 1) return;
   const int64_t n = a.p.n;
-  gu64* commA = (gu64*)a.comm;
-  gu64* commC = commA + 2 * (int64_t)a.ntiles;
-  gu64* commE = commC + 2 * (int64_t)a.ntiles;
+  gran_u64* commA = (gran_u64*)a.comm;
+  gran_u64* commC = commA + 2 * (int64_t)a.ntiles;
+  gran_u64* commE = commC + 2 * (int64_t)a.ntiles;
   // The start-up exchange of the x edges has its OWN slots: that phase waits for the two neighbours only, so a fast
   // workgroup may be a whole phase ahead of a neighbour that has not read its x edge yet -- were the r edges of the
   // next phase written to the same granules, that neighbour would wait for an epoch that is gone (seen as a timeout
   // when the pollers' back-off sleep was lengthened in an experiment).  All later phases are separated by an
   // all-to-all dependency (every workgroup needs every tile partial), which is what makes slot reuse safe there.
-  gu64* commX = commE + 4 * (int64_t)gridDim.x;
+  gran_u64* commX = commE + 4 * (int64_t)gridDim.x;
   const double coef = a.p.coef;
   const bool has_shift = a.shift != nullptr;
   const double s = has_shift ? a.shift[0] : 0.0;
@@ -2476,7 +2434,7 @@ __global__ __launch_bounds__(256 * NVB) void k_cg_persist_stencil(PersistArgs a)
     __syncthreads();
   };
   // per-tile partial sum_t (a.x b.x + a.y b.y) of sub-round q published under `epoch` in `dst`
-  auto publish_tiles = [&](gu64* dst, unsigned epoch, const double2* u, const double2* w) {
+  auto publish_tiles = [&](gran_u64* dst, unsigned epoch, const double2* u, const double2* w) {
 #pragma unroll
     for (int q = 0; q < PPT; ++q) {
       double acc = 0.0;
@@ -2491,22 +2449,22 @@ __global__ __launch_bounds__(256 * NVB) void k_cg_persist_stencil(PersistArgs a)
       for (int q = 0; q < PPT; ++q)
         if (tile[q] < a.ntiles) {
           const double tot = ((sm->red[q][4 * vb] + sm->red[q][4 * vb + 1]) + sm->red[q][4 * vb + 2]) + sm->red[q][4 * vb + 3];
-          put_f64(dst + 2 * tile[q], epoch, tot);
+          granule_put(dst + 2 * tile[q], epoch, tot);
         }
     }
     __syncthreads();
   };
   auto publish_edges = [&](unsigned epoch, const double2* w) {
-    if (tid == 0) put_f64(commE + (g * 2 + 0) * 2, epoch, w[0].x);
-    if (tid == 256 * NVB - 1) put_f64(commE + (g * 2 + 1) * 2, epoch, w[PPT - 1].y);
+    if (tid == 0) granule_put(commE + (g * 2 + 0) * 2, epoch, w[0].x);
+    if (tid == 256 * NVB - 1) granule_put(commE + (g * 2 + 1) * 2, epoch, w[PPT - 1].y);
   };
 
   double el, er;
   bool fail;
   unsigned epoch = 1;
   // ---- r = b - A' x0 ; d = r ; rr = r.r                                          (CG.py:26-30)
-  if (tid == 0) put_f64(commX + (g * 2 + 0) * 2, epoch, xv[0].x);
-  if (tid == 256 * NVB - 1) put_f64(commX + (g * 2 + 1) * 2, epoch, xv[PPT - 1].y);
+  if (tid == 0) granule_put(commX + (g * 2 + 0) * 2, epoch, xv[0].x);
+  if (tid == 256 * NVB - 1) granule_put(commX + (g * 2 + 1) * 2, epoch, xv[PPT - 1].y);
   {
     double dummy = persist_gather<NVB>(commA, 0, epoch, true, commX, true, g, G, sm, el, er, fail);
     (void)dummy;
@@ -2616,8 +2574,8 @@ __global__ __launch_bounds__(256 * NVB) void k_cg_persist_stencil_merged(Persist
   const int g = blockIdx.x, G = gridDim.x;
   if (a.lose_peer && G > 1 && g == G - 1) return;
   const int64_t n = a.p.n;
-  gu64* commS = (gu64*)a.comm;                       // [2 parities][G][4 values][2 granules]
-  gu64* commX = commS + 16 * (int64_t)G;             // x edges of the start-up: [G][2][2]
+  gran_u64* commS = (gran_u64*)a.comm;                       // [2 parities][G][4 values][2 granules]
+  gran_u64* commX = commS + 16 * (int64_t)G;             // x edges of the start-up: [G][2][2]
   const double coef = a.p.coef;
   const bool has_shift = a.shift != nullptr;
   const double sh = has_shift ? a.shift[0] : 0.0;
@@ -2662,28 +2620,17 @@ __global__ __launch_bounds__(256 * NVB) void k_cg_persist_stencil_merged(Persist
     }
     __syncthreads();
   };
-  // bounded spin on one value
-  auto wait_f64 = [&](gu64* src, unsigned epoch, double& v, long long t0) -> bool {
-    bool ok;
-    do {
-      ok = try_get_f64(src, epoch, v);
-      if (!ok) {
-        __builtin_amdgcn_s_sleep(DSEA_PERSIST_SLEEP);
-        if (wall_clock64() - t0 > DSEA_PERSIST_TIMEOUT_TICKS) break;
-      }
-    } while (!ok);
-    return ok;
-  };
 
   // ---- start-up: x edges to the two neighbours (slots of their own), r = b - A' x0           (CG.py:26-27)
-  if (tid == 0) put_f64(commX + (g * 2 + 0) * 2, 1u, xv[0].x);
-  if (tid == 256 * NVB - 1) put_f64(commX + (g * 2 + 1) * 2, 1u, xv[PPT - 1].y);
+  if (tid == 0) granule_put(commX + (g * 2 + 0) * 2, 1u, xv[0].x);
+  if (tid == 256 * NVB - 1) granule_put(commX + (g * 2 + 1) * 2, 1u, xv[PPT - 1].y);
   if (tid == 0 || tid == 64) {
     const bool left = tid == 0;
     const int peer = left ? g - 1 : g + 1;
     double v = 0.0;
     if (peer >= 0 && peer < G) {
-      if (!wait_f64(commX + (peer * 2 + (left ? 1 : 0)) * 2, 1u, v, wall_clock64())) sm->bcast[4] = 1.0;
+      if (!granule_wait(commX + (peer * 2 + (left ? 1 : 0)) * 2, 1u, v, wall_clock64(), DSEA_GRANULE_TIMEOUT_TICKS))
+        sm->bcast[4] = 1.0;
     }
     sm->bcast[left ? 2 : 3] = v;
   }
@@ -2724,7 +2671,7 @@ __global__ __launch_bounds__(256 * NVB) void k_cg_persist_stencil_merged(Persist
       sm->red[1][wave] = da;
     }
     __syncthreads();
-    gu64* slot = commS + (int64_t)(epoch & 1u) * 8 * G;
+    gran_u64* slot = commS + (int64_t)(epoch & 1u) * 8 * G;
     if (tid < 4) {
       double v;
       if (tid < 2) {
@@ -2735,7 +2682,7 @@ __global__ __launch_bounds__(256 * NVB) void k_cg_persist_stencil_merged(Persist
       } else {
         v = dsm[2 + ROWS - 1];     // last row
       }
-      put_f64(slot + ((int64_t)g * 4 + tid) * 2, epoch, v);
+      granule_put(slot + ((int64_t)g * 4 + tid) * 2, epoch, v);
     }
     // gather all 4 G values (threads 0..255, up to four each)
     if (tid < 256) {
@@ -2746,7 +2693,7 @@ __global__ __launch_bounds__(256 * NVB) void k_cg_persist_stencil_merged(Persist
         const int idx = tid + 256 * m;
         if (idx < 4 * G) {
           double v = 0.0;
-          ok &= wait_f64(slot + (int64_t)idx * 2, epoch, v, t0);
+          ok &= granule_wait(slot + (int64_t)idx * 2, epoch, v, t0, DSEA_GRANULE_TIMEOUT_TICKS);
           sm->vals[idx] = v;
         }
       }
@@ -3523,6 +3470,33 @@ void launch_finalize_slot(const double* P, int count, double* out, const double*
   hipLaunchKernelGGL(k_cg_finalize_slot, dim3(1), dim3(256), 0, st, P, count, out, skip);
 }
 
+// The persistent kernels' workgroups spin on each other: all G must be resident at the same time.  At most one
+// workgroup per CU of THIS device (256 on an MI355X in SPX mode, 32 per partition in CPX mode) guarantees that on an
+// otherwise idle device when the kernel's registers and LDS admit one workgroup per CU; a launcher that cannot show
+// that from its geometry passes the kernel for the occupancy query.  (A device shared with other work is caught by the
+// bounded waits -> DSEA_ERR_TIMEOUT.)
+int device_cu_count() {
+  static thread_local int cu_dev = -1, cu_count = 0;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return -1;
+  if (dev != cu_dev) {
+    if (hipDeviceGetAttribute(&cu_count, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return -1;
+    cu_dev = dev;
+  }
+  return cu_count;
+}
+int persist_resident(int G, const void* kernel, int threads, size_t dyn_lds) {
+  const int cus = device_cu_count();
+  if (cus < 0) return -2;
+  if (G > cus) return -1;
+  if (kernel) {
+    int occ = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, threads, dyn_lds) != hipSuccess) return -2;
+    if (occ < 1) return -1;
+  }
+  return 0;
+}
+
 // Persistent CG (see k_cg_persist_stencil).  Returns 0 if launched, -1 if the problem is outside its envelope
 // (then the caller runs the streaming 3-launch form), -2 on a HIP error.  `comm` must hold persist_comm_bytes().
 size_t persist_comm_bytes(int64_t n) {
@@ -3562,20 +3536,8 @@ int launch_cg_persist(const OpDesc& op, const double* shift, const double* b, do
   if (G > 256) {
     return -1;
   }
-  {
-    // The workgroups spin on each other: all G must be resident at the same time.  One workgroup (<= 1024 threads,
-    // <= 70 KB of LDS) always fits a compute unit of its own, so G <= number of CUs of THIS device (256 on an MI355X in
-    // SPX mode, 32 per partition in CPX mode) guarantees co-residency on an otherwise idle device; beyond that the
-    // streaming form is used.  (A device shared with other work is caught by the bounded spins -> DSEA_ERR_TIMEOUT.)
-    static thread_local int cu_dev = -1, cu_count = 0;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return -2;
-    if (dev != cu_dev) {
-      if (hipDeviceGetAttribute(&cu_count, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return -2;
-      cu_dev = dev;
-    }
-    if (G > cu_count) return -1;
-  }
+  // one workgroup (<= 1024 threads, <= 70 KB of LDS) always fits a compute unit of its own: no occupancy query
+  if (const int rc = persist_resident(G)) return rc;
   const size_t cbytes = merged ? (size_t)(16 + 4) * G * sizeof(unsigned long long)
                                : (size_t)(4 * nt + 8 * G) * sizeof(unsigned long long);
   if (hipMemsetAsync(comm, 0, cbytes, st) != hipSuccess) return -2;

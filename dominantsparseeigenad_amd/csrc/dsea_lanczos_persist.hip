@@ -43,35 +43,10 @@
 
 namespace dsea {
 
-namespace {
-typedef gran_u64 lzp_gu64;
-#define LZP_TIMEOUT_TICKS 30000000ll   /* 0.3 s of the 100 MHz wall clock: a healthy step takes ~10 us, a lost peer must not hold
-                                          up to 64 CUs for seconds before the host falls back to the multi-launch kernels */
 #define LZP_ROWS 128
 #define LZP_MAX_K 512
 #define LZP_MAX_G 64
 #define LZP_CACHE 112   // basis vectors whose own rows stay in LDS (112 KB of the CU's 160; a multiple of the chunk of 4)
-
-// spin until the granule carries `epoch`; false on timeout
-__device__ __forceinline__ bool lzp_wait(lzp_gu64* g, unsigned epoch, double& v, long long t0) {
-  while (!granule_try_get(g, epoch, v)) {
-    __builtin_amdgcn_s_sleep(1);
-    if (wall_clock64() - t0 > LZP_TIMEOUT_TICKS) return false;
-  }
-  return true;
-}
-
-__device__ __forceinline__ double lzp_stencil_row(double coef, double Vi, double xi, double up, double dn) {
-  const double lap = __dadd_rn(__dadd_rn(__dmul_rn(-2.0, xi), up), dn);
-  return __dadd_rn(__dmul_rn(coef, lap), __dmul_rn(Vi, xi));
-}
-__device__ __forceinline__ double lzp_tfim_diag(const TfimParams& p, int64_t i, uint64_t maskL) {
-  const uint64_t gi = (uint64_t)(p.row_offset + i);
-  const uint64_t rot = ((gi << 1) | (gi >> (p.L - 1))) & maskL;
-  const int pop = __popcll(gi ^ rot);
-  return p.diag_scale * (double)(-(p.L - 2 * pop));
-}
-}  // namespace
 
 struct LzpArgs {
   int opk;  // OP_TFIM / OP_STENCIL3
@@ -112,9 +87,9 @@ __global__ __launch_bounds__(1024) void k_lanczos_persist(LzpArgs a) {
   const int nlocal = Lbits < 7 ? Lbits : 7;     // bit flips inside the 128-row slab
   const int nfar = tfim ? Lbits - nlocal : 0;   // partner workgroups g ^ (1 << b)
   const uint64_t maskL = (Lbits >= 64) ? ~0ull : ((1ull << Lbits) - 1ull);
-  lzp_gu64* E2 = (lzp_gu64*)a.comm;
-  lzp_gu64* E3 = E2 + (int64_t)2 * G * a.kslots;
-  lzp_gu64* EA = E3 + (int64_t)2 * G * (1 + LZP_ROWS);
+  gran_u64* E2 = (gran_u64*)a.comm;
+  gran_u64* E3 = E2 + (int64_t)2 * G * a.kslots;
+  gran_u64* EA = E3 + (int64_t)2 * G * (1 + LZP_ROWS);
   if (tid == 0) s_b[1] = 0.0;
   if (tid < LZP_ROWS) s_q[tid] = 0.0;
   double scale = 0.0;                           // running max |alpha|, |beta| (same in every thread of every workgroup)
@@ -134,14 +109,15 @@ __global__ __launch_bounds__(1024) void k_lanczos_persist(LzpArgs a) {
     // ---- E3: publish ||r||^2 partial and the rows of r; gather all partials (+ the partner rows / edge rows)
     if (wv == 0) {
       const double acc = wave_sum(fma(rv.x, rv.x, rv.y * rv.y));
-      lzp_gu64* mine = E3 + (int64_t)g * (1 + LZP_ROWS) * 2;
+      gran_u64* mine = E3 + (int64_t)g * (1 + LZP_ROWS) * 2;
       granule_put(mine + (1 + 2 * lane) * 2, epoch, rv.x);
       granule_put(mine + (2 + 2 * lane) * 2, epoch, rv.y);
       if (lane == 0) granule_put(mine, epoch, acc);
     } else if (wv == 1) {
       // the G slab partials, one per lane, summed by the wave itself in its fixed order (identical in every workgroup)
       double v = 0.0;
-      if (lane < G && !lzp_wait(E3 + (int64_t)lane * (1 + LZP_ROWS) * 2, epoch, v, t0)) s_b[1] = 1.0;
+      if (lane < G && !granule_wait(E3 + (int64_t)lane * (1 + LZP_ROWS) * 2, epoch, v, t0, DSEA_GRANULE_SHORT_TIMEOUT_TICKS))
+        s_b[1] = 1.0;
       v = wave_sum(v);
       if (lane == 0) s_b[0] = v;
     }
@@ -150,7 +126,9 @@ __global__ __launch_bounds__(1024) void k_lanczos_persist(LzpArgs a) {
       if (t >= 0 && t < nfar * LZP_ROWS) {
         const int b = t >> 7, rr = t & 127;
         double v = 0.0;
-        if (!lzp_wait(E3 + ((int64_t)(g ^ (1 << b)) * (1 + LZP_ROWS) + 1 + rr) * 2, epoch, v, t0)) s_b[1] = 1.0;
+        if (!granule_wait(E3 + ((int64_t)(g ^ (1 << b)) * (1 + LZP_ROWS) + 1 + rr) * 2, epoch, v, t0,
+                          DSEA_GRANULE_SHORT_TIMEOUT_TICKS))
+          s_b[1] = 1.0;
         s_nb[b][rr] = v;
       }
     } else if (tid == 128 || tid == 192) {
@@ -158,7 +136,9 @@ __global__ __launch_bounds__(1024) void k_lanczos_persist(LzpArgs a) {
       const int peer = left ? g - 1 : g + 1;
       double v = 0.0;
       if (peer >= 0 && peer < G)
-        if (!lzp_wait(E3 + ((int64_t)peer * (1 + LZP_ROWS) + 1 + (left ? LZP_ROWS - 1 : 0)) * 2, epoch, v, t0)) s_b[1] = 1.0;
+        if (!granule_wait(E3 + ((int64_t)peer * (1 + LZP_ROWS) + 1 + (left ? LZP_ROWS - 1 : 0)) * 2, epoch, v, t0,
+                          DSEA_GRANULE_SHORT_TIMEOUT_TICKS))
+          s_b[1] = 1.0;
       s_b[left ? 2 : 3] = v;
     }
     __syncthreads();
@@ -212,14 +192,14 @@ __global__ __launch_bounds__(1024) void k_lanczos_persist(LzpArgs a) {
           s0 += f0 / beta;
           s1 += f1 / beta;
         }
-        if (row < n) uu.x = __dsub_rn(__dmul_rn(x0, lzp_tfim_diag(a.tf, row, maskL)), __dmul_rn(gpar, s0));
-        if (row + 1 < n) uu.y = __dsub_rn(__dmul_rn(x1, lzp_tfim_diag(a.tf, row + 1, maskL)), __dmul_rn(gpar, s1));
+        if (row < n) uu.x = __dsub_rn(__dmul_rn(x0, tfim_diag(a.tf, row, maskL)), __dmul_rn(gpar, s0));
+        if (row + 1 < n) uu.y = __dsub_rn(__dmul_rn(x1, tfim_diag(a.tf, row + 1, maskL)), __dmul_rn(gpar, s1));
       } else {
         const double2 Vv = ld2<true>(a.st.V, row, n);
         const double dn = lane > 0 ? s_q[2 * lane - 1] : s_b[2] / beta;                 // x[row - 1]
         const double up = lane < 63 ? s_q[2 * lane + 2] : s_b[3] / beta;                // x[row + 2]
-        if (row < n) uu.x = lzp_stencil_row(a.st.coef, Vv.x, x0, (row + 1 < n) ? x1 : 0.0, dn);
-        if (row + 1 < n) uu.y = lzp_stencil_row(a.st.coef, Vv.y, x1, (row + 2 < n) ? up : 0.0, x0);
+        if (row < n) uu.x = stencil_row(a.st.coef, Vv.x, x0, (row + 1 < n) ? x1 : 0.0, dn);
+        if (row + 1 < n) uu.y = stencil_row(a.st.coef, Vv.y, x1, (row + 2 < n) ? up : 0.0, x0);
       }
       // ---- EA: alpha_s = q_s . u  (Lanczos.py:72): slab partial published, everybody's gathered below
       const double pa = wave_sum(fma(x0, uu.x, x1 * uu.y));
@@ -228,7 +208,7 @@ __global__ __launch_bounds__(1024) void k_lanczos_persist(LzpArgs a) {
       s_u[2 * lane + 1] = uu.y;
     } else if (wv == 1) {
       double v = 0.0;
-      if (lane < G && !lzp_wait(EA + (int64_t)lane * 2, epoch, v, t0)) s_b[1] = 1.0;
+      if (lane < G && !granule_wait(EA + (int64_t)lane * 2, epoch, v, t0, DSEA_GRANULE_SHORT_TIMEOUT_TICKS)) s_b[1] = 1.0;
       v = wave_sum(v);
       if (lane == 0) s_alpha = v;
     }
@@ -282,23 +262,15 @@ __global__ __launch_bounds__(1024) void k_lanczos_persist(LzpArgs a) {
         const int w0 = part * Gp, w1 = (w0 + Gp < G) ? w0 + Gp : G;
         const long long t1 = wall_clock64();
         for (int wb = w0; wb < w1; wb += 8) {
+          gran_u64* gp[8];
+          bool on[8];
           double pv[8];
-          bool ok;
-          do {
-            ok = true;
 #pragma unroll
-            for (int m = 0; m < 8; ++m) {
-              pv[m] = 0.0;
-              if (wb + m < w1) ok &= granule_try_get(E2 + ((int64_t)(wb + m) * a.kslots + j) * 2, epoch, pv[m]);
-            }
-            if (!ok) {
-              __builtin_amdgcn_s_sleep(1);
-              if (wall_clock64() - t1 > LZP_TIMEOUT_TICKS) {
-                s_b[1] = 1.0;
-                break;
-              }
-            }
-          } while (!ok);
+          for (int m = 0; m < 8; ++m) {
+            gp[m] = E2 + ((int64_t)(wb + m) * a.kslots + j) * 2;
+            on[m] = wb + m < w1;
+          }
+          if (!granule_wait_all(gp, on, epoch, pv, t1, DSEA_GRANULE_SHORT_TIMEOUT_TICKS)) s_b[1] = 1.0;
 #pragma unroll
           for (int m = 0; m < 8; ++m) acc += pv[m];      // absent ones are 0
         }
@@ -384,20 +356,7 @@ int launch_lanczos_persist(const OpDesc& op, int k, const double* q0, double* Q,
     // all G workgroups must be resident together: 1024 threads and ~153 KB of static LDS each (s_cache 112 KB, s_part 16 KB,
     // s_red 8 KB, s_c / s_cpart 8 KB, s_nb 6 KB ...), i.e. one per CU and nothing else holding LDS there -- the occupancy
     // query below refuses the form otherwise (the host then takes the multi-launch kernels at once instead of timing out)
-    static thread_local int cu_dev = -1, cu_count = 0;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return -2;
-    if (dev != cu_dev) {
-      if (hipDeviceGetAttribute(&cu_count, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return -2;
-      cu_dev = dev;
-    }
-    if (G > cu_count) return -1;
-    static thread_local int occ_dev = -1, occ = 0;
-    if (dev != occ_dev) {
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_lanczos_persist, 1024, 0) != hipSuccess) return -2;
-      occ_dev = dev;
-    }
-    if (occ < 1) return -1;
+    if (const int rc = persist_resident(G, reinterpret_cast<const void*>(k_lanczos_persist), 1024, 0)) return rc;
   }
   if (hipMemsetAsync(comm, 0, lanczos_persist_comm_bytes(n, k), st) != hipSuccess) return -2;
   LzpArgs a;

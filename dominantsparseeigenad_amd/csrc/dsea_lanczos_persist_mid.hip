@@ -42,9 +42,6 @@
 
 namespace dsea {
 
-namespace {
-typedef gran_u64 lzm_gu64;
-#define LZM_TIMEOUT_TICKS DSEA_GRANULE_TIMEOUT_TICKS
 #ifndef LZM_WAVES
 #define LZM_WAVES 4               /* one wave per SIMD: each may use the full 512 registers (256 VGPR + 256 AGPR) */
 #endif
@@ -68,34 +65,6 @@ typedef gran_u64 lzm_gu64;
 #endif
 //                  /* register-cache slots per wave (one slot = this wave's copy of a slab of one vector) */
 #define LZM_LDS_BYTES 163840      /* 160 KiB per CU */
-
-__device__ __forceinline__ double lzm_stencil_row(double coef, double Vi, double xi, double up, double dn) {
-  const double lap = __dadd_rn(__dadd_rn(__dmul_rn(-2.0, xi), up), dn);
-  return __dadd_rn(__dmul_rn(coef, lap), __dmul_rn(Vi, xi));
-}
-
-// one lane's records of the workgroups lane, lane + 64, lane + 128, lane + 192 (NF doubles each): poll until every one
-// carries `epoch`; absent workgroups (>= G) read as zeros
-template <int NF>
-__device__ __forceinline__ bool lzm_poll_records(lzm_gu64* buf, int G, int lane, unsigned epoch, double (&v)[4][NF],
-                                                 long long t0) {
-  for (;;) {
-    bool ok = true;
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-      const int gg = lane + 64 * m;
-#pragma unroll
-      for (int f = 0; f < NF; ++f) {
-        v[m][f] = 0.0;
-        if (gg < G) ok &= granule_try_get(buf + ((int64_t)gg * NF + f) * 2, epoch, v[m][f]);
-      }
-    }
-    if (ok) return true;
-    __builtin_amdgcn_s_sleep(1);
-    if (wall_clock64() - t0 > LZM_TIMEOUT_TICKS) return false;
-  }
-}
-}  // namespace
 
 struct LzmArgs {
   Stencil3Params st;
@@ -139,9 +108,9 @@ __global__ __launch_bounds__(LZM_THREADS, LZM_WAVES / 4) void k_lanczos_persist_
   const int64_t n = a.n, base = (int64_t)g * R;
   const int Rg = (int)((n - base < R) ? (n - base) : R);          // rows of this slab (>= 1 by construction)
   const int NL = a.NL, M = NL + LZM_WAVES * LZM_NR;               // vectors j < M live on chip
-  lzm_gu64* X1 = (lzm_gu64*)a.comm;                               // [G][4]
-  lzm_gu64* X2a = X1 + (int64_t)G * 4 * 2;                        // [kslots][G]
-  lzm_gu64* X2b = X2a + (int64_t)a.kslots * G * 2;                // [kslots]
+  gran_u64* X1 = (gran_u64*)a.comm;                               // [G][4]
+  gran_u64* X2a = X1 + (int64_t)G * 4 * 2;                        // [kslots][G]
+  gran_u64* X2b = X2a + (int64_t)a.kslots * G * 2;                // [kslots]
   const double coef = a.st.coef;
 
   // lane-local rows: chunk c -> local rows lr = 128 c + 2 lane, lr + 1
@@ -209,8 +178,8 @@ __global__ __launch_bounds__(LZM_THREADS, LZM_WAVES / 4) void k_lanczos_persist_
         if (lr < R) {
           const double dn = s_r[lr + 1], up = s_r[lr + 4];      // rows lr - 1 and lr + 2
           const double2 Vv = *reinterpret_cast<const double2*>(s_V + lr);
-          if (vx[c]) y.x = lzm_stencil_row(coef, Vv.x, r[c].x, r[c].y, dn);
-          if (vy[c]) y.y = lzm_stencil_row(coef, Vv.y, r[c].y, up, r[c].x);
+          if (vx[c]) y.x = stencil_row(coef, Vv.x, r[c].x, r[c].y, dn);
+          if (vy[c]) y.y = stencil_row(coef, Vv.y, r[c].y, up, r[c].x);
           *reinterpret_cast<double2*>(s_y + lr) = y;
         }
         prr = fma(r[c].x, r[c].x, fma(r[c].y, r[c].y, prr));
@@ -230,17 +199,11 @@ __global__ __launch_bounds__(LZM_THREADS, LZM_WAVES / 4) void k_lanczos_persist_
       const int gg = lane + 64 * m;
       double rec[4] = {0.0, 0.0, 0.0, 0.0};
       if (gg < G) {
-        for (;;) {
-          bool ok = true;
+        gran_u64* gp[4];
+        const bool on[4] = {true, true, true, true};
 #pragma unroll
-          for (int f = 0; f < 4; ++f) ok &= granule_try_get(X1 + ((int64_t)gg * 4 + f) * 2, epoch, rec[f]);
-          if (ok) break;
-          __builtin_amdgcn_s_sleep(1);
-          if (wall_clock64() - t0 > LZM_TIMEOUT_TICKS) {
-            s_b[1] = 1.0;
-            break;
-          }
-        }
+        for (int f = 0; f < 4; ++f) gp[f] = X1 + ((int64_t)gg * 4 + f) * 2;
+        if (!granule_wait_all(gp, on, epoch, rec, t0, DSEA_GRANULE_TIMEOUT_TICKS)) s_b[1] = 1.0;
       }
       const double nxt = __shfl_down(rec[2], 1);
       double cross = (lane < 63 && gg + 1 < G) ? rec[3] * nxt : 0.0;
@@ -298,9 +261,9 @@ __global__ __launch_bounds__(LZM_THREADS, LZM_WAVES / 4) void k_lanczos_persist_
         double2 y = make_double2(0.0, 0.0);
         if (lr < R) y = *reinterpret_cast<const double2*>(s_y + lr);
         // the two edge rows of the slab see their neighbours' rows (zero halos in s_y): recomputed in full
-        if (lr == 0 && vx[c]) y.x = lzm_stencil_row(coef, s_V[0], r[c].x, vy[c] ? r[c].y : hr, hl);
-        if (lr == Rg - 1) y.x = lzm_stencil_row(coef, s_V[lr], r[c].x, hr, lr > 0 ? s_r[lr + 1] : hl);
-        if (lr + 1 == Rg - 1) y.y = lzm_stencil_row(coef, s_V[lr + 1], r[c].y, hr, r[c].x);
+        if (lr == 0 && vx[c]) y.x = stencil_row(coef, s_V[0], r[c].x, vy[c] ? r[c].y : hr, hl);
+        if (lr == Rg - 1) y.x = stencil_row(coef, s_V[lr], r[c].x, hr, lr > 0 ? s_r[lr + 1] : hl);
+        if (lr + 1 == Rg - 1) y.y = stencil_row(coef, s_V[lr + 1], r[c].y, hr, r[c].x);
         q[c].x = r[c].x / beta;
         q[c].y = r[c].y / beta;
         const double ux = y.x / beta, uy = y.y / beta;
@@ -440,22 +403,25 @@ __global__ __launch_bounds__(LZM_THREADS, LZM_WAVES / 4) void k_lanczos_persist_
     const int nvec = s + 2;
     for (int t = tid; t < nvec; t += LZM_THREADS) granule_put(X2a + ((int64_t)t * G + g) * 2, epoch, s_cpart[t]);
     for (int j = g + wv * G; j < nvec; j += LZM_WAVES * G) {          // the coefficients this workgroup owns
-      double v[4][1];
-      if (!lzm_poll_records<1>(X2a + (int64_t)j * G * 2, G, lane, epoch, v, t0)) s_b[1] = 1.0;
-      double tot = ((v[0][0] + v[1][0]) + v[2][0]) + v[3][0];
+      // lane takes the partials of workgroups lane, lane + 64, lane + 128, lane + 192 (absent ones read as zeros)
+      gran_u64* gp[4];
+      bool on[4];
+      double v[4];
+#pragma unroll
+      for (int m = 0; m < 4; ++m) {
+        const int gg = lane + 64 * m;
+        gp[m] = X2a + (int64_t)j * G * 2 + (int64_t)gg * 2;
+        on[m] = gg < G;
+      }
+      if (!granule_wait_all(gp, on, epoch, v, t0, DSEA_GRANULE_TIMEOUT_TICKS)) s_b[1] = 1.0;
+      double tot = ((v[0] + v[1]) + v[2]) + v[3];
       tot = wave_sum(tot);
       if (lane == 0) granule_put(X2b + (int64_t)j * 2, epoch, tot);
     }
     LZM_TICK(3)
     for (int t = tid; t < nvec; t += LZM_THREADS) {
       double v = 0.0;
-      while (!granule_try_get(X2b + (int64_t)t * 2, epoch, v)) {
-        __builtin_amdgcn_s_sleep(1);
-        if (wall_clock64() - t0 > LZM_TIMEOUT_TICKS) {
-          s_b[1] = 1.0;
-          break;
-        }
-      }
+      if (!granule_wait(X2b + (int64_t)t * 2, epoch, v, t0, DSEA_GRANULE_TIMEOUT_TICKS)) s_b[1] = 1.0;
       s_c[t] = v;
     }
     if (tid == 0) s_b[5] = 0.0;
@@ -647,23 +613,13 @@ inline int lzm_rows(int64_t n, int cus, int* G_out) {
 inline size_t lzm_lds_doubles(int R, int NL) {
   return (size_t)2 * LZM_K2 + 32 + (size_t)(R + 4) + (size_t)R * 4 + (size_t)LZM_WAVES * R + (size_t)NL * R;
 }
-inline int lzm_cus() {
-  static thread_local int cu_dev = -1, cu_count = 0;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return -1;
-  if (dev != cu_dev) {
-    if (hipDeviceGetAttribute(&cu_count, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return -1;
-    cu_dev = dev;
-  }
-  return cu_count;
-}
 }  // namespace
 
 // Is the mid-size single-launch form applicable?  (halo-free 3-point stencil, 8192 < n <= G x 512 rows, 2 <= k <= 512)
 bool lanczos_persist_mid_applicable(const OpDesc& op, int64_t n, int k) {
   if (op.kind != OP_STENCIL3 || op.st3.halo_lo || op.st3.halo_hi) return false;
   if (k < 2 || k > LZM_MAX_K || n <= 8192) return false;
-  const int cus = lzm_cus();
+  const int cus = device_cu_count();
   if (cus < 1) return false;
   int G = 0;
   const int R = lzm_rows(n, cus, &G);
@@ -672,7 +628,7 @@ bool lanczos_persist_mid_applicable(const OpDesc& op, int64_t n, int k) {
 
 size_t lanczos_persist_mid_comm_bytes(int64_t n, int k) {
   int G = 0;
-  const int cus = lzm_cus();
+  const int cus = device_cu_count();
   lzm_rows(n, cus < 1 ? LZM_MAX_G : cus, &G);
   const int64_t kslots = (int64_t)k + 2;
   return (size_t)(2 * ((int64_t)G * 4 + kslots * G + kslots)) * sizeof(unsigned long long);   // X1 | X2a | X2b
@@ -684,7 +640,7 @@ int launch_lanczos_persist_mid(const OpDesc& op, int k, const double* q0, double
                                void* comm, hipStream_t st, int lose_peer) {
   const int64_t n = op.n;
   if (!lanczos_persist_mid_applicable(op, n, k)) return -1;
-  const int cus = lzm_cus();
+  const int cus = device_cu_count();
   int G = 0;
   const int R = lzm_rows(n, cus, &G);
   // the 8-row octets of the shadow pass read up to the end of the slab's last octet: inside the row as long as the row
@@ -706,9 +662,8 @@ int launch_lanczos_persist_mid(const OpDesc& op, int k, const double* q0, double
   if (NL > k) NL = k;
   NL = NL / 4 * 4;
   const size_t lds_bytes = lzm_lds_doubles(R, NL) * sizeof(double);
-  int occ = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_lanczos_persist_mid, LZM_THREADS, lds_bytes) != hipSuccess || occ < 1)
-    return -1;
+  if (const int rc = persist_resident(G, reinterpret_cast<const void*>(k_lanczos_persist_mid), LZM_THREADS, lds_bytes))
+    return rc;
   if (hipMemsetAsync(comm, 0, lanczos_persist_mid_comm_bytes(n, k), st) != hipSuccess) return -2;
   LzmArgs a;
   a.st = op.st3;
