@@ -12,18 +12,7 @@
 using namespace dsea;
 
 namespace {
-thread_local int g_last_hip = 0;
-
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
-inline int check_launch() {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    g_last_hip = (int)e;
-    return DSEA_ERR_HIP;
-  }
-  return DSEA_OK;
-}
+thread_local int g_last_hip = 0;   // dsea_last_hip_error(): written by hip_fail() alone
 
 inline int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
 
@@ -53,6 +42,12 @@ WsLayout ws_layout(int64_t n, int kmax) {
 }  // namespace
 
 namespace dsea {
+int hip_fail(hipError_t e) {
+  g_last_hip = (int)e;
+  (void)hipGetLastError();   // the runtime's sticky copy: a later check_launch() must not report this failure again
+  return DSEA_ERR_HIP;
+}
+
 StatePoller* state_poller() {
   // one per host thread AND device: events belong to the device they were created on
   constexpr int MAXDEV = 16;
@@ -74,6 +69,58 @@ StatePoller* state_poller() {
     }
   }
   return sp[dev].ok ? &sp[dev] : nullptr;
+}
+
+int cg_poll(const double* state, double* hs, int64_t budget, int poll_every, StatePoller* sp,
+            const std::function<int(int64_t, int64_t)>& enqueue, hipStream_t st, int64_t* issued_out) {
+  const size_t bytes = DSEA_CG_STATE_LEN * sizeof(double);
+  int64_t issued = 0;
+  auto next_chunk = [&]() -> int {
+    const int64_t chunk = (budget - issued) < poll_every ? (budget - issued) : poll_every;
+    const int rc = enqueue(issued, chunk);
+    issued += chunk;
+    if (issued_out) *issued_out = issued;
+    return rc;
+  };
+  if (!sp) {
+    do {
+      DSEA_TRY(next_chunk());
+      DSEA_TRY(read_to_host(hs, state, bytes, st));
+    } while (hs[DSEA_CG_DONE] == 0.0 && issued < budget);
+    return DSEA_OK;
+  }
+  // pipelined: the device never idles across a host round trip (measured: ~55 us per poll at the headline size)
+  auto snapshot = [&](int slot) -> hipError_t {
+    const hipError_t e = hipMemcpyAsync(sp->pinned + slot * DSEA_CG_STATE_LEN, state, bytes, hipMemcpyDeviceToHost, st);
+    return e != hipSuccess ? e : hipEventRecord(sp->ev[slot], st);
+  };
+  auto look = [&](int slot) -> hipError_t {
+    const hipError_t e = hipEventSynchronize(sp->ev[slot]);
+    if (e == hipSuccess) memcpy(hs, sp->pinned + slot * DSEA_CG_STATE_LEN, bytes);
+    return e;
+  };
+  int slot = 0;
+  HIP_TRY(snapshot(slot));                   // the state the caller left (e.g. the early out of CG.py:28-29)
+  for (;; slot ^= 1) {
+    const bool more = issued < budget;
+    if (more) {
+      DSEA_TRY(next_chunk());
+      HIP_TRY(snapshot(slot ^ 1));
+    }
+    HIP_TRY(look(slot));
+    if (hs[DSEA_CG_DONE] != 0.0 || !more) {
+      if (more) HIP_TRY(look(slot ^ 1));     // one chunk was enqueued behind the converged state: its snapshot is final
+      return DSEA_OK;
+    }
+  }
+}
+
+int cg_result(const double* hs, int64_t* iters_out, double* resnorm_out) {
+  if (iters_out) *iters_out = (int64_t)hs[DSEA_CG_ITERS];
+  if (resnorm_out) *resnorm_out = hs[DSEA_CG_RESNORM];
+  DSEA_TRY(check_launch());
+  if (hs[DSEA_CG_DONE] < 0.0) return DSEA_ERR_TIMEOUT;   // a workgroup of a persistent launch did not show up
+  return hs[DSEA_CG_DONE] != 0.0 ? DSEA_OK : DSEA_ERR_NOT_CONVERGED;
 }
 }  // namespace dsea
 
@@ -148,32 +195,32 @@ const char* dsea_error_string(int status) {
 int dsea_last_hip_error(void) { return g_last_hip; }
 
 int dsea_op_set_tuning(dsea_op_t op, int key, int value) {
-  if (!op) return DSEA_ERR_ARG;
+  REQUIRE(op, DSEA_ERR_ARG);
   switch (key) {
     case DSEA_TUNE_TFIM_TILE_LOG2:
-      if (value < 6 || value > 12) return DSEA_ERR_ARG;
+      REQUIRE(value >= 6 && value <= 12, DSEA_ERR_ARG);
       op->d.tune_tile_log2 = value;
       return DSEA_OK;
     case DSEA_TUNE_CSR_GROUP:
-      if (value != 0 && value != 4 && value != 8 && value != 16 && value != 32 && value != 64) return DSEA_ERR_ARG;
+      REQUIRE(value == 0 || value == 4 || value == 8 || value == 16 || value == 32 || value == 64, DSEA_ERR_ARG);
       op->d.tune_csr_group = value;
       return DSEA_OK;
     case DSEA_TUNE_SELL_UNROLL:
-      if (value != 0 && value != 1 && value != 2 && value != 4 && value != 8) return DSEA_ERR_ARG;
+      REQUIRE(value == 0 || value == 1 || value == 2 || value == 4 || value == 8, DSEA_ERR_ARG);
       op->d.tune_sell_unroll = value;
       return DSEA_OK;
     case DSEA_TUNE_SELL_XCD_MAP:
-      if (op->d.kind != OP_SELL || (value != 0 && value != 1)) return DSEA_ERR_ARG;
+      REQUIRE(op->d.kind == OP_SELL && (value == 0 || value == 1), DSEA_ERR_ARG);
       op->d.sell.xcd = value;
       return DSEA_OK;
     case DSEA_TUNE_SELL_NT:
-      if (op->d.kind != OP_SELL || (value != 0 && value != 1)) return DSEA_ERR_ARG;
+      REQUIRE(op->d.kind == OP_SELL && (value == 0 || value == 1), DSEA_ERR_ARG);
       // (an A/B switch of the unpacked 16-bit layout: the packed and the value-coded kernels have no such variant)
       if (value && (op->d.sell.pack2 || op->d.sell.code8)) return DSEA_ERR_UNSUPPORTED;
       op->d.sell.nt = value;
       return DSEA_OK;
     case DSEA_TUNE_SELL_MAX_WIDTH:
-      if (op->d.kind != OP_SELL || value < 0) return DSEA_ERR_ARG;
+      REQUIRE(op->d.kind == OP_SELL && value >= 0, DSEA_ERR_ARG);
       op->d.sell.max_width = value;
       return DSEA_OK;
     default: return DSEA_ERR_ARG;
@@ -182,18 +229,18 @@ int dsea_op_set_tuning(dsea_op_t op, int key, int value) {
 
 // ---------------------------------------------------------------------------- workspace
 int dsea_ws_bytes(int64_t n, int kmax, size_t* bytes) {
-  if (!bytes || n < 1 || kmax < 0 || kmax > DSEA_MAX_KRYLOV) return DSEA_ERR_ARG;
+  REQUIRE(bytes && n >= 1 && kmax >= 0 && kmax <= DSEA_MAX_KRYLOV, DSEA_ERR_ARG);
   *bytes = ws_layout(n, kmax).total;
   return DSEA_OK;
 }
 
 int dsea_ws_create(void* device_buffer, size_t bytes, int64_t n, int kmax, dsea_ws_t* out) {
-  if (!device_buffer || !out || n < 1 || kmax < 0 || kmax > DSEA_MAX_KRYLOV) return DSEA_ERR_ARG;
-  if (!aligned16(device_buffer)) return DSEA_ERR_ALIGN;
+  REQUIRE(device_buffer && out && n >= 1 && kmax >= 0 && kmax <= DSEA_MAX_KRYLOV, DSEA_ERR_ARG);
+  REQUIRE(aligned16(device_buffer), DSEA_ERR_ALIGN);
   WsLayout L = ws_layout(n, kmax);
   if (bytes < L.total) return DSEA_ERR_WORKSPACE;
   dsea_ws_s* ws = new (std::nothrow) dsea_ws_s;
-  if (!ws) return DSEA_ERR_ARG;
+  REQUIRE(ws, DSEA_ERR_ARG);
   char* base = static_cast<char*>(device_buffer);
   ws->w.n = n;
   ws->w.npad = L.npad;
@@ -224,10 +271,10 @@ int dsea_ws_create(void* device_buffer, size_t bytes, int64_t n, int kmax, dsea_
   ws->w.coef2 = ws->w.coef + round_up((kmax < 1 ? 1 : kmax) + 2, 32);
   ws->w.scal = reinterpret_cast<double*>(base + L.scal_off);
   ws->w.zero = ws->w.scal + 30;
-  if (hipMemset(ws->w.scal, 0, DSEA_SCALARS * sizeof(double)) != hipSuccess) {   // scal[30] stays 0 for good
-    g_last_hip = (int)hipGetLastError();
+  const hipError_t me = hipMemset(ws->w.scal, 0, DSEA_SCALARS * sizeof(double));   // scal[30] stays 0 for good
+  if (me != hipSuccess) {
     delete ws;
-    return DSEA_ERR_HIP;
+    return hip_fail(me);
   }
   for (int v = 0; v < 4; ++v)
     ws->w.vec[v] = reinterpret_cast<double*>(base + L.vec_off) + (size_t)v * (size_t)L.npad;
@@ -253,7 +300,7 @@ int dsea_ws_destroy(dsea_ws_t ws) {
 }
 
 int dsea_profile_begin(dsea_ws_t ws, int max_records) {
-  if (!ws || max_records < 1) return DSEA_ERR_ARG;
+  REQUIRE(ws && max_records >= 1, DSEA_ERR_ARG);
   prof_free(ws->w);
   Profiler* p = new (std::nothrow) Profiler;
   if (!p) return DSEA_ERR_ARG;
@@ -261,26 +308,24 @@ int dsea_profile_begin(dsea_ws_t ws, int max_records) {
   p->capacity = max_records;
   p->used = 0;
   for (int e = 0; e < max_records; ++e) {
-    if (hipEventCreate(&p->pairs[e].a) != hipSuccess || hipEventCreate(&p->pairs[e].b) != hipSuccess) {
-      g_last_hip = (int)hipGetLastError();
-      return DSEA_ERR_HIP;
-    }
+    HIP_TRY(hipEventCreate(&p->pairs[e].a));
+    HIP_TRY(hipEventCreate(&p->pairs[e].b));
   }
   ws->w.prof = p;
   return DSEA_OK;
 }
 
 int dsea_profile_end(dsea_ws_t ws, int64_t* launches, double* total_ms) {
-  if (!ws || !ws->w.prof || !launches || !total_ms) return DSEA_ERR_ARG;
+  REQUIRE(ws && ws->w.prof && launches && total_ms, DSEA_ERR_ARG);
   Profiler* p = ws->w.prof;
   for (int kd = 0; kd < PROF_KINDS; ++kd) {
     launches[kd] = 0;
     total_ms[kd] = 0.0;
   }
   for (int e = 0; e < p->used; ++e) {
-    if (hipEventSynchronize(p->pairs[e].b) != hipSuccess) return DSEA_ERR_HIP;
+    HIP_TRY(hipEventSynchronize(p->pairs[e].b));
     float ms = 0.f;
-    if (hipEventElapsedTime(&ms, p->pairs[e].a, p->pairs[e].b) != hipSuccess) return DSEA_ERR_HIP;
+    HIP_TRY(hipEventElapsedTime(&ms, p->pairs[e].a, p->pairs[e].b));
     launches[p->pairs[e].kind] += 1;
     total_ms[p->pairs[e].kind] += (double)ms;
   }
@@ -289,15 +334,15 @@ int dsea_profile_end(dsea_ws_t ws, int64_t* launches, double* total_ms) {
 }
 
 int dsea_ws_set_shadow(dsea_ws_t ws, void* shadow_bf16, int64_t ld, int rows, double tau) {
-  if (!ws) return DSEA_ERR_ARG;
+  REQUIRE(ws, DSEA_ERR_ARG);
   if (!shadow_bf16) {
     ws->w.shadow = nullptr;
     ws->w.shadow_ld = 0;
     ws->w.shadow_rows = 0;
     return DSEA_OK;
   }
-  if (rows < 1 || ld < 8 || tau < 0.0) return DSEA_ERR_ARG;
-  if (!aligned16(shadow_bf16) || (ld % 8) != 0) return DSEA_ERR_ALIGN;
+  REQUIRE(rows >= 1 && ld >= 8 && tau >= 0.0, DSEA_ERR_ARG);
+  REQUIRE(aligned16(shadow_bf16) && (ld % 8) == 0, DSEA_ERR_ALIGN);
   ws->w.shadow = static_cast<uint16_t*>(shadow_bf16);
   ws->w.shadow_ld = ld;
   ws->w.shadow_rows = rows;
@@ -306,74 +351,62 @@ int dsea_ws_set_shadow(dsea_ws_t ws, void* shadow_bf16, int64_t ld, int rows, do
 }
 
 int dsea_lanczos_lp_stats(dsea_ws_t ws, int64_t* lp_steps, int64_t* fp64_steps, void* stream) {
-  if (!ws || !lp_steps || !fp64_steps) return DSEA_ERR_ARG;
+  REQUIRE(ws && lp_steps && fp64_steps, DSEA_ERR_ARG);
   double h[2] = {0.0, 0.0};
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (hipMemcpyAsync(h, ws->w.scal + 16, sizeof(h), hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipStreamSynchronize(st) != hipSuccess) {
-    g_last_hip = (int)hipGetLastError();
-    return DSEA_ERR_HIP;
-  }
+  DSEA_TRY(read_to_host(h, ws->w.scal + 16, sizeof(h), static_cast<hipStream_t>(stream)));
   *lp_steps = (int64_t)h[0];
   *fp64_steps = (int64_t)h[1];
   return DSEA_OK;
 }
 
 int dsea_lanczos_reorth_stats(dsea_ws_t ws, int64_t* reorth_steps, double* anorm, void* stream) {
-  if (!ws || !reorth_steps) return DSEA_ERR_ARG;
+  REQUIRE(ws && reorth_steps, DSEA_ERR_ARG);
   double h[2] = {0.0, 0.0};
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (hipMemcpyAsync(h, ws->w.scal + DSEA_SCAL_PRO + 2, sizeof(h), hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipStreamSynchronize(st) != hipSuccess) {
-    g_last_hip = (int)hipGetLastError();
-    return DSEA_ERR_HIP;
-  }
+  DSEA_TRY(read_to_host(h, ws->w.scal + DSEA_SCAL_PRO + 2, sizeof(h), static_cast<hipStream_t>(stream)));
   if (anorm) *anorm = h[0];
   *reorth_steps = (int64_t)h[1];
   return DSEA_OK;
 }
 
 int dsea_ws_set_rows_per_lane(dsea_ws_t ws, int rpl) {
-  if (!ws) return DSEA_ERR_ARG;
-  if (rpl != 0 && rpl != 2 && rpl != 4 && rpl != 8 && rpl != 16) return DSEA_ERR_ARG;
+  REQUIRE(ws && (rpl == 0 || rpl == 2 || rpl == 4 || rpl == 8 || rpl == 16), DSEA_ERR_ARG);
   ws->w.rpl_override = rpl;
   return DSEA_OK;
 }
 
 int dsea_ws_set_persist(dsea_ws_t ws, int mode) {
-  if (!ws) return DSEA_ERR_ARG;
+  REQUIRE(ws, DSEA_ERR_ARG);
   if (mode == 200) {     // TFIM, 2^11 ... 2^20 rows: the two-exchange persistent form (iterates bit-identical to the streaming
     ws->w.persist_override = mode;   // kernels) instead of the default one-exchange form; other operands: as -1
     return DSEA_OK;
   }
   const int geo = mode >= 100 ? mode - 100 : mode;     // >= 100: merged-reduction form with geometry code mode - 100
-  if (geo != -1 && geo != 0 && geo != 1 && geo != 2 && geo != 11 && geo != 12 && geo != 21 && geo != 22)
-    return DSEA_ERR_ARG;
-  if (mode >= 100 && geo == -1) return DSEA_ERR_ARG;
+  REQUIRE(geo == -1 || geo == 0 || geo == 1 || geo == 2 || geo == 11 || geo == 12 || geo == 21 || geo == 22, DSEA_ERR_ARG);
+  REQUIRE(mode < 100 || geo != -1, DSEA_ERR_ARG);
   ws->w.persist_override = mode;
   return DSEA_OK;
 }
 
 int dsea_cg_last_form(dsea_ws_t ws, int* form) {
-  if (!ws || !form) return DSEA_ERR_ARG;
+  REQUIRE(ws && form, DSEA_ERR_ARG);
   *form = ws->w.last_cg_form;
   return DSEA_OK;
 }
 
 int dsea_ws_set_fault_injection(dsea_ws_t ws, int lose_peer) {
-  if (!ws) return DSEA_ERR_ARG;
+  REQUIRE(ws, DSEA_ERR_ARG);
   ws->w.lose_peer = lose_peer ? 1 : 0;
   return DSEA_OK;
 }
 
 int dsea_ws_set_reorth_passes(dsea_ws_t ws, int passes) {
-  if (!ws || (passes != 1 && passes != 2)) return DSEA_ERR_ARG;
+  REQUIRE(ws && (passes == 1 || passes == 2), DSEA_ERR_ARG);
   ws->w.reorth_passes = passes;
   return DSEA_OK;
 }
 
 int dsea_ws_set_partial_reorth(dsea_ws_t ws, int on, double delta) {
-  if (!ws || !(delta >= 0.0)) return DSEA_ERR_ARG;
+  REQUIRE(ws && delta >= 0.0, DSEA_ERR_ARG);
   ws->w.partial_reorth = on ? 1 : 0;
   ws->w.pro_delta = delta > 0.0 ? delta : DSEA_PRO_DELTA_DEFAULT;
   return DSEA_OK;
@@ -382,7 +415,7 @@ int dsea_ws_set_partial_reorth(dsea_ws_t ws, int on, double delta) {
 int dsea_ws_set_lanczos_persist(dsea_ws_t ws, int mode) {
   // -1 automatic, 0 off, 1 forced wherever a single-launch form applies, 2 = only the README-sized form (the mid-size
   // form of dsea_lanczos_persist_mid.hip off: A/B measurements)
-  if (!ws || (mode != -1 && mode != 0 && mode != 1 && mode != 2)) return DSEA_ERR_ARG;
+  REQUIRE(ws && (mode == -1 || mode == 0 || mode == 1 || mode == 2), DSEA_ERR_ARG);
   ws->w.lz_persist = mode;
   return DSEA_OK;
 }
@@ -403,8 +436,7 @@ inline int lp_rows_per_step(int64_t n, bool dots_are_split) {
 }  // namespace
 
 int dsea_ws_set_split(dsea_ws_t ws, int waves) {
-  if (!ws) return DSEA_ERR_ARG;
-  if (waves != -1 && waves != 0 && waves != 4 && waves != 8 && waves != 16) return DSEA_ERR_ARG;
+  REQUIRE(ws && (waves == -1 || waves == 0 || waves == 4 || waves == 8 || waves == 16), DSEA_ERR_ARG);
   ws->w.split_override = waves;
   return DSEA_OK;
 }
@@ -412,8 +444,8 @@ int dsea_ws_set_split(dsea_ws_t ws, int waves) {
 // ---------------------------------------------------------------------------- operators
 int dsea_op_create_tfim(int L, int L_local, int64_t row_offset, const double* g_dev, double g_const,
                         double diag_scale, dsea_op_t* out) {
-  if (!out || L < 1 || L > 62 || L_local < 0 || L_local > L || row_offset < 0) return DSEA_ERR_ARG;
-  if (row_offset & (((int64_t)1 << L_local) - 1)) return DSEA_ERR_ARG;  // slab must be aligned
+  REQUIRE(out && L >= 1 && L <= 62 && L_local >= 0 && L_local <= L && row_offset >= 0, DSEA_ERR_ARG);
+  REQUIRE((row_offset & (((int64_t)1 << L_local) - 1)) == 0, DSEA_ERR_ARG);  // slab must be aligned
   dsea_op_s* op = new (std::nothrow) dsea_op_s;
   if (!op) return DSEA_ERR_ARG;
   memset(&op->d, 0, sizeof(op->d));
@@ -427,7 +459,7 @@ int dsea_op_create_tfim(int L, int L_local, int64_t row_offset, const double* g_
 
 int dsea_op_create_csr(int64_t n, int64_t nnz, const int64_t* rowptr, const int32_t* colidx,
                        const double* vals, dsea_op_t* out) {
-  if (!out || n < 1 || nnz < 0 || !rowptr || (nnz > 0 && (!colidx || !vals))) return DSEA_ERR_ARG;
+  REQUIRE(out && n >= 1 && nnz >= 0 && rowptr && (nnz == 0 || (colidx && vals)), DSEA_ERR_ARG);
   dsea_op_s* op = new (std::nothrow) dsea_op_s;
   if (!op) return DSEA_ERR_ARG;
   memset(&op->d, 0, sizeof(op->d));
@@ -441,7 +473,7 @@ int dsea_op_create_csr(int64_t n, int64_t nnz, const int64_t* rowptr, const int3
 
 int dsea_op_create_sell(int64_t n, int64_t nslices, const int64_t* slice_ptr, const int32_t* colidx,
                         const double* vals, dsea_op_t* out) {
-  if (!out || n < 1 || nslices != (n + 63) / 64 || !slice_ptr || !colidx || !vals) return DSEA_ERR_ARG;
+  REQUIRE(out && n >= 1 && nslices == (n + 63) / 64 && slice_ptr && colidx && vals, DSEA_ERR_ARG);
   dsea_op_s* op = new (std::nothrow) dsea_op_s;
   if (!op) return DSEA_ERR_ARG;
   memset(&op->d, 0, sizeof(op->d));
@@ -463,7 +495,7 @@ int dsea_op_create_sell16p2(int64_t n, int64_t nslices, const int64_t* slice_ptr
 
 int dsea_op_create_sell16v8(int64_t n, int64_t nslices, const int64_t* slice_ptr, const int32_t* colbase,
                             const uint16_t* coldelta, const uint8_t* code, const double* table256, dsea_op_t* out) {
-  if (!out || n < 1 || nslices != (n + 63) / 64 || !slice_ptr || !colbase || !coldelta || !code || !table256) return DSEA_ERR_ARG;
+  REQUIRE(out && n >= 1 && nslices == (n + 63) / 64 && slice_ptr && colbase && coldelta && code && table256, DSEA_ERR_ARG);
   dsea_op_s* op = new (std::nothrow) dsea_op_s;
   if (!op) return DSEA_ERR_ARG;
   memset(&op->d, 0, sizeof(op->d));
@@ -482,7 +514,7 @@ int dsea_op_create_sell16v8(int64_t n, int64_t nslices, const int64_t* slice_ptr
 
 int dsea_op_create_sell16(int64_t n, int64_t nslices, const int64_t* slice_ptr, const int32_t* colbase,
                           const uint16_t* coldelta, const double* vals, dsea_op_t* out) {
-  if (!out || n < 1 || nslices != (n + 63) / 64 || !slice_ptr || !colbase || !coldelta || !vals) return DSEA_ERR_ARG;
+  REQUIRE(out && n >= 1 && nslices == (n + 63) / 64 && slice_ptr && colbase && coldelta && vals, DSEA_ERR_ARG);
   dsea_op_s* op = new (std::nothrow) dsea_op_s;
   if (!op) return DSEA_ERR_ARG;
   memset(&op->d, 0, sizeof(op->d));
@@ -499,8 +531,8 @@ int dsea_op_create_sell16(int64_t n, int64_t nslices, const int64_t* slice_ptr, 
 
 int dsea_op_create_stencil3(int64_t n, double coef, const double* V_dev, const double* halo_lo,
                             const double* halo_hi, dsea_op_t* out) {
-  if (!out || n < 1 || !V_dev) return DSEA_ERR_ARG;
-  if (!aligned16(V_dev)) return DSEA_ERR_ALIGN;  // read as row pairs (16-byte loads)
+  REQUIRE(out && n >= 1 && V_dev, DSEA_ERR_ARG);
+  REQUIRE(aligned16(V_dev), DSEA_ERR_ALIGN);  // read as row pairs (16-byte loads)
   dsea_op_s* op = new (std::nothrow) dsea_op_s;
   if (!op) return DSEA_ERR_ARG;
   memset(&op->d, 0, sizeof(op->d));
@@ -513,7 +545,7 @@ int dsea_op_create_stencil3(int64_t n, double coef, const double* V_dev, const d
 }
 
 int dsea_op_create_dense(int64_t n, const double* A_dev, int64_t lda, int transpose, dsea_op_t* out) {
-  if (!out || n < 1 || !A_dev || lda < n || n > 2147483647ll || lda > 2147483647ll) return DSEA_ERR_ARG;
+  REQUIRE(out && n >= 1 && A_dev && lda >= n && n <= 2147483647ll && lda <= 2147483647ll, DSEA_ERR_ARG);
   dsea_op_s* op = new (std::nothrow) dsea_op_s;
   if (!op) return DSEA_ERR_ARG;
   memset(&op->d, 0, sizeof(op->d));
@@ -532,9 +564,9 @@ size_t dsea_op_symdense_work_bytes(int64_t n) {
 }
 
 int dsea_op_create_symdense(int64_t n, const void* A_dev, int elem_bytes, int64_t lda, double* work, dsea_op_t* out) {
-  if (!out || n < 1 || !A_dev || !work || lda < n || (n + 63) / 64 > 65535 || (elem_bytes != 8 && elem_bytes != 4))
-    return DSEA_ERR_ARG;
-  if (!aligned16(A_dev) || (lda % 2) != 0) return DSEA_ERR_ALIGN;   // rows are read as element pairs
+  REQUIRE(out && n >= 1 && A_dev && work && lda >= n && (n + 63) / 64 <= 65535 && (elem_bytes == 8 || elem_bytes == 4),
+          DSEA_ERR_ARG);
+  REQUIRE(aligned16(A_dev) && (lda % 2) == 0, DSEA_ERR_ALIGN);   // rows are read as element pairs
   dsea_op_s* op = new (std::nothrow) dsea_op_s;
   if (!op) return DSEA_ERR_ARG;
   memset(&op->d, 0, sizeof(op->d));
@@ -557,8 +589,8 @@ size_t dsea_op_transfer_work_bytes(int D, int d) {
 
 int dsea_op_create_transfer(int D, int d, const double* A_dev, int transpose, double* work, void* stream,
                             dsea_op_t* out) {
-  if (!out || D < 1 || d < 1 || !A_dev || !work || (int64_t)d * D > 2147483647ll) return DSEA_ERR_ARG;
-  if (!aligned16(A_dev) || !aligned16(work)) return DSEA_ERR_ALIGN;
+  REQUIRE(out && D >= 1 && d >= 1 && A_dev && work && (int64_t)d * D <= 2147483647ll, DSEA_ERR_ARG);
+  REQUIRE(aligned16(A_dev) && aligned16(work), DSEA_ERR_ALIGN);
   dsea_op_s* op = new (std::nothrow) dsea_op_s;
   if (!op) return DSEA_ERR_ARG;
   memset(&op->d, 0, sizeof(op->d));
@@ -581,20 +613,18 @@ int dsea_op_create_transfer(int D, int d, const double* A_dev, int transpose, do
 }
 
 int dsea_op_update_vals(dsea_op_t op, const int64_t* rowptr, const double* vals_csr, void* stream) {
-  if (!op || !vals_csr) return DSEA_ERR_ARG;
+  REQUIRE(op && vals_csr, DSEA_ERR_ARG);
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (op->d.kind == OP_SELL) {
-    if (!rowptr) return DSEA_ERR_ARG;
+    REQUIRE(rowptr, DSEA_ERR_ARG);
     if (op->d.sell.code8) return DSEA_ERR_UNSUPPORTED;      // value-coded operand: read-only (dsea_op_create_sell16v8)
     launch_sell_update_vals(op->d, rowptr, vals_csr, st);
     return check_launch();
   }
   if (op->d.kind == OP_CSR) {
     const CsrParams& p = op->d.csr;
-    if (vals_csr != p.vals && p.nnz > 0 &&
-        hipMemcpyAsync(const_cast<double*>(p.vals), vals_csr, (size_t)p.nnz * sizeof(double), hipMemcpyDeviceToDevice, st) !=
-            hipSuccess)
-      return DSEA_ERR_HIP;
+    if (vals_csr != p.vals && p.nnz > 0)
+      HIP_TRY(hipMemcpyAsync(const_cast<double*>(p.vals), vals_csr, (size_t)p.nnz * sizeof(double), hipMemcpyDeviceToDevice, st));
     return DSEA_OK;
   }
   return DSEA_ERR_UNSUPPORTED;
@@ -602,9 +632,9 @@ int dsea_op_update_vals(dsea_op_t op, const int64_t* rowptr, const double* vals_
 
 int dsea_op_sddmm(dsea_op_t op, const int64_t* rowptr, const double* v1, const double* v2, double alpha, int flags,
                   double* out, void* stream) {
-  if (!op || !v1 || !v2 || !out || (flags & ~(DSEA_SDDMM_ACCUMULATE | DSEA_SDDMM_SYMMETRIC))) return DSEA_ERR_ARG;
-  if (op->d.kind != OP_SELL && op->d.kind != OP_CSR) return DSEA_ERR_UNSUPPORTED;
-  if (op->d.kind == OP_SELL && !rowptr) return DSEA_ERR_ARG;
+  REQUIRE(op && v1 && v2 && out && !(flags & ~(DSEA_SDDMM_ACCUMULATE | DSEA_SDDMM_SYMMETRIC)), DSEA_ERR_ARG);
+  REQUIRE(op->d.kind == OP_SELL || op->d.kind == OP_CSR, DSEA_ERR_UNSUPPORTED);
+  REQUIRE(op->d.kind != OP_SELL || rowptr, DSEA_ERR_ARG);
   // a slab (dsea_op_set_slab): the caller has exchanged v2's halo / gathered copy; the symmetric form needs both operands
   // exchanged -- dsea_pop_sddmm issues it as two one-sided launches
   if (op->d.kind == OP_SELL && op->d.sell.mode != 0 && (flags & DSEA_SDDMM_SYMMETRIC)) return DSEA_ERR_UNSUPPORTED;
@@ -618,14 +648,14 @@ int dsea_op_set_slab(dsea_op_t op, int64_t halo_width, double* halo_lo, double* 
   if (!op || op->d.kind != OP_SELL || op->d.sell.code8) return op ? DSEA_ERR_UNSUPPORTED : DSEA_ERR_ARG;
   SellParams& p = op->d.sell;
   if (halo_width == -1) {
-    if (!x_gathered) return DSEA_ERR_ARG;
+    REQUIRE(x_gathered, DSEA_ERR_ARG);
     p.mode = 2;
     p.hb = 0;
     p.halo_lo = p.halo_hi = nullptr;
     p.xg = x_gathered;
     return DSEA_OK;
   }
-  if (halo_width < 0 || halo_width > p.n) return DSEA_ERR_ARG;
+  REQUIRE(halo_width >= 0 && halo_width <= p.n, DSEA_ERR_ARG);
   p.mode = 1;
   p.hb = halo_width;
   p.halo_lo = halo_lo;
@@ -640,16 +670,15 @@ int dsea_op_destroy(dsea_op_t op) {
 }
 
 int dsea_op_dim(dsea_op_t op, int64_t* n) {
-  if (!op || !n) return DSEA_ERR_ARG;
+  REQUIRE(op && n, DSEA_ERR_ARG);
   *n = op->d.n;
   return DSEA_OK;
 }
 
 int dsea_spmv(dsea_op_t op, dsea_ws_t ws, const double* x, double* y, const double* shift,
               double* dot_out, const double* skip_flag, void* stream) {
-  if (!op || !x || !y || x == y) return DSEA_ERR_ARG;
-  if (dot_out && !ws) return DSEA_ERR_ARG;
-  if (!aligned16(x) || !aligned16(y)) return DSEA_ERR_ALIGN;
+  REQUIRE(op && x && y && x != y && (!dot_out || ws), DSEA_ERR_ARG);
+  REQUIRE(aligned16(x) && aligned16(y), DSEA_ERR_ALIGN);
   hipStream_t st = static_cast<hipStream_t>(stream);
   double* P = dot_out ? ws->w.partials : nullptr;
   int nb = launch_spmv(op->d, x, y, shift, skip_flag, P, st);
@@ -667,11 +696,6 @@ int dsea_spmv(dsea_op_t op, dsea_ws_t ws, const double* x, double* y, const doub
 }
 
 // ---------------------------------------------------------------------------- vector phases
-#define REQUIRE(cond, code) \
-  do {                      \
-    if (!(cond)) return (code); \
-  } while (0)
-
 int dsea_dot(dsea_ws_t ws, const double* x, const double* y, int64_t n, double* out, void* stream) {
   REQUIRE(ws && x && y && out && n >= 1, DSEA_ERR_ARG);
   REQUIRE(aligned16(x) && aligned16(y), DSEA_ERR_ALIGN);
@@ -758,10 +782,7 @@ int dsea_lanczos_partial_step(dsea_ws_t ws, const double* Q, int64_t ldq, int64_
   const TileGeom g = w.geom(n);
   double* flag = w.scal + DSEA_SCAL_PRO;
   double* om = w.aux + 4 * DSEA_MAX_WAVE_TILES;
-  if (i == 1 && hipMemsetAsync(flag, 0, 4 * sizeof(double), st) != hipSuccess) {   // a new run: estimates and counters restart
-    g_last_hip = (int)hipGetLastError();
-    return DSEA_ERR_HIP;
-  }
+  if (i == 1) HIP_TRY(hipMemsetAsync(flag, 0, 4 * sizeof(double), st));   // a new run: estimates and counters restart
   // the sequence of dsea_lanczos_run's partial mode, as one phase call around the caller's own mat-vec
   launch_rdots(g, Q, ldq, n, i, u, alphas + (i - 1), i >= 2 ? betas + (i - 2) : nullptr, r, w.partials, nullptr, st, nullptr,
                nullptr, 0, nullptr, true, nullptr, w.zero, false);
@@ -1036,30 +1057,18 @@ int dsea_lanczos_run(dsea_op_t op, dsea_ws_t ws, int k, const double* q0, double
   }
   double* lp_count = w.scal + 16;
   double* brk = w.scal + DSEA_SCAL_BREAK;  // [0] breakdown step (0 = none), [1] running max |alpha|,|beta|
-  {
-    hipError_t me = hipMemsetAsync(lp_count, 0, (DSEA_SCAL_BREAK + 2 - 16) * sizeof(double), st);
-    if (me != hipSuccess) {
-      g_last_hip = (int)me;
-      return DSEA_ERR_HIP;
-    }
-  }
+  HIP_TRY(hipMemsetAsync(lp_count, 0, (DSEA_SCAL_BREAK + 2 - 16) * sizeof(double), st));
   // the lost-peer record of the single-launch form is per run (dsea_lanczos_status reads it); so is the state of the
   // partial re-orthogonalisation (scal[38..43])
-  if (hipMemsetAsync(w.scal + DSEA_SCAL_LZ_FAIL, 0, (DSEA_SCAL_PRO + 4 - DSEA_SCAL_LZ_FAIL) * sizeof(double), st) != hipSuccess) {
-    g_last_hip = (int)hipGetLastError();
-    return DSEA_ERR_HIP;
-  }
+  HIP_TRY(hipMemsetAsync(w.scal + DSEA_SCAL_LZ_FAIL, 0, (DSEA_SCAL_PRO + 4 - DSEA_SCAL_LZ_FAIL) * sizeof(double), st));
   // README-sized problems (n <= 8192, k <= 512; full-space TFIM / halo-free stencil): the whole loop as ONE launch
   // (dsea_lanczos_persist.hip).  The granule buffers live in the partial-sum area, unused by that form.
   // (automatic: up to 32 workgroups = 4096 rows, where it is measured to win; mode 1 forces it up to its envelope)
   if (w.lz_persist != 0 && w.reorth_passes == 1 && !w.partial_reorth && (w.lz_persist == 1 || n <= 4096) && !prof && lanczos_persist_applicable(op->d, n, k) &&
-      lanczos_persist_comm_bytes(n, k) <= (size_t)DSEA_MAX_WAVE_TILES * (size_t)((w.kmax < 1 ? 1 : w.kmax) + 1) * sizeof(double)) {
-    const int pr = launch_lanczos_persist(op->d, k, q0, Q, ldq, alphas, betas, brk, w.scal + DSEA_SCAL_LZ_FAIL, P, st, w.lose_peer);
-    if (pr == -2) {
-      g_last_hip = (int)hipGetLastError();
-      return DSEA_ERR_HIP;
-    }
-    if (pr == 0) return check_launch();
+      lanczos_persist_comm_bytes(n, k) <= w.partials_bytes()) {
+    const int rc = persist_status(launch_lanczos_persist(op->d, k, q0, Q, ldq, alphas, betas, brk, w.scal + DSEA_SCAL_LZ_FAIL, P,
+                                                         st, w.lose_peer));
+    if (rc != PERSIST_SKIPPED) return rc == DSEA_OK ? check_launch() : rc;
   }
   // Mid-size halo-1 operators (3-point stencil, 8192 < n <= 131072 rows: BASELINE configs[2]): ONE launch that keeps a
   // third of the basis in registers and LDS and streams the rest (dsea_lanczos_persist_mid.hip).  mode 2 = off for this
@@ -1068,29 +1077,43 @@ int dsea_lanczos_run(dsea_op_t op, dsea_ws_t ws, int k, const double* q0, double
   // wherever it applies
   if (w.lz_persist != 0 && w.lz_persist != 2 && (w.lz_persist == 1 || (n >= 49152 && k <= 400)) && w.reorth_passes == 1 &&
       !w.partial_reorth && !prof && lanczos_persist_mid_applicable(op->d, n, k) &&
-      lanczos_persist_mid_comm_bytes(n, k) <= (size_t)DSEA_MAX_WAVE_TILES * (size_t)((w.kmax < 1 ? 1 : w.kmax) + 1) * sizeof(double)) {
-    const int pr = launch_lanczos_persist_mid(op->d, k, q0, Q, ldq, Qs, lds, w.lp_tau, alphas, betas, brk,
-                                              w.scal + DSEA_SCAL_LZ_FAIL, lp_count, P, st, w.lose_peer);
-    if (pr == -2) {
-      g_last_hip = (int)hipGetLastError();
-      return DSEA_ERR_HIP;
-    }
-    if (pr == 0) return check_launch();
+      lanczos_persist_mid_comm_bytes(n, k) <= w.partials_bytes()) {
+    const int rc = persist_status(launch_lanczos_persist_mid(op->d, k, q0, Q, ldq, Qs, lds, w.lp_tau, alphas, betas, brk,
+                                                             w.scal + DSEA_SCAL_LZ_FAIL, lp_count, P, st, w.lose_peer));
+    if (rc != PERSIST_SKIPPED) return rc == DSEA_OK ? check_launch() : rc;
   }
   const int rps = lp_rows_per_step(n, g.split_w != 0);   // 0 = split form
-  const bool has_fused_tail = (op->d.kind == OP_TFIM && op->d.tfim.L_local >= 1) || (op->d.kind == OP_SELL && op->d.sell.mode == 0) ||
-                              op->d.kind == OP_STENCIL3;
+  const bool fused_tail = has_fused_tail(op->d);
   // (operators without a fused tail: full re-orthogonalisation only -- refused BEFORE anything is enqueued; the partial
   //  option reaches them through dsea_lanczos_partial_step)
-  if (w.partial_reorth && !has_fused_tail) return DSEA_ERR_UNSUPPORTED;
+  if (w.partial_reorth && !fused_tail) return DSEA_ERR_UNSUPPORTED;
+  double* aP = w.aux;
+  double* nP = w.aux + DSEA_MAX_WAVE_TILES;
+  // The correction r -= Q c of step i (the bf16 shadow's pass when there is one): its ||r||^2 partials are left in nP, or
+  // in fp64P on the fp64 pass; returns their count.  close: sum them into nrm2 (the unfused sequence).
+  auto correct = [&](int i, double* fp64P, EventPair* ev, bool close) -> int {
+    int nn = g.nw;
+    if (Qs)
+      nn = launch_axpy_norm_lp(n, rps, Q, ldq, Qs, lds, i, w.coef, w.lp_tau, r, nP, lp_count, st, ev, brk);
+    else
+      launch_axpy_norm(g, Q, ldq, n, i, w.coef, r, fp64P, nullptr, st, ev, brk);
+    if (close) launch_finalize_slot(Qs ? nP : fp64P, nn, nrm2, brk, st);
+    return nn;
+  };
+  // CGS2 option (the reference makes ONE pass, Lanczos.py:66): c' = Q^T r of the corrected r, r -= Q c'.  The dots kernel
+  // rewrites r from a snapshot (alpha = 0) so that its input and output do not alias.
+  auto second_pass = [&](int i, double* fp64P, bool close, int& nn) -> int {
+    HIP_TRY(hipMemcpyAsync(w.vec[2], r, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st));
+    launch_rdots(g, Q, ldq, n, i, w.vec[2], w.zero, nullptr, r, P, w.coef, st, nullptr, nullptr, 0, nullptr, Qs != nullptr, brk);
+    nn = correct(i, fp64P, nullptr, close);
+    return DSEA_OK;
+  };
   launch_dot(q0, q0, n, P, nrm2, st);
   launch_scale_store(q0, nrm2, Q, nullptr, n, st, Qs);
-  if (has_fused_tail) {
+  if (fused_tail) {
     // Fused sequence, 4 launches per step and no stand-alone scalar reductions: the mat-vec leaves
     // per-block partials of alpha (aP), the dots kernel sums them in its prologue; the axpy kernel leaves
     // per-wave partials of ||r||^2 (nP), the fused scale + mat-vec kernel sums those.
-    double* aP = w.aux;
-    double* nP = w.aux + DSEA_MAX_WAVE_TILES;
     int na = launch_spmv(op->d, Q, u, nullptr, nullptr, aP, st, prof ? prof->next(PROF_SPMV) : nullptr);
     if (na < 0) return DSEA_ERR_UNSUPPORTED;
     // partial re-orthogonalisation (option): the three-term vector goes to vec[2] with its norm, k_pro_update advances the
@@ -1117,26 +1140,8 @@ int dsea_lanczos_run(dsea_op_t op, dsea_ws_t ws, int k, const double* q0, double
       }
       launch_rdots(g, Q, ldq, n, i, u, nullptr, beta_prev, r, P, w.coef, st,
                    prof ? prof->next(PROF_RDOTS) : nullptr, aP, na, alphas + (i - 1), Qs != nullptr, brk);
-      int nn = g.nw;
-      if (Qs)
-        nn = launch_axpy_norm_lp(n, rps, Q, ldq, Qs, lds, i, w.coef, w.lp_tau, r, nP, lp_count, st,
-                                 prof ? prof->next(PROF_AXPY) : nullptr, brk);
-      else
-        launch_axpy_norm(g, Q, ldq, n, i, w.coef, r, nP, nullptr, st, prof ? prof->next(PROF_AXPY) : nullptr, brk);
-      if (w.reorth_passes == 2) {
-        // CGS2 option (the reference makes ONE pass, Lanczos.py:66): c' = Q^T r of the corrected r, r -= Q c'.  The dots
-        // kernel rewrites r from a snapshot (alpha = 0) so that its input and output do not alias.
-        if (hipMemcpyAsync(w.vec[2], r, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st) != hipSuccess) {
-          g_last_hip = (int)hipGetLastError();
-          return DSEA_ERR_HIP;
-        }
-        launch_rdots(g, Q, ldq, n, i, w.vec[2], w.zero, nullptr, r, P, w.coef, st, nullptr, nullptr, 0, nullptr,
-                     Qs != nullptr, brk);
-        if (Qs)
-          nn = launch_axpy_norm_lp(n, rps, Q, ldq, Qs, lds, i, w.coef, w.lp_tau, r, nP, lp_count, st, nullptr, brk);
-        else
-          launch_axpy_norm(g, Q, ldq, n, i, w.coef, r, nP, nullptr, st, nullptr, brk);
-      }
+      int nn = correct(i, nP, prof ? prof->next(PROF_AXPY) : nullptr, false);
+      if (w.reorth_passes == 2) DSEA_TRY(second_pass(i, nP, false, nn));
       // beta_{i-1} ~ 0 (relative to the running |alpha|, |beta| scale): the tail records step i in brk and every
       // later launch of this run returns at once (Lanczos.py:69-70 would divide by it)
       na = launch_tfim_fused(op->d, r, nP, nn, Q + (int64_t)i * ldq, u, betas + (i - 1), aP, st,
@@ -1145,7 +1150,6 @@ int dsea_lanczos_run(dsea_op_t op, dsea_ws_t ws, int k, const double* q0, double
     launch_finalize_slot(aP, na, alphas + (k - 1), brk, st);
     return check_launch();
   }
-  if (w.partial_reorth) return DSEA_ERR_UNSUPPORTED;   // (operators without a fused tail: full re-orthogonalisation only)
   int nb = launch_spmv(op->d, Q, u, nullptr, nullptr, P, st, prof ? prof->next(PROF_SPMV) : nullptr);
   if (nb < 0) return DSEA_ERR_UNSUPPORTED;
   launch_finalize1(P, nb, alphas, st);
@@ -1153,31 +1157,8 @@ int dsea_lanczos_run(dsea_op_t op, dsea_ws_t ws, int k, const double* q0, double
     const double* beta_prev = (i >= 2) ? betas + (i - 2) : nullptr;
     launch_rdots(g, Q, ldq, n, i, u, alphas + (i - 1), beta_prev, r, P, w.coef, st,
                  prof ? prof->next(PROF_RDOTS) : nullptr, nullptr, 0, nullptr, Qs != nullptr, brk);
-    if (Qs) {
-      double* nP = w.aux + DSEA_MAX_WAVE_TILES;
-      int nn = launch_axpy_norm_lp(n, rps, Q, ldq, Qs, lds, i, w.coef, w.lp_tau, r, nP, lp_count, st,
-                                   prof ? prof->next(PROF_AXPY) : nullptr, brk);
-      launch_finalize_slot(nP, nn, nrm2, brk, st);
-    } else {
-      launch_axpy_norm(g, Q, ldq, n, i, w.coef, r, P, nullptr, st, prof ? prof->next(PROF_AXPY) : nullptr, brk);
-      launch_finalize_slot(P, g.nw, nrm2, brk, st);
-    }
-    if (w.reorth_passes == 2) {   // CGS2 option, see the fused sequence above
-      if (hipMemcpyAsync(w.vec[2], r, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st) != hipSuccess) {
-        g_last_hip = (int)hipGetLastError();
-        return DSEA_ERR_HIP;
-      }
-      launch_rdots(g, Q, ldq, n, i, w.vec[2], w.zero, nullptr, r, P, w.coef, st, nullptr, nullptr, 0, nullptr,
-                   Qs != nullptr, brk);
-      if (Qs) {
-        double* nP2 = w.aux + DSEA_MAX_WAVE_TILES;
-        int nn2 = launch_axpy_norm_lp(n, rps, Q, ldq, Qs, lds, i, w.coef, w.lp_tau, r, nP2, lp_count, st, nullptr, brk);
-        launch_finalize_slot(nP2, nn2, nrm2, brk, st);
-      } else {
-        launch_axpy_norm(g, Q, ldq, n, i, w.coef, r, P, nullptr, st, nullptr, brk);
-        launch_finalize_slot(P, g.nw, nrm2, brk, st);
-      }
-    }
+    int nn = correct(i, P, prof ? prof->next(PROF_AXPY) : nullptr, true);
+    if (w.reorth_passes == 2) DSEA_TRY(second_pass(i, P, true, nn));
     double* qi = Q + (int64_t)i * ldq;
     launch_scale_store(r, nrm2, qi, betas + (i - 1), n, st, Qs ? Qs + (int64_t)i * lds : nullptr, brk, i);
     nb = launch_spmv(op->d, qi, u, nullptr, brk, P, st, prof ? prof->next(PROF_SPMV) : nullptr);
@@ -1192,9 +1173,7 @@ int dsea_lanczos_run_basisfree(dsea_op_t op, dsea_ws_t ws, int k, const double* 
   const int64_t n = op->d.n;
   REQUIRE(ldq >= n && ws->w.n >= n, DSEA_ERR_ARG);
   REQUIRE(aligned16(q0) && aligned16(Qrot) && (!psi || aligned16(psi)) && (ldq % 2 == 0), DSEA_ERR_ALIGN);
-  const bool has_fused_tail = (op->d.kind == OP_TFIM && op->d.tfim.L_local >= 1) || (op->d.kind == OP_SELL && op->d.sell.mode == 0) ||
-                              op->d.kind == OP_STENCIL3;
-  REQUIRE(has_fused_tail, DSEA_ERR_UNSUPPORTED);
+  REQUIRE(has_fused_tail(op->d), DSEA_ERR_UNSUPPORTED);
   hipStream_t st = static_cast<hipStream_t>(stream);
   Workspace& w = ws->w;
   double* u = w.vec[0];
@@ -1203,15 +1182,9 @@ int dsea_lanczos_run_basisfree(dsea_op_t op, dsea_ws_t ws, int k, const double* 
   double* aP = w.aux;
   double* nP = w.aux + DSEA_MAX_WAVE_TILES;
   double* brk = w.scal + DSEA_SCAL_BREAK;
-  if (hipMemsetAsync(brk, 0, 2 * sizeof(double), st) != hipSuccess ||
-      hipMemsetAsync(w.scal + DSEA_SCAL_LZ_FAIL, 0, sizeof(double), st) != hipSuccess) {
-    g_last_hip = (int)hipGetLastError();
-    return DSEA_ERR_HIP;
-  }
-  if (psi && hipMemsetAsync(psi, 0, (size_t)n * sizeof(double), st) != hipSuccess) {
-    g_last_hip = (int)hipGetLastError();
-    return DSEA_ERR_HIP;
-  }
+  HIP_TRY(hipMemsetAsync(brk, 0, 2 * sizeof(double), st));
+  HIP_TRY(hipMemsetAsync(w.scal + DSEA_SCAL_LZ_FAIL, 0, sizeof(double), st));
+  if (psi) HIP_TRY(hipMemsetAsync(psi, 0, (size_t)n * sizeof(double), st));
   auto slot = [&](int i) { return Qrot + (int64_t)(i % 3) * ldq; };
   launch_dot(q0, q0, n, w.partials, nrm2, st);
   launch_scale_store(q0, nrm2, slot(0), nullptr, n, st, nullptr);
@@ -1241,12 +1214,9 @@ int dsea_arnoldi_extend(dsea_op_t op, dsea_ws_t ws, const double* shift, double*
   double* brk = w.scal + DSEA_SCAL_BREAK;
   if (j0 == 0) {   // a new factorisation: clear the break record (a continued one keeps it)
     // second-pass counter (dsea_arnoldi_second_passes) and the break record
-    if (hipMemsetAsync(w.scal + 31, 0, sizeof(double), st) != hipSuccess ||
-        hipMemsetAsync(w.scal + DSEA_SCAL_LZ_FAIL, 0, sizeof(double), st) != hipSuccess ||
-        hipMemsetAsync(brk, 0, 2 * sizeof(double), st) != hipSuccess) {
-      g_last_hip = (int)hipGetLastError();
-      return DSEA_ERR_HIP;
-    }
+    HIP_TRY(hipMemsetAsync(w.scal + 31, 0, sizeof(double), st));
+    HIP_TRY(hipMemsetAsync(w.scal + DSEA_SCAL_LZ_FAIL, 0, sizeof(double), st));
+    HIP_TRY(hipMemsetAsync(brk, 0, 2 * sizeof(double), st));
   }
   for (int j = j0; j < j1; ++j) {
     if (arnoldi_step(op->d, w, shift ? shift : w.zero, V, ldv, j, H + (int64_t)j * ldh, brk, w.scal + 24, w.scal + 26,
@@ -1257,50 +1227,38 @@ int dsea_arnoldi_extend(dsea_op_t op, dsea_ws_t ws, const double* shift, double*
 }
 
 int dsea_ws_set_arnoldi_optimistic(dsea_ws_t ws, int on) {
-  if (!ws || (on != 0 && on != 1)) return DSEA_ERR_ARG;
+  REQUIRE(ws && (on == 0 || on == 1), DSEA_ERR_ARG);
   ws->w.arnoldi_optimistic = on;
   return DSEA_OK;
 }
 
 int dsea_arnoldi_status(dsea_ws_t ws, int* break_step, int* redo_step, void* stream) {
-  if (!ws) return DSEA_ERR_ARG;
+  REQUIRE(ws, DSEA_ERR_ARG);
   double h = 0.0;
   hipStream_t st = static_cast<hipStream_t>(stream);
   double* brk = ws->w.scal + DSEA_SCAL_BREAK;
-  if (hipMemcpyAsync(&h, brk, sizeof(h), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-    g_last_hip = (int)hipGetLastError();
-    return DSEA_ERR_HIP;
-  }
+  DSEA_TRY(read_to_host(&h, brk, sizeof(h), st));
   if (break_step) *break_step = h > 0.0 ? (int)h : 0;
   if (redo_step) *redo_step = -1;
   if (h < 0.0) {
     // optimistic mode: step -h - 1 needs its second Gram-Schmidt pass.  The record is cleared here so that the caller
     // can continue: repeat that step with the option off, then go on.
     if (redo_step) *redo_step = (int)(-h) - 1;
-    if (hipMemsetAsync(brk, 0, sizeof(double), st) != hipSuccess) {
-      g_last_hip = (int)hipGetLastError();
-      return DSEA_ERR_HIP;
-    }
+    HIP_TRY(hipMemsetAsync(brk, 0, sizeof(double), st));
     return DSEA_ERR_SECOND_PASS;
   }
   return h != 0.0 ? DSEA_ERR_BREAKDOWN : DSEA_OK;
 }
 
 int dsea_arnoldi_clear_record(dsea_ws_t ws, void* stream) {
-  if (!ws) return DSEA_ERR_ARG;
-  if (hipMemsetAsync(ws->w.scal + DSEA_SCAL_BREAK, 0, sizeof(double), static_cast<hipStream_t>(stream)) != hipSuccess) {
-    g_last_hip = (int)hipGetLastError();
-    return DSEA_ERR_HIP;
-  }
+  REQUIRE(ws, DSEA_ERR_ARG);
+  HIP_TRY(hipMemsetAsync(ws->w.scal + DSEA_SCAL_BREAK, 0, sizeof(double), static_cast<hipStream_t>(stream)));
   return DSEA_OK;
 }
 int dsea_arnoldi_status_enqueue(dsea_ws_t ws, double* host_record, void* stream) {
-  if (!ws || !host_record) return DSEA_ERR_ARG;
-  if (hipMemcpyAsync(host_record, ws->w.scal + DSEA_SCAL_BREAK, sizeof(double), hipMemcpyDeviceToHost,
-                     static_cast<hipStream_t>(stream)) != hipSuccess) {
-    g_last_hip = (int)hipGetLastError();
-    return DSEA_ERR_HIP;
-  }
+  REQUIRE(ws && host_record, DSEA_ERR_ARG);
+  HIP_TRY(hipMemcpyAsync(host_record, ws->w.scal + DSEA_SCAL_BREAK, sizeof(double), hipMemcpyDeviceToHost,
+                         static_cast<hipStream_t>(stream)));
   return DSEA_OK;
 }
 
@@ -1312,10 +1270,9 @@ int dsea_arnoldi_orth(dsea_ws_t ws, const double* u, const double* shift, double
   hipStream_t st = static_cast<hipStream_t>(stream);
   Workspace& w = ws->w;
   double* brk = w.scal + DSEA_SCAL_BREAK;
-  if (j == 0 && (hipMemsetAsync(brk, 0, 2 * sizeof(double), st) != hipSuccess ||
-                 hipMemsetAsync(w.scal + DSEA_SCAL_LZ_FAIL, 0, sizeof(double), st) != hipSuccess)) {
-    g_last_hip = (int)hipGetLastError();
-    return DSEA_ERR_HIP;
+  if (j == 0) {
+    HIP_TRY(hipMemsetAsync(brk, 0, 2 * sizeof(double), st));
+    HIP_TRY(hipMemsetAsync(w.scal + DSEA_SCAL_LZ_FAIL, 0, sizeof(double), st));
   }
   arnoldi_orth(w, n, u, shift ? shift : w.zero, V, ldv, j, H + (int64_t)j * ldh, brk, w.scal + 24, w.scal + 26,
                w.scal + 27, st);
@@ -1323,14 +1280,9 @@ int dsea_arnoldi_orth(dsea_ws_t ws, const double* u, const double* shift, double
 }
 
 int dsea_arnoldi_second_passes(dsea_ws_t ws, int64_t* count, void* stream) {
-  if (!ws || !count) return DSEA_ERR_ARG;
+  REQUIRE(ws && count, DSEA_ERR_ARG);
   double h = 0.0;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (hipMemcpyAsync(&h, ws->w.scal + 31, sizeof(h), hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipStreamSynchronize(st) != hipSuccess) {
-    g_last_hip = (int)hipGetLastError();
-    return DSEA_ERR_HIP;
-  }
+  DSEA_TRY(read_to_host(&h, ws->w.scal + 31, sizeof(h), static_cast<hipStream_t>(stream)));
   *count = (int64_t)h;
   return DSEA_OK;
 }
@@ -1433,14 +1385,9 @@ int dsea_gmres_cycle(dsea_op_t op, dsea_ws_t ws, const double* shift, const doub
 }
 
 int dsea_lanczos_status(dsea_ws_t ws, int* break_step, void* stream) {
-  if (!ws) return DSEA_ERR_ARG;
+  REQUIRE(ws, DSEA_ERR_ARG);
   double h[DSEA_SCAL_LZ_FAIL - DSEA_SCAL_BREAK + 1];
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (hipMemcpyAsync(h, ws->w.scal + DSEA_SCAL_BREAK, sizeof(h), hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipStreamSynchronize(st) != hipSuccess) {
-    g_last_hip = (int)hipGetLastError();
-    return DSEA_ERR_HIP;
-  }
+  DSEA_TRY(read_to_host(h, ws->w.scal + DSEA_SCAL_BREAK, sizeof(h), static_cast<hipStream_t>(stream)));
   if (break_step) *break_step = (int)h[0];
   if (h[DSEA_SCAL_LZ_FAIL - DSEA_SCAL_BREAK] != 0.0) return DSEA_ERR_TIMEOUT;   // single-launch form: a peer was lost
   return h[0] != 0.0 ? DSEA_ERR_BREAKDOWN : DSEA_OK;
@@ -1468,14 +1415,13 @@ int dsea_cg_run(dsea_op_t op, dsea_ws_t ws, const double* shift, const double* b
   // Its granule buffer lives in w.aux (the streaming form's partial buffers, unused there).  README-sized full-space
   // TFIM operators (n <= 8192): k_cg_persist_tfim, granules in the partial-sum area.
   const bool tfim_persist = w.persist_override != 0 && cg_persist_tfim_applicable(op->d) &&
-                            cg_persist_tfim_comm_bytes(n) <=
-                                (size_t)DSEA_MAX_WAVE_TILES * (size_t)((w.kmax < 1 ? 1 : w.kmax) + 1) * sizeof(double);
+                            cg_persist_tfim_comm_bytes(n) <= w.partials_bytes();
   // 2^11 ... 2^20 rows: k_cg_persist_tfim_big (iterates bit-identical to the streaming form; d double-buffered in the
   // workspace vectors the streaming form uses for d and A'd, granules in w.aux)
   const bool tfim_big = w.persist_override != 0 && cg_persist_tfim_big_applicable(op->d) &&
-                        cg_persist_tfim_big_comm_bytes(n) <= (size_t)4 * DSEA_MAX_WAVE_TILES * sizeof(double);
-  if (tfim_big || tfim_persist ||
-      (w.persist_override != 0 && persist_comm_bytes(n) <= (size_t)4 * DSEA_MAX_WAVE_TILES * sizeof(double))) {
+                        cg_persist_tfim_big_comm_bytes(n) <= w.aux_bytes();
+  double hs[DSEA_CG_STATE_LEN];
+  if (tfim_big || tfim_persist || (w.persist_override != 0 && persist_comm_bytes(n) <= w.aux_bytes())) {
     // (persist_override 200 = the two-exchange form whose iterates are bit-identical to the streaming kernels; default: the
     //  one-exchange form, csrc/dsea_cg_persist_tfim_big.hip MERGED)
     const int pr = tfim_big ? launch_cg_persist_tfim_big(op->d, shift, b, x, state, eps, maxiter, w.aux, d, Ad, st, w.lose_peer,
@@ -1483,26 +1429,14 @@ int dsea_cg_run(dsea_op_t op, dsea_ws_t ws, const double* shift, const double* b
                    : tfim_persist ? launch_cg_persist_tfim(op->d, shift, b, x, state, eps, maxiter, P, st, w.lose_peer)
                                   : launch_cg_persist(op->d, shift, b, x, state, eps, maxiter, w.aux,
                                                       (w.persist_override > 0 && w.persist_override != 200) ? w.persist_override : 0, st, w.lose_peer);
-    if (pr == -2) {
-      g_last_hip = (int)hipGetLastError();
-      return DSEA_ERR_HIP;
-    }
-    if (pr == 0) {
+    const int rc = persist_status(pr);
+    if (rc != PERSIST_SKIPPED) {
+      if (rc != DSEA_OK) return rc;
       const bool merged_form = tfim_big ? (w.persist_override != 200)
                                         : (!tfim_persist && w.persist_override >= 100 && w.persist_override != 200);
       w.last_cg_form = merged_form ? DSEA_CG_FORM_PERSISTENT_MERGED : DSEA_CG_FORM_PERSISTENT;
-      double hs[DSEA_CG_STATE_LEN];
-      if (hipMemcpyAsync(hs, state, sizeof(hs), hipMemcpyDeviceToHost, st) != hipSuccess ||
-          hipStreamSynchronize(st) != hipSuccess) {
-        g_last_hip = (int)hipGetLastError();
-        return DSEA_ERR_HIP;
-      }
-      if (iters_out) *iters_out = (int64_t)hs[DSEA_CG_ITERS];
-      if (resnorm_out) *resnorm_out = hs[DSEA_CG_RESNORM];
-      int rc0 = check_launch();
-      if (rc0 != DSEA_OK) return rc0;
-      if (hs[DSEA_CG_DONE] < 0.0) return DSEA_ERR_TIMEOUT;   // a workgroup of the persistent launch did not show up
-      return hs[DSEA_CG_DONE] != 0.0 ? DSEA_OK : DSEA_ERR_NOT_CONVERGED;
+      DSEA_TRY(read_to_host(hs, state, sizeof(hs), st));
+      return cg_result(hs, iters_out, resnorm_out);
     }
   }
 
@@ -1512,77 +1446,19 @@ int dsea_cg_run(dsea_op_t op, dsea_ws_t ws, const double* shift, const double* b
   if (nb < 0) return DSEA_ERR_UNSUPPORTED;
   launch_cg_init(b, Ad, r, d, state, n, P, st);
   launch_cg_init_check(state, eps, st);
-
-  double host_state[DSEA_CG_STATE_LEN];
-  int64_t issued = 0;
-  auto issue_chunk = [&]() -> int {      // the next <= poll_every iterations; returns how many were enqueued
-    const int64_t chunk = (maxiter - issued) < poll_every ? (maxiter - issued) : poll_every;
-    for (int64_t it = 0; it < chunk; ++it) {
-      const int parity = (int)((issued + it) & 1);
+  auto iterations = [&](int64_t first, int64_t count) -> int {
+    for (int64_t it = first; it < first + count; ++it) {
+      const int parity = (int)(it & 1);
       nb = launch_spmv(op->d, d, Ad, shift, done, dP, st);                              // A'd, d.A'd partials (CG.py:31/40)
       const int nr = launch_cg_update_fused(x, r, d, Ad, state, parity, dP, nb, n, rP, st);  // CG.py:31,33-34
       launch_cg_direction_fused(r, d, state, parity, rP, nr, eps, n, st);              // CG.py:35-39
     }
-    issued += chunk;
-    return (int)chunk;
+    return DSEA_OK;
   };
-  StatePoller* sp = state_poller();
-  if (sp) {
-    // Pipelined polling: chunk j + 1 is enqueued BEFORE the host looks at the state left by chunk j, so the device never
-    // idles across a host round trip (measured: ~55 us per poll at the headline size).  Launches issued after
-    // convergence are no-ops on the device (DONE flag), at most one chunk of them.
-    int slot = 0;
-    auto snapshot = [&](int sl) -> bool {
-      return hipMemcpyAsync(sp->pinned + sl * DSEA_CG_STATE_LEN, state, sizeof(host_state), hipMemcpyDeviceToHost, st) ==
-                 hipSuccess &&
-             hipEventRecord(sp->ev[sl], st) == hipSuccess;
-    };
-    bool okh = snapshot(slot);                 // the state after the initial residual (early out, CG.py:28-29)
-    while (okh) {
-      const bool more = issued < maxiter;
-      if (more) {
-        issue_chunk();
-        okh = snapshot(slot ^ 1);
-        if (!okh) break;
-      }
-      if (hipEventSynchronize(sp->ev[slot]) != hipSuccess) {
-        okh = false;
-        break;
-      }
-      memcpy(host_state, sp->pinned + slot * DSEA_CG_STATE_LEN, sizeof(host_state));
-      if (host_state[DSEA_CG_DONE] != 0.0 || !more) {
-        if (more) {   // one chunk was enqueued behind the converged state: wait for it, its snapshot is the final state
-          if (hipEventSynchronize(sp->ev[slot ^ 1]) != hipSuccess) {
-            okh = false;
-            break;
-          }
-          memcpy(host_state, sp->pinned + (slot ^ 1) * DSEA_CG_STATE_LEN, sizeof(host_state));
-        }
-        break;
-      }
-      slot ^= 1;
-    }
-    if (!okh) {
-      g_last_hip = (int)hipGetLastError();
-      return DSEA_ERR_HIP;
-    }
-  } else {
-    bool finished = false;
-    while (!finished) {
-      issue_chunk();
-      if (hipMemcpyAsync(host_state, state, sizeof(host_state), hipMemcpyDeviceToHost, st) != hipSuccess ||
-          hipStreamSynchronize(st) != hipSuccess) {
-        g_last_hip = (int)hipGetLastError();
-        return DSEA_ERR_HIP;
-      }
-      finished = (host_state[DSEA_CG_DONE] != 0.0) || issued >= maxiter;
-    }
-  }
-  if (iters_out) *iters_out = (int64_t)host_state[DSEA_CG_ITERS];
-  if (resnorm_out) *resnorm_out = host_state[DSEA_CG_RESNORM];
-  int rc = check_launch();
-  if (rc != DSEA_OK) return rc;
-  return host_state[DSEA_CG_DONE] != 0.0 ? DSEA_OK : DSEA_ERR_NOT_CONVERGED;
+  // pipelined polling where the runtime gives pinned memory and events (launches issued after convergence are no-ops on
+  // the device, at most one chunk of them), blocking otherwise
+  DSEA_TRY(cg_poll(state, hs, maxiter, poll_every, state_poller(), iterations, st));
+  return cg_result(hs, iters_out, resnorm_out);
 }
 
 
@@ -1668,44 +1544,32 @@ int dsea_cg_run_deflated(dsea_op_t op, dsea_ws_t ws, const double* shift, const 
   w.last_cg_form = DSEA_CG_FORM_STREAMING;
 
   double hs[DSEA_CG_STATE_LEN];
-  auto read_state = [&]() -> bool {
-    return hipMemcpyAsync(hs, state, sizeof(hs), hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
-  };
   // x <- P x ; r = P(b - A'x) ; d = r ; the stop flag on ||r||  (the entry, and the check of every stop the recurrence makes)
   auto restart = [&](int keep) -> int {
     launch_block_project(x, Psi, ldpsi, m, x, nullptr, n, w.partials, DSEA_MAX_WAVE_TILES, st);
     if (launch_spmv(op->d, x, Ad, shift, nullptr, nullptr, st) < 0) return DSEA_ERR_UNSUPPORTED;
     launch_dfl_restart(b, Ad, x, nullptr, Psi, ldpsi, m, r, d, state, eps, keep, n, w.partials, DSEA_MAX_WAVE_TILES, rP, st);
-    return read_state() ? DSEA_OK : DSEA_ERR_HIP;
+    return read_to_host(hs, state, sizeof(hs), st);
   };
-  int rc = restart(0);
-  int64_t issued = 0, local = 0;
-  while (rc == DSEA_OK && hs[DSEA_CG_DONE] == 0.0 && issued < maxiter) {
-    const int64_t chunk = (maxiter - issued) < poll_every ? (maxiter - issued) : poll_every;
-    for (int64_t it = 0; it < chunk; ++it, ++local) {
+  auto iterations = [&](int64_t first, int64_t count) -> int {   // (numbered from the last restart)
+    for (int64_t it = first; it < first + count; ++it) {
       const int nd = launch_spmv(op->d, d, Ad, shift, done, dP, st);                  // A'd, d.A'd partials
       if (nd < 0) return DSEA_ERR_UNSUPPORTED;
-      dfl_step(w, x, r, d, Ad, state, (int)(local & 1), eps, dP, nd, Psi, ldpsi, m, n, st);
+      dfl_step(w, x, r, d, Ad, state, (int)(it & 1), eps, dP, nd, Psi, ldpsi, m, n, st);
     }
-    issued += chunk;
-    if (!read_state()) rc = DSEA_ERR_HIP;
-    else if (hs[DSEA_CG_DONE] != 0.0) {   // the recurrence says converged: accept only on the recomputed true residual
-      rc = restart(1);
-      local = 0;
-    }
+    return DSEA_OK;
+  };
+  DSEA_TRY(restart(0));
+  int64_t issued = 0;
+  while (hs[DSEA_CG_DONE] == 0.0 && issued < maxiter) {
+    int64_t run = 0;
+    DSEA_TRY(cg_poll(state, hs, maxiter - issued, poll_every, nullptr, iterations, st, &run));
+    issued += run;
+    if (hs[DSEA_CG_DONE] != 0.0) DSEA_TRY(restart(1));   // the recurrence says converged: accept only on the recomputed true residual
   }
-  if (rc == DSEA_OK && hs[DSEA_CG_DONE] == 0.0)   // maxiter: leave x in range(P) all the same
+  if (hs[DSEA_CG_DONE] == 0.0)   // maxiter: leave x in range(P) all the same
     launch_block_project(x, Psi, ldpsi, m, x, nullptr, n, w.partials, DSEA_MAX_WAVE_TILES, st);
-  if (rc == DSEA_ERR_HIP) {
-    g_last_hip = (int)hipGetLastError();
-    return rc;
-  }
-  if (rc != DSEA_OK) return rc;
-  if (iters_out) *iters_out = (int64_t)hs[DSEA_CG_ITERS];
-  if (resnorm_out) *resnorm_out = hs[DSEA_CG_RESNORM];
-  rc = check_launch();
-  if (rc != DSEA_OK) return rc;
-  return hs[DSEA_CG_DONE] != 0.0 ? DSEA_OK : DSEA_ERR_NOT_CONVERGED;
+  return cg_result(hs, iters_out, resnorm_out);
 }
 
 }  // extern "C"

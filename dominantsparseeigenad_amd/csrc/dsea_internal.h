@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <functional>
+
 #include "../../include/dsea.h"
 
 #define DSEA_MAX_EW_BLOCKS 2048   /* grid cap of the grid-stride streaming kernels            */
@@ -160,7 +162,7 @@ struct Workspace {
   int partial_reorth;    // 1 = re-orthogonalise only when the omega recurrence says so (option; dsea_ws_set_partial_reorth)
   double pro_delta;      // its threshold on the estimated |q_i . q_k| (DSEA_PRO_DELTA_DEFAULT)
   double* partials;  // DSEA_MAX_WAVE_TILES * max(kmax,1) doubles (also >= DSEA_MAX_EW_BLOCKS)
-  double* aux;       // 4 * DSEA_MAX_WAVE_TILES doubles: small partial buffers that must not alias `partials`
+  double* aux;       // 6 * DSEA_MAX_WAVE_TILES doubles: small partial buffers that must not alias `partials`
   double* coef;      // kmax doubles
   double* coef2;     // second coefficient vector (Arnoldi: DGKS second pass)
   double* zero;      // one device double that is always 0
@@ -179,6 +181,10 @@ struct Workspace {
   int pend_count;
   double* pend_out;
   TileGeom geom(int64_t n_rows) const;
+  // what the single-launch kernels may borrow for their exchange buffers: the whole partial-sum area ((kmax + 1) rows, see
+  // ws_layout) and the first four rows of aux
+  size_t partials_bytes() const { return (size_t)DSEA_MAX_WAVE_TILES * (size_t)((kmax < 1 ? 1 : kmax) + 1) * sizeof(double); }
+  size_t aux_bytes() const { return (size_t)4 * DSEA_MAX_WAVE_TILES * sizeof(double); }
 };
 
 void launch_finalize1(const double* P, int count, double* out, hipStream_t st);
@@ -326,16 +332,67 @@ int launch_lanczos_persist_mid(const OpDesc& op, int k, const double* q0, double
 
 }  // namespace dsea
 
-// Host-side polling of the CG state without draining the stream (dsea_capi.hip): the state of chunk j is copied into
-// pinned memory behind an event while chunk j + 1 is already enqueued -- the device never waits for the host round trip
-// (the launches of a chunk issued after convergence are no-ops on the device: every CG kernel tests the DONE flag).
+// ---- the host layer's one error path (dsea_capi.hip, dsea_partitioned.hip) ----------------------------------------------
+#define REQUIRE(cond, code)     \
+  do {                          \
+    if (!(cond)) return (code); \
+  } while (0)
+#define DSEA_TRY(call)                \
+  do {                                \
+    const int rc__ = (call);          \
+    if (rc__ != DSEA_OK) return rc__; \
+  } while (0)
+#define HIP_TRY(call)                                   \
+  do {                                                  \
+    const hipError_t e__ = (call);                      \
+    if (e__ != hipSuccess) return dsea::hip_fail(e__); \
+  } while (0)
+
 namespace dsea {
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+// records e as this host thread's dsea_last_hip_error() (and clears the runtime's sticky copy); returns DSEA_ERR_HIP
+int hip_fail(hipError_t e);
+inline int check_launch() {
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? DSEA_OK : hip_fail(e);
+}
+// dst <- src (device to host) and wait for it
+inline int read_to_host(void* dst, const void* src, size_t bytes, hipStream_t st) {
+  HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return DSEA_OK;
+}
+// The answer of a persistent single-launch launcher: 0 = it ran, -2 = a HIP error (recorded here), anything else = it
+// does not apply and the caller goes on with the multi-launch kernels (PERSIST_SKIPPED, not a DSEA status).
+constexpr int PERSIST_SKIPPED = 1;
+inline int persist_status(int pr) { return pr == -2 ? hip_fail(hipGetLastError()) : pr == 0 ? DSEA_OK : PERSIST_SKIPPED; }
+// the operators whose mat-vec kernel also takes the Lanczos step's tail (launch_tfim_fused): both Lanczos entry points
+inline bool has_fused_tail(const OpDesc& op) {
+  return (op.kind == OP_TFIM && op.tfim.L_local >= 1) || (op.kind == OP_SELL && op.sell.mode == 0) ||
+         op.kind == OP_STENCIL3;
+}
+
+// Host-side polling of the CG state without draining the stream: the state of chunk j is copied into pinned memory
+// behind an event while chunk j + 1 is already enqueued -- the device never waits for the host round trip (the launches
+// of a chunk issued after convergence are no-ops on the device: every CG kernel tests the DONE flag).
 struct StatePoller {
   double* pinned;        // 2 x DSEA_CG_STATE_LEN doubles of page-locked host memory
   hipEvent_t ev[2];
   bool ok;
 };
 StatePoller* state_poller();   // per host thread, created on first use, nullptr if the runtime refuses
+// The CG polling loop of every driver (dsea_capi.hip).  enqueue(first, count) enqueues iterations [first, first + count)
+// (numbered from 0 in this call) and returns a DSEA status.  Chunks of <= poll_every iterations are issued until the
+// state copied to hs says DONE or `budget` iterations have been issued; *issued (optional) = how many.
+//   sp == nullptr: blocking -- the first chunk is always issued (the caller decides whether to start), the state is read
+//                  with a stream synchronisation after every chunk.
+//   sp:            pipelined -- the state is snapshot before the first chunk and after each one, and the snapshot of chunk
+//                  j is looked at only once chunk j + 1 is enqueued; after convergence at most one chunk of no-ops runs.
+int cg_poll(const double* state, double* hs, int64_t budget, int poll_every, StatePoller* sp,
+            const std::function<int(int64_t, int64_t)>& enqueue, hipStream_t st, int64_t* issued = nullptr);
+// the final host state as a status (DONE < 0: TIMEOUT, DONE != 0: OK, else NOT_CONVERGED) after a check of the launches;
+// fills iters_out / resnorm_out (optional)
+int cg_result(const double* hs, int64_t* iters_out, double* resnorm_out);
 }  // namespace dsea
 
 // the opaque handles of include/dsea.h

@@ -109,20 +109,9 @@ struct dsea_pop_s {
 };
 
 namespace {
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 #define NCCL_OK(call)                      \
   do {                                     \
     if ((call) != ncclSuccess) return DSEA_ERR_COMM; \
-  } while (0)
-#define DSEA_TRY(call)            \
-  do {                            \
-    int rc__ = (call);            \
-    if (rc__ != DSEA_OK) return rc__; \
-  } while (0)
-#define HIP_TRY(call)                       \
-  do {                                      \
-    if ((call) != hipSuccess) return DSEA_ERR_HIP; \
   } while (0)
 
 // ---- collectives on one communicator ------------------------------------------------------------------------------
@@ -317,14 +306,9 @@ int pop_cg_run_reference(dsea_pop_s* P, dsea_ws_t ws, const double* shift, const
   DSEA_TRY(comm_allreduce(P->comm, state + DSEA_CG_RR, 1, st));
   DSEA_TRY(dsea_cg_init_check(ws, state, eps, stream));
   double host_state[DSEA_CG_STATE_LEN];
-  int64_t issued = 0;
-  bool finished = false;
-  HIP_TRY(hipMemcpyAsync(host_state, state, sizeof(host_state), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  finished = host_state[DSEA_CG_DONE] != 0.0 || maxiter == 0;
-  while (!finished) {
-    const int64_t chunk = (maxiter - issued) < poll_every ? (maxiter - issued) : poll_every;
-    for (int64_t it = 0; it < chunk; ++it) {
+  DSEA_TRY(read_to_host(host_state, state, sizeof(host_state), st));
+  auto iterations = [&](int64_t, int64_t count) -> int {
+    for (int64_t it = 0; it < count; ++it) {
       DSEA_TRY(pop_apply(P, ws, d, Ad, shift, done, state + DSEA_CG_DAD, st));          // A'd, local d.A'd  (CG.py:31/40)
       DSEA_TRY(comm_allreduce(P->comm, state + DSEA_CG_DAD, 1, st));
       DSEA_TRY(dsea_cg_update(ws, x, r, d, Ad, state, n, stream));                       // CG.py:31,33-34
@@ -332,15 +316,12 @@ int pop_cg_run_reference(dsea_pop_s* P, dsea_ws_t ws, const double* shift, const
       DSEA_TRY(dsea_cg_check(ws, state, eps, stream));                                   // CG.py:35-38
       DSEA_TRY(dsea_cg_direction(ws, r, d, state, n, stream));                           // CG.py:39
     }
-    issued += chunk;
-    HIP_TRY(hipMemcpyAsync(host_state, state, sizeof(host_state), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    finished = (host_state[DSEA_CG_DONE] != 0.0) || issued >= maxiter;
-  }
-  if (iters_out) *iters_out = (int64_t)host_state[DSEA_CG_ITERS];
-  if (resnorm_out) *resnorm_out = host_state[DSEA_CG_RESNORM];
-  if (hipGetLastError() != hipSuccess) return DSEA_ERR_HIP;
-  return host_state[DSEA_CG_DONE] != 0.0 ? DSEA_OK : DSEA_ERR_NOT_CONVERGED;
+    return DSEA_OK;
+  };
+  // blocking polls: a chunk issued after convergence would still run its collectives
+  if (host_state[DSEA_CG_DONE] == 0.0 && maxiter > 0)
+    DSEA_TRY(cg_poll(state, host_state, maxiter, poll_every, nullptr, iterations, st));
+  return cg_result(host_state, iters_out, resnorm_out);
 }
 
 // ---- CG with ONE all-reduce per iteration (Chronopoulos-Gear; kernels: k_pcg_update / k_pcg_scalars) ------------------
@@ -375,6 +356,22 @@ int pop_cg_run_one_reduction(dsea_pop_s* P, dsea_ws_t ws, const double* shift, c
     explicit PendGuard(Workspace& ww) : w(ww) { w.pend_P = nullptr; }
     ~PendGuard() { w.pend_P = nullptr; }
   } pend_guard(w);
+  auto iterations = [&](int64_t, int64_t count) -> int {
+    for (int64_t it = 0; it < count; ++it) {
+      const int nb = launch_pcg_update(x, r, p, s, wv, state, n, rrP, st);
+      w.pend_P = rrP;                                             // closed by the mat-vec's own dot-closing launch
+      w.pend_count = nb;
+      w.pend_out = pair;
+      DSEA_TRY(pop_apply(P, ws, r, wv, shift, done, pair + 1, st));
+      if (w.pend_P) {
+        launch_finalize1(w.pend_P, w.pend_count, w.pend_out, st);
+        w.pend_P = nullptr;
+      }
+      DSEA_TRY(comm_allreduce(P->comm, pair, 2, st));
+      launch_pcg_scalars(state, pair, eps, 0, st);
+    }
+    return DSEA_OK;
+  };
   double host_state[DSEA_CG_STATE_LEN];
   int64_t total_iters = 0;
   for (int attempt = 0;; ++attempt) {
@@ -383,8 +380,7 @@ int pop_cg_run_one_reduction(dsea_pop_s* P, dsea_ws_t ws, const double* shift, c
     DSEA_TRY(dsea_cg_init(ws, b, wv, r, p, state, n, (void*)st));       // (p = r: what beta = 0 makes of it anyway)
     DSEA_TRY(comm_allreduce(P->comm, state + DSEA_CG_RR, 1, st));
     DSEA_TRY(dsea_cg_init_check(ws, state, eps, (void*)st));
-    HIP_TRY(hipMemcpyAsync(host_state, state, sizeof(host_state), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    DSEA_TRY(read_to_host(host_state, state, sizeof(host_state), st));
     if (host_state[DSEA_CG_DONE] != 0.0 || total_iters >= maxiter) break;
     if (attempt > DSEA_PCG_MAX_RESTARTS) {
       // the one-reduction recurrences keep stopping above the true tolerance: finish on the reference's
@@ -398,37 +394,14 @@ int pop_cg_run_one_reduction(dsea_pop_s* P, dsea_ws_t ws, const double* shift, c
     DSEA_TRY(pop_apply(P, ws, r, wv, shift, done, pair + 1, st));
     DSEA_TRY(comm_allreduce(P->comm, pair + 1, 1, st));
     launch_pcg_scalars(state, pair, eps, 1, st);
-    int64_t issued = 0;
-    const int64_t budget = maxiter - total_iters;
-    bool finished = false;
-    while (!finished) {
-      const int64_t chunk = (budget - issued) < poll_every ? (budget - issued) : poll_every;
-      for (int64_t it = 0; it < chunk; ++it) {
-        const int nb = launch_pcg_update(x, r, p, s, wv, state, n, rrP, st);
-        w.pend_P = rrP;                                             // closed by the mat-vec's own dot-closing launch
-        w.pend_count = nb;
-        w.pend_out = pair;
-        DSEA_TRY(pop_apply(P, ws, r, wv, shift, done, pair + 1, st));
-        if (w.pend_P) {
-          launch_finalize1(w.pend_P, w.pend_count, w.pend_out, st);
-          w.pend_P = nullptr;
-        }
-        DSEA_TRY(comm_allreduce(P->comm, pair, 2, st));
-        launch_pcg_scalars(state, pair, eps, 0, st);
-      }
-      issued += chunk;
-      HIP_TRY(hipMemcpyAsync(host_state, state, sizeof(host_state), hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipStreamSynchronize(st));
-      finished = (host_state[DSEA_CG_DONE] != 0.0) || issued >= budget;
-    }
+    DSEA_TRY(cg_poll(state, host_state, maxiter - total_iters, poll_every, nullptr, iterations, st));   // (blocking, as above)
     total_iters += (int64_t)host_state[DSEA_CG_ITERS];
     if (host_state[DSEA_CG_DONE] == 0.0) break;                     // iteration budget spent
     // the recursive residual passed the test: the next round's first step recomputes the true one and decides
   }
+  const int rc = cg_result(host_state, nullptr, resnorm_out);
   if (iters_out) *iters_out = total_iters;
-  if (resnorm_out) *resnorm_out = host_state[DSEA_CG_RESNORM];
-  if (hipGetLastError() != hipSuccess) return DSEA_ERR_HIP;
-  return host_state[DSEA_CG_DONE] != 0.0 ? DSEA_OK : DSEA_ERR_NOT_CONVERGED;
+  return rc;
 }
 }  // namespace
 
@@ -584,10 +557,11 @@ int dsea_pop_create_tfim(int L, dsea_comm_t comm, const double* g_dev, double g_
   }
   P->side = static_cast<hipStream_t>(side_stream);
   if (P->side) {
-    if (hipEventCreateWithFlags(&P->ev_ready, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&P->ev_done, hipEventDisableTiming) != hipSuccess) {
+    hipError_t e = hipEventCreateWithFlags(&P->ev_ready, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&P->ev_done, hipEventDisableTiming);
+    if (e != hipSuccess) {
       delete P;
-      return DSEA_ERR_HIP;
+      return hip_fail(e);
     }
   }
   *out = P;
@@ -652,7 +626,7 @@ int dsea_pop_sddmm(dsea_pop_t P, const int64_t* rowptr, const double* v1, const 
     DSEA_TRY(sell_halo_exchange(P, v1, st));
     if (launch_sddmm(P->local.d, rowptr, v2, v1, 0.5 * alpha, 1, false, out, st) != 0) return DSEA_ERR_UNSUPPORTED;
   }
-  return hipGetLastError() == hipSuccess ? DSEA_OK : DSEA_ERR_HIP;
+  return check_launch();
 }
 
 int dsea_pop_destroy(dsea_pop_t P) {
@@ -802,15 +776,13 @@ int dsea_pop_lanczos_run(dsea_pop_t P, dsea_ws_t ws, int k, const double* q0, do
                                stream));
     }
   }
-  return hipGetLastError() == hipSuccess ? DSEA_OK : DSEA_ERR_HIP;
+  return check_launch();
 }
 
 int dsea_pop_lanczos_status(dsea_pop_t P, dsea_ws_t ws, int* step, void* stream) {
   if (!P || !ws) return DSEA_ERR_ARG;
   double h = 0.0;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  HIP_TRY(hipMemcpyAsync(&h, ws->w.scal + 34, sizeof(h), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
+  DSEA_TRY(read_to_host(&h, ws->w.scal + 34, sizeof(h), static_cast<hipStream_t>(stream)));
   if (step) *step = (int)h;
   return h != 0.0 ? DSEA_ERR_PREMISE : DSEA_OK;
 }

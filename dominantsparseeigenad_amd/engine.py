@@ -411,6 +411,20 @@ class PartialNeedsPhases(NotImplementedError):
     run through the phase calls (Lanczos._lanczos_core does)"""
 
 
+def _repeat_on_timeout(run, lose_persist, warning):
+    """run() -> the status of a native solve that may take a persistent single-launch form.  On a device shared with other
+    work the bounded spins of that form give up and report ERR_TIMEOUT instead of hanging: warn, make the fallback to the
+    multi-launch kernels STICKY for the workspace (lose_persist(): every later solve would otherwise wait out the same
+    timeout again) and run once more."""
+    rc = run()
+    if rc == _lib.ERR_TIMEOUT:
+        import warnings
+        warnings.warn(warning, RuntimeWarning)
+        lose_persist()
+        rc = run()
+    return rc
+
+
 # --------------------------------------------------------------------------- Lanczos
 def lanczos(A, k, n, device, q0, native=None, callable_A=None, arena=False):
     """k-step Lanczos on the GPU (reference Lanczos.py:49-77).
@@ -460,27 +474,25 @@ def lanczos(A, k, n, device, q0, native=None, callable_A=None, arena=False):
                     (1 if LANCZOS_PERSIST == "force" else (2 if LANCZOS_PERSIST == "small" else -1))
                 if ws.lanczos_persist_mode != want:
                     ws.set_lanczos_persist(want)
-                rc0 = lib.dsea_lanczos_run(native.handle, ws.handle, int(k), _ptr(q0), _ptr(Q), ldq, _ptr(alphas),
-                                           _ptr(betas), st)
-                if partial and rc0 == _lib.ERR_UNSUPPORTED:
-                    # an operand without a fused Lanczos tail (plain CSR, dense): the option runs through the phase calls
-                    raise PartialNeedsPhases("operand without a fused tail")
-                check(rc0, "dsea_lanczos_run")
                 brk = ctypes.c_int(0)
-                rc = lib.dsea_lanczos_status(ws.handle, byref(brk), st)
-                if rc == _lib.ERR_TIMEOUT:
-                    # the single-launch form (README-sized problems) needs its <= 64 workgroups resident together; on a
-                    # device shared with other work its bounded spins give up.  Repeat with the multi-launch kernels and
-                    # keep this workspace on them (``ws.lanczos_persist_lost = False`` re-enables the single-launch form).
-                    import warnings
-                    warnings.warn("single-launch Lanczos timed out waiting for a peer workgroup (device shared with "
-                                  "other work?): repeating the run with the multi-launch kernels, which this workspace "
-                                  "keeps using from now on", RuntimeWarning)
+
+                def run():
+                    rc0 = lib.dsea_lanczos_run(native.handle, ws.handle, int(k), _ptr(q0), _ptr(Q), ldq, _ptr(alphas),
+                                               _ptr(betas), st)
+                    if partial and rc0 == _lib.ERR_UNSUPPORTED:
+                        # an operand without a fused Lanczos tail (plain CSR, dense): the option runs through the phase calls
+                        raise PartialNeedsPhases("operand without a fused tail")
+                    check(rc0, "dsea_lanczos_run")
+                    return lib.dsea_lanczos_status(ws.handle, byref(brk), st)
+
+                def lose_persist():
+                    # (``ws.lanczos_persist_lost = False`` re-enables the single-launch form)
                     ws.lanczos_persist_lost = True
                     ws.set_lanczos_persist(0)
-                    check(lib.dsea_lanczos_run(native.handle, ws.handle, int(k), _ptr(q0), _ptr(Q), ldq, _ptr(alphas),
-                                               _ptr(betas), st), "dsea_lanczos_run")
-                    rc = lib.dsea_lanczos_status(ws.handle, byref(brk), st)
+                # the single-launch form (README-sized problems) needs its <= 64 workgroups resident together
+                rc = _repeat_on_timeout(run, lose_persist, "single-launch Lanczos timed out waiting for a peer workgroup "
+                                        "(device shared with other work?): repeating the run with the multi-launch kernels, "
+                                        "which this workspace keeps using from now on")
                 check(rc, "dsea_lanczos_status", allow=(_lib.ERR_BREAKDOWN,))
                 last_break = int(brk.value)
                 if partial:
@@ -754,24 +766,23 @@ def cg(b, x0, *, native=None, callable_A=None, shift=None, eps=1e-7, maxiter=Non
                 ws.set_persist(100)
             elif CG_TFIM_REFERENCE_RECURRENCES and prev_mode == -1:
                 ws.set_persist(200)
+
+            def run():
+                return lib.dsea_cg_run(native.handle, ws.handle, _ptr(shift_t), _ptr(b), _ptr(x), _ptr(state), float(eps),
+                                       cap, int(poll_every), byref(iters), byref(res), st)
+
+            def lose_persist():
+                # (``ws.set_persist(-1)`` re-enables the persistent form)
+                nonlocal prev_mode
+                x.copy_(as_vector(x0, n))
+                ws.set_persist(0)
+                prev_mode = 0
             try:
-                rc = lib.dsea_cg_run(native.handle, ws.handle, _ptr(shift_t), _ptr(b), _ptr(x), _ptr(state), float(eps),
-                                     cap, int(poll_every), byref(iters), byref(res), st)
-                if rc == _lib.ERR_TIMEOUT:
-                    # The persistent single-launch form needs all of its workgroups resident at the same time; if other
-                    # work holds compute units (e.g. a second persistent solve on another stream) its bounded spins
-                    # give up and report instead of hanging.  The solve is repeated in the streaming form, and the
-                    # fallback is STICKY for this workspace: on a shared device every later solve would otherwise wait
-                    # out the same timeout again (``ws.set_persist(-1)`` re-enables the persistent form).
-                    import warnings
-                    warnings.warn("persistent CG launch timed out waiting for a peer workgroup (device shared with "
-                                  "other work?): repeating the solve with the streaming kernels, which this workspace "
-                                  "keeps using from now on", RuntimeWarning)
-                    x.copy_(as_vector(x0, n))
-                    ws.set_persist(0)
-                    prev_mode = 0
-                    rc = lib.dsea_cg_run(native.handle, ws.handle, _ptr(shift_t), _ptr(b), _ptr(x), _ptr(state),
-                                         float(eps), cap, int(poll_every), byref(iters), byref(res), st)
+                # the persistent single-launch form needs all of its workgroups resident at the same time (e.g. a second
+                # persistent solve on another stream holds compute units)
+                rc = _repeat_on_timeout(run, lose_persist, "persistent CG launch timed out waiting for a peer workgroup "
+                                        "(device shared with other work?): repeating the solve with the streaming kernels, "
+                                        "which this workspace keeps using from now on")
             finally:
                 if (merged or CG_TFIM_REFERENCE_RECURRENCES) and prev_mode == -1:
                     ws.set_persist(-1)
