@@ -127,54 +127,29 @@ __global__ __launch_bounds__(W * 64) void k_ritz_block_split(const double* __res
   }
 }
 
-template <int RPL, int M>
-static void ritzb_launch(const double* Q, int64_t ldq, int64_t n, int k, const double* S, int64_t lds, double* Y,
-                         int64_t ldy, hipStream_t st) {
-  int64_t ntiles = (n + 64 * RPL - 1) / (64 * RPL);
-  if (ntiles < 1) ntiles = 1;
-  const int nw = (int)(ntiles < DSEA_MAX_WAVE_TILES ? ntiles : DSEA_MAX_WAVE_TILES);
-  hipLaunchKernelGGL((k_ritz_block<RPL, M>), dim3((nw + 3) / 4), dim3(256), 0, st, Q, ldq, k, n, S, lds, Y, ldy, nw,
-                     ntiles);
-}
-
-template <int M>
-static void ritzb_tiled(int rpl, const double* Q, int64_t ldq, int64_t n, int k, const double* S, int64_t lds,
-                        double* Y, int64_t ldy, hipStream_t st) {
-  // accumulator registers: M * RPL doubles per lane, kept at <= 32
-  constexpr int CAP = M <= 2 ? 16 : (M <= 4 ? 8 : 4);
-  const int r = rpl < CAP ? rpl : CAP;
-  if (r <= 2) {
-    ritzb_launch<2, M>(Q, ldq, n, k, S, lds, Y, ldy, st);
-  } else if (r == 4) {
-    ritzb_launch<4, M>(Q, ldq, n, k, S, lds, Y, ldy, st);
-  } else if (r == 8) {
-    if constexpr (CAP >= 8) ritzb_launch<8, M>(Q, ldq, n, k, S, lds, Y, ldy, st);
-  } else {
-    if constexpr (CAP >= 16) ritzb_launch<16, M>(Q, ldq, n, k, S, lds, Y, ldy, st);
-  }
-}
-
 void launch_ritz_block(const TileGeom& g, const double* Q, int64_t ldq, int64_t n, int k, const double* S, int64_t lds,
                        int m, double* Y, int64_t ldy, hipStream_t st) {
   if (g.split_w) {
-    const unsigned tiles = (unsigned)g.ntiles;
-    switch (g.split_w) {
-      case 4: hipLaunchKernelGGL((k_ritz_block_split<4>), dim3(tiles), dim3(256), 0, st, Q, ldq, k, n, S, lds, m, Y, ldy); break;
-      case 8: hipLaunchKernelGGL((k_ritz_block_split<8>), dim3(tiles), dim3(512), 0, st, Q, ldq, k, n, S, lds, m, Y, ldy); break;
-      default: hipLaunchKernelGGL((k_ritz_block_split<16>), dim3(tiles), dim3(1024), 0, st, Q, ldq, k, n, S, lds, m, Y, ldy); break;
-    }
+    dispatch_split_w(g.split_w, [&](auto w) {
+      constexpr int W = decltype(w)::value;
+      klaunch(nullptr, k_ritz_block_split<W>, (unsigned)g.ntiles, W * 64, 0, st, Q, ldq, k, n, S, lds, m, Y, ldy);
+    });
     return;
   }
-  switch (m) {
-    case 1: ritzb_tiled<1>(g.rpl, Q, ldq, n, k, S, lds, Y, ldy, st); break;
-    case 2: ritzb_tiled<2>(g.rpl, Q, ldq, n, k, S, lds, Y, ldy, st); break;
-    case 3: ritzb_tiled<3>(g.rpl, Q, ldq, n, k, S, lds, Y, ldy, st); break;
-    case 4: ritzb_tiled<4>(g.rpl, Q, ldq, n, k, S, lds, Y, ldy, st); break;
-    case 5: ritzb_tiled<5>(g.rpl, Q, ldq, n, k, S, lds, Y, ldy, st); break;
-    case 6: ritzb_tiled<6>(g.rpl, Q, ldq, n, k, S, lds, Y, ldy, st); break;
-    case 7: ritzb_tiled<7>(g.rpl, Q, ldq, n, k, S, lds, Y, ldy, st); break;
-    default: ritzb_tiled<8>(g.rpl, Q, ldq, n, k, S, lds, Y, ldy, st); break;
-  }
+  dispatch_int<1, 2, 3, 4, 5, 6, 7, 8>(m, [&](auto cols) {
+    constexpr int M = decltype(cols)::value;
+    // accumulator registers: M * RPL doubles per lane, kept at <= 32
+    constexpr int CAP = M <= 2 ? 16 : (M <= 4 ? 8 : 4);
+    dispatch_rpl(g.rpl < CAP ? g.rpl : CAP, [&](auto rpl) {
+      constexpr int RPL = decltype(rpl)::value;
+      if constexpr (RPL <= CAP) {
+        int64_t ntiles = (n + 64 * RPL - 1) / (64 * RPL);
+        if (ntiles < 1) ntiles = 1;
+        const int nw = (int)(ntiles < DSEA_MAX_WAVE_TILES ? ntiles : DSEA_MAX_WAVE_TILES);
+        klaunch(nullptr, k_ritz_block<RPL, M>, (nw + 3) / 4, 256, 0, st, Q, ldq, k, n, S, lds, Y, ldy, nw, ntiles);
+      }
+    });
+  });
 }
 
 // ------------------------------------------------------------------------------------------

@@ -2,10 +2,12 @@
 #ifndef DSEA_INTERNAL_H
 #define DSEA_INTERNAL_H
 
+#include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <functional>
+#include <type_traits>
 
 #include "../../include/dsea.h"
 
@@ -132,12 +134,48 @@ struct TileGeom {
   int dots_nt;     // ... and 128-row sub-tiles per block (1 or 2); partial count = ceil(ntiles / dots_nt)
 };
 
+// Run-time value -> template argument, the one way every launcher picks an instantiation: f(int_c<V>{}) for the V equal
+// to v, the LAST value listed when none is (the `default:` of a switch); dispatch_bool likewise.  In f,
+// decltype(arg)::value is the compile-time value.
+template <int V>
+using int_c = std::integral_constant<int, V>;
+template <int V, int... Rest, class F>
+inline void dispatch_int(int v, F&& f) {
+  if constexpr (sizeof...(Rest) == 0) {
+    f(int_c<V>{});
+  } else {
+    if (v == V) f(int_c<V>{});
+    else dispatch_int<Rest...>(v, f);
+  }
+}
+template <class F>
+inline void dispatch_bool(bool b, F&& f) {
+  if (b) f(std::true_type{});
+  else f(std::false_type{});
+}
+// the two ladders of the basis-streaming kernels (TileGeom): rows per lane, and waves per block of the split form
+template <class F>
+inline void dispatch_rpl(int rpl, F&& f) { dispatch_int<2, 4, 8, 16>(rpl, f); }
+template <class F>
+inline void dispatch_split_w(int w, F&& f) { dispatch_int<4, 8, 16>(w, f); }
+
 // optional per-launch HIP-event timing of the dominant kernels (bench.py roofline); host objects only
 enum ProfKind { PROF_RDOTS = 0, PROF_AXPY = 1, PROF_SPMV = 2, PROF_KINDS = 3 };
 struct EventPair {
   hipEvent_t a, b;
   int kind;
 };
+// Launch, optionally with a start/stop event pair attached to the dispatch itself (hipExtLaunchKernelGGL): the events
+// then carry the kernel's own begin/end timestamps, i.e. the same duration a profiler reports.  The arguments are
+// converted to the kernel's parameter types here (a bare nullptr or int is fine at the call site).
+template <class... Params, class... Args>
+inline void klaunch(EventPair* ev, void (*kernel)(Params...), dim3 grid, dim3 block, size_t lds, hipStream_t st,
+                    Args&&... args) {
+  if (ev)
+    hipExtLaunchKernelGGL(kernel, grid, block, lds, st, ev->a, ev->b, 0, static_cast<Params>(args)...);
+  else
+    hipLaunchKernelGGL(kernel, grid, block, lds, st, static_cast<Params>(args)...);
+}
 struct Profiler {
   EventPair* pairs;
   int capacity, used;

@@ -511,6 +511,18 @@ __global__ __launch_bounds__(W * 64) void k_axpy_norm_split(const double* __rest
 //
 // Geometry: a lane owns RPS groups of 8 consecutive rows (one 16-byte shadow load each); a wave tile is
 // 512*RPS rows.  j runs downwards (most recently streamed vectors first).
+
+// w[e] += cj * (shadow value e of h), fp64 arithmetic
+__device__ __forceinline__ void fma_shadow8(double (&w)[8], double cj, uint4 h) {
+  w[0] = fma(cj, bf16lo_to_f64(h.x), w[0]);
+  w[1] = fma(cj, bf16hi_to_f64(h.x), w[1]);
+  w[2] = fma(cj, bf16lo_to_f64(h.y), w[2]);
+  w[3] = fma(cj, bf16hi_to_f64(h.y), w[3]);
+  w[4] = fma(cj, bf16lo_to_f64(h.z), w[4]);
+  w[5] = fma(cj, bf16hi_to_f64(h.z), w[5]);
+  w[6] = fma(cj, bf16lo_to_f64(h.w), w[6]);
+  w[7] = fma(cj, bf16hi_to_f64(h.w), w[7]);
+}
 template <int RPS, bool GUARD>
 __device__ __forceinline__ double axpy_lp_tile(const double* __restrict__ Q, int64_t ldq,
                                                const uint16_t* __restrict__ Qs, int64_t lds, int i,
@@ -547,14 +559,7 @@ __device__ __forceinline__ double axpy_lp_tile(const double* __restrict__ Q, int
             if (row + e < n) t[e >> 1] |= (uint32_t)qj[row + e] << ((e & 1) * 16);
           h = make_uint4(t[0], t[1], t[2], t[3]);
         }
-        w[s][0] = fma(cj, bf16lo_to_f64(h.x), w[s][0]);
-        w[s][1] = fma(cj, bf16hi_to_f64(h.x), w[s][1]);
-        w[s][2] = fma(cj, bf16lo_to_f64(h.y), w[s][2]);
-        w[s][3] = fma(cj, bf16hi_to_f64(h.y), w[s][3]);
-        w[s][4] = fma(cj, bf16lo_to_f64(h.z), w[s][4]);
-        w[s][5] = fma(cj, bf16hi_to_f64(h.z), w[s][5]);
-        w[s][6] = fma(cj, bf16lo_to_f64(h.w), w[s][6]);
-        w[s][7] = fma(cj, bf16hi_to_f64(h.w), w[s][7]);
+        fma_shadow8(w[s], cj, h);
       }
     }
   } else {
@@ -680,16 +685,7 @@ __global__ __launch_bounds__(W * 64) void k_axpy_norm_lp_split(const double* __r
         }
       }
 #pragma unroll
-      for (int v = 0; v < LPV; ++v) {
-        w[0] = fma(cj[v], bf16lo_to_f64(h[v].x), w[0]);
-        w[1] = fma(cj[v], bf16hi_to_f64(h[v].x), w[1]);
-        w[2] = fma(cj[v], bf16lo_to_f64(h[v].y), w[2]);
-        w[3] = fma(cj[v], bf16hi_to_f64(h[v].y), w[3]);
-        w[4] = fma(cj[v], bf16lo_to_f64(h[v].z), w[4]);
-        w[5] = fma(cj[v], bf16hi_to_f64(h[v].z), w[5]);
-        w[6] = fma(cj[v], bf16lo_to_f64(h[v].w), w[6]);
-        w[7] = fma(cj[v], bf16hi_to_f64(h[v].w), w[7]);
-      }
+      for (int v = 0; v < LPV; ++v) fma_shadow8(w, cj[v], h[v]);
     } else {
       for (int v = 0; v < LPV; ++v) {
         if (j0 + v >= i) break;
@@ -2782,33 +2778,21 @@ static inline int tile_blocks(int64_t n) {
   return nt <= DSEA_PERSIST_MAX_TILES ? (int)(nt < 1 ? 1 : nt) : ew_blocks(n);
 }
 
-// Launch, optionally with a start/stop event pair attached to the dispatch itself (hipExtLaunchKernelGGL):
-// the events then carry the kernel's own begin/end timestamps, i.e. the same duration a profiler reports.
-#define KLAUNCH(ev, KERNEL, grid, block, stream, ...)                                              \
-  do {                                                                                             \
-    if (ev)                                                                                        \
-      hipExtLaunchKernelGGL(KERNEL, dim3(grid), dim3(block), 0, stream, (ev)->a, (ev)->b, 0, __VA_ARGS__); \
-    else                                                                                           \
-      hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(block), 0, stream, __VA_ARGS__);                 \
-  } while (0)
-
-#define KLAUNCH_LDS(ev, KERNEL, grid, block, lds, stream, ...)                                     \
-  do {                                                                                             \
-    if (ev)                                                                                        \
-      hipExtLaunchKernelGGL(KERNEL, dim3(grid), dim3(block), lds, stream, (ev)->a, (ev)->b, 0, __VA_ARGS__); \
-    else                                                                                           \
-      hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(block), lds, stream, __VA_ARGS__);               \
-  } while (0)
-
-#define LAUNCH_RPL(ev, KERNEL, rpl, grid, block, lds, stream, ...)                                \
-  do {                                                                                            \
-    switch (rpl) {                                                                                \
-      case 2: KLAUNCH_LDS(ev, (KERNEL<2>), grid, block, lds, stream, __VA_ARGS__); break;         \
-      case 4: KLAUNCH_LDS(ev, (KERNEL<4>), grid, block, lds, stream, __VA_ARGS__); break;         \
-      case 8: KLAUNCH_LDS(ev, (KERNEL<8>), grid, block, lds, stream, __VA_ARGS__); break;         \
-      default: KLAUNCH_LDS(ev, (KERNEL<16>), grid, block, lds, stream, __VA_ARGS__); break;       \
-    }                                                                                             \
-  } while (0)
+// the grid rules of the operator kernels, each stated once
+static inline int sell_blocks(const SellParams& p) {   // four 64-row slices (one per wave) to a block
+  int64_t nb = (p.nslices + 3) / 4;
+  if (nb > DSEA_MAX_TFIM_BLOCKS) nb = DSEA_MAX_TFIM_BLOCKS;
+  if (nb < 1) nb = 1;
+  return (int)nb;
+}
+static inline int tfim_blocks(const TfimParams& p, int T) {   // one tile of 2^T rows per block
+  int64_t nb = ((int64_t)1 << p.L_local) >> T;
+  if (nb > DSEA_MAX_TFIM_BLOCKS) nb = DSEA_MAX_TFIM_BLOCKS;  // blocks then walk several tiles
+  return (int)nb;
+}
+// dots pass, wave-owned form: one row of i + 1 partial sums per wave in LDS (see rdots_tile); 64 KiB of dynamic LDS hold
+// 4 waves up to i = 2047, 2 waves up to 4095, 1 wave up to 8191 (dsea_ws_create caps kmax at DSEA_MAX_KRYLOV = 8000)
+static inline int rdots_waves_per_block(int i) { return (i + 1) <= 2048 ? 4 : ((i + 1) <= 4096 ? 2 : 1); }
 
 // ------------------------------------------------------------------------------------------
 // Partial re-orthogonalisation (Simon 1984; an OPTION -- the reference re-orthogonalises on every step, Lanczos.py:66).
@@ -2897,127 +2881,77 @@ void launch_rdots(const TileGeom& g, const double* Q, int64_t ldq, int64_t n, in
                   hipStream_t st, EventPair* ev, const double* aP, int aCount, double* a_store, bool want_rr,
                   double* brk, const double* sel, bool sel_exit, const double* uscale) {
   // (uscale: wave-owned geometry without the partial re-orthogonalisation gate only -- callers check rdots_uscale_ok)
+  const int wr = want_rr ? 1 : 0;
+  const int count = rdots_partial_count(g, i);
   if (g.split_w) {
-    const int wr = want_rr ? 1 : 0;
-    const size_t slds = (size_t)(i + 1) * sizeof(double);     // the tile's partial sums (see k_rdots_split)
-    const int nt = g.dots_nt;
-    const unsigned tiles = (unsigned)((g.ntiles + nt - 1) / nt);
-#define RDS(Wv, NTv)                                                                                                         \
-  do {                                                                                                                       \
-    if (sel)                                                                                                                 \
-      KLAUNCH_LDS(ev, (k_rdots_split<Wv, NTv, true>), tiles, Wv * 64, slds, st, Q, ldq, i, n, u, alpha, beta, r, P,          \
-                  (int64_t)g.pstride, aP, aCount, a_store, wr, brk, sel, sel_exit ? 1 : 0);                                  \
-    else                                                                                                                     \
-      KLAUNCH_LDS(ev, (k_rdots_split<Wv, NTv, false>), tiles, Wv * 64, slds, st, Q, ldq, i, n, u, alpha, beta, r, P,         \
-                  (int64_t)g.pstride, aP, aCount, a_store, wr, brk, sel, 0);                                                 \
-  } while (0)
-    if (nt == 2) {
-      RDS(16, 2);
-    } else {
-      switch (g.dots_w) {
-        case 4: RDS(4, 1); break;
-        case 8: RDS(8, 1); break;
-        default: RDS(16, 1); break;
-      }
-    }
-#undef RDS
-    if (c_out && sel_exit)
-      hipLaunchKernelGGL(k_finalize_multi<true>, dim3(want_rr ? i + 1 : i), dim3(256), 0, st, (const double*)P,
-                         (int64_t)g.pstride, (int)tiles, c_out, (const double*)brk, sel);
-    else if (c_out)
-      hipLaunchKernelGGL(k_finalize_multi<false>, dim3(want_rr ? i + 1 : i), dim3(256), 0, st, (const double*)P,
-                         (int64_t)g.pstride, (int)tiles, c_out, (const double*)brk, (const double*)nullptr);
-    return;
-  }
-  // one row of i + 1 partial sums per wave in LDS (see rdots_tile); 64 KiB of dynamic LDS hold 4 waves up to
-  // i = 2047, 2 waves up to 4095, 1 wave up to 8191 (dsea_ws_create caps kmax at DSEA_MAX_KRYLOV = 8000)
-  const int wpb = (i + 1) <= 2048 ? 4 : ((i + 1) <= 4096 ? 2 : 1);
-  const int grid = (g.nw + wpb - 1) / wpb;
-  const size_t lds = (size_t)wpb * (i + 1) * sizeof(double);
-  if (sel) {
-    switch (g.rpl) {
-      case 2: KLAUNCH_LDS(ev, (k_rdots<2, true>), grid, 64 * wpb, lds, st, Q, ldq, i, n, u, alpha, beta, r, P, (int64_t)g.pstride, g.nw,
-             g.ntiles, aP, aCount, a_store, want_rr ? 1 : 0, brk, sel, sel_exit ? 1 : 0, (const double*)nullptr); break;
-      case 4: KLAUNCH_LDS(ev, (k_rdots<4, true>), grid, 64 * wpb, lds, st, Q, ldq, i, n, u, alpha, beta, r, P, (int64_t)g.pstride, g.nw,
-             g.ntiles, aP, aCount, a_store, want_rr ? 1 : 0, brk, sel, sel_exit ? 1 : 0, (const double*)nullptr); break;
-      case 8: KLAUNCH_LDS(ev, (k_rdots<8, true>), grid, 64 * wpb, lds, st, Q, ldq, i, n, u, alpha, beta, r, P, (int64_t)g.pstride, g.nw,
-             g.ntiles, aP, aCount, a_store, want_rr ? 1 : 0, brk, sel, sel_exit ? 1 : 0, (const double*)nullptr); break;
-      default: KLAUNCH_LDS(ev, (k_rdots<16, true>), grid, 64 * wpb, lds, st, Q, ldq, i, n, u, alpha, beta, r, P, (int64_t)g.pstride, g.nw,
-             g.ntiles, aP, aCount, a_store, want_rr ? 1 : 0, brk, sel, sel_exit ? 1 : 0, (const double*)nullptr); break;
-    }
-  } else if (uscale) {
-    switch (g.rpl) {
-      case 2: KLAUNCH_LDS(ev, (k_rdots<2, false, true>), grid, 64 * wpb, lds, st, Q, ldq, i, n, u, alpha, beta, r, P, (int64_t)g.pstride,
-             g.nw, g.ntiles, aP, aCount, a_store, want_rr ? 1 : 0, brk, sel, 0, uscale); break;
-      case 4: KLAUNCH_LDS(ev, (k_rdots<4, false, true>), grid, 64 * wpb, lds, st, Q, ldq, i, n, u, alpha, beta, r, P, (int64_t)g.pstride,
-             g.nw, g.ntiles, aP, aCount, a_store, want_rr ? 1 : 0, brk, sel, 0, uscale); break;
-      case 8: KLAUNCH_LDS(ev, (k_rdots<8, false, true>), grid, 64 * wpb, lds, st, Q, ldq, i, n, u, alpha, beta, r, P, (int64_t)g.pstride,
-             g.nw, g.ntiles, aP, aCount, a_store, want_rr ? 1 : 0, brk, sel, 0, uscale); break;
-      default: KLAUNCH_LDS(ev, (k_rdots<16, false, true>), grid, 64 * wpb, lds, st, Q, ldq, i, n, u, alpha, beta, r, P, (int64_t)g.pstride,
-             g.nw, g.ntiles, aP, aCount, a_store, want_rr ? 1 : 0, brk, sel, 0, uscale); break;
-    }
+    const size_t lds = (size_t)(i + 1) * sizeof(double);     // the tile's partial sums (see k_rdots_split)
+    auto go = [&](auto w, auto nt) {
+      dispatch_bool(sel != nullptr, [&](auto s) {
+        constexpr int W = decltype(w)::value;
+        constexpr bool SEL = decltype(s)::value;
+        klaunch(ev, k_rdots_split<W, decltype(nt)::value, SEL>, count, W * 64, lds, st, Q, ldq, i, n, u, alpha, beta, r,
+                P, g.pstride, aP, aCount, a_store, wr, brk, sel, SEL && sel_exit ? 1 : 0);
+      });
+    };
+    if (g.dots_nt == 2) go(int_c<16>{}, int_c<2>{});
+    else dispatch_split_w(g.dots_w, [&](auto w) { go(w, int_c<1>{}); });
   } else {
-    LAUNCH_RPL(ev, k_rdots, g.rpl, grid, 64 * wpb, lds, st, Q, ldq, i, n, u, alpha, beta, r, P, (int64_t)g.pstride, g.nw,
-             g.ntiles, aP, aCount, a_store, want_rr ? 1 : 0, brk, sel, sel_exit ? 1 : 0, (const double*)nullptr);
+    const int wpb = rdots_waves_per_block(i);
+    const size_t lds = (size_t)wpb * (i + 1) * sizeof(double);
+    // the instantiations: plain, SEL (partial re-orthogonalisation gate), USCALE (without the gate only)
+    dispatch_int<1, 2, 0>(sel ? 1 : (uscale ? 2 : 0), [&](auto variant) {
+      dispatch_rpl(g.rpl, [&](auto rpl) {
+        constexpr bool SEL = decltype(variant)::value == 1, USCALE = decltype(variant)::value == 2;
+        klaunch(ev, k_rdots<decltype(rpl)::value, SEL, USCALE>, count, 64 * wpb, lds, st, Q, ldq, i, n, u, alpha, beta, r,
+                P, g.pstride, g.nw, g.ntiles, aP, aCount, a_store, wr, brk, sel, !USCALE && sel_exit ? 1 : 0,
+                USCALE ? uscale : nullptr);
+      });
+    });
   }
   // want_rr: one more row of partials (||r||^2) -> c_out[i]
   // (c_out null: the caller's next kernel sums the partial rows it needs itself -- rdots_partial_count of them)
-  if (c_out && sel_exit)
-    hipLaunchKernelGGL(k_finalize_multi<true>, dim3(want_rr ? i + 1 : i), dim3(256), 0, st, (const double*)P,
-                       (int64_t)g.pstride, grid, c_out, (const double*)brk, sel);
-  else if (c_out)
-    hipLaunchKernelGGL(k_finalize_multi<false>, dim3(want_rr ? i + 1 : i), dim3(256), 0, st, (const double*)P,
-                       (int64_t)g.pstride, grid, c_out, (const double*)brk, (const double*)nullptr);
+  if (c_out)
+    dispatch_bool(sel_exit, [&](auto gate) {
+      constexpr bool GATE = decltype(gate)::value;
+      klaunch(nullptr, k_finalize_multi<GATE>, want_rr ? i + 1 : i, 256, 0, st, P, g.pstride, count, c_out, brk,
+              GATE ? sel : nullptr);
+    });
 }
 
 // partials per basis vector the dots pass of step i leaves in P (row stride g.pstride)
 int rdots_partial_count(const TileGeom& g, int i) {
   if (g.split_w) return (int)((g.ntiles + g.dots_nt - 1) / g.dots_nt);
-  const int wpb = (i + 1) <= 2048 ? 4 : ((i + 1) <= 4096 ? 2 : 1);
+  const int wpb = rdots_waves_per_block(i);
   return (g.nw + wpb - 1) / wpb;
+}
+
+// r -= Q[0..i) c with the partial ||r||^2 (MODE 0: the correction pass), or out = Q[0..k) s (MODE 1: the Ritz combine,
+// which has no gate and no partials)
+template <int MODE>
+static void launch_axpy_family(const TileGeom& g, const double* Q, int64_t ldq, int64_t n, int i, const double* c,
+                               double* r, double* P, hipStream_t st, EventPair* ev, const double* brk,
+                               const double* sel) {
+  auto go = [&](auto s) {
+    constexpr bool SEL = decltype(s)::value;
+    if (g.split_w)
+      dispatch_split_w(g.split_w, [&](auto w) {
+        constexpr int W = decltype(w)::value;
+        klaunch(ev, k_axpy_norm_split<W, MODE, SEL>, (unsigned)g.ntiles, W * 64, 0, st, Q, ldq, i, n, c, r, P, brk, sel);
+      });
+    else
+      dispatch_rpl(g.rpl, [&](auto rpl) {
+        klaunch(ev, k_axpy_norm<decltype(rpl)::value, MODE, SEL>, (g.nw + 3) / 4, 256, 0, st, Q, ldq, i, n, c, r, P, g.nw,
+                g.ntiles, brk, sel);
+      });
+  };
+  if constexpr (MODE == 0) dispatch_bool(sel != nullptr, go);
+  else go(std::false_type{});
 }
 
 void launch_axpy_norm(const TileGeom& g, const double* Q, int64_t ldq, int64_t n, int i, const double* c,
                       double* r, double* P, double* nrm2_out, hipStream_t st, EventPair* ev, const double* brk,
                       const double* sel) {
-  if (g.split_w) {
-    const unsigned tiles = (unsigned)g.ntiles;
-#define AXS(Wv, SELv) KLAUNCH(ev, (k_axpy_norm_split<Wv, 0, SELv>), tiles, Wv * 64, st, Q, ldq, i, n, c, r, P, brk, sel)
-    if (sel) {
-      switch (g.split_w) {
-        case 4: AXS(4, true); break;
-        case 8: AXS(8, true); break;
-        default: AXS(16, true); break;
-      }
-    } else {
-      switch (g.split_w) {
-        case 4: AXS(4, false); break;
-        case 8: AXS(8, false); break;
-        default: AXS(16, false); break;
-      }
-    }
-#undef AXS
-    if (nrm2_out) launch_finalize1(P, g.nw, nrm2_out, st);
-    return;
-  }
-  const int grid = (g.nw + 3) / 4;
-#define AXN(Rv, SELv) KLAUNCH(ev, (k_axpy_norm<Rv, 0, SELv>), grid, 256, st, Q, ldq, i, n, c, r, P, g.nw, g.ntiles, brk, sel)
-  if (sel) {
-    switch (g.rpl) {
-      case 2: AXN(2, true); break;
-      case 4: AXN(4, true); break;
-      case 8: AXN(8, true); break;
-      default: AXN(16, true); break;
-    }
-  } else {
-    switch (g.rpl) {
-      case 2: AXN(2, false); break;
-      case 4: AXN(4, false); break;
-      case 8: AXN(8, false); break;
-      default: AXN(16, false); break;
-    }
-  }
-#undef AXN
+  launch_axpy_family<0>(g, Q, ldq, n, i, c, r, P, st, ev, brk, sel);
   if (nrm2_out) launch_finalize1(P, g.nw, nrm2_out, st);  // null: the consumer sums the g.nw partials itself
 }
 
@@ -3027,43 +2961,23 @@ int launch_axpy_norm_lp(int64_t n, int rps, const double* Q, int64_t ldq, const 
                         EventPair* ev, const double* brk) {
   if (rps == 0) {   // small-n split form: one block of 16 waves per 512-row tile
     const int64_t nt = (n + 511) / 512;
-    KLAUNCH(ev, (k_axpy_norm_lp_split<16>), (unsigned)nt, 1024, st, Q, ldq, Qs, lds, i, n, c, tau * tau, r, P, lp_count, brk);
+    klaunch(ev, k_axpy_norm_lp_split<16>, (unsigned)nt, 1024, 0, st, Q, ldq, Qs, lds, i, n, c, tau * tau, r, P, lp_count, brk);
     return (int)nt;
   }
   const int64_t tile = 512 * (int64_t)rps;
   int64_t ntiles = (n + tile - 1) / tile;
   if (ntiles < 1) ntiles = 1;
   const int nw = (int)(ntiles < DSEA_MAX_WAVE_TILES ? ntiles : DSEA_MAX_WAVE_TILES);
-  const int grid = (nw + 3) / 4;
-  const double tau2 = tau * tau;
-  if (rps == 1)
-    KLAUNCH(ev, (k_axpy_norm_lp<1>), grid, 256, st, Q, ldq, Qs, lds, i, n, c, tau2, r, P, nw, ntiles, lp_count, brk);
-  else
-    KLAUNCH(ev, (k_axpy_norm_lp<2>), grid, 256, st, Q, ldq, Qs, lds, i, n, c, tau2, r, P, nw, ntiles, lp_count, brk);
+  dispatch_int<1, 2>(rps, [&](auto rows) {
+    klaunch(ev, k_axpy_norm_lp<decltype(rows)::value>, (nw + 3) / 4, 256, 0, st, Q, ldq, Qs, lds, i, n, c, tau * tau, r, P,
+            nw, ntiles, lp_count, brk);
+  });
   return nw;
 }
 
 void launch_ritz(const TileGeom& g, const double* Q, int64_t ldq, int64_t n, int k, const double* s,
                  double* out, hipStream_t st) {
-  double* nullP = nullptr;
-  const double* nullc = nullptr;
-  if (g.split_w) {
-    const unsigned tiles = (unsigned)g.ntiles;
-    EventPair* ev = nullptr;
-    switch (g.split_w) {
-      case 4: KLAUNCH(ev, (k_axpy_norm_split<4, 1>), tiles, 256, st, Q, ldq, k, n, s, out, nullP, nullc, nullc); break;
-      case 8: KLAUNCH(ev, (k_axpy_norm_split<8, 1>), tiles, 512, st, Q, ldq, k, n, s, out, nullP, nullc, nullc); break;
-      default: KLAUNCH(ev, (k_axpy_norm_split<16, 1>), tiles, 1024, st, Q, ldq, k, n, s, out, nullP, nullc, nullc); break;
-    }
-    return;
-  }
-  const int grid = (g.nw + 3) / 4;
-  switch (g.rpl) {
-    case 2: hipLaunchKernelGGL((k_axpy_norm<2, 1>), dim3(grid), dim3(256), 0, st, Q, ldq, k, n, s, out, nullP, g.nw, g.ntiles, nullc, nullc); break;
-    case 4: hipLaunchKernelGGL((k_axpy_norm<4, 1>), dim3(grid), dim3(256), 0, st, Q, ldq, k, n, s, out, nullP, g.nw, g.ntiles, nullc, nullc); break;
-    case 8: hipLaunchKernelGGL((k_axpy_norm<8, 1>), dim3(grid), dim3(256), 0, st, Q, ldq, k, n, s, out, nullP, g.nw, g.ntiles, nullc, nullc); break;
-    default: hipLaunchKernelGGL((k_axpy_norm<16, 1>), dim3(grid), dim3(256), 0, st, Q, ldq, k, n, s, out, nullP, g.nw, g.ntiles, nullc, nullc); break;
-  }
+  launch_axpy_family<1>(g, Q, ldq, n, k, s, out, nullptr, st, nullptr, nullptr, nullptr);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -3190,29 +3104,61 @@ void launch_cg_direction(const double* r, double* d, const double* state, int64_
   hipLaunchKernelGGL(k_cg_direction, dim3(ew_blocks(n)), dim3(256), 0, st, r, d, state, n);
 }
 
+// The TFIM mat-vec of one tile size, plain or with the Lanczos tail (fa); returns the number of partials or -1
+template <bool FUSED>
+static int launch_tfim(const OpDesc& op, const double* x, double* y, const double* shift, const double* skip, double* P,
+                       const TfimFusedArgs& fa, hipStream_t st, EventPair* ev) {
+  const TfimParams& p = op.tfim;
+  const int T = p.L_local < op.tune_tile_log2 ? p.L_local : op.tune_tile_log2;
+  if (T < 1 || T > 12) return -1;
+  const int nb = tfim_blocks(p, T);
+  dispatch_int<1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12>(T, [&](auto t) {
+    klaunch(ev, k_spmv_tfim<decltype(t)::value, FUSED>, nb, 256, 0, st, p, x, y, shift, skip, P, fa);
+  });
+  return nb;
+}
+
+// The SELL mat-vec: which kernel serves which storage form, plain or with the Lanczos tail (fa).  The fused tail exists
+// for mode 0 only (has_fused_tail), so the slab modes are not instantiated for it.  Returns the number of partials.
+template <bool FUSED>
+static int launch_sell(const OpDesc& op, const double* x, double* y, const double* shift, const double* skip, double* P,
+                       const TfimFusedArgs& fa, hipStream_t st, EventPair* ev) {
+  const SellParams& p = op.sell;
+  const int nb = sell_blocks(p);
+  auto go = [&](auto kernel) { klaunch(ev, kernel, nb, 256, 0, st, p, x, y, shift, skip, P, fa); };
+  auto pick = [&](auto mode) {
+    constexpr int M = decltype(mode)::value;
+    if (p.pack2) {
+      go(k_spmv_sell<FUSED, M, 8, true, false, false, true>);
+    } else if constexpr (M != 0) {
+      if (p.col16) go(k_spmv_sell<FUSED, M, 8, true>);
+      else go(k_spmv_sell<FUSED, M, 4, false>);
+    } else if (p.col16) {
+      if (p.code8) go(k_spmv_sell<FUSED, 0, 8, true, false, true>);
+      else if (p.nt) go(k_spmv_sell<FUSED, 0, 8, true, true>);
+      else go(k_spmv_sell<FUSED, 0, 8, true>);
+    } else if (op.tune_sell_unroll == 1) {
+      go(k_spmv_sell_r5<FUSED>);
+    } else {
+      dispatch_int<2, 8, 4>(op.tune_sell_unroll, [&](auto un) { go(k_spmv_sell<FUSED, 0, decltype(un)::value, false>); });
+    }
+  };
+  if constexpr (FUSED) pick(int_c<0>{});
+  else dispatch_int<1, 2, 0>(p.mode, pick);
+  return nb;
+}
+
 // returns the number of partials written (0 when P == nullptr)
 int launch_spmv(const OpDesc& op, const double* x, double* y, const double* shift, const double* skip,
                 double* P, hipStream_t st, EventPair* ev) {
+  const TfimFusedArgs plain = {nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0};
   switch (op.kind) {
     case OP_TFIM: {
-      const TfimParams& p = op.tfim;
-      if (p.L_local == 0) {
-        KLAUNCH(ev, k_spmv_tfim_single, 1, 1, st, p, x, y, shift, skip, P);
+      if (op.tfim.L_local == 0) {
+        klaunch(ev, k_spmv_tfim_single, 1, 1, 0, st, op.tfim, x, y, shift, skip, P);
         return 1;
       }
-      const int T = p.L_local < op.tune_tile_log2 ? p.L_local : op.tune_tile_log2;
-      int64_t nb = ((int64_t)1 << p.L_local) >> T;
-      if (nb > DSEA_MAX_TFIM_BLOCKS) nb = DSEA_MAX_TFIM_BLOCKS;  // blocks then walk several tiles
-      TfimFusedArgs fa = {nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0};
-#define TFIM_CASE(TT) \
-  case TT: KLAUNCH(ev, (k_spmv_tfim<TT, false>), (unsigned)nb, 256, st, p, x, y, shift, skip, P, fa); break;
-      switch (T) {
-        TFIM_CASE(1) TFIM_CASE(2) TFIM_CASE(3) TFIM_CASE(4) TFIM_CASE(5) TFIM_CASE(6)
-        TFIM_CASE(7) TFIM_CASE(8) TFIM_CASE(9) TFIM_CASE(10) TFIM_CASE(11) TFIM_CASE(12)
-        default: return -1;
-      }
-#undef TFIM_CASE
-      return (int)nb;
+      return launch_tfim<false>(op, x, y, shift, skip, P, plain, st, ev);
     }
     case OP_CSR: {
       const CsrParams& p = op.csr;
@@ -3221,7 +3167,7 @@ int launch_spmv(const OpDesc& op, const double* x, double* y, const double* shif
         // typical sparse operators (a few to ~48 non-zeros per row): coalesced streaming form
         int64_t nbs = (p.n + CSR_ROWS - 1) / CSR_ROWS;
         if (nbs > DSEA_MAX_TFIM_BLOCKS) nbs = DSEA_MAX_TFIM_BLOCKS;
-        KLAUNCH(ev, k_spmv_csr_stream, (unsigned)nbs, 256, st, p, x, y, shift, skip, P);
+        klaunch(ev, k_spmv_csr_stream, (unsigned)nbs, 256, 0, st, p, x, y, shift, skip, P);
         return (int)nbs;
       }
       int G = 4;
@@ -3231,52 +3177,19 @@ int launch_spmv(const OpDesc& op, const double* x, double* y, const double* shif
       int64_t nb = (p.n + rows_per_block - 1) / rows_per_block;
       if (nb > DSEA_MAX_EW_BLOCKS) nb = DSEA_MAX_EW_BLOCKS;
       if (nb < 1) nb = 1;
-      switch (G) {
-        case 4: KLAUNCH(ev, (k_spmv_csr<4>), (unsigned)nb, 256, st, p, x, y, shift, skip, P); break;
-        case 8: KLAUNCH(ev, (k_spmv_csr<8>), (unsigned)nb, 256, st, p, x, y, shift, skip, P); break;
-        case 16: KLAUNCH(ev, (k_spmv_csr<16>), (unsigned)nb, 256, st, p, x, y, shift, skip, P); break;
-        case 32: KLAUNCH(ev, (k_spmv_csr<32>), (unsigned)nb, 256, st, p, x, y, shift, skip, P); break;
-        default: KLAUNCH(ev, (k_spmv_csr<64>), (unsigned)nb, 256, st, p, x, y, shift, skip, P); break;
-      }
+      dispatch_int<4, 8, 16, 32, 64>(G, [&](auto group) {
+        klaunch(ev, k_spmv_csr<decltype(group)::value>, (unsigned)nb, 256, 0, st, p, x, y, shift, skip, P);
+      });
       return (int)nb;
     }
-    case OP_SELL: {
-      const SellParams& p = op.sell;
-      int64_t nb = (p.nslices + 3) / 4;
-      if (nb > DSEA_MAX_TFIM_BLOCKS) nb = DSEA_MAX_TFIM_BLOCKS;
-      if (nb < 1) nb = 1;
-      TfimFusedArgs fa0 = {nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0};
-#define SELL_GO(F, M, U, C) KLAUNCH(ev, (k_spmv_sell<F, M, U, C>), (unsigned)nb, 256, st, p, x, y, shift, skip, P, fa0)
-      const bool c16 = p.col16 != nullptr;
-#define SELL_P2(M) KLAUNCH(ev, (k_spmv_sell<false, M, 8, true, false, false, true>), (unsigned)nb, 256, st, p, x, y, shift, skip, P, fa0)
-      if (p.pack2) {
-        if (p.mode == 1) SELL_P2(1); else if (p.mode == 2) SELL_P2(2); else SELL_P2(0);
-      } else if (p.mode == 1) {
-        if (c16) SELL_GO(false, 1, 8, true); else SELL_GO(false, 1, 4, false);
-      } else if (p.mode == 2) {
-        if (c16) SELL_GO(false, 2, 8, true); else SELL_GO(false, 2, 4, false);
-      } else if (c16) {
-        if (p.code8) KLAUNCH(ev, (k_spmv_sell<false, 0, 8, true, false, true>), (unsigned)nb, 256, st, p, x, y, shift, skip, P, fa0);
-        else if (p.nt) KLAUNCH(ev, (k_spmv_sell<false, 0, 8, true, true>), (unsigned)nb, 256, st, p, x, y, shift, skip, P, fa0);
-        else SELL_GO(false, 0, 8, true);
-      } else {
-        switch (op.tune_sell_unroll) {
-          case 1: KLAUNCH(ev, (k_spmv_sell_r5<false>), (unsigned)nb, 256, st, p, x, y, shift, skip, P, fa0); break;
-          case 2: SELL_GO(false, 0, 2, false); break;
-          case 8: SELL_GO(false, 0, 8, false); break;
-          default: SELL_GO(false, 0, 4, false);
-        }
-      }
-#undef SELL_GO
-#undef SELL_P2
-      return (int)nb;
-    }
+    case OP_SELL:
+      return launch_sell<false>(op, x, y, shift, skip, P, plain, st, ev);
     case OP_SYMDENSE: {
       const SymDenseParams& p = op.symdense;
       if (p.elem == 4)
-        KLAUNCH(ev, k_symv_upper<float>, dim3(p.nb, p.nb), 256, st, p, x, skip);
+        klaunch(ev, k_symv_upper<float>, dim3(p.nb, p.nb), 256, 0, st, p, x, skip);
       else
-        KLAUNCH(ev, k_symv_upper<double>, dim3(p.nb, p.nb), 256, st, p, x, skip);
+        klaunch(ev, k_symv_upper<double>, dim3(p.nb, p.nb), 256, 0, st, p, x, skip);
       int64_t nbr = p.nb;
       if (nbr > DSEA_MAX_EW_BLOCKS) nbr = DSEA_MAX_EW_BLOCKS;
       hipLaunchKernelGGL(k_symv_reduce, dim3((unsigned)nbr), dim3(256), 0, st, p, x, y, shift, skip, P);
@@ -3292,11 +3205,9 @@ int launch_spmv(const OpDesc& op, const double* x, double* y, const double* shif
       return P ? nbk : 0;
     }
     case OP_STENCIL3: {
-      const Stencil3Params& p = op.st3;
-      const int64_t nb = tile_blocks(p.n);
-      TfimFusedArgs fa0 = {nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0};
-      KLAUNCH(ev, (k_spmv_stencil3<false>), (unsigned)nb, 256, st, p, x, y, shift, skip, P, fa0);
-      return (int)nb;
+      const int nb = tile_blocks(op.st3.n);
+      klaunch(ev, k_spmv_stencil3<false>, nb, 256, 0, st, op.st3, x, y, shift, skip, P, plain);
+      return nb;
     }
   }
   return -1;
@@ -3308,62 +3219,25 @@ int launch_spmv(const OpDesc& op, const double* x, double* y, const double* shif
 int launch_tfim_fused(const OpDesc& op, const double* r, const double* nP, int nCount, double* q_out, double* y,
                       double* beta_store, double* P, hipStream_t st, EventPair* ev, uint16_t* qs_out, double* brk,
                       int step) {
-  TfimFusedArgs fa = {nP, nCount, q_out, qs_out, beta_store, brk, step};
-  const double* nullc = nullptr;
-  if (op.kind == OP_SELL) {
-    const SellParams& p = op.sell;
-    int64_t nb = (p.nslices + 3) / 4;
-    if (nb > DSEA_MAX_TFIM_BLOCKS) nb = DSEA_MAX_TFIM_BLOCKS;
-    if (p.mode != 0) return -1;                         // slab of a row-partitioned matrix: the unfused sequence
-#define SELL_GO(U, C) KLAUNCH(ev, (k_spmv_sell<true, 0, U, C>), (unsigned)nb, 256, st, p, r, y, nullc, nullc, P, fa)
-    if (p.pack2) {
-      KLAUNCH(ev, (k_spmv_sell<true, 0, 8, true, false, false, true>), (unsigned)nb, 256, st, p, r, y, nullc, nullc, P, fa);
-    } else if (p.col16) {
-      if (p.code8) KLAUNCH(ev, (k_spmv_sell<true, 0, 8, true, false, true>), (unsigned)nb, 256, st, p, r, y, nullc, nullc, P, fa);
-      else if (p.nt) KLAUNCH(ev, (k_spmv_sell<true, 0, 8, true, true>), (unsigned)nb, 256, st, p, r, y, nullc, nullc, P, fa);
-      else SELL_GO(8, true);
-    } else {
-      switch (op.tune_sell_unroll) {
-        case 1: KLAUNCH(ev, (k_spmv_sell_r5<true>), (unsigned)nb, 256, st, p, r, y, nullc, nullc, P, fa); break;
-        case 2: SELL_GO(2, false); break;
-        case 8: SELL_GO(8, false); break;
-        default: SELL_GO(4, false);
-      }
+  if (!has_fused_tail(op)) return -1;
+  const TfimFusedArgs fa = {nP, nCount, q_out, qs_out, beta_store, brk, step};
+  switch (op.kind) {
+    case OP_SELL: return launch_sell<true>(op, r, y, nullptr, nullptr, P, fa, st, ev);
+    case OP_TFIM: return launch_tfim<true>(op, r, y, nullptr, nullptr, P, fa, st, ev);
+    default: {   // OP_STENCIL3
+      const int nb = tile_blocks(op.st3.n);
+      klaunch(ev, k_spmv_stencil3<true>, nb, 256, 0, st, op.st3, r, y, nullptr, nullptr, P, fa);
+      return nb;
     }
-#undef SELL_GO
-    return (int)nb;
   }
-  if (op.kind == OP_STENCIL3) {
-    const Stencil3Params& p = op.st3;
-    const int64_t nb = tile_blocks(p.n);
-    KLAUNCH(ev, (k_spmv_stencil3<true>), (unsigned)nb, 256, st, p, r, y, nullc, nullc, P, fa);
-    return (int)nb;
-  }
-  if (op.kind != OP_TFIM) return -1;
-  const TfimParams& p = op.tfim;
-  if (p.L_local == 0) return -1;  // callers use the unfused sequence for a 1-row slab
-  const int T = p.L_local < op.tune_tile_log2 ? p.L_local : op.tune_tile_log2;
-  int64_t nb = ((int64_t)1 << p.L_local) >> T;
-  if (nb > DSEA_MAX_TFIM_BLOCKS) nb = DSEA_MAX_TFIM_BLOCKS;
-#define TFIM_FCASE(TT) \
-  case TT: KLAUNCH(ev, (k_spmv_tfim<TT, true>), (unsigned)nb, 256, st, p, r, y, nullc, nullc, P, fa); break;
-  switch (T) {
-    TFIM_FCASE(1) TFIM_FCASE(2) TFIM_FCASE(3) TFIM_FCASE(4) TFIM_FCASE(5) TFIM_FCASE(6)
-    TFIM_FCASE(7) TFIM_FCASE(8) TFIM_FCASE(9) TFIM_FCASE(10) TFIM_FCASE(11) TFIM_FCASE(12)
-    default: return -1;
-  }
-#undef TFIM_FCASE
-  return (int)nb;
 }
 
 // explicit-matrix operand as a parameter: refresh of the SELL copy / sampled outer product, CSR order through rowptr
 int launch_sell_update_vals(const OpDesc& op, const int64_t* rowptr, const double* vals_csr, hipStream_t st) {
   const SellParams& p = op.sell;
-  int64_t nb = (p.nslices + 3) / 4;
-  if (nb > DSEA_MAX_TFIM_BLOCKS) nb = DSEA_MAX_TFIM_BLOCKS;
   const int cap = sell_seg_cap(p);
-  hipLaunchKernelGGL(k_sell_update_vals, dim3((unsigned)nb), dim3(256), (size_t)cap * 4 * sizeof(double), st, p, rowptr, vals_csr,
-                     const_cast<double*>(p.vals), cap);
+  hipLaunchKernelGGL(k_sell_update_vals, dim3(sell_blocks(p)), dim3(256), (size_t)cap * 4 * sizeof(double), st, p, rowptr,
+                     vals_csr, const_cast<double*>(p.vals), cap);
   return 0;
 }
 
@@ -3371,22 +3245,14 @@ int launch_sddmm(const OpDesc& op, const int64_t* rowptr, const double* v1, cons
                  bool sym, double* out, hipStream_t st) {
   if (op.kind == OP_SELL) {
     const SellParams& p = op.sell;
-    int64_t nb = (p.nslices + 3) / 4;
-    if (nb > DSEA_MAX_TFIM_BLOCKS) nb = DSEA_MAX_TFIM_BLOCKS;
+    if (sym && p.mode != 0) return -1;                    // (the slab driver issues two one-sided launches instead)
     const int cap = sell_seg_cap(p);
-#define SDDMM_CASE(M, S)                                                                                                  \
-  hipLaunchKernelGGL((k_sell_sddmm<M, S>), dim3((unsigned)nb), dim3(256), (size_t)cap * 4 * sizeof(double), st, p, rowptr, v1, v2, \
-                     alpha, accumulate, out, cap)
-    if (p.mode == 0) {
-      if (sym) SDDMM_CASE(0, true); else SDDMM_CASE(0, false);
-    } else if (sym) {
-      return -1;                                        // (the slab driver issues two one-sided launches instead)
-    } else if (p.mode == 1) {
-      SDDMM_CASE(1, false);
-    } else {
-      SDDMM_CASE(2, false);
-    }
-#undef SDDMM_CASE
+    auto go = [&](auto kernel) {
+      klaunch(nullptr, kernel, sell_blocks(p), 256, (size_t)cap * 4 * sizeof(double), st, p, rowptr, v1, v2, alpha,
+              accumulate, out, cap);
+    };
+    if (sym) go(k_sell_sddmm<0, true>);
+    else dispatch_int<0, 1, 2>(p.mode, [&](auto mode) { go(k_sell_sddmm<decltype(mode)::value, false>); });
     return 0;
   }
   if (op.kind == OP_CSR) {
@@ -3394,8 +3260,9 @@ int launch_sddmm(const OpDesc& op, const int64_t* rowptr, const double* v1, cons
     int64_t nb = (p.n + 31) / 32;
     if (nb > DSEA_MAX_EW_BLOCKS) nb = DSEA_MAX_EW_BLOCKS;
     if (nb < 1) nb = 1;
-    if (sym) hipLaunchKernelGGL(k_csr_sddmm<true>, dim3((unsigned)nb), dim3(256), 0, st, p, v1, v2, alpha, accumulate, out);
-    else hipLaunchKernelGGL(k_csr_sddmm<false>, dim3((unsigned)nb), dim3(256), 0, st, p, v1, v2, alpha, accumulate, out);
+    dispatch_bool(sym, [&](auto s) {
+      klaunch(nullptr, k_csr_sddmm<decltype(s)::value>, (unsigned)nb, 256, 0, st, p, v1, v2, alpha, accumulate, out);
+    });
     return 0;
   }
   return -1;
@@ -3553,15 +3420,12 @@ int launch_cg_persist(const OpDesc& op, const double* shift, const double* b, do
   a.ntiles = (int)nt;
   a.lose_peer = lose_peer;
   const size_t lds = (size_t)(tpw * 512 + 4) * sizeof(double) + (merged ? sizeof(PersistSmM) : sizeof(PersistSm));
-#define PERSIST_CASE(P, V)                                                                                      \
-  if (ppt == P && nvb == V) {                                                                                   \
-    if (merged)                                                                                                 \
-      hipLaunchKernelGGL((k_cg_persist_stencil_merged<P, V>), dim3(G), dim3(256 * V), lds, st, a);              \
-    else                                                                                                        \
-      hipLaunchKernelGGL((k_cg_persist_stencil<P, V>), dim3(G), dim3(256 * V), lds, st, a);                     \
-  }
-  PERSIST_CASE(1, 4) PERSIST_CASE(2, 4) PERSIST_CASE(1, 2) PERSIST_CASE(2, 2) PERSIST_CASE(1, 1) PERSIST_CASE(2, 1)
-#undef PERSIST_CASE
+  dispatch_int<1, 2>(ppt, [&](auto pairs) {
+    dispatch_int<4, 2, 1>(nvb, [&](auto blocks) {
+      constexpr int P = decltype(pairs)::value, V = decltype(blocks)::value;
+      klaunch(nullptr, merged ? k_cg_persist_stencil_merged<P, V> : k_cg_persist_stencil<P, V>, G, 256 * V, lds, st, a);
+    });
+  });
   return 0;
 }
 
