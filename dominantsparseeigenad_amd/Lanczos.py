@@ -4,7 +4,7 @@
     symeigLanczos(A, k, device, extreme, *, sparse, dim)      reference Lanczos.py:79-105
 
 Same names, argument meaning and return values.  On a CUDA (= MI355X / ROCm) device the loop runs in
-hand-written HIP kernels (csrc/dsea_kernels.hip) behind the C ABI of include/dsea.h:
+hand-written HIP kernels (csrc/dsea_lanczos_kernels.hip, dsea_spmv.hip) behind the C ABI of include/dsea.h:
 
   * ``A`` a native operator (operators.TFIMOperator / CSROperator / Stencil3Operator): the whole k-step
     loop, mat-vec included, is one library call with no host synchronisation;

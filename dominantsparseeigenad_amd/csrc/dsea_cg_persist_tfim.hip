@@ -4,7 +4,7 @@
 // whatever the size below 2^16 rows (tools/cg_small_timing.py); the three adjoint solves of a second-order point
 // (E0.py:53-67) then take as long as the Lanczos forward.
 //
-// Same recipe as k_cg_persist_stencil (dsea_kernels.hip), with the hypercube coupling of the TFIM mat-vec in place of
+// Same recipe as k_cg_persist_stencil (dsea_cg_persist_stencil.hip), with the hypercube coupling of the TFIM mat-vec in place of
 // the halo: G = n / 128 workgroups own 128 rows each and keep x, r, d of their rows in registers for the whole solve.
 // Per iteration two grid-wide exchanges through data-tagged granules (8-byte word = 32 bits of data + 32-bit epoch,
 // relaxed agent-scope stores / polls, no fences; state zeroed per launch; spins bounded by a wall-clock timeout):

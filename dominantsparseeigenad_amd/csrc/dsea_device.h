@@ -1,4 +1,4 @@
-// dsea_device.h -- device-side helpers shared by the kernel translation units (dsea_kernels.hip, dsea_krylov.hip).
+// dsea_device.h -- device-side helpers shared by the kernel translation units (every .hip file that defines kernels).
 #ifndef DSEA_DEVICE_H
 #define DSEA_DEVICE_H
 

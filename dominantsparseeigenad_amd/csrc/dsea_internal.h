@@ -1,4 +1,4 @@
-// dsea_internal.h -- shared between dsea_kernels.hip (device code + launchers) and dsea_capi.hip (C ABI).
+// dsea_internal.h -- shared between the kernel files (device code + launchers) and dsea_capi.hip (C ABI).
 #ifndef DSEA_INTERNAL_H
 #define DSEA_INTERNAL_H
 
@@ -224,6 +224,21 @@ struct Workspace {
   size_t partials_bytes() const { return (size_t)DSEA_MAX_WAVE_TILES * (size_t)((kmax < 1 ? 1 : kmax) + 1) * sizeof(double); }
   size_t aux_bytes() const { return (size_t)4 * DSEA_MAX_WAVE_TILES * sizeof(double); }
 };
+
+// grid of the grid-stride streaming kernels
+inline int ew_blocks(int64_t n) {
+  int64_t nb = (n + 2047) / 2048;  // 256 threads x double2 x 4 iterations
+  if (nb < 1) nb = 1;
+  if (nb > DSEA_MAX_EW_BLOCKS) nb = DSEA_MAX_EW_BLOCKS;
+  return (int)nb;
+}
+// Kernels with a fused reduction in the CG loop: up to DSEA_PERSIST_MAX_TILES tiles of 512 rows (n <= 2^21) one
+// block per tile, so that P[tile] is a function of the tile alone (the "canonical tile" partial the persistent CG
+// kernel reproduces); beyond that the capped grid-stride form.
+inline int tile_blocks(int64_t n) {
+  const int64_t nt = (n + 511) / 512;
+  return nt <= DSEA_PERSIST_MAX_TILES ? (int)(nt < 1 ? 1 : nt) : ew_blocks(n);
+}
 
 void launch_finalize1(const double* P, int count, double* out, hipStream_t st);
 int launch_three_term(const double* u, const double* q1, const double* q2, const double* aP, int aCount,

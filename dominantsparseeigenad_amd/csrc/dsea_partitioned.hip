@@ -1,7 +1,7 @@
 // dsea_partitioned.hip -- row-partitioned solvers with the collectives inside the library (include/dsea.h,
 // "row-partitioned solvers").  Host code + one tiny kernel: the slab kernels are
-// the phase kernels of dsea_kernels.hip reached through the C ABI of dsea_capi.hip; what this file adds is the
-// SEQUENCING of a distributed Lanczos step / CG iteration -- kernels and RCCL calls issued back to back on the
+// the phase kernels of the one-GPU path (dsea_lanczos_kernels.hip, dsea_vector_kernels.hip, dsea_spmv.hip) reached
+// through the C ABI of dsea_capi.hip; what this file adds is the SEQUENCING of a distributed Lanczos step / CG iteration -- kernels and RCCL calls issued back to back on the
 // caller's stream (slab exchange on a side stream), no host language and no host synchronisation in between.
 //
 // RCCL is bound at run time (dlopen of the copy already in the process -- PyTorch-ROCm ships and loads its own --

@@ -1,7 +1,7 @@
 """Source invariants of the host layer of libdsea (read from the sources: no build, no GPU).  One HIP error path: the
 slot behind dsea_last_hip_error() is written by one function, and every hipGetLastError() of the two host files goes
 through it or is discarded on purpose.  One CG polling loop, and one predicate for the fused Lanczos tail.  The launchers: one
-dispatch rule per kernel family and each grid rule once."""
+dispatch rule per kernel family and each grid rule once.  The kernels: each defined in one file and launched from that file."""
 import glob
 import os
 import re
@@ -52,8 +52,7 @@ def test_one_fused_tail_predicate():
 
 
 # ---- the launch wrappers: every run-time choice of an instantiation and every grid rule is written once ---------------
-
-LAUNCHERS = "// host-side launch wrappers"   # dsea_kernels.hip: the kernels above this line, their launchers below
+# (over all of csrc/: no assertion names the file a kernel family lives in)
 
 
 def code(text):
@@ -68,6 +67,22 @@ def function_spans(text):
     for m in re.finditer(r"^(?:template <[^\n]*>\n)?(?:static |inline )*[\w:<>*&]+\s+(\w+)\([^;{}]*\)\s*\{\n", text, re.M):
         spans.append((m.group(1), m.start(), text.index("\n}\n", m.end())))
     return spans
+
+
+def device_spans(text):
+    """(name, start, end) of the kernels and device functions, found the same way."""
+    spans = []
+    for m in re.finditer(r"^(?:template <[^\n]*>\n)?__(?:global|device)__ [^;{}]*?(\w+)\([^;{}]*\)\s*\{\n", text, re.M):
+        spans.append((m.group(1), m.start(), text.index("\n}\n", m.end())))
+    return spans
+
+
+def host_code(text):
+    """code(text) with the bodies of its kernels and device functions cut out."""
+    text = code(text)
+    for _, a, b in reversed(device_spans(text)):
+        text = text[:a] + text[b:]
+    return text
 
 
 def enclosing_functions(text, needle):
@@ -97,24 +112,49 @@ def test_each_streaming_kernel_family_has_one_launch_expression():
     src = {name: code(text) for name, text in sources().items()}
     for family in ("k_rdots<", "k_axpy_norm<", "k_rdots_split<", "k_axpy_norm_split<"):
         hits = {name: text.count(family) for name, text in src.items() if family in text}
-        assert hits == {"dsea_kernels.hip": 1}, (family, hits)
+        assert list(hits.values()) == [1], (family, hits)   # one expression, in one file
     for family in ("k_spmv_sell<", "k_spmv_tfim<"):
-        assert [name for name, text in src.items() if family in text] == ["dsea_kernels.hip"]
-        owners = set(enclosing_functions(src["dsea_kernels.hip"], family))
+        files = [name for name, text in src.items() if family in text]
+        assert len(files) == 1, (family, files)
+        owners = set(enclosing_functions(src[files[0]], family))
         assert len(owners) == 1 and None not in owners, (family, owners)
 
 
 def test_each_grid_rule_is_stated_once():
-    """In host code: the SELL kernels' own slice map (device code above the launchers) divides by the same four slices
-    per block and is not a launcher's grid."""
+    """In host code: the SELL kernels' own slice map (k_spmv_sell, sell_slice_of) divides by the same four slices per
+    block and is not a launcher's grid -- kernels and device functions are left out by their spans."""
     src = sources()
-    assert src["dsea_kernels.hip"].count(LAUNCHERS) == 1
-    src["dsea_kernels.hip"] = src["dsea_kernels.hip"].split(LAUNCHERS)[1]
     for rule in ("nslices + 3) / 4", "<= 2048 ? 4"):
-        hits = {name: text.count(rule) for name, text in src.items() if rule in text}
-        assert hits == {"dsea_kernels.hip": 1}, (rule, hits)
+        hits = {name: host_code(text).count(rule) for name, text in src.items()}
+        assert sorted(hits.values())[-2:] == [0, 1], (rule, {k: v for k, v in hits.items() if v})
+    # (and the exclusion is what it says: the device code does use the first rule)
+    assert sum(code(text).count("nslices + 3) / 4") for text in src.values()) > 1
 
 
 def test_the_fused_launcher_asks_the_fused_tail_predicate():
-    text = sources()["dsea_kernels.hip"]
-    assert "launch_tfim_fused" in enclosing_functions(text, "has_fused_tail(")
+    owners = [f for text in sources().values() for f in enclosing_functions(text, "has_fused_tail(")]
+    assert "launch_tfim_fused" in owners, owners
+
+
+def test_each_kernel_is_defined_in_one_file_and_launched_from_that_file():
+    """A kernel copied into a second file, or launched from a file that does not define it, fails here."""
+    src = {name: code(text) for name, text in sources().items() if name.endswith(".hip")}
+    defined = {}
+    for name, text in src.items():
+        for m in re.finditer(r"__global__[^;{}]*?\bvoid\s+(k_\w+)\s*\(", text):
+            defined.setdefault(m.group(1), []).append(name)
+    assert len(defined) > 50, len(defined)   # (the pattern still finds them)
+    twice = {k: v for k, v in defined.items() if len(v) > 1}
+    assert not twice, twice
+    # a launch site: a klaunch( or hipLaunchKernelGGL( / hipExtLaunchKernelGGL( call, up to the `;` that ends it (a lambda
+    # handed a kernel, `go(k_x<...>)`, sits in the launcher that holds the klaunch and is looked for by name below)
+    strays = []
+    for name, text in src.items():
+        for m in re.finditer(r"\b(?:klaunch|hip(?:Ext)?LaunchKernelGGL)\s*\([^;]*;", text):
+            for k in re.findall(r"\bk_\w+", m.group(0)):
+                if defined.get(k) != [name]:
+                    strays.append((name, k))
+        for k in set(re.findall(r"\bk_\w+", text)):
+            if k in defined and defined[k] != [name]:
+                strays.append((name, k))
+    assert not strays, strays
