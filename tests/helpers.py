@@ -70,6 +70,38 @@ def rel(a, b):
     return float(np.max(np.abs(a - b)) / max(np.max(np.abs(b)), 1e-300))
 
 
+# ---- the bf16 storage shadow of the basis as its documented definition (csrc/dsea_device.h f64_to_bf16), in numpy integers
+def bf16_bits(x_f64):
+    """fp64 -> the uint16 the shadow stores: fp64 -> fp32 round-to-nearest-even, then (u + 0x7FFF + ((u >> 16) & 1)) >> 16 on
+    the fp32 bit pattern u.  TWO roundings (the second sees the already rounded fp32), finite inputs only."""
+    x = np.ascontiguousarray(np.asarray(x_f64, dtype=np.float64))
+    with np.errstate(over="ignore", under="ignore"):
+        u = x.astype(np.float32).view(np.uint32).astype(np.uint64)     # 64-bit so that the addition cannot wrap
+    return ((u + np.uint64(0x7FFF) + ((u >> np.uint64(16)) & np.uint64(1))) >> np.uint64(16)).astype(np.uint16)
+
+
+def bf16_chosen_values():
+    """fp64 inputs where a wrong fp64 -> bf16 conversion shows (both signs of each): zeros, exact ties with an even and an odd
+    lower neighbour, a value whose two-step rounding differs from a one-step rounding, the largest fp64 / fp32 below a power
+    of two (carry into the exponent), fp32 subnormals (below, at and above half a bf16 step), a value that vanishes."""
+    pos = [0.0,
+           1.0 + 2.0 ** -8,                   # tie, lower neighbour 0x3F80 even  -> 0x3F80
+           1.0 + 3.0 * 2.0 ** -8,             # tie, lower neighbour 0x3F81 odd   -> 0x3F82
+           1.0 + 2.0 ** -8 + 2.0 ** -40,      # fp32 step drops 2^-40, then the tie goes to even: 0x3F80 (one step: 0x3F81)
+           float(np.nextafter(2.0, 0.0)),     # largest fp64 below 2 -> 2.0f -> 0x4000
+           2.0 - 2.0 ** -23,                  # largest fp32 below 2 -> carries to 0x4000
+           1.0 + 2.0 ** -7 - 2.0 ** -30,      # just below a representable value
+           2.0 ** -149, 2.0 ** -134, 2.0 ** -133, 3.0 * 2.0 ** -134, 2.0 ** -127, 1e-40,      # fp32 subnormals
+           1e-300]                            # -> 0
+    return np.array(pos + [-v for v in pos], dtype=np.float64)
+
+
+def bf16_value(bits):
+    """the fp64 value of a stored uint16 (exact: bf16 is the upper half of an fp32)"""
+    b = np.ascontiguousarray(np.asarray(bits)).astype(np.uint16)
+    return (b.astype(np.uint32) << np.uint32(16)).view(np.float32).astype(np.float64)
+
+
 # ---- explicit sparse matrices as parameters (tests/test_gpu_csr_param.py, tests/test_partitioned_gloo.py)
 def banded_spd(n, hb, seed):
     import scipy.sparse as sp
