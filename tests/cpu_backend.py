@@ -25,6 +25,7 @@ class CpuBackend:
     def attach_tfim(self, L, L_local, row_offset, g):
         assert (1 << L_local) == self.n
         self.L, self.Lloc, self.off, self.g = L, L_local, row_offset, g
+        self._local = lambda x, y: self.tfim_local(x, y, "H")
         idx = torch.arange(self.n, dtype=torch.int64)
         gi = idx + row_offset
         rot = ((gi << 1) | (gi >> (L - 1))) & ((1 << L) - 1)
@@ -47,6 +48,7 @@ class CpuBackend:
     def attach_stencil(self, n_local, coef, V, halo, has_lo, has_hi):
         assert n_local == self.n
         self.coef, self.V, self.halo, self.has_lo, self.has_hi = coef, V, halo, has_lo, has_hi
+        self._local = lambda x, y: self.stencil_local(x, y, None, None, None)
 
     def stencil_local(self, x, y, shift, out, skip):
         if skip is not None and skip[0] != 0:
@@ -70,6 +72,7 @@ class CpuBackend:
         self.csr_rows = torch.repeat_interleave(torch.arange(n_local, dtype=torch.int64), rp[1:] - rp[:-1])
         self.csr_cols, self.csr_vals = cols.to(torch.int64), vals
         self.csr_hb, self.csr_halo, self.csr_xg = int(hb), halo, xg
+        self._local = lambda x, y: self.csr_local(x, y, None, None, None)
 
         class _Local:            # what PartitionedCSROperator keeps as the slab operator
             pass
@@ -135,7 +138,8 @@ class CpuBackend:
             beta_out[0] = beta
 
     def rdots(self, Q, ldq, n, i, u, alpha, beta, r, c):
-        r.copy_(u - alpha[0] * Q[i - 1, :n] - (beta[0] * Q[i - 2, :n] if beta is not None else 0.0))
+        # (i = 1: there is no Q[i-2]; the beta term drops whether or not beta is given, as in form_r and in the kernels)
+        r.copy_(u - alpha[0] * Q[i - 1, :n] - (beta[0] * Q[i - 2, :n] if (beta is not None and i >= 2) else 0.0))
         c[:i] = Q[:i, :n] @ r
 
     def axpy_norm(self, Q, ldq, n, i, c, r, nrm2):
@@ -156,8 +160,9 @@ class CpuBackend:
         pair[0] = torch.dot(r, r)
 
     def plz_correct_matvec(self, Q, ldq, row, c, r, y, pair):
+        # y = A_local r for whichever slab operator is attached (include/dsea.h: "the same followed by y = A_local r")
         self.plz_correct(Q, ldq, r.numel(), row, c, r, pair)
-        self.tfim_local(r, y, "H")
+        self._local(r, y)
 
     def axpy_multi_dot(self, a_host, a_dev, xs, shift, skip, x, y, out):
         if skip is not None and skip[0] != 0:
