@@ -66,6 +66,9 @@ _SIGNATURES = {
     "dsea_profile_begin": (c_int, [c_void_p, c_int]),
     "dsea_profile_end": (c_int, [c_void_p, POINTER(c_int64), POINTER(c_double)]),
     "dsea_op_create_tfim": (c_int, [c_int, c_int, c_int64, c_void_p, c_double, c_double, POINTER(c_void_p)]),
+    "dsea_op_create_chain": (c_int, [c_int, c_void_p, POINTER(c_void_p)]),
+    "dsea_op_chain_forms_scratch_doubles": (c_int, [c_int, POINTER(c_int64)]),
+    "dsea_op_chain_forms": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dsea_op_create_csr": (c_int, [c_int64, c_int64, c_void_p, c_void_p, c_void_p, POINTER(c_void_p)]),
     "dsea_op_create_sell": (c_int, [c_int64, c_int64, c_void_p, c_void_p, c_void_p, POINTER(c_void_p)]),
     "dsea_op_create_sell16": (c_int, [c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_void_p)]),

@@ -171,7 +171,8 @@ TileGeom Workspace::geom(int64_t n_rows) const {
 
 extern "C" {
 
-int dsea_version(void) { return 141; }   // 141: lowest-nev eigenpairs (block Ritz combine, block projection, deflated CG)
+int dsea_version(void) { return 142; }   // 142: matrix-free XYZ spin chain with per-site couplings (mat-vec + parameter adjoint)
+                                          // 141: lowest-nev eigenpairs (block Ritz combine, block projection, deflated CG)
                                           // 140: fp64-MFMA transfer mat-vec on packed operands, optimistic Arnoldi second pass
 
 const char* dsea_error_string(int status) {
@@ -455,6 +456,32 @@ int dsea_op_create_tfim(int L, int L_local, int64_t row_offset, const double* g_
   op->d.tfim = TfimParams{L, L_local, row_offset, g_dev, g_const, diag_scale};
   *out = op;
   return DSEA_OK;
+}
+
+int dsea_op_create_chain(int L, const double* couplings_dev, dsea_op_t* out) {
+  REQUIRE(out && L >= 2 && L <= 62 && couplings_dev, DSEA_ERR_ARG);
+  dsea_op_s* op = new (std::nothrow) dsea_op_s;
+  if (!op) return DSEA_ERR_ARG;
+  memset(&op->d, 0, sizeof(op->d));
+  op->d.tune_tile_log2 = DSEA_TFIM_TILE_LOG2;
+  op->d.kind = OP_CHAIN;
+  op->d.n = (int64_t)1 << L;
+  op->d.chain = ChainParams{L, couplings_dev};
+  *out = op;
+  return DSEA_OK;
+}
+
+int dsea_op_chain_forms_scratch_doubles(int L, int64_t* out) {
+  REQUIRE(out && L >= 2 && L <= 62, DSEA_ERR_ARG);
+  *out = chain_forms_scratch_doubles(L);
+  return DSEA_OK;
+}
+
+int dsea_op_chain_forms(dsea_op_t op, const double* v1, const double* v2, double* out5L, double* scratch, void* stream) {
+  REQUIRE(op && op->d.kind == OP_CHAIN && v1 && v2 && out5L && scratch, DSEA_ERR_ARG);
+  REQUIRE(aligned16(v1) && aligned16(v2), DSEA_ERR_ALIGN);
+  if (launch_chain_forms(op->d, v1, v2, out5L, scratch, static_cast<hipStream_t>(stream)) != 0) return DSEA_ERR_UNSUPPORTED;
+  return check_launch();
 }
 
 int dsea_op_create_csr(int64_t n, int64_t nnz, const int64_t* rowptr, const int32_t* colidx,

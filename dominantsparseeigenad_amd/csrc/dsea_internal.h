@@ -107,11 +107,17 @@ struct SymDenseParams {
   int nb;           // 64-row blocks
   int elem;         // bytes per matrix element: 8 or 4
 };
-enum OpKind { OP_TFIM = 1, OP_CSR = 2, OP_STENCIL3 = 3, OP_SELL = 4, OP_DENSE = 5, OP_TRANSFER = 6, OP_SYMDENSE = 7 };
+// XYZ spin chain with per-site couplings (dsea_chain.hip): c = (5, L) row-major device array, rows Jx, Jy, Jz, hx, hz -- read
+// through the pointer on every launch
+struct ChainParams {
+  int L;
+  const double* c;
+};
+enum OpKind { OP_TFIM = 1, OP_CSR = 2, OP_STENCIL3 = 3, OP_SELL = 4, OP_DENSE = 5, OP_TRANSFER = 6, OP_SYMDENSE = 7, OP_CHAIN = 8 };
 struct OpDesc {
   OpKind kind;
   int64_t n;
-  int tune_tile_log2;  // TFIM: log2 rows of x staged in LDS per block (6..12)
+  int tune_tile_log2;  // TFIM, spin chain: log2 rows of x staged in LDS per block (6..12)
   int tune_csr_group;  // CSR: lanes per row, 0 = automatic
   int tune_sell_unroll;  // SELL: slice-column pairs in flight per lane {0 = automatic, 2, 4, 6, 8}; 1 = the round-5 kernel (A/B)
   TfimParams tfim;
@@ -121,6 +127,7 @@ struct OpDesc {
   DenseParams dense;
   TransferParams transfer;
   SymDenseParams symdense;
+  ChainParams chain;
 };
 
 // how the rows of one vector are cut into wave tiles for the basis-streaming kernels
@@ -355,6 +362,13 @@ int launch_spmv(const OpDesc& op, const double* x, double* y, const double* shif
 int launch_sell_update_vals(const OpDesc& op, const int64_t* rowptr, const double* vals_csr, hipStream_t st);
 int launch_sddmm(const OpDesc& op, const int64_t* rowptr, const double* v1, const double* v2, double alpha, int accumulate,
                  bool sym, double* out, hipStream_t st);
+// dsea_chain.hip (XYZ spin chain): the mat-vec of launch_spmv's OP_CHAIN case; the 5 L bilinear forms v1^T (dH/dp) v2 into out
+// through per-block partials in the caller's scratch (chain_forms_scratch_doubles(L) doubles); both return -1 when L or the
+// tile is out of range
+int launch_spmv_chain(const OpDesc& op, const double* x, double* y, const double* shift, const double* skip, double* P,
+                      hipStream_t st, EventPair* ev);
+int launch_chain_forms(const OpDesc& op, const double* v1, const double* v2, double* out, double* scratch, hipStream_t st);
+int64_t chain_forms_scratch_doubles(int L);
 // dsea_cg_persist_tfim_big.hip
 bool cg_persist_tfim_big_applicable(const OpDesc& op);
 size_t cg_persist_tfim_big_comm_bytes(int64_t n);

@@ -1172,6 +1172,8 @@ int launch_spmv(const OpDesc& op, const double* x, double* y, const double* shif
       klaunch(ev, k_spmv_stencil3<false>, nb, 256, 0, st, op.st3, x, y, shift, skip, P, plain);
       return nb;
     }
+    case OP_CHAIN:
+      return launch_spmv_chain(op, x, y, shift, skip, P, st, ev);
   }
   return -1;
 }

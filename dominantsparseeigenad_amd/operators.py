@@ -11,7 +11,7 @@ Each operator is
 """
 from __future__ import annotations
 
-from ctypes import byref, c_void_p
+from ctypes import byref, c_int64, c_void_p
 
 import torch
 
@@ -171,6 +171,189 @@ class _TFIMApply(torch.autograd.Function):
         if ctx.needs_input_grad[1]:
             gg = op.pHpg(v).matmul(gy).reshape(g.shape)
         return gv, gg, None
+
+
+# ------------------------------------------------------------------------------------------ XYZ spin chain
+def _chain_view(L, couplings, like=None):
+    """(handle, n) of the chain Hamiltonian whose couplings are the (5, L) tensor ``couplings``; ``like``: a view whose tile
+    tuning the new handle takes over."""
+    data = couplings.detach()
+    if data.dtype != F64 or not data.is_contiguous():
+        data = data.to(F64).contiguous()
+    raw = c_void_p()
+    check(_lib.load().dsea_op_create_chain(int(L), c_void_p(data.data_ptr()), byref(raw)), "dsea_op_create_chain")
+    view = _NativeView(_Handle(raw, 1 << int(L), data))
+    view.tile_log2 = None
+    if like is not None and like.tile_log2 is not None:
+        _set_chain_tile(view, like.tile_log2)
+    return view
+
+
+def _set_chain_tile(view, tile_log2):
+    check(_lib.load().dsea_op_set_tuning(view.handle, _lib.TUNE_TFIM_TILE_LOG2, int(tile_log2)), "dsea_op_set_tuning")
+    view.tile_log2 = int(tile_log2)
+
+
+def _chain_forms(view, L, v1, v2):
+    """all 5 L bilinear forms v1^T (dH/dp) v2 as a (5, L) tensor (dsea_op_chain_forms: one pass, deterministic)"""
+    lib = _lib.load()
+    n = view.n
+    v1, v2 = engine.as_vector(v1, n), engine.as_vector(v2, n)
+    need = c_int64()
+    check(lib.dsea_op_chain_forms_scratch_doubles(int(L), byref(need)), "dsea_op_chain_forms_scratch_doubles")
+    scratch = torch.empty(need.value, dtype=F64, device=v1.device)
+    out = torch.empty((5, int(L)), dtype=F64, device=v1.device)
+    check(lib.dsea_op_chain_forms(view.handle, c_void_p(v1.data_ptr()), c_void_p(v2.data_ptr()), c_void_p(out.data_ptr()),
+                                  c_void_p(scratch.data_ptr()), engine._stream(v1.device)), "dsea_op_chain_forms")
+    return out
+
+
+class SpinChainOperator:
+    """H = sum_b [Jx_b X_b X_b+1 + Jy_b Y_b Y_b+1 + Jz_b Z_b Z_b+1] + sum_i [hx_i X_i + hz_i Z_i] on a periodic chain of L
+    sites, dimension 2^L, matrix-free (docs/design/14-spin-chain.md).  Site i is bit i of the row index, bond b joins sites
+    b and (b + 1) mod L; an open chain is J_{L-1} = 0; at L = 2 bonds 0 and 1 join the same two sites and both count.
+
+    ``couplings`` is ONE float64 device tensor of shape (5, L), rows Jx, Jy, Jz, hx, hz -- the parameter (it may require
+    grad).  The kernels read it through its device pointer on every launch: in-place optimiser steps are seen, binding another
+    tensor rebuilds the handle.  ``H(v)`` is differentiable in v and in ``couplings``;
+    ``Hadjoint_to_couplingsadjoint(v1, v2)`` is the hook for ``setDominantSparseSymeig`` / ``setLowestSparseSymeig``: all
+    5 L forms v1^T (dH/dp) v2 in one pass.  Both are re-entrant (H is linear in the couplings: the backward of the forms is a
+    mat-vec with the incoming (5, L) adjoint as couplings), so second order works as for ``TFIMOperator``.
+    Row-partitioned slabs, a fused Lanczos tail and the persistent single-launch forms do not exist for this operator."""
+
+    _native_methods = ("H", "__call__")
+
+    def __init__(self, L, couplings, device=None):
+        self.N = int(L)
+        if not 2 <= self.N <= 62:
+            raise ValueError("SpinChainOperator needs 2 <= L <= 62, got %d" % self.N)
+        self.dim = self.n = 1 << self.N
+        if device is None:
+            device = couplings.device if torch.is_tensor(couplings) else "cuda"
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError("SpinChainOperator is a device operator; use device='cuda'")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self._c = None
+        self._H = None
+        self._tile_log2 = None
+        self.couplings = couplings
+
+    @property
+    def couplings(self):
+        return self._c
+
+    @couplings.setter
+    def couplings(self, value):
+        if not torch.is_tensor(value):
+            value = torch.as_tensor(value, dtype=F64).to(self.device)
+        if value.device != self.device or value.dtype != F64:
+            raise ValueError("couplings must be a float64 tensor on %s" % self.device)
+        if tuple(value.shape) != (5, self.N) or not value.is_contiguous():
+            raise ValueError("couplings must be a contiguous tensor of shape (5, %d): rows Jx, Jy, Jz, hx, hz" % self.N)
+        self._c = value
+        self._H = _chain_view(self.N, value)          # the kernels read the couplings through this tensor's pointer
+        if self._tile_log2 is not None:
+            _set_chain_tile(self._H, self._tile_log2)
+
+    def set_tile_log2(self, tile_log2):
+        """log2 of the rows of x a block stages in LDS (6..12; measurement aid, dsea_op_set_tuning)"""
+        _set_chain_tile(self._H, tile_log2)
+        self._tile_log2 = int(tile_log2)
+
+    @classmethod
+    def tfim(cls, L, g, device=None):
+        """the transverse-field Ising chain of ``TFIMOperator``: Jz = -1, hx = -g"""
+        dev = torch.device(device if device is not None else "cuda")
+        c = torch.zeros((5, int(L)), dtype=F64, device=dev)
+        c[2] = -1.0
+        c[3] = -float(g)
+        return cls(L, c, dev)
+
+    @property
+    def handle(self):
+        return self._H.handle
+
+    def H(self, v):
+        """H v, differentiable in v and in the couplings"""
+        return _ChainApply.apply(v, self._c, self, self._H)
+
+    __call__ = H
+
+    def Hadjoint_to_couplingsadjoint(self, v1, v2):
+        """adjoint hook: couplings-bar[t] = v1^T (dH/dp_t) v2, shape (5, L)"""
+        return _ChainForms.apply(v1, v2, self, self._H)
+
+    def to_csr(self, layout="sell", col16="auto", values="auto"):
+        """The same matrix as an explicit device CSR operand (2 L + 1 stored entries per row; at L = 2 the two bonds share a
+        column and are summed).  Built on the device with index arithmetic."""
+        L, n = self.N, self.n
+        c = self._c.detach()
+        jx, jy, jz, hx, hz = c[0], c[1], c[2], c[3], c[4]
+        idx = torch.arange(n, dtype=torch.int64, device=self.device)
+        z = [(1 - 2 * ((idx >> i) & 1)).to(F64) for i in range(L)]
+        zz = [z[b] * z[(b + 1) % L] for b in range(L)]
+        diag = torch.zeros(n, dtype=F64, device=self.device)
+        for b in range(L):
+            diag = diag + jz[b] * zz[b] + hz[b] * z[b]
+        cols, vals = [idx], [diag]
+        for i in range(L):
+            cols.append(idx ^ (1 << i))
+            vals.append(hx[i].expand(n))
+        bond = [(jx[b] - jy[b] * zz[b], idx ^ ((1 << b) | (1 << ((b + 1) % L)))) for b in range(L)]
+        if L == 2:                                      # bonds 0 and 1: one column, summed
+            bond = [(bond[0][0] + bond[1][0], bond[0][1])]
+        for v, col in bond:
+            cols.append(col)
+            vals.append(v)
+        cols, vals = torch.stack(cols, dim=1), torch.stack(vals, dim=1)
+        order = torch.argsort(cols, dim=1)
+        cols, vals = torch.gather(cols, 1, order), torch.gather(vals, 1, order)
+        per = cols.shape[1]
+        rowptr = torch.arange(n + 1, dtype=torch.int64, device=self.device) * per
+        return CSROperator(rowptr, cols.reshape(-1), vals.reshape(-1).contiguous(), n, layout=layout, col16=col16, values=values)
+
+
+class _ChainApply(torch.autograd.Function):
+    """y = H[c] v.  Backward: H[c] gy (symmetric) and the forms(gy, v) -- both re-entrant."""
+
+    @staticmethod
+    def forward(ctx, v, c, op, view):
+        ctx.op, ctx.view = op, view
+        ctx.save_for_backward(v, c)
+        return engine.spmv(view, v.detach())
+
+    @staticmethod
+    def backward(ctx, gy):
+        v, c = ctx.saved_tensors
+        gv = _ChainApply.apply(gy, c, ctx.op, ctx.view) if ctx.needs_input_grad[0] else None
+        gc = _ChainForms.apply(gy, v, ctx.op, ctx.view).reshape(c.shape) if ctx.needs_input_grad[1] else None
+        return gv, gc, None, None
+
+
+class _ChainForms(torch.autograd.Function):
+    """out[t] = v1^T (dH/dp_t) v2, shape (5, L).  H is linear in the couplings, so with the incoming adjoint G as couplings the
+    backward is d/dv1 = H[G] v2 and d/dv2 = H[G] v1: the same mat-vec kernel."""
+
+    @staticmethod
+    def forward(ctx, v1, v2, op, view):
+        ctx.op, ctx.view = op, view
+        ctx.save_for_backward(v1, v2)
+        return _chain_forms(view, op.N, v1.detach(), v2.detach())
+
+    @staticmethod
+    def backward(ctx, G):
+        v1, v2 = ctx.saved_tensors
+        g1 = g2 = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            G = G.reshape(5, ctx.op.N)
+            adj = _chain_view(ctx.op.N, G, like=ctx.view)     # the chain Hamiltonian whose couplings are the adjoint
+            if ctx.needs_input_grad[0]:
+                g1 = _ChainApply.apply(v2, G, ctx.op, adj)
+            if ctx.needs_input_grad[1]:
+                g2 = _ChainApply.apply(v1, G, ctx.op, adj)
+        return g1, g2, None, None
 
 
 # ------------------------------------------------------------------------------------------ stencil

@@ -142,6 +142,22 @@ int dsea_profile_end(dsea_ws_t ws, int64_t *launches, double *total_ms);
 int dsea_op_create_tfim(int L, int L_local, int64_t row_offset, const double *g_dev, double g_const,
                         double diag_scale, dsea_op_t *out);
 
+/* XYZ spin chain with per-site couplings, matrix-free (docs/design/14-spin-chain.md): periodic chain of L sites, site i =
+ * bit i of the row index s, z_i(s) = 1 - 2 bit_i(s), bond b joins sites b and (b+1) mod L, m_b = its two bits:
+ *     H = sum_b [ Jx_b X_b X_b+1 + Jy_b Y_b Y_b+1 + Jz_b Z_b Z_b+1 ] + sum_i [ hx_i X_i + hz_i Z_i ]
+ *     y[s] = ( sum_b Jz_b z_b z_b+1 + sum_i hz_i z_i ) x[s] + sum_i hx_i x[s ^ (1<<i)] + sum_b ( Jx_b - Jy_b z_b z_b+1 ) x[s ^ m_b]
+ * couplings_dev: fp64 (5, L) row-major on the device, rows Jx, Jy, Jz, hx, hz; READ THROUGH THE POINTER ON EVERY LAUNCH (no
+ * host copy: in-place updates are seen).  2 <= L <= 62 and a non-null pointer are checked before any device work; nothing is
+ * launched at creation.  L = 2: bonds 0 and 1 join the same two sites and both count; an open chain is J_{L-1} = 0.
+ * n = 2^L.  dsea_op_set_tuning DSEA_TUNE_TFIM_TILE_LOG2 applies.  No fused Lanczos tail, no persistent forms. */
+int dsea_op_create_chain(int L, const double *couplings_dev, dsea_op_t *out);
+/* The parameter adjoint of dsea_op_create_chain: out5L[t] = v1^T (dH/dp_t) v2 for all 5 L couplings in the order of
+ * couplings_dev, in one pass over v1 and v2 (per-block partials in `scratch`, then a fixed-order reduction: no atomics,
+ * repeated calls return identical bits).  `scratch`: caller-owned, dsea_op_chain_forms_scratch_doubles(L) doubles (enough
+ * for every tile tuning); the library allocates nothing.  v1, v2 16-byte aligned.  DSEA_ERR_ARG for any other operator kind. */
+int dsea_op_chain_forms_scratch_doubles(int L, int64_t *out);
+int dsea_op_chain_forms(dsea_op_t op, const double *v1, const double *v2, double *out5L, double *scratch, void *stream);
+
 /* CSR, caller-owned device arrays: rowptr int64 [n+1], colidx int32 [nnz], vals fp64 [nnz]. */
 int dsea_op_create_csr(int64_t n, int64_t nnz, const int64_t *rowptr, const int32_t *colidx,
                        const double *vals, dsea_op_t *out);
