@@ -58,6 +58,7 @@ _SIGNATURES = {
     "dsea_ws_set_reorth_passes": (c_int, [c_void_p, c_int]),
     "dsea_ws_set_fault_injection": (c_int, [c_void_p, c_int]),
     "dsea_ws_set_shadow": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_double]),
+    "dsea_ws_set_shadow8": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_double]),
     "dsea_lanczos_lp_stats": (c_int, [c_void_p, POINTER(c_int64), POINTER(c_int64), c_void_p]),
     "dsea_ws_set_partial_reorth": (c_int, [c_void_p, c_int, c_double]),
     "dsea_lanczos_partial_step": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -261,6 +261,10 @@ int dsea_ws_create(void* device_buffer, size_t bytes, int64_t n, int kmax, dsea_
   ws->w.shadow_ld = 0;
   ws->w.shadow_rows = 0;
   ws->w.lp_tau = 1e-12;
+  ws->w.shadow8 = nullptr;
+  ws->w.shadow8_ld = 0;
+  ws->w.shadow8_rows = 0;
+  ws->w.lp8_tau = 0.0;
   ws->w.callable_na = 0;
   ws->w.defer_norm = 0;
   ws->w.pend_P = nullptr;
@@ -334,21 +338,57 @@ int dsea_profile_end(dsea_ws_t ws, int64_t* launches, double* total_ms) {
   return DSEA_OK;
 }
 
+namespace {
+void drop_shadow(Workspace& w) {
+  w.shadow = nullptr;
+  w.shadow_ld = 0;
+  w.shadow_rows = 0;
+}
+void drop_shadow8(Workspace& w) {
+  w.shadow8 = nullptr;
+  w.shadow8_ld = 0;
+  w.shadow8_rows = 0;
+}
+}  // namespace
+
 int dsea_ws_set_shadow(dsea_ws_t ws, void* shadow_bf16, int64_t ld, int rows, double tau) {
   REQUIRE(ws, DSEA_ERR_ARG);
   if (!shadow_bf16) {
-    ws->w.shadow = nullptr;
-    ws->w.shadow_ld = 0;
-    ws->w.shadow_rows = 0;
+    drop_shadow(ws->w);
     return DSEA_OK;
   }
   REQUIRE(rows >= 1 && ld >= 8 && tau >= 0.0, DSEA_ERR_ARG);
   REQUIRE(aligned16(shadow_bf16) && (ld % 8) == 0, DSEA_ERR_ALIGN);
+  drop_shadow8(ws->w);   // a workspace has at most one shadow
   ws->w.shadow = static_cast<uint16_t*>(shadow_bf16);
   ws->w.shadow_ld = ld;
   ws->w.shadow_rows = rows;
   ws->w.lp_tau = tau;
   return DSEA_OK;
+}
+
+int dsea_ws_set_shadow8(dsea_ws_t ws, void* shadow_e5m2, int64_t ld, int rows, double tau) {
+  REQUIRE(ws, DSEA_ERR_ARG);
+  if (!shadow_e5m2) {
+    drop_shadow8(ws->w);
+    return DSEA_OK;
+  }
+  REQUIRE(rows >= 1 && ld >= 16 && tau >= 0.0, DSEA_ERR_ARG);
+  REQUIRE(aligned16(shadow_e5m2) && (ld % 16) == 0, DSEA_ERR_ALIGN);
+  drop_shadow(ws->w);
+  ws->w.shadow8 = static_cast<uint8_t*>(shadow_e5m2);
+  ws->w.shadow8_ld = ld;
+  ws->w.shadow8_rows = rows;
+  ws->w.lp8_tau = tau;
+  return DSEA_OK;
+}
+
+// the shadow row that a writer of basis row `row` keeps current
+ShadowRow Workspace::shadow_row(int row, int64_t n_rows) const {
+  if (shadow && shadow_rows > row && shadow_ld >= n_rows) return ShadowRow(shadow + (int64_t)row * shadow_ld);
+  if (shadow8 && shadow8_rows > row && shadow8_ld >= n_rows)
+    return ShadowRow(shadow8 + (int64_t)row * shadow8_ld, shadow8_scale(n_rows));
+  return ShadowRow();
 }
 
 int dsea_lanczos_lp_stats(dsea_ws_t ws, int64_t* lp_steps, int64_t* fp64_steps, void* stream) {
@@ -434,6 +474,8 @@ inline int lp_rows_per_step(int64_t n, bool dots_are_split) {
 #endif
   return DSEA_LP_RPS;
 }
+// the 8-bit shadow is read by the wave-owned form only
+inline bool lp8_applies(int64_t n, bool dots_are_split) { return !dots_are_split && n >= ((int64_t)1 << 20); }
 }  // namespace
 
 int dsea_ws_set_split(dsea_ws_t ws, int waves) {
@@ -791,6 +833,11 @@ int dsea_lanczos_axpy_norm(dsea_ws_t ws, const double* Q, int64_t ldq, int64_t n
     const int rps = lp_rows_per_step(n, false);
     int nn = launch_axpy_norm_lp(n, rps, Q, ldq, w.shadow, w.shadow_ld, i, c, w.lp_tau, r, nP, w.scal + 16, st);
     launch_finalize1(nP, nn, nrm2_out, st);
+  } else if (w.shadow8 && w.shadow8_rows >= i && w.shadow8_ld >= n && lp8_applies(n, w.geom(n).split_w != 0)) {
+    // an 8-bit shadow is registered: the same, in the wave-owned regime only
+    double* nP = w.aux + DSEA_MAX_WAVE_TILES;
+    int nn = launch_axpy_norm_lp8(n, Q, ldq, w.shadow8, w.shadow8_ld, shadow8_scale(n), i, c, w.lp8_tau, r, nP, w.scal + 16, st);
+    launch_finalize1(nP, nn, nrm2_out, st);
   } else {
     TileGeom g = w.geom(n);
     launch_axpy_norm(g, Q, ldq, n, i, c, r, w.partials, nrm2_out, st);
@@ -826,9 +873,7 @@ int dsea_lanczos_store(dsea_ws_t ws, const double* r, const double* nrm2, double
   REQUIRE(ws && r && nrm2 && Q && n >= 1 && row >= 0 && ldq >= n, DSEA_ERR_ARG);
   REQUIRE(aligned16(r) && aligned16(Q) && (ldq % 2 == 0), DSEA_ERR_ALIGN);
   Workspace& w = ws->w;
-  uint16_t* qs = nullptr;
-  if (w.shadow && w.shadow_rows > row && w.shadow_ld >= n) qs = w.shadow + (int64_t)row * w.shadow_ld;
-  launch_scale_store(r, nrm2, Q + (int64_t)row * ldq, beta_out, n, static_cast<hipStream_t>(stream), qs);
+  launch_scale_store(r, nrm2, Q + (int64_t)row * ldq, beta_out, n, static_cast<hipStream_t>(stream), w.shadow_row(row, n));
   return check_launch();
 }
 
@@ -1082,6 +1127,17 @@ int dsea_lanczos_run(dsea_op_t op, dsea_ws_t ws, int k, const double* q0, double
     Qs = w.shadow;
     lds = w.shadow_ld;
   }
+  // ... or its 8-bit shadow, which only the wave-owned form of the multi-launch loop reads and keeps current
+  uint8_t* Qs8 = nullptr;
+  if (!w.partial_reorth && w.shadow8 && w.shadow8_rows >= k && w.shadow8_ld >= n && lp8_applies(n, g.split_w != 0))
+    Qs8 = w.shadow8;
+  const int64_t ld8 = w.shadow8_ld;
+  const double scale8 = shadow8_scale(n);
+  const bool lp = Qs || Qs8;   // the correction pass streams a shadow
+  auto shadow_row = [&](int i) -> ShadowRow {
+    if (Qs8) return ShadowRow(Qs8 + (int64_t)i * ld8, scale8);
+    return ShadowRow(Qs ? Qs + (int64_t)i * lds : nullptr);
+  };
   double* lp_count = w.scal + 16;
   double* brk = w.scal + DSEA_SCAL_BREAK;  // [0] breakdown step (0 = none), [1] running max |alpha|,|beta|
   HIP_TRY(hipMemsetAsync(lp_count, 0, (DSEA_SCAL_BREAK + 2 - 16) * sizeof(double), st));
@@ -1120,23 +1176,25 @@ int dsea_lanczos_run(dsea_op_t op, dsea_ws_t ws, int k, const double* q0, double
   // in fp64P on the fp64 pass; returns their count.  close: sum them into nrm2 (the unfused sequence).
   auto correct = [&](int i, double* fp64P, EventPair* ev, bool close) -> int {
     int nn = g.nw;
-    if (Qs)
+    if (Qs8)
+      nn = launch_axpy_norm_lp8(n, Q, ldq, Qs8, ld8, scale8, i, w.coef, w.lp8_tau, r, nP, lp_count, st, ev, brk);
+    else if (Qs)
       nn = launch_axpy_norm_lp(n, rps, Q, ldq, Qs, lds, i, w.coef, w.lp_tau, r, nP, lp_count, st, ev, brk);
     else
       launch_axpy_norm(g, Q, ldq, n, i, w.coef, r, fp64P, nullptr, st, ev, brk);
-    if (close) launch_finalize_slot(Qs ? nP : fp64P, nn, nrm2, brk, st);
+    if (close) launch_finalize_slot(lp ? nP : fp64P, nn, nrm2, brk, st);
     return nn;
   };
   // CGS2 option (the reference makes ONE pass, Lanczos.py:66): c' = Q^T r of the corrected r, r -= Q c'.  The dots kernel
   // rewrites r from a snapshot (alpha = 0) so that its input and output do not alias.
   auto second_pass = [&](int i, double* fp64P, bool close, int& nn) -> int {
     HIP_TRY(hipMemcpyAsync(w.vec[2], r, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st));
-    launch_rdots(g, Q, ldq, n, i, w.vec[2], w.zero, nullptr, r, P, w.coef, st, nullptr, nullptr, 0, nullptr, Qs != nullptr, brk);
+    launch_rdots(g, Q, ldq, n, i, w.vec[2], w.zero, nullptr, r, P, w.coef, st, nullptr, nullptr, 0, nullptr, lp, brk);
     nn = correct(i, fp64P, nullptr, close);
     return DSEA_OK;
   };
   launch_dot(q0, q0, n, P, nrm2, st);
-  launch_scale_store(q0, nrm2, Q, nullptr, n, st, Qs);
+  launch_scale_store(q0, nrm2, Q, nullptr, n, st, shadow_row(0));
   if (fused_tail) {
     // Fused sequence, 4 launches per step and no stand-alone scalar reductions: the mat-vec leaves
     // per-block partials of alpha (aP), the dots kernel sums them in its prologue; the axpy kernel leaves
@@ -1166,13 +1224,13 @@ int dsea_lanczos_run(dsea_op_t op, dsea_ws_t ws, int k, const double* q0, double
         continue;
       }
       launch_rdots(g, Q, ldq, n, i, u, nullptr, beta_prev, r, P, w.coef, st,
-                   prof ? prof->next(PROF_RDOTS) : nullptr, aP, na, alphas + (i - 1), Qs != nullptr, brk);
+                   prof ? prof->next(PROF_RDOTS) : nullptr, aP, na, alphas + (i - 1), lp, brk);
       int nn = correct(i, nP, prof ? prof->next(PROF_AXPY) : nullptr, false);
       if (w.reorth_passes == 2) DSEA_TRY(second_pass(i, nP, false, nn));
       // beta_{i-1} ~ 0 (relative to the running |alpha|, |beta| scale): the tail records step i in brk and every
       // later launch of this run returns at once (Lanczos.py:69-70 would divide by it)
       na = launch_tfim_fused(op->d, r, nP, nn, Q + (int64_t)i * ldq, u, betas + (i - 1), aP, st,
-                             prof ? prof->next(PROF_SPMV) : nullptr, Qs ? Qs + (int64_t)i * lds : nullptr, brk, i);
+                             prof ? prof->next(PROF_SPMV) : nullptr, shadow_row(i), brk, i);
     }
     launch_finalize_slot(aP, na, alphas + (k - 1), brk, st);
     return check_launch();
@@ -1183,11 +1241,11 @@ int dsea_lanczos_run(dsea_op_t op, dsea_ws_t ws, int k, const double* q0, double
   for (int i = 1; i < k; ++i) {
     const double* beta_prev = (i >= 2) ? betas + (i - 2) : nullptr;
     launch_rdots(g, Q, ldq, n, i, u, alphas + (i - 1), beta_prev, r, P, w.coef, st,
-                 prof ? prof->next(PROF_RDOTS) : nullptr, nullptr, 0, nullptr, Qs != nullptr, brk);
+                 prof ? prof->next(PROF_RDOTS) : nullptr, nullptr, 0, nullptr, lp, brk);
     int nn = correct(i, P, prof ? prof->next(PROF_AXPY) : nullptr, true);
     if (w.reorth_passes == 2) DSEA_TRY(second_pass(i, P, true, nn));
     double* qi = Q + (int64_t)i * ldq;
-    launch_scale_store(r, nrm2, qi, betas + (i - 1), n, st, Qs ? Qs + (int64_t)i * lds : nullptr, brk, i);
+    launch_scale_store(r, nrm2, qi, betas + (i - 1), n, st, shadow_row(i), brk, i);
     nb = launch_spmv(op->d, qi, u, nullptr, brk, P, st, prof ? prof->next(PROF_SPMV) : nullptr);
     launch_finalize_slot(P, nb, alphas + i, brk, st);
   }

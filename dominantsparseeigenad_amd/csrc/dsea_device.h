@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dsea_internal.h"   // ShadowRow
+
 namespace dsea {
 
 // ------------------------------------------------------------------------------------------
@@ -153,6 +155,43 @@ __device__ __forceinline__ void st_bf16x2(uint16_t* __restrict__ p, int64_t row,
   } else if (row < n) {
     p[row] = f64_to_bf16(v.x);
   }
+}
+
+// 8-bit shadow of the basis (storage only, see k_axpy_norm_lp8): code = e5m2(float(v * S)), S a power of two fixed per run,
+// both roundings to nearest even -- bit for bit torch's (v * S).to(float32).to(float8_e5m2).  Integer arithmetic on the
+// fp32 bits: normal codes (|x| >= 2^-14) keep two mantissa bits and re-bias the exponent 127 -> 15; below that x + 128.0f
+// has its last place at 2^-16, the unit of the subnormal codes, so the fp32 addition does the rounding.  |v| <= 1 and
+// S <= 2^15 stay below the largest finite code (57344).
+__device__ __forceinline__ uint32_t f64_to_e5m2(double v, double S) {
+  const uint32_t u = __float_as_uint((float)(v * S));
+  const uint32_t a = u & 0x7FFFFFFFu;
+  uint32_t code;
+  if (a >= 0x38800000u)
+    code = (a + 0x000FFFFFu + ((a >> 21) & 1u) - 0x38000000u) >> 21;
+  else
+    code = __float_as_uint(__uint_as_float(a) + 128.0f) - 0x43000000u;
+  return code | ((u >> 24) & 0x80u);
+}
+__device__ __forceinline__ void st_e5m2x2(uint8_t* __restrict__ p, int64_t row, int64_t n, double2 v, double S) {
+  if (row + 1 < n) {
+    *reinterpret_cast<uint16_t*>(p + row) = (uint16_t)(f64_to_e5m2(v.x, S) | (f64_to_e5m2(v.y, S) << 8));
+  } else if (row < n) {
+    p[row] = (uint8_t)f64_to_e5m2(v.x, S);
+  }
+}
+// one basis row's shadow, whichever form is registered (ShadowRow: dsea_internal.h)
+__device__ __forceinline__ void st_shadow_x2(const ShadowRow& s, int64_t row, int64_t n, double2 v) {
+  if (s.h) st_bf16x2(s.h, row, n, v);
+  if (s.b) st_e5m2x2(s.b, row, n, v, s.S);
+}
+__device__ __forceinline__ void st_shadow(const ShadowRow& s, int64_t row, double v) {
+  if (s.h) s.h[row] = f64_to_bf16(v);
+  if (s.b) s.b[row] = (uint8_t)f64_to_e5m2(v, s.S);
+}
+__device__ __forceinline__ uint4 ld_u4_stream(const uint8_t* __restrict__ p) {
+  typedef unsigned int v4u __attribute__((ext_vector_type(4)));
+  v4u t = __builtin_nontemporal_load(reinterpret_cast<const v4u*>(p));
+  return make_uint4(t.x, t.y, t.z, t.w);
 }
 
 // Breakdown record of a native Lanczos run: brk[0] = step at which beta ~ 0 was found (0 = none),

@@ -130,6 +130,16 @@ struct OpDesc {
   ChainParams chain;
 };
 
+// One basis row's storage shadow as the writers see it: bf16 (h), e5m2 codes of q * S (b), or neither.  At most one of
+// the two pointers is set; a plain bf16 row pointer converts by itself.
+struct ShadowRow {
+  uint16_t* h;
+  uint8_t* b;
+  double S;
+  ShadowRow(uint16_t* bf16 = nullptr) : h(bf16), b(nullptr), S(0.0) {}
+  ShadowRow(uint8_t* e5m2, double scale) : h(nullptr), b(e5m2), S(scale) {}
+};
+
 // how the rows of one vector are cut into wave tiles for the basis-streaming kernels
 struct TileGeom {
   int rpl;         // rows per lane (2,4,8,16): a wave tile is 64*rpl rows
@@ -218,6 +228,12 @@ struct Workspace {
   int64_t shadow_ld;
   int shadow_rows;
   double lp_tau;     // low-precision pass allowed while max|c_j| <= lp_tau * ||r||
+  uint8_t* shadow8;  // caller-owned 8-bit (e5m2) shadow of the basis, or null; never set together with `shadow`
+  int64_t shadow8_ld;
+  int shadow8_rows;
+  double lp8_tau;    // the same premise for the 8-bit pass
+  // the shadow row a writer of basis row `row` keeps current (n: rows of the vector)
+  ShadowRow shadow_row(int row, int64_t n) const;
   // row-partitioned library driver: dsea_plz_correct leaves its ||r||^2 partials un-summed (defer_norm) and the NEXT
   // dot-closing call of the step sums both in one launch (k_finalize_pair) -- bit-identical, one launch fewer per step
   int callable_na;       // dsea_lanczos_callable_alpha: number of alpha partials left in aux[0..] for the next callable step
@@ -263,9 +279,19 @@ inline bool rdots_uscale_ok(const TileGeom& g) { return g.split_w == 0; }   // s
 int launch_axpy_norm_lp(int64_t n, int rps, const double* Q, int64_t ldq, const uint16_t* Qs, int64_t lds, int i,
                         const double* c, double tau, double* r, double* P, double* lp_count, hipStream_t st,
                         EventPair* ev = nullptr, const double* brk = nullptr);
+// the 8-bit form of the same pass (wave-owned geometry only): Qs8 holds e5m2 codes of q * scale
+int launch_axpy_norm_lp8(int64_t n, const double* Q, int64_t ldq, const uint8_t* Qs8, int64_t ld8, double scale, int i,
+                         const double* c, double tau, double* r, double* P, double* lp_count, hipStream_t st,
+                         EventPair* ev = nullptr, const double* brk = nullptr);
+// scale of the 8-bit codes of an n-row run: 2^ceil(log2(n) / 2), at most 2^15 (|q| <= 1 stays below the largest code)
+inline double shadow8_scale(int64_t n) {
+  int e = 0;
+  while (e < 15 && ((int64_t)1 << (2 * e)) < n) ++e;
+  return (double)((int64_t)1 << e);
+}
 int launch_tfim_fused(const OpDesc& op, const double* r, const double* nP, int nCount, double* q_out, double* y,
                       double* beta_store, double* P, hipStream_t st, EventPair* ev = nullptr,
-                      uint16_t* qs_out = nullptr, double* brk = nullptr, int step = 0);
+                      ShadowRow qs_out = ShadowRow(), double* brk = nullptr, int step = 0);
 int launch_cg_update_fused(double* x, double* r, const double* d, const double* Ad, const double* state,
                            int parity, const double* dP, int dCount, int64_t n, double* P, hipStream_t st);
 void launch_cg_direction_fused(const double* r, double* d, double* state, int parity, const double* rP,
@@ -287,8 +313,8 @@ int launch_shift_dot_partials(const double* x, double* y, const double* shift, c
                               hipStream_t st);
 void launch_axpy(double a_host, const double* a_dev, const double* x, double* y, int64_t n, hipStream_t st);
 void launch_scale_store(const double* r, const double* nrm2, double* q, double* beta_out, int64_t n,
-                        hipStream_t st, uint16_t* qs = nullptr, double* brk = nullptr, int step = 0);
-void launch_scale_store_fused(const double* r, const double* nP, int nCount, double* q, uint16_t* qs, double* beta_store,
+                        hipStream_t st, ShadowRow qs = ShadowRow(), double* brk = nullptr, int step = 0);
+void launch_scale_store_fused(const double* r, const double* nP, int nCount, double* q, ShadowRow qs, double* beta_store,
                               int64_t n, hipStream_t st);
 int launch_dot_partials(const double* x, const double* y, int64_t n, double* P, hipStream_t st);
 void launch_project_apply(const double* v, const double* a, const double* dot, double* out, int64_t n,

@@ -843,6 +843,169 @@ int launch_axpy_norm_lp(int64_t n, int rps, const double* Q, int64_t ldq, const 
 }
 
 // ------------------------------------------------------------------------------------------
+// The same pass reading an 8-BIT shadow of the basis: one e5m2 code of q * S per element (S a power of two fixed per run,
+// f64_to_e5m2 in dsea_device.h), wave-owned geometry only (n >= 2^20 rows).  docs/design/15-shadow8.md has the argument:
+// the error  sum_j c_j (dec(code_j) / S - q_j)  is a combination of storage-rounding noise vectors, uncorrelated with every
+// basis vector, of norm ~0.07 sqrt(sum c_j^2) -- below the rounding already committed when u - alpha q - beta q' was formed.
+// The premise is the bf16 pass's, against a bound 2^-6 times tighter (the ratio of the two codes' relative errors).
+//
+// Arithmetic: the correction only has to be known to three digits, so it is accumulated in fp32,
+//   w_k = sum_j chat_j dec(code_jk),  chat_j = float(c_j / (S sqrt(c[i]))),      then ONE fp64 step  r_k -= double(w_k) sqrt(c[i]);
+// under the premise |chat_j S| <= tau8, so nothing overflows, and products that flush are below 1e-38 ||r||.  Two packed
+// converts and two packed FMAs per four elements keep the pass on memory at twice the bf16 pass's element rate.
+// ||r||^2 partials come from the updated r in fp64.
+//
+// Geometry: a lane owns RPS groups of 16 consecutive rows (one 16-byte load each); a wave tile is 1024*RPS rows; j runs
+// downwards.  The fp64 fallback walks the same tile as eight 128-row slices (a lane owns one double2 of each).
+typedef float dsea_v2f __attribute__((ext_vector_type(2)));
+// w[0..3] += ch * (the four e5m2 codes of word x)
+__device__ __forceinline__ void fma_e5m2x4(dsea_v2f& w01, dsea_v2f& w23, dsea_v2f ch, uint32_t x) {
+  w01 = __builtin_elementwise_fma(ch, __builtin_amdgcn_cvt_pk_f32_bf8((int)x, false), w01);
+  w23 = __builtin_elementwise_fma(ch, __builtin_amdgcn_cvt_pk_f32_bf8((int)x, true), w23);
+}
+template <int RPS, bool GUARD>
+__device__ __forceinline__ double axpy_lp8_tile(const uint8_t* __restrict__ Qs8, int64_t ld8, int i, int64_t n, int64_t base,
+                                                int lane, const double* __restrict__ c, double cs, double rnorm,
+                                                double* __restrict__ r) {
+  dsea_v2f w[RPS][8];
+#pragma unroll
+  for (int s = 0; s < RPS; ++s)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) w[s][e] = (dsea_v2f)(0.0f);
+  // (no prologue prefetch of r or of the first rows: see the note in axpy_lp_tile; unroll 8 = eight 16-byte loads in flight
+  //  per lane at RPS = 1, what the bf16 pass has at its measured optimum)
+#ifndef DSEA_LP8_UNROLL
+#define DSEA_LP8_UNROLL 8
+#endif
+#pragma unroll DSEA_LP8_UNROLL
+  for (int jj = 0; jj < i; ++jj) {
+    const int j = i - 1 - jj;
+    const uint8_t* __restrict__ qj = Qs8 + (int64_t)j * ld8;
+    const float chf = (float)(c[j] * cs);
+    const dsea_v2f ch = (dsea_v2f)(chf);
+#pragma unroll
+    for (int s = 0; s < RPS; ++s) {
+      const int64_t row = base + s * 1024 + lane * 16;
+      uint4 h;
+      if (!GUARD || row + 16 <= n) {
+        h = ld_u4_stream(qj + row);
+      } else {
+        uint32_t t[4] = {0u, 0u, 0u, 0u};   // rows >= n: code 0 = +0.0
+        for (int e = 0; e < 16; ++e)
+          if (row + e < n) t[e >> 2] |= (uint32_t)qj[row + e] << ((e & 3) * 8);
+        h = make_uint4(t[0], t[1], t[2], t[3]);
+      }
+      fma_e5m2x4(w[s][0], w[s][1], ch, h.x);
+      fma_e5m2x4(w[s][2], w[s][3], ch, h.y);
+      fma_e5m2x4(w[s][4], w[s][5], ch, h.z);
+      fma_e5m2x4(w[s][6], w[s][7], ch, h.w);
+    }
+  }
+  double acc = 0.0;
+#pragma unroll
+  for (int s = 0; s < RPS; ++s) {
+    const int64_t row = base + s * 1024 + lane * 16;
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+      double2 rv = ld2<GUARD>(r, row + 2 * t, n);
+      rv.x = fma(-(double)w[s][t].x, rnorm, rv.x);
+      rv.y = fma(-(double)w[s][t].y, rnorm, rv.y);
+      st2<GUARD>(r, row + 2 * t, n, rv);
+      acc = fma(rv.x, rv.x, acc);
+      acc = fma(rv.y, rv.y, acc);
+    }
+  }
+  return acc;
+}
+// the fp64 fallback of the 8-bit pass over one 1024*RPS-row tile
+template <int RPS, bool GUARD>
+__device__ __forceinline__ double axpy_lp8_tile_fp64(const double* __restrict__ Q, int64_t ldq, int i, int64_t n, int64_t base,
+                                                     int lane, const double* __restrict__ c, double* __restrict__ r) {
+  double2 w[RPS * 8];
+#pragma unroll
+  for (int t = 0; t < RPS * 8; ++t) w[t] = make_double2(0.0, 0.0);
+  for (int jj = 0; jj < i; ++jj) {
+    const int j = i - 1 - jj;
+    const double* __restrict__ qj = Q + (int64_t)j * ldq;
+    const double cj = c[j];
+#pragma unroll
+    for (int t = 0; t < RPS * 8; ++t) {
+      const double2 q = ld2_stream<GUARD>(qj, base + t * 128 + lane * 2, n);
+      w[t].x = fma(cj, q.x, w[t].x);
+      w[t].y = fma(cj, q.y, w[t].y);
+    }
+  }
+  double acc = 0.0;
+#pragma unroll
+  for (int t = 0; t < RPS * 8; ++t) {
+    const int64_t row = base + t * 128 + lane * 2;
+    double2 rv = ld2<GUARD>(r, row, n);
+    rv.x -= w[t].x;
+    rv.y -= w[t].y;
+    st2<GUARD>(r, row, n, rv);
+    acc = fma(rv.x, rv.x, acc);
+    acc = fma(rv.y, rv.y, acc);
+  }
+  return acc;
+}
+
+template <int RPS>
+__global__ __launch_bounds__(256) void k_axpy_norm_lp8(const double* __restrict__ Q, int64_t ldq,
+                                                       const uint8_t* __restrict__ Qs8, int64_t ld8, double scale, int i,
+                                                       int64_t n, const double* __restrict__ c, double tau2,
+                                                       double* __restrict__ r, double* __restrict__ P, int nw,
+                                                       int64_t ntiles, double* __restrict__ lp_count,
+                                                       const double* __restrict__ brk) {
+  const int lane = threadIdx.x & 63;
+  const int64_t widx = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (widx >= nw) return;
+  if (broken(brk)) return;
+  // premise check, identical in every wave: max_j c_j^2 <= tau8^2 ||r||^2   (c[i] = ||r||^2 from the dots pass)
+  double m = 0.0;
+  for (int b = lane; b < i; b += 64) {
+    const double v = c[b];
+    m = fmax(m, v * v);
+  }
+  m = wave_max(m);
+  const double rr = c[i];
+  const bool use_lp = m <= tau2 * rr;
+  if (widx == 0 && lane == 0 && lp_count) lp_count[use_lp ? 0 : 1] += 1.0;
+  const double rnorm = sqrt(rr);
+  const double cs = rnorm > 0.0 ? 1.0 / (scale * rnorm) : 0.0;   // (r = 0: the premise holds only with c = 0)
+  constexpr int64_t TILE = 1024 * RPS;
+  double acc = 0.0;
+  for (int64_t tile = widx; tile < ntiles; tile += nw) {
+    const int64_t base = tile * TILE;
+    const bool whole = base + TILE <= n;
+    if (use_lp)
+      acc += whole ? axpy_lp8_tile<RPS, false>(Qs8, ld8, i, n, base, lane, c, cs, rnorm, r)
+                   : axpy_lp8_tile<RPS, true>(Qs8, ld8, i, n, base, lane, c, cs, rnorm, r);
+    else
+      acc += whole ? axpy_lp8_tile_fp64<RPS, false>(Q, ldq, i, n, base, lane, c, r)
+                   : axpy_lp8_tile_fp64<RPS, true>(Q, ldq, i, n, base, lane, c, r);
+  }
+  acc = wave_sum(acc);
+  if (lane == 0) P[widx] = acc;
+}
+
+// returns the number of partials written
+int launch_axpy_norm_lp8(int64_t n, const double* Q, int64_t ldq, const uint8_t* Qs8, int64_t ld8, double scale, int i,
+                         const double* c, double tau, double* r, double* P, double* lp_count, hipStream_t st,
+                         EventPair* ev, const double* brk) {
+#ifndef DSEA_LP8_RPS
+#define DSEA_LP8_RPS 1   /* 2^20 rows: 1024 tiles, one wave per SIMD */
+#endif
+  constexpr int RPS = DSEA_LP8_RPS;
+  const int64_t tile = 1024 * (int64_t)RPS;
+  int64_t ntiles = (n + tile - 1) / tile;
+  if (ntiles < 1) ntiles = 1;
+  const int nw = (int)(ntiles < DSEA_MAX_WAVE_TILES ? ntiles : DSEA_MAX_WAVE_TILES);
+  klaunch(ev, k_axpy_norm_lp8<RPS>, (nw + 3) / 4, 256, 0, st, Q, ldq, Qs8, ld8, scale, i, n, c, tau * tau, r, P, nw, ntiles,
+          lp_count, brk);
+  return nw;
+}
+
+// ------------------------------------------------------------------------------------------
 // Partial re-orthogonalisation (Simon 1984; an OPTION -- the reference re-orthogonalises on every step, Lanczos.py:66).
 // omega_{i,k} estimates q_i . q_k from the scalars of the recurrence alone:
 //   beta_{i-1} omega_{i,k} = beta_k omega_{i-1,k+1} + (alpha_k - alpha_{i-1}) omega_{i-1,k} + beta_{k-1} omega_{i-1,k-1}

@@ -27,7 +27,7 @@ struct TfimFusedArgs {
   const double* nP;      // partials of ||r||^2
   int nCount;
   double* q_out;         // Q[i]
-  uint16_t* qs_out;      // bf16 shadow row or null
+  ShadowRow qs_out;      // shadow row (bf16 or 8-bit) or none
   double* beta_store;    // betas[i-1]
   double* brk;           // breakdown record (see broken()) or null
   int step;              // Lanczos step i (recorded on breakdown)
@@ -60,11 +60,11 @@ __global__ __launch_bounds__(256) void k_scale_store_fused(const double* __restr
     v.x = v.x / beta;
     v.y = v.y / beta;
     st2<true>(fa.q_out, row, n, v);
-    if (fa.qs_out) st_bf16x2(fa.qs_out, row, n, v);
+    st_shadow_x2(fa.qs_out, row, n, v);
   }
 }
 
-void launch_scale_store_fused(const double* r, const double* nP, int nCount, double* q, uint16_t* qs, double* beta_store,
+void launch_scale_store_fused(const double* r, const double* nP, int nCount, double* q, ShadowRow qs, double* beta_store,
                               int64_t n, hipStream_t st) {
   TfimFusedArgs fa = {nP, nCount, q, qs, beta_store, nullptr, 0};
   hipLaunchKernelGGL(k_scale_store_fused, dim3(ew_blocks(n)), dim3(256), 0, st, r, fa, n);
@@ -138,9 +138,7 @@ __global__ __launch_bounds__(256) void k_spmv_tfim(TfimParams p, const double* _
           v.x = v.x / beta;
           v.y = v.y / beta;
           *reinterpret_cast<double2*>(fa.q_out + base + 2 * lp) = v;
-          if (fa.qs_out)
-            *reinterpret_cast<uint32_t*>(fa.qs_out + base + 2 * lp) =
-                (uint32_t)f64_to_bf16(v.x) | ((uint32_t)f64_to_bf16(v.y) << 16);
+          st_shadow_x2(fa.qs_out, base + 2 * lp, base + TILE, v);   // (whole pairs: the tile lies inside the vector)
         }
         tile2[lp] = v;
       }
@@ -397,7 +395,7 @@ __global__ __launch_bounds__(256) void k_spmv_sell_r5(SellParams p, const double
       if (FUSED) {
         xi = xi / beta;
         fa.q_out[row] = xi;
-        if (fa.qs_out) fa.qs_out[row] = f64_to_bf16(xi);
+        st_shadow(fa.qs_out, row, xi);
       }
       double v = s0 + s1;
       if (!FUSED && shift) v = __dsub_rn(v, __dmul_rn(s, xi));
@@ -616,7 +614,7 @@ __global__ __launch_bounds__(256) void k_spmv_sell(SellParams p, const double* _
         xi = xi / beta;
         v = v / beta;
         fa.q_out[row] = xi;
-        if (fa.qs_out) fa.qs_out[row] = f64_to_bf16(xi);
+        st_shadow(fa.qs_out, row, xi);
       }
       if (!FUSED && shift) v = __dsub_rn(v, __dmul_rn(s, xi));
       y[row] = v;
@@ -976,7 +974,7 @@ __global__ __launch_bounds__(256) void k_spmv_stencil3(Stencil3Params p, const d
       if (i > 0) dn = dn / beta;
       if (i + 2 < p.n) up = up / beta;
       st2<true>(fa.q_out, i, p.n, xv);
-      if (fa.qs_out) st_bf16x2(fa.qs_out, i, p.n, xv);
+      st_shadow_x2(fa.qs_out, i, p.n, xv);
     }
     double2 v, Vv = ld2<true>(p.V, i, p.n);
     v.x = stencil_row(p.coef, Vv.x, xv.x, up0, dn);
@@ -1182,7 +1180,7 @@ int launch_spmv(const OpDesc& op, const double* x, double* y, const double* shif
 // for the operator kinds that have one; returns the number of alpha partials or -1 (caller falls back to the
 // unfused sequence scale_store + mat-vec + finalize).
 int launch_tfim_fused(const OpDesc& op, const double* r, const double* nP, int nCount, double* q_out, double* y,
-                      double* beta_store, double* P, hipStream_t st, EventPair* ev, uint16_t* qs_out, double* brk,
+                      double* beta_store, double* P, hipStream_t st, EventPair* ev, ShadowRow qs_out, double* brk,
                       int step) {
   if (!has_fused_tail(op)) return -1;
   const TfimFusedArgs fa = {nP, nCount, q_out, qs_out, beta_store, brk, step};

@@ -98,7 +98,7 @@ void launch_axpy(double a_host, const double* a_dev, const double* x, double* y,
 __global__ __launch_bounds__(256) void k_scale_store(const double* __restrict__ r,
                                                      const double* __restrict__ nrm2,
                                                      double* __restrict__ q, double* __restrict__ beta_out,
-                                                     int64_t n, uint16_t* __restrict__ qs,
+                                                     int64_t n, ShadowRow qs,
                                                      double* __restrict__ brk, int step) {
   if (broken(brk)) return;
   const double beta = sqrt(nrm2[0]);
@@ -113,12 +113,12 @@ __global__ __launch_bounds__(256) void k_scale_store(const double* __restrict__ 
     v.x = v.x / beta;
     v.y = v.y / beta;
     st2<true>(q, row, n, v);
-    if (qs) st_bf16x2(qs, row, n, v);
+    st_shadow_x2(qs, row, n, v);
   }
 }
 
 void launch_scale_store(const double* r, const double* nrm2, double* q, double* beta_out, int64_t n,
-                        hipStream_t st, uint16_t* qs, double* brk, int step) {
+                        hipStream_t st, ShadowRow qs, double* brk, int step) {
   hipLaunchKernelGGL(k_scale_store, dim3(ew_blocks(n)), dim3(256), 0, st, r, nrm2, q, beta_out, n, qs, brk, step);
 }
 

@@ -23,6 +23,27 @@ _CACHE_LOCK = threading.RLock()
 # dsea_ws_set_shadow).  SHADOW_TAU is the device-side premise bound max|c_j| <= tau ||r||.
 USE_SHADOW = True
 SHADOW_TAU = 1e-12
+# From 2^20 rows on (the wave-owned correction kernel) the native one-GPU run keeps an 8-BIT shadow instead: one e5m2 code
+# of q * S per element, dsea_ws_set_shadow8, docs/design/15-shadow8.md.  SHADOW_BITS = 16 keeps the bf16 shadow there
+# too (same-box A/B; environment override DSEA_SHADOW_BITS).  SHADOW8_TAU is that pass's premise bound: 2^-6 SHADOW_TAU,
+# the ratio of the two codes' relative errors.  The rounding floor of the coefficients grows with sqrt(n) -- the CPU oracle
+# measures max_j|c_j| / ||r|| = 7.3e-15 / 1.5e-14 / 3.1e-14 at L = 16 / 18 / 20 (k = 200, g = 1), i.e. 3.0e-17 sqrt(n) -- so
+# where SHADOW8_TAU leaves no 4x margin above it the bound registered for a run is four times that floor (shadow8_tau).
+SHADOW_BITS = int(__import__("os").environ.get("DSEA_SHADOW_BITS", "8"))
+SHADOW8_TAU = 2.0 ** -6 * SHADOW_TAU
+SHADOW8_C_FLOOR = 3.0e-17          # measured max_j|c_j| / (||r|| sqrt(n)) of a healthy fully re-orthogonalised step
+SHADOW8_MIN_ROWS = 1 << 20
+
+
+def shadow8_tau(n):
+    """premise bound of the 8-bit pass for an n-row run: SHADOW8_TAU, or 4 x the measured rounding floor of the
+    coefficients where that is larger (from 2^14 rows on; 1.23e-13 at 2^20 rows), never above SHADOW_TAU"""
+    return min(float(SHADOW_TAU), max(float(SHADOW8_TAU), 4.0 * SHADOW8_C_FLOOR * float(n) ** 0.5))
+
+
+def shadow8_scale(n):
+    """S of the 8-bit codes of an n-row run: 2^ceil(log2(n) / 2), at most 2^15 (csrc/dsea_internal.h shadow8_scale)"""
+    return float(1 << min(15, ((int(n) - 1).bit_length() + 1) // 2))
 # Dense tensors handed to the SYMMETRIC primitives (DominantSymeig, CGSubspace) are applied by the hand-written
 # upper-triangle mat-vec (operators.SymmetricDenseOperator): only the upper triangle of the tensor is read.  Set to
 # False to apply them with torch.matmul (rocBLAS GEMV on the full matrix) instead.
@@ -332,14 +353,14 @@ def _dots_probe_us(buf, rows, ldq, n, device):
     return e0.elapsed_time(e1) / 3 * 1e3
 
 
-def shadow_fits(device, k, ldq, n, arena=False):
-    """True if the bf16 shadow of a (k, ldq) basis can be allocated next to it with room for the work vectors of a
+def shadow_fits(device, k, ldq, n, arena=False, bytes_per_element=2):
+    """True if the bf16 (or 8-bit) shadow of a (k, ldq) basis can be allocated next to it with room for the work vectors of a
     forward + backward pass (8 n-vectors).  At L = 28, k = 100 on one 288 GB GPU the fp64 basis is 215 GB and the shadow
     would be another 54 GB: the solve then runs with the all-fp64 correction pass instead of dying in the allocator."""
     device = torch.device(device)
     if device.type != "cuda":
         return True
-    need = 2 * int(k) * int(ldq)
+    need = int(bytes_per_element) * int(k) * int(ldq)
     if arena:
         held = BasisArena._bufs.get((str(device), int(torch.cuda.current_stream(device).cuda_stream), "Qs"))
         if held is not None and held.numel() >= need:
@@ -444,8 +465,13 @@ def lanczos(A, k, n, device, q0, native=None, callable_A=None, arena=False):
     ldq = round_up(n, 32)
     # arena: the caller does not keep the basis (symeigLanczos) -> persistent buffer instead of a fresh allocation
     Q = BasisArena.matrix(device, "Q", k, ldq, F64, n_hint=n) if arena else torch.empty((k, ldq), dtype=F64, device=device)
-    new_shadow = (lambda: BasisArena.matrix(device, "Qs", k, ldq, torch.bfloat16)) if arena else \
-        (lambda: torch.empty((k, ldq), dtype=torch.bfloat16, device=device))
+    # the native one-GPU run keeps the 8-bit shadow in the regime whose correction kernel reads it; everything else bf16
+    if SHADOW_BITS not in (8, 16):
+        raise ValueError("engine.SHADOW_BITS must be 8 or 16, not %r" % (SHADOW_BITS,))
+    shadow8 = native is not None and SHADOW_BITS == 8 and n >= SHADOW8_MIN_ROWS
+    shadow_dtype = torch.uint8 if shadow8 else torch.bfloat16
+    new_shadow = (lambda: BasisArena.matrix(device, "Qs", k, ldq, shadow_dtype)) if arena else \
+        (lambda: torch.empty((k, ldq), dtype=shadow_dtype, device=device))
     alphas = torch.empty(k, dtype=F64, device=device)
     betas = torch.empty(max(k - 1, 1), dtype=F64, device=device)
     q0 = as_vector(q0, n)
@@ -453,7 +479,7 @@ def lanczos(A, k, n, device, q0, native=None, callable_A=None, arena=False):
     partial = PARTIAL_REORTH is not None
     if partial and REORTH_PASSES != 1:
         raise NotImplementedError("reorth='partial' and reorth='twice' exclude each other")
-    use_shadow = USE_SHADOW and k > 1 and not partial and shadow_fits(device, k, ldq, n, arena)
+    use_shadow = USE_SHADOW and k > 1 and not partial and shadow_fits(device, k, ldq, n, arena, 1 if shadow8 else 2)
     global last_reorth_steps
     last_reorth_steps = None
     if native is not None:
@@ -461,7 +487,10 @@ def lanczos(A, k, n, device, q0, native=None, callable_A=None, arena=False):
         with ws.owned_by("Lanczos (native operator)"):
             if use_shadow:
                 shadow = new_shadow()
-                check(lib.dsea_ws_set_shadow(ws.handle, _ptr(shadow), ldq, int(k), float(SHADOW_TAU)), "dsea_ws_set_shadow")
+                if shadow8:
+                    check(lib.dsea_ws_set_shadow8(ws.handle, _ptr(shadow), ldq, int(k), float(shadow8_tau(n))), "dsea_ws_set_shadow8")
+                else:
+                    check(lib.dsea_ws_set_shadow(ws.handle, _ptr(shadow), ldq, int(k), float(SHADOW_TAU)), "dsea_ws_set_shadow")
             try:
                 if getattr(ws, "reorth_passes", 1) != int(REORTH_PASSES):
                     check(lib.dsea_ws_set_reorth_passes(ws.handle, int(REORTH_PASSES)), "dsea_ws_set_reorth_passes")
@@ -502,6 +531,7 @@ def lanczos(A, k, n, device, q0, native=None, callable_A=None, arena=False):
             finally:
                 if shadow is not None:
                     check(lib.dsea_ws_set_shadow(ws.handle, None, 0, 0, 0.0), "dsea_ws_set_shadow")
+                    check(lib.dsea_ws_set_shadow8(ws.handle, None, 0, 0, 0.0), "dsea_ws_set_shadow8")
         if last_break:
             # The device loop stopped itself at step last_break (beta ~ 0: the Krylov space of q0 is exhausted).  What
             # lies behind was never written: make it recognisable instead of handing out stale memory -- NaN alphas,
@@ -627,7 +657,7 @@ def lanczos_basisfree(native, k, n, device, q0, which="min"):
 
 
 def lanczos_lp_stats(n, device):
-    """(steps that streamed the bf16 shadow, steps that fell back to the fp64 basis) of the last native run"""
+    """(steps that streamed the bf16 or 8-bit shadow, steps that fell back to the fp64 basis) of the last native run"""
     lib = _lib.load()
     ws = Workspace.get(n, 8, device)
     a, b = c_int64(0), c_int64(0)

@@ -118,6 +118,14 @@ int dsea_ws_set_fault_injection(dsea_ws_t ws, int lose_peer);
  * max|c_j| <= tau ||r|| on the device each step and otherwise reads the fp64 basis.
  * dsea_lanczos_lp_stats (synchronises) reports how many steps of the last run took each path.       */
 int dsea_ws_set_shadow(dsea_ws_t ws, void *shadow_bf16, int64_t ld, int rows, double tau);
+/* The same with ONE byte per element (caller-owned, `rows` x `ld` uint8, ld % 16 == 0, 16-byte aligned; null = off):
+ * code = float8_e5m2(float32(q * S)), S = 2^ceil(log2(n) / 2) (at most 2^15), both roundings to nearest even.  Read by
+ * the correction pass of dsea_lanczos_run's multi-launch loop and of dsea_lanczos_axpy_norm from 2^20 rows on (below,
+ * and in the single-launch forms, the pass reads the fp64 basis); kept current by dsea_lanczos_run in that regime and by
+ * dsea_lanczos_store.  The correction is accumulated in fp32 and applied in one fp64 step; the device-side premise is
+ * max|c_j| <= tau8 ||r||.  Registering either shadow un-registers the other: a workspace has at most one.
+ * dsea_lanczos_lp_stats counts this pass like the bf16 one.                                                    */
+int dsea_ws_set_shadow8(dsea_ws_t ws, void *shadow_e5m2, int64_t ld, int rows, double tau8);
 int dsea_lanczos_lp_stats(dsea_ws_t ws, int64_t *lp_steps, int64_t *fp64_steps, void *stream);
 
 /* Per-launch timing of the dominant kernels with HIP events recorded on the launch stream
