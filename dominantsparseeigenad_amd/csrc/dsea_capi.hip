@@ -171,7 +171,8 @@ TileGeom Workspace::geom(int64_t n_rows) const {
 
 extern "C" {
 
-int dsea_version(void) { return 142; }   // 142: matrix-free XYZ spin chain with per-site couplings (mat-vec + parameter adjoint)
+int dsea_version(void) { return 143; }   // 143: matrix-free XYZ spins on a caller-given bond list (mat-vec + parameter adjoint)
+                                          // 142: matrix-free XYZ spin chain with per-site couplings (mat-vec + parameter adjoint)
                                           // 141: lowest-nev eigenpairs (block Ritz combine, block projection, deflated CG)
                                           // 140: fp64-MFMA transfer mat-vec on packed operands, optimistic Arnoldi second pass
 
@@ -523,6 +524,42 @@ int dsea_op_chain_forms(dsea_op_t op, const double* v1, const double* v2, double
   REQUIRE(op && op->d.kind == OP_CHAIN && v1 && v2 && out5L && scratch, DSEA_ERR_ARG);
   REQUIRE(aligned16(v1) && aligned16(v2), DSEA_ERR_ALIGN);
   if (launch_chain_forms(op->d, v1, v2, out5L, scratch, static_cast<hipStream_t>(stream)) != 0) return DSEA_ERR_UNSUPPORTED;
+  return check_launch();
+}
+
+int dsea_op_create_lattice(int L, int nb, const int32_t* bonds_host, const double* couplings_dev, dsea_op_t* out) {
+  REQUIRE(out && L >= 2 && L <= 62 && nb >= 1 && nb <= DSEA_LATTICE_MAX_BONDS && bonds_host && couplings_dev, DSEA_ERR_ARG);
+  for (int t = 0; t < nb; ++t) {
+    const int32_t a = bonds_host[2 * t], b = bonds_host[2 * t + 1];
+    REQUIRE(a >= 0 && a < L && b >= 0 && b < L && a != b, DSEA_ERR_ARG);
+  }
+  dsea_op_s* op = new (std::nothrow) dsea_op_s;
+  if (!op) return DSEA_ERR_ARG;
+  memset(&op->d, 0, sizeof(op->d));
+  op->d.tune_tile_log2 = DSEA_TFIM_TILE_LOG2;
+  op->d.kind = OP_LATTICE;
+  op->d.n = (int64_t)1 << L;
+  op->d.lattice.L = L;
+  op->d.lattice.nb = nb;
+  op->d.lattice.c = couplings_dev;
+  for (int t = 0; t < nb; ++t) {
+    op->d.lattice.a[t] = (uint8_t)bonds_host[2 * t];
+    op->d.lattice.b[t] = (uint8_t)bonds_host[2 * t + 1];
+  }
+  *out = op;
+  return DSEA_OK;
+}
+
+int dsea_op_lattice_forms_scratch_doubles(int L, int nb, int64_t* out) {
+  REQUIRE(out && L >= 2 && L <= 62 && nb >= 1 && nb <= DSEA_LATTICE_MAX_BONDS, DSEA_ERR_ARG);
+  *out = lattice_forms_scratch_doubles(L, nb);
+  return DSEA_OK;
+}
+
+int dsea_op_lattice_forms(dsea_op_t op, const double* v1, const double* v2, double* out, double* scratch, void* stream) {
+  REQUIRE(op && op->d.kind == OP_LATTICE && v1 && v2 && out && scratch, DSEA_ERR_ARG);
+  REQUIRE(aligned16(v1) && aligned16(v2), DSEA_ERR_ALIGN);
+  if (launch_lattice_forms(op->d, v1, v2, out, scratch, static_cast<hipStream_t>(stream)) != 0) return DSEA_ERR_UNSUPPORTED;
   return check_launch();
 }
 

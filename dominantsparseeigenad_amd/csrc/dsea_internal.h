@@ -113,11 +113,19 @@ struct ChainParams {
   int L;
   const double* c;
 };
-enum OpKind { OP_TFIM = 1, OP_CSR = 2, OP_STENCIL3 = 3, OP_SELL = 4, OP_DENSE = 5, OP_TRANSFER = 6, OP_SYMDENSE = 7, OP_CHAIN = 8 };
+// XYZ spins on a caller-given bond list (dsea_lattice.hip): bond t joins sites a[t] != b[t] (host copies, the caller's order);
+// c = [Jx(nb), Jy(nb), Jz(nb), hx(L), hz(L)] on the device -- read through the pointer on every launch
+struct LatticeDesc {
+  int L, nb;
+  const double* c;
+  uint8_t a[DSEA_LATTICE_MAX_BONDS], b[DSEA_LATTICE_MAX_BONDS];
+};
+enum OpKind { OP_TFIM = 1, OP_CSR = 2, OP_STENCIL3 = 3, OP_SELL = 4, OP_DENSE = 5, OP_TRANSFER = 6, OP_SYMDENSE = 7, OP_CHAIN = 8,
+              OP_LATTICE = 9 };
 struct OpDesc {
   OpKind kind;
   int64_t n;
-  int tune_tile_log2;  // TFIM, spin chain: log2 rows of x staged in LDS per block (6..12)
+  int tune_tile_log2;  // TFIM, spin chain, spin lattice: log2 rows of x staged in LDS per block (6..12)
   int tune_csr_group;  // CSR: lanes per row, 0 = automatic
   int tune_sell_unroll;  // SELL: slice-column pairs in flight per lane {0 = automatic, 2, 4, 6, 8}; 1 = the round-5 kernel (A/B)
   TfimParams tfim;
@@ -128,6 +136,7 @@ struct OpDesc {
   TransferParams transfer;
   SymDenseParams symdense;
   ChainParams chain;
+  LatticeDesc lattice;
 };
 
 // One basis row's storage shadow as the writers see it: bf16 (h), e5m2 codes of q * S (b), or neither.  At most one of
@@ -395,6 +404,13 @@ int launch_spmv_chain(const OpDesc& op, const double* x, double* y, const double
                       hipStream_t st, EventPair* ev);
 int launch_chain_forms(const OpDesc& op, const double* v1, const double* v2, double* out, double* scratch, hipStream_t st);
 int64_t chain_forms_scratch_doubles(int L);
+// dsea_lattice.hip (XYZ spins on a bond list): the mat-vec of launch_spmv's OP_LATTICE case; the 3 nb + 2 L bilinear forms
+// v1^T (dH/dp) v2 into out through per-block partials in the caller's scratch (lattice_forms_scratch_doubles(L, nb) doubles);
+// both return -1 when L, nb or the tile is out of range
+int launch_spmv_lattice(const OpDesc& op, const double* x, double* y, const double* shift, const double* skip, double* P,
+                        hipStream_t st, EventPair* ev);
+int launch_lattice_forms(const OpDesc& op, const double* v1, const double* v2, double* out, double* scratch, hipStream_t st);
+int64_t lattice_forms_scratch_doubles(int L, int nb);
 // dsea_cg_persist_tfim_big.hip
 bool cg_persist_tfim_big_applicable(const OpDesc& op);
 size_t cg_persist_tfim_big_comm_bytes(int64_t n);

@@ -1172,6 +1172,8 @@ int launch_spmv(const OpDesc& op, const double* x, double* y, const double* shif
     }
     case OP_CHAIN:
       return launch_spmv_chain(op, x, y, shift, skip, P, st, ev);
+    case OP_LATTICE:
+      return launch_spmv_lattice(op, x, y, shift, skip, P, st, ev);
   }
   return -1;
 }

@@ -11,7 +11,7 @@ Each operator is
 """
 from __future__ import annotations
 
-from ctypes import byref, c_int64, c_void_p
+from ctypes import byref, c_int32, c_int64, c_void_p
 
 import torch
 
@@ -353,6 +353,244 @@ class _ChainForms(torch.autograd.Function):
                 g1 = _ChainApply.apply(v2, G, ctx.op, adj)
             if ctx.needs_input_grad[1]:
                 g2 = _ChainApply.apply(v1, G, ctx.op, adj)
+        return g1, g2, None, None
+
+
+# ------------------------------------------------------------------------------------------ XYZ spins on a bond list
+def ring_bonds(L, distance=1):
+    """the L bonds (i, (i + distance) mod L) of a ring, i = 0 .. L - 1 (pure Python; a ring whose distance wraps onto the same
+    pair, L = 2 distance, lists that pair twice -- the TFIM convention)"""
+    L, distance = int(L), int(distance)
+    if L < 2 or distance % L == 0:
+        raise ValueError("ring_bonds needs L >= 2 and a distance that is no multiple of L")
+    return [(i, (i + distance) % L) for i in range(L)]
+
+
+def square_bonds(Lx, Ly, periodic=(True, True)):
+    """nearest-neighbour bonds of an Lx x Ly square lattice, site = y * Lx + x: for every site its +x bond, then its +y bond
+    (pure Python).  An open direction has no bond across its edge; a periodic direction of length 2 lists its bond twice (the
+    TFIM convention); a direction of length 1 has no bonds."""
+    Lx, Ly = int(Lx), int(Ly)
+    if Lx < 1 or Ly < 1:
+        raise ValueError("square_bonds needs Lx, Ly >= 1")
+    px, py = bool(periodic[0]), bool(periodic[1])
+    bonds = []
+    for y in range(Ly):
+        for x in range(Lx):
+            if Lx > 1 and (x + 1 < Lx or px):
+                bonds.append((y * Lx + x, y * Lx + (x + 1) % Lx))
+            if Ly > 1 and (y + 1 < Ly or py):
+                bonds.append((y * Lx + x, ((y + 1) % Ly) * Lx + x))
+    return bonds
+
+
+def _check_bonds(L, bonds):
+    """the bond list as a tuple of int pairs; ValueError for what dsea_op_create_lattice refuses"""
+    out = tuple((int(a), int(b)) for a, b in bonds)
+    if not 1 <= len(out) <= _lib.LATTICE_MAX_BONDS:
+        raise ValueError("SpinLatticeOperator needs 1 <= len(bonds) <= %d, got %d" % (_lib.LATTICE_MAX_BONDS, len(out)))
+    for a, b in out:
+        if not (0 <= a < L and 0 <= b < L) or a == b:
+            raise ValueError("bond (%d, %d): two different sites in 0 .. %d are needed" % (a, b, L - 1))
+    return out
+
+
+def _lattice_view(L, bonds, couplings, like=None):
+    """(handle, n) of the bond-list Hamiltonian whose couplings are the (3 nb + 2 L,) tensor ``couplings``; ``like``: a view
+    whose tile tuning the new handle takes over."""
+    data = couplings.detach()
+    if data.dtype != F64 or not data.is_contiguous():
+        data = data.to(F64).contiguous()
+    flat = (c_int32 * (2 * len(bonds)))(*[s for bond in bonds for s in bond])
+    raw = c_void_p()
+    check(_lib.load().dsea_op_create_lattice(int(L), len(bonds), flat, c_void_p(data.data_ptr()), byref(raw)),
+          "dsea_op_create_lattice")
+    view = _NativeView(_Handle(raw, 1 << int(L), data))
+    view.tile_log2 = None
+    if like is not None and like.tile_log2 is not None:
+        _set_chain_tile(view, like.tile_log2)
+    return view
+
+
+def _lattice_forms(view, L, nb, v1, v2):
+    """all 3 nb + 2 L bilinear forms v1^T (dH/dp) v2 (dsea_op_lattice_forms: one pass, deterministic)"""
+    lib = _lib.load()
+    n = view.n
+    v1, v2 = engine.as_vector(v1, n), engine.as_vector(v2, n)
+    need = c_int64()
+    check(lib.dsea_op_lattice_forms_scratch_doubles(int(L), int(nb), byref(need)), "dsea_op_lattice_forms_scratch_doubles")
+    scratch = torch.empty(need.value, dtype=F64, device=v1.device)
+    out = torch.empty(3 * int(nb) + 2 * int(L), dtype=F64, device=v1.device)
+    check(lib.dsea_op_lattice_forms(view.handle, c_void_p(v1.data_ptr()), c_void_p(v2.data_ptr()), c_void_p(out.data_ptr()),
+                                    c_void_p(scratch.data_ptr()), engine._stream(v1.device)), "dsea_op_lattice_forms")
+    return out
+
+
+class SpinLatticeOperator:
+    """H = sum_t [Jx_t X_a X_b + Jy_t Y_a Y_b + Jz_t Z_a Z_b] + sum_i [hx_i X_i + hz_i Z_i] on L sites, dimension 2^L,
+    matrix-free, with bond t joining the sites ``bonds[t] = (a_t, b_t)`` of a caller-given list
+    (docs/design/16-spin-lattice.md).  Site i is bit i of the row index; (a, b) and (b, a) are the same bond; a repeated bond
+    counts each time it is listed; 1 <= len(bonds) <= 128.  ``ring_bonds`` and ``square_bonds`` build common lists.
+
+    ``couplings`` is ONE contiguous float64 device tensor of length 3 nb + 2 L in the order [Jx(nb), Jy(nb), Jz(nb), hx(L),
+    hz(L)] -- the parameter (it may require grad; ``pack`` / ``unpack`` convert).  The kernels read it through its device
+    pointer on every launch: in-place optimiser steps are seen, binding another tensor rebuilds the handle.  ``H(v)`` is
+    differentiable in v and in ``couplings``; ``Hadjoint_to_couplingsadjoint(v1, v2)`` is the hook for
+    ``setDominantSparseSymeig`` / ``setLowestSparseSymeig``: all 3 nb + 2 L forms v1^T (dH/dp) v2 in one pass.  Both are
+    re-entrant (H is linear in the couplings: the backward of the forms is a mat-vec with the incoming adjoint as couplings),
+    so second order works as for ``SpinChainOperator``.
+    Row-partitioned slabs, a fused Lanczos tail and the persistent single-launch forms do not exist for this operator."""
+
+    _native_methods = ("H", "__call__")
+
+    def __init__(self, L, bonds, couplings, device=None):
+        self.N = int(L)
+        if not 2 <= self.N <= 62:
+            raise ValueError("SpinLatticeOperator needs 2 <= L <= 62, got %d" % self.N)
+        self._bonds = _check_bonds(self.N, bonds)
+        self.nb = len(self._bonds)
+        self.nparam = 3 * self.nb + 2 * self.N
+        self.dim = self.n = 1 << self.N
+        if device is None:
+            device = couplings.device if torch.is_tensor(couplings) else "cuda"
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError("SpinLatticeOperator is a device operator; use device='cuda'")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self._c = None
+        self._H = None
+        self._tile_log2 = None
+        self.couplings = couplings
+
+    @property
+    def bonds(self):
+        """the bond list as a tuple of (a, b) pairs, in the order of the couplings (read-only)"""
+        return self._bonds
+
+    @property
+    def couplings(self):
+        return self._c
+
+    @couplings.setter
+    def couplings(self, value):
+        if not torch.is_tensor(value):
+            value = torch.as_tensor(value, dtype=F64).to(self.device)
+        if value.device != self.device or value.dtype != F64:
+            raise ValueError("couplings must be a float64 tensor on %s" % self.device)
+        if tuple(value.shape) != (self.nparam,) or not value.is_contiguous():
+            raise ValueError("couplings must be a contiguous tensor of shape (%d,): Jx(nb), Jy(nb), Jz(nb), hx(L), hz(L)"
+                             % self.nparam)
+        self._c = value
+        self._H = _lattice_view(self.N, self._bonds, value)   # the kernels read the couplings through this tensor's pointer
+        if self._tile_log2 is not None:
+            _set_chain_tile(self._H, self._tile_log2)
+
+    def set_tile_log2(self, tile_log2):
+        """log2 of the rows of x a block stages in LDS (6..12; measurement aid, dsea_op_set_tuning)"""
+        _set_chain_tile(self._H, tile_log2)
+        self._tile_log2 = int(tile_log2)
+
+    def pack(self, Jx, Jy, Jz, hx, hz):
+        """the five families (scalars, or one value per bond / per site) as one parameter tensor on the operator's device"""
+        sizes = (self.nb, self.nb, self.nb, self.N, self.N)
+        parts = []
+        for value, size in zip((Jx, Jy, Jz, hx, hz), sizes):
+            t = torch.as_tensor(value, dtype=F64).to(self.device)
+            parts.append(t.expand(size) if t.dim() == 0 else t.reshape(size))
+        return torch.cat(parts).contiguous()
+
+    def unpack(self, t):
+        """views (Jx, Jy, Jz, hx, hz) of a parameter tensor"""
+        nb, L = self.nb, self.N
+        if tuple(t.shape) != (self.nparam,):
+            raise ValueError("expected a tensor of shape (%d,)" % self.nparam)
+        return t[:nb], t[nb:2 * nb], t[2 * nb:3 * nb], t[3 * nb:3 * nb + L], t[3 * nb + L:]
+
+    @property
+    def handle(self):
+        return self._H.handle
+
+    def H(self, v):
+        """H v, differentiable in v and in the couplings"""
+        return _LatticeApply.apply(v, self._c, self, self._H)
+
+    __call__ = H
+
+    def Hadjoint_to_couplingsadjoint(self, v1, v2):
+        """adjoint hook: couplings-bar[t] = v1^T (dH/dp_t) v2, shape (3 nb + 2 L,)"""
+        return _LatticeForms.apply(v1, v2, self, self._H)
+
+    def to_csr(self, layout="sell", col16="auto", values="auto"):
+        """The same matrix as an explicit device CSR operand: the diagonal, L field columns and one column per distinct bond
+        mask (bonds with equal masks are summed into one stored entry).  Built on the device with index arithmetic."""
+        L, n = self.N, self.n
+        jx, jy, jz, hx, hz = self.unpack(self._c.detach())
+        idx = torch.arange(n, dtype=torch.int64, device=self.device)
+        z = [(1 - 2 * ((idx >> i) & 1)).to(F64) for i in range(L)]
+        diag = torch.zeros(n, dtype=F64, device=self.device)
+        for i in range(L):
+            diag = diag + hz[i] * z[i]
+        by_mask = {}
+        for t, (a, b) in enumerate(self._bonds):
+            zz = z[a] * z[b]
+            diag = diag + jz[t] * zz
+            m = (1 << a) | (1 << b)
+            v = jx[t] - jy[t] * zz
+            by_mask[m] = by_mask[m] + v if m in by_mask else v
+        cols, vals = [idx], [diag]
+        for i in range(L):
+            cols.append(idx ^ (1 << i))
+            vals.append(hx[i].expand(n))
+        for m, v in by_mask.items():
+            cols.append(idx ^ m)
+            vals.append(v)
+        cols, vals = torch.stack(cols, dim=1), torch.stack(vals, dim=1)
+        order = torch.argsort(cols, dim=1)
+        cols, vals = torch.gather(cols, 1, order), torch.gather(vals, 1, order)
+        per = cols.shape[1]
+        rowptr = torch.arange(n + 1, dtype=torch.int64, device=self.device) * per
+        return CSROperator(rowptr, cols.reshape(-1), vals.reshape(-1).contiguous(), n, layout=layout, col16=col16, values=values)
+
+
+class _LatticeApply(torch.autograd.Function):
+    """y = H[c] v.  Backward: H[c] gy (symmetric) and the forms(gy, v) -- both re-entrant."""
+
+    @staticmethod
+    def forward(ctx, v, c, op, view):
+        ctx.op, ctx.view = op, view
+        ctx.save_for_backward(v, c)
+        return engine.spmv(view, v.detach())
+
+    @staticmethod
+    def backward(ctx, gy):
+        v, c = ctx.saved_tensors
+        gv = _LatticeApply.apply(gy, c, ctx.op, ctx.view) if ctx.needs_input_grad[0] else None
+        gc = _LatticeForms.apply(gy, v, ctx.op, ctx.view).reshape(c.shape) if ctx.needs_input_grad[1] else None
+        return gv, gc, None, None
+
+
+class _LatticeForms(torch.autograd.Function):
+    """out[t] = v1^T (dH/dp_t) v2, shape (3 nb + 2 L,).  H is linear in the couplings, so with the incoming adjoint G as
+    couplings the backward is d/dv1 = H[G] v2 and d/dv2 = H[G] v1: the same mat-vec kernel on the same bond list."""
+
+    @staticmethod
+    def forward(ctx, v1, v2, op, view):
+        ctx.op, ctx.view = op, view
+        ctx.save_for_backward(v1, v2)
+        return _lattice_forms(view, op.N, op.nb, v1.detach(), v2.detach())
+
+    @staticmethod
+    def backward(ctx, G):
+        v1, v2 = ctx.saved_tensors
+        g1 = g2 = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            G = G.reshape(ctx.op.nparam)
+            adj = _lattice_view(ctx.op.N, ctx.op.bonds, G, like=ctx.view)   # the Hamiltonian whose couplings are the adjoint
+            if ctx.needs_input_grad[0]:
+                g1 = _LatticeApply.apply(v2, G, ctx.op, adj)
+            if ctx.needs_input_grad[1]:
+                g2 = _LatticeApply.apply(v1, G, ctx.op, adj)
         return g1, g2, None, None
 
 

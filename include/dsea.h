@@ -166,6 +166,27 @@ int dsea_op_create_chain(int L, const double *couplings_dev, dsea_op_t *out);
 int dsea_op_chain_forms_scratch_doubles(int L, int64_t *out);
 int dsea_op_chain_forms(dsea_op_t op, const double *v1, const double *v2, double *out5L, double *scratch, void *stream);
 
+#define DSEA_LATTICE_MAX_BONDS 128 /* most bonds of dsea_op_create_lattice (a 4 x 6 J1-J2 torus has 96, K16 has 120) */
+/* XYZ spins on a caller-given bond list, matrix-free (docs/design/16-spin-lattice.md): L sites, site i = bit i of the row
+ * index s, z_i(s) = 1 - 2 bit_i(s); bond t joins sites a_t != b_t (bonds_host[2t], bonds_host[2t+1], a HOST array that is
+ * copied at creation), m_t = (1<<a_t)|(1<<b_t):
+ *     H = sum_t [ Jx_t X_a X_b + Jy_t Y_a Y_b + Jz_t Z_a Z_b ] + sum_i [ hx_i X_i + hz_i Z_i ]
+ *     y[s] = ( sum_t Jz_t z_a z_b + sum_i hz_i z_i ) x[s] + sum_i hx_i x[s ^ (1<<i)] + sum_t ( Jx_t - Jy_t z_a z_b ) x[s ^ m_t]
+ * (a, b) and (b, a) are the same bond; a repeated bond counts each time it is listed.
+ * couplings_dev: fp64 [3 nb + 2 L] on the device in the order Jx(nb), Jy(nb), Jz(nb), hx(L), hz(L); READ THROUGH THE POINTER
+ * ON EVERY LAUNCH (no host copy: in-place updates are seen).  Checked on the host before any device work (DSEA_ERR_ARG):
+ * 2 <= L <= 62, 1 <= nb <= DSEA_LATTICE_MAX_BONDS, 0 <= a_t, b_t < L, a_t != b_t, non-null pointers.  Nothing is launched and
+ * nothing is allocated on the device at creation.  n = 2^L.  dsea_op_set_tuning DSEA_TUNE_TFIM_TILE_LOG2 applies.  No fused
+ * Lanczos tail, no persistent forms. */
+int dsea_op_create_lattice(int L, int nb, const int32_t *bonds_host, const double *couplings_dev, dsea_op_t *out);
+/* The parameter adjoint of dsea_op_create_lattice: out[t] = v1^T (dH/dp_t) v2 for all 3 nb + 2 L couplings in the order of
+ * couplings_dev, in one pass over v1 and v2 (per-block partials in `scratch`, then a fixed-order reduction: no atomics,
+ * repeated calls return identical bits).  `scratch`: caller-owned, dsea_op_lattice_forms_scratch_doubles(L, nb) =
+ * (3 nb + 2 L) * min(4096, 2^max(L-6, 0)) doubles (enough for every tile tuning); the library allocates nothing.  v1, v2
+ * 16-byte aligned.  DSEA_ERR_ARG for any other operator kind. */
+int dsea_op_lattice_forms_scratch_doubles(int L, int nb, int64_t *out);
+int dsea_op_lattice_forms(dsea_op_t op, const double *v1, const double *v2, double *out, double *scratch, void *stream);
+
 /* CSR, caller-owned device arrays: rowptr int64 [n+1], colidx int32 [nnz], vals fp64 [nnz]. */
 int dsea_op_create_csr(int64_t n, int64_t nnz, const int64_t *rowptr, const int32_t *colidx,
                        const double *vals, dsea_op_t *out);
