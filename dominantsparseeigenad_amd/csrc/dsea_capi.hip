@@ -171,7 +171,8 @@ TileGeom Workspace::geom(int64_t n_rows) const {
 
 extern "C" {
 
-int dsea_version(void) { return 143; }   // 143: matrix-free XYZ spins on a caller-given bond list (mat-vec + parameter adjoint)
+int dsea_version(void) { return 144; }   // 144: GMRES state[6] (singular column), dsea_gmres_step repeats begin's checks, second-pass counter cleared by every start
+                                          // 143: matrix-free XYZ spins on a caller-given bond list (mat-vec + parameter adjoint)
                                           // 142: matrix-free XYZ spin chain with per-site couplings (mat-vec + parameter adjoint)
                                           // 141: lowest-nev eigenpairs (block Ritz combine, block projection, deflated CG)
                                           // 140: fp64-MFMA transfer mat-vec on packed operands, optimistic Arnoldi second pass
@@ -1393,6 +1394,7 @@ int dsea_arnoldi_orth(dsea_ws_t ws, const double* u, const double* shift, double
   Workspace& w = ws->w;
   double* brk = w.scal + DSEA_SCAL_BREAK;
   if (j == 0) {
+    HIP_TRY(hipMemsetAsync(w.scal + 31, 0, sizeof(double), st));   // second-pass counter, as dsea_arnoldi_extend(j0 = 0)
     HIP_TRY(hipMemsetAsync(brk, 0, 2 * sizeof(double), st));
     HIP_TRY(hipMemsetAsync(w.scal + DSEA_SCAL_LZ_FAIL, 0, sizeof(double), st));
   }
@@ -1438,6 +1440,7 @@ int dsea_gmres_begin(dsea_ws_t ws, const double* b, const double* Ax, double* V,
   GmresWork gw = gmres_carve(work, m);
   double* nrm0 = w.scal + 0;
   double* r0 = w.vec[3];
+  HIP_TRY(hipMemsetAsync(w.scal + 31, 0, sizeof(double), st));         // second-pass counter: a cycle is a new factorisation
   launch_residual(b, Ax, r0, n, w.partials, nrm0, st);                 // r0 = b - (A - shift) x  (Ax null: x = 0)
   launch_gmres_begin(nrm0, target, gw.g, m, state, w.scal + 28, st);
   // v0 = r0 / ||r0|| -- skipped on the device when the cycle starts converged (r0 = 0 would give 0/0)
@@ -1450,6 +1453,8 @@ int dsea_gmres_step(dsea_op_t op, dsea_ws_t ws, const double* shift, const doubl
   REQUIRE(ws && V && work && state && m >= 1 && m <= 64 && j >= 0 && j < m && (op || u), DSEA_ERR_ARG);
   if (op) n = op->d.n;
   REQUIRE(n >= 1 && ldv >= n && ws->w.n >= n, DSEA_ERR_ARG);
+  REQUIRE(m + 1 <= ws->w.kmax, DSEA_ERR_WORKSPACE);                    // (the step writes coef[0..j+1])
+  REQUIRE(aligned16(V) && (ldv % 2 == 0), DSEA_ERR_ALIGN);
   hipStream_t st = static_cast<hipStream_t>(stream);
   Workspace& w = ws->w;
   GmresWork gw = gmres_carve(work, m);

@@ -440,6 +440,8 @@ __global__ __launch_bounds__(256) void k_arnoldi_finish_opt(const double* __rest
 // gw = device work: H (m+1) x m column-major | cs[m] | sn[m] | g[m+1] | y[m]
 // state: [0] residual estimate  [1] converged (0/1)  [2] columns processed in this cycle  [3] ||r0||
 //        [4] cycle finished early (converged, or the Krylov space is exhausted)
+//        [5] optimistic mode: a step needed the second Gram-Schmidt pass (the cycle ended before it)
+//        [6] singular: a column's rotated diagonal is exactly 0 -- no progress possible, the column is not counted
 // brk  : the skip / breakdown record handed to the Arnoldi step kernels of the cycle (non-zero = steps are no-ops)
 // ------------------------------------------------------------------------------------------
 __global__ void k_gmres_begin(const double* __restrict__ nrm2, double target, double* __restrict__ g, int m,
@@ -454,6 +456,7 @@ __global__ void k_gmres_begin(const double* __restrict__ nrm2, double target, do
   state[1] = conv ? 1.0 : 0.0;
   state[4] = conv ? 1.0 : 0.0;
   state[5] = 0.0;              // (optimistic mode: a step of this cycle needed the second Gram-Schmidt pass)
+  state[6] = 0.0;              // (singular column, see k_gmres_givens)
   brk[0] = conv ? 1.0 : 0.0;   // converged already: every step kernel of the cycle returns at once
   brk[1] = 0.0;
 }
@@ -478,7 +481,15 @@ __global__ void k_gmres_givens(double* __restrict__ H, int ldh, int j, double* _
     h[t + 1] = -sn[t] * a + cs[t] * b;
   }
   const double rho = hypot(h[j], h[j + 1]);
-  const double c = rho == 0.0 ? 1.0 : h[j] / rho, s = rho == 0.0 ? 0.0 : h[j + 1] / rho;
+  if (rho == 0.0) {
+    // (A - shift I) v_j lies in span(V[0..j)) and the rotated column has no diagonal: R would be singular and the system has
+    // no solution in this Krylov space beyond what columns 0..j-1 give.  The column is not counted (state[2] stays j, the
+    // back-substitution never divides by 0), the cycle ends, and nothing claims convergence.
+    state[4] = 1.0;
+    state[6] = 1.0;
+    return;
+  }
+  const double c = h[j] / rho, s = h[j + 1] / rho;
   cs[j] = c;
   sn[j] = s;
   h[j] = rho;

@@ -550,6 +550,14 @@ def gmres(A, b, shift=None, rtol=1e-12, atol=1e-12, restart=20, maxiter=None):
         info = state.cpu()
         if info[1].item() != 0.0:
             break
+        if info[6].item() != 0.0:
+            # include/dsea.h state[6]: (A - shift I) v_j fell into the span of the basis with a zero rotated diagonal -- the
+            # system is singular and inconsistent for this right-hand side; a restart would meet the same column again
+            DIAG.gmres_cycles = c + 1
+            DIAG.gmres_residual = float(info[0].item())
+            raise RuntimeError("gmres: singular system -- (A - shift I) maps the Krylov space of b into itself without reaching "
+                               "b (residual %.3e after %d columns of cycle %d); no progress is possible"
+                               % (float(info[0].item()), int(info[2].item()), c + 1))
         if optimistic and info[5].item() != 0.0:
             optimistic = False
             DIAG.gmres_second_pass_fallbacks += 1

@@ -633,7 +633,9 @@ int dsea_lanczos_status(dsea_ws_t ws, int *break_step, void *stream);
 int dsea_arnoldi_extend(dsea_op_t op, dsea_ws_t ws, const double *shift, double *V, int64_t ldv, int j0, int j1,
                         double *H, int ldh, void *stream);
 
-/* diagnostics (synchronises): how many steps since the last j0 == 0 call needed the second Gram-Schmidt pass */
+/* diagnostics (synchronises): how many steps needed the second Gram-Schmidt pass since the last START of a factorisation:
+ * dsea_arnoldi_extend with j0 == 0, dsea_arnoldi_orth with j == 0 and dsea_gmres_begin (so every GMRES cycle) clear the
+ * count.  In the optimistic mode a step that fails the test is counted when it is repeated with the pass, not before.  */
 int dsea_arnoldi_second_passes(dsea_ws_t ws, int64_t *count, void *stream);
 
 /* OPTIMISTIC second pass (round 4; off by default).  The second Gram-Schmidt pass of dsea_arnoldi_extend is needed rarely
@@ -671,12 +673,26 @@ int dsea_arnoldi_orth(dsea_ws_t ws, const double *u, const double *shift, double
  * Givens rotations, back-substitution and the update x += V y -- all on the stream, no host sync inside.  `first`
  * != 0: x is taken as 0 (r0 = b).  `target` = absolute residual bound max(rtol ||b||, atol) (scipy's rule,
  * eig.py:54).  work: dsea_gmres_work_doubles(m) device doubles; V: (m+1) x ldv, zero-initialised once by the caller.
- * state (8 device doubles): [0] residual estimate  [1] converged  [2] columns used  [3] ||r0||  [4] finished early.
- * The caller reads `state` after the cycle (its one sync) and issues the next cycle if [1] == 0.                 */
+ * state (8 device doubles): [0] residual estimate  [1] converged  [2] columns used  [3] ||r0||  [4] finished early
+ * (converged, Krylov space exhausted, or one of the next two)  [5] optimistic mode: a step needed the second pass
+ * [6] SINGULAR: (A - shift I) v_j lay in span(V[0..j]) and the rotated column j has an exactly zero diagonal -- no
+ * progress is possible from this start.  Column j is not counted ([2] stays j), [1] is NOT set, x receives the update of
+ * the j columns before it (none for j = 0: x unchanged) and stays finite.  A caller must not restart on [6]: the next
+ * cycle would meet the same column (krylov.gmres raises).
+ * The caller reads `state` after the cycle (its one sync) and issues the next cycle if [1] == 0 and [6] == 0.
+ * Layout of `work` (ldh = m + 1), readable after a cycle:
+ *   H  (m+1) x m column-major at work[0]          column j at work + j*ldh: after the Givens update the upper triangle
+ *                                                 R of the rotated H, exact zeros below the diagonal
+ *   cs[m] at work + (m+1)*m, sn[m] behind it      the rotations (cs[j], sn[j]) that annihilate h[j+1][j]
+ *   g[m+1] behind sn                              the rotated right-hand side; |g[k]| is the residual after k columns
+ *   y[m] behind g                                 written by dsea_gmres_end: R y = g over the state[2] columns used,
+ *                                                 y[t >= state[2]] = 0                                                  */
 size_t dsea_gmres_work_doubles(int m);
 /* the three stages of a cycle (the gmres calls of eig.py:54,57,140,144), for operands whose mat-vec is the caller's code
  * (op == NULL, u = A v_j supplied per step; Ax = (A - shift) x supplied to begin, NULL for x = 0); dsea_gmres_cycle
- * composes them for native operators                                                                              */
+ * composes them for native operators.  dsea_gmres_step repeats the checks of dsea_gmres_begin that concern it: the
+ * workspace was created with kmax >= m + 1 (DSEA_ERR_WORKSPACE), V 16-byte aligned and ldv even (DSEA_ERR_ALIGN); a
+ * refused call enqueues nothing.                                                                                    */
 int dsea_gmres_begin(dsea_ws_t ws, const double *b, const double *Ax, double *V, int64_t ldv, int64_t n, int m,
                      double *work, double target, double *state, void *stream);
 int dsea_gmres_step(dsea_op_t op, dsea_ws_t ws, const double *shift, const double *u, double *V, int64_t ldv,
