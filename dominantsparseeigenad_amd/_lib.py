@@ -27,6 +27,7 @@ ERR_SECOND_PASS = -11
 ERR_UNSUPPORTED = -6
 MAX_NEV = 8            # DSEA_MAX_NEV
 LATTICE_MAX_BONDS = 128  # DSEA_LATTICE_MAX_BONDS
+SECTOR_MAX_L = 40        # the spin-sector operator: 2 <= L <= 40, C(L, ndown) <= 2^31 - 1
 COMM_ID_BYTES = 128
 TUNE_TFIM_TILE_LOG2, TUNE_CSR_GROUP, TUNE_SELL_UNROLL, TUNE_SELL_XCD_MAP, TUNE_SELL_NT = 1, 2, 3, 4, 5
 TUNE_SELL_MAX_WIDTH = 6
@@ -74,6 +75,12 @@ _SIGNATURES = {
     "dsea_op_create_lattice": (c_int, [c_int, c_int, POINTER(c_int32), c_void_p, POINTER(c_void_p)]),
     "dsea_op_lattice_forms_scratch_doubles": (c_int, [c_int, c_int, POINTER(c_int64)]),
     "dsea_op_lattice_forms": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dsea_sector_table_sizes": (c_int, [c_int, c_int, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)]),
+    "dsea_sector_build_tables": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dsea_op_create_sector": (c_int, [c_int, c_int, c_int, POINTER(c_int32), c_void_p, c_void_p, c_void_p, c_void_p,
+                                      POINTER(c_void_p)]),
+    "dsea_op_sector_forms_scratch_doubles": (c_int, [c_int, c_int, c_int, POINTER(c_int64)]),
+    "dsea_op_sector_forms": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dsea_op_create_csr": (c_int, [c_int64, c_int64, c_void_p, c_void_p, c_void_p, POINTER(c_void_p)]),
     "dsea_op_create_sell": (c_int, [c_int64, c_int64, c_void_p, c_void_p, c_void_p, POINTER(c_void_p)]),
     "dsea_op_create_sell16": (c_int, [c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_void_p)]),

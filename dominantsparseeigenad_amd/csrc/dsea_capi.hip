@@ -564,6 +564,63 @@ int dsea_op_lattice_forms(dsea_op_t op, const double* v1, const double* v2, doub
   return check_launch();
 }
 
+int dsea_sector_table_sizes(int L, int ndown, int64_t* n, int64_t* n_lo, int64_t* n_hi) {
+  REQUIRE(n && n_lo && n_hi && sector_sizes(L, ndown, n, n_lo, n_hi), DSEA_ERR_ARG);
+  return DSEA_OK;
+}
+
+int dsea_sector_build_tables(int L, int ndown, int64_t* states, int32_t* lo_rank, int32_t* hi_base, void* stream) {
+  REQUIRE(states && lo_rank && hi_base, DSEA_ERR_ARG);
+  if (launch_sector_build_tables(L, ndown, reinterpret_cast<uint64_t*>(states), reinterpret_cast<uint32_t*>(lo_rank),
+                                 reinterpret_cast<uint32_t*>(hi_base), static_cast<hipStream_t>(stream)) != 0)
+    return DSEA_ERR_ARG;
+  return check_launch();
+}
+
+int dsea_op_create_sector(int L, int ndown, int nb, const int32_t* bonds_host, const double* couplings_dev,
+                          const int64_t* states, const int32_t* lo_rank, const int32_t* hi_base, dsea_op_t* out) {
+  int64_t n, n_lo, n_hi;
+  REQUIRE(out && sector_sizes(L, ndown, &n, &n_lo, &n_hi) && nb >= 1 && nb <= DSEA_LATTICE_MAX_BONDS && bonds_host &&
+              couplings_dev && states && lo_rank && hi_base,
+          DSEA_ERR_ARG);
+  for (int t = 0; t < nb; ++t) {
+    const int32_t a = bonds_host[2 * t], b = bonds_host[2 * t + 1];
+    REQUIRE(a >= 0 && a < L && b >= 0 && b < L && a != b, DSEA_ERR_ARG);
+  }
+  dsea_op_s* op = new (std::nothrow) dsea_op_s;
+  if (!op) return DSEA_ERR_ARG;
+  memset(&op->d, 0, sizeof(op->d));
+  op->d.tune_tile_log2 = 12;   // this kind: log2 of the grid cap (DSEA_MAX_TFIM_BLOCKS)
+  op->d.kind = OP_SECTOR;
+  op->d.n = n;
+  op->d.sector.L = L;
+  op->d.sector.ndown = ndown;
+  op->d.sector.nb = nb;
+  op->d.sector.c = couplings_dev;
+  op->d.sector.states = reinterpret_cast<const uint64_t*>(states);
+  op->d.sector.lo_rank = reinterpret_cast<const uint32_t*>(lo_rank);
+  op->d.sector.hi_base = reinterpret_cast<const uint32_t*>(hi_base);
+  for (int t = 0; t < nb; ++t) {
+    op->d.sector.a[t] = (uint8_t)bonds_host[2 * t];
+    op->d.sector.b[t] = (uint8_t)bonds_host[2 * t + 1];
+  }
+  *out = op;
+  return DSEA_OK;
+}
+
+int dsea_op_sector_forms_scratch_doubles(int L, int ndown, int nb, int64_t* out) {
+  int64_t n, n_lo, n_hi;
+  REQUIRE(out && sector_sizes(L, ndown, &n, &n_lo, &n_hi) && nb >= 1 && nb <= DSEA_LATTICE_MAX_BONDS, DSEA_ERR_ARG);
+  *out = sector_forms_scratch_doubles(n, L, nb);
+  return DSEA_OK;
+}
+
+int dsea_op_sector_forms(dsea_op_t op, const double* v1, const double* v2, double* out, double* scratch, void* stream) {
+  REQUIRE(op && op->d.kind == OP_SECTOR && v1 && v2 && out && scratch, DSEA_ERR_ARG);
+  if (launch_sector_forms(op->d, v1, v2, out, scratch, static_cast<hipStream_t>(stream)) != 0) return DSEA_ERR_UNSUPPORTED;
+  return check_launch();
+}
+
 int dsea_op_create_csr(int64_t n, int64_t nnz, const int64_t* rowptr, const int32_t* colidx,
                        const double* vals, dsea_op_t* out) {
   REQUIRE(out && n >= 1 && nnz >= 0 && rowptr && (nnz == 0 || (colidx && vals)), DSEA_ERR_ARG);

@@ -120,12 +120,24 @@ struct LatticeDesc {
   const double* c;
   uint8_t a[DSEA_LATTICE_MAX_BONDS], b[DSEA_LATTICE_MAX_BONDS];
 };
+// XXZ spins on a caller-given bond list in the sector of ndown set bits (dsea_sector.hip): bond t joins sites a[t] != b[t] (host
+// copies, the caller's order); c = [Jxy(nb), Jz(nb), hz(L)] on the device -- read through the pointer on every launch; states
+// (n words), lo_rank (2^Llo) and hi_base (2^Lhi), Llo = (L + 1) / 2: the caller's device tables (dsea_sector_build_tables)
+#define DSEA_SECTOR_MAX_L 40
+struct SectorDesc {
+  int L, ndown, nb;
+  const double* c;
+  const uint64_t* states;
+  const uint32_t* lo_rank;
+  const uint32_t* hi_base;
+  uint8_t a[DSEA_LATTICE_MAX_BONDS], b[DSEA_LATTICE_MAX_BONDS];
+};
 enum OpKind { OP_TFIM = 1, OP_CSR = 2, OP_STENCIL3 = 3, OP_SELL = 4, OP_DENSE = 5, OP_TRANSFER = 6, OP_SYMDENSE = 7, OP_CHAIN = 8,
-              OP_LATTICE = 9 };
+              OP_LATTICE = 9, OP_SECTOR = 10 };
 struct OpDesc {
   OpKind kind;
   int64_t n;
-  int tune_tile_log2;  // TFIM, spin chain, spin lattice: log2 rows of x staged in LDS per block (6..12)
+  int tune_tile_log2;  // TFIM, spin chain, spin lattice: log2 rows of x staged in LDS per block (6..12); spin sector: log2 of the grid cap
   int tune_csr_group;  // CSR: lanes per row, 0 = automatic
   int tune_sell_unroll;  // SELL: slice-column pairs in flight per lane {0 = automatic, 2, 4, 6, 8}; 1 = the round-5 kernel (A/B)
   TfimParams tfim;
@@ -137,6 +149,7 @@ struct OpDesc {
   SymDenseParams symdense;
   ChainParams chain;
   LatticeDesc lattice;
+  SectorDesc sector;
 };
 
 // One basis row's storage shadow as the writers see it: bf16 (h), e5m2 codes of q * S (b), or neither.  At most one of
@@ -411,6 +424,16 @@ int launch_spmv_lattice(const OpDesc& op, const double* x, double* y, const doub
                         hipStream_t st, EventPair* ev);
 int launch_lattice_forms(const OpDesc& op, const double* v1, const double* v2, double* out, double* scratch, hipStream_t st);
 int64_t lattice_forms_scratch_doubles(int L, int nb);
+// dsea_sector.hip (XXZ spins on a bond list in one magnetisation sector): the sizes n = C(L, ndown), 2^Llo, 2^Lhi (false when
+// L, ndown or n is out of range); the three table fills; the mat-vec of launch_spmv's OP_SECTOR case; the 2 nb + L bilinear
+// forms v1^T (dH/dp) v2 into out through per-block partials in the caller's scratch (sector_forms_scratch_doubles doubles);
+// the launchers return -1 when the descriptor is out of range
+bool sector_sizes(int L, int ndown, int64_t* n, int64_t* n_lo, int64_t* n_hi);
+int launch_sector_build_tables(int L, int ndown, uint64_t* states, uint32_t* lo_rank, uint32_t* hi_base, hipStream_t st);
+int launch_spmv_sector(const OpDesc& op, const double* x, double* y, const double* shift, const double* skip, double* P,
+                       hipStream_t st, EventPair* ev);
+int launch_sector_forms(const OpDesc& op, const double* v1, const double* v2, double* out, double* scratch, hipStream_t st);
+int64_t sector_forms_scratch_doubles(int64_t n, int L, int nb);
 // dsea_cg_persist_tfim_big.hip
 bool cg_persist_tfim_big_applicable(const OpDesc& op);
 size_t cg_persist_tfim_big_comm_bytes(int64_t n);

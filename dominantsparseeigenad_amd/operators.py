@@ -11,6 +11,7 @@ Each operator is
 """
 from __future__ import annotations
 
+import math
 from ctypes import byref, c_int32, c_int64, c_void_p
 
 import torch
@@ -591,6 +592,275 @@ class _LatticeForms(torch.autograd.Function):
                 g1 = _LatticeApply.apply(v2, G, ctx.op, adj)
             if ctx.needs_input_grad[1]:
                 g2 = _LatticeApply.apply(v1, G, ctx.op, adj)
+        return g1, g2, None, None
+
+
+# ------------------------------------------------------------------------------------------ XXZ spins in one S^z sector
+def sector_dim(L, ndown):
+    """the dimension C(L, ndown) of the sector of L sites with ndown set bits (pure Python)"""
+    L, ndown = int(L), int(ndown)
+    if L < 0 or not 0 <= ndown <= L:
+        raise ValueError("sector_dim needs 0 <= ndown <= L")
+    return math.comb(L, ndown)
+
+
+def sector_states(L, ndown):
+    """the L-bit words with ndown set bits as a list of ints in increasing order: the row order of ``SpinSectorOperator``
+    (pure Python, Gosper's next word of the same popcount)"""
+    n = sector_dim(L, ndown)
+    if int(ndown) == 0:
+        return [0]
+    out, s = [], (1 << int(ndown)) - 1
+    for _ in range(n):
+        out.append(s)
+        low = s & -s
+        ripple = s + low
+        s = ripple | (((s ^ ripple) >> 2) // low)
+    return out
+
+
+def _check_sector(L, ndown):
+    """(L, ndown, n) as ints; ValueError for what dsea_sector_table_sizes refuses -- host arithmetic only"""
+    L, ndown = int(L), int(ndown)
+    if not 2 <= L <= _lib.SECTOR_MAX_L:
+        raise ValueError("SpinSectorOperator needs 2 <= L <= %d, got %d" % (_lib.SECTOR_MAX_L, L))
+    if not 1 <= ndown <= L - 1:
+        raise ValueError("SpinSectorOperator needs 1 <= ndown <= L - 1 = %d, got %d" % (L - 1, ndown))
+    n = math.comb(L, ndown)
+    if n > 2 ** 31 - 1:
+        raise ValueError("the sector L = %d, ndown = %d has %d rows; ranks are 32-bit: at most 2^31 - 1" % (L, ndown, n))
+    return L, ndown, n
+
+
+def _sector_view(op, couplings, like=None):
+    """(handle, n) of the sector Hamiltonian of ``op`` (its bonds and its tables) whose couplings are the (2 nb + L,) tensor
+    ``couplings``; ``like``: a view whose grid cap the new handle takes over."""
+    data = couplings.detach()
+    if data.dtype != F64 or not data.is_contiguous():
+        data = data.to(F64).contiguous()
+    bonds = op.bonds
+    flat = (c_int32 * (2 * len(bonds)))(*[s for bond in bonds for s in bond])
+    states, lo_rank, hi_base = op._tables
+    raw = c_void_p()
+    check(_lib.load().dsea_op_create_sector(op.N, op.ndown, len(bonds), flat, c_void_p(data.data_ptr()),
+                                            c_void_p(states.data_ptr()), c_void_p(lo_rank.data_ptr()),
+                                            c_void_p(hi_base.data_ptr()), byref(raw)), "dsea_op_create_sector")
+    view = _NativeView(_Handle(raw, op.n, (data, op._tables)))
+    view.grid_log2 = None
+    if like is not None and like.grid_log2 is not None:
+        _set_sector_grid(view, like.grid_log2)
+    return view
+
+
+def _set_sector_grid(view, grid_log2):
+    check(_lib.load().dsea_op_set_tuning(view.handle, _lib.TUNE_TFIM_TILE_LOG2, int(grid_log2)), "dsea_op_set_tuning")
+    view.grid_log2 = int(grid_log2)
+
+
+def _sector_forms(view, op, v1, v2):
+    """all 2 nb + L bilinear forms v1^T (dH/dp) v2 (dsea_op_sector_forms: one pass, deterministic)"""
+    lib = _lib.load()
+    v1, v2 = engine.as_vector(v1, view.n), engine.as_vector(v2, view.n)
+    need = c_int64()
+    check(lib.dsea_op_sector_forms_scratch_doubles(op.N, op.ndown, op.nb, byref(need)), "dsea_op_sector_forms_scratch_doubles")
+    scratch = torch.empty(need.value, dtype=F64, device=v1.device)
+    out = torch.empty(op.nparam, dtype=F64, device=v1.device)
+    check(lib.dsea_op_sector_forms(view.handle, c_void_p(v1.data_ptr()), c_void_p(v2.data_ptr()), c_void_p(out.data_ptr()),
+                                   c_void_p(scratch.data_ptr()), engine._stream(v1.device)), "dsea_op_sector_forms")
+    return out
+
+
+class SpinSectorOperator:
+    """H = sum_t [Jxy_t (X_a X_b + Y_a Y_b) + Jz_t Z_a Z_b] + sum_i hz_i Z_i on L sites, restricted to the states with exactly
+    ``ndown`` set bits (total S^z fixed), matrix-free (docs/design/18-spin-sector.md).  Sites, bits and ``bonds`` are those of
+    ``SpinLatticeOperator`` (this is its Hamiltonian with Jx = Jy = Jxy and hx = 0); 2 <= L <= 40, 1 <= ndown <= L - 1 and
+    n = C(L, ndown) <= 2^31 - 1.  Row r is the r-th such state in increasing integer order: ``states`` (int64, on the device),
+    ``sector_states(L, ndown)`` on the host.
+
+    ``couplings`` is ONE contiguous float64 device tensor of length 2 nb + L in the order [Jxy(nb), Jz(nb), hz(L)] -- the
+    parameter (it may require grad; ``pack`` / ``unpack`` convert).  The kernels read it through its device pointer on every
+    launch: in-place optimiser steps are seen, binding another tensor makes a new handle on the same tables.  ``H(v)`` is
+    differentiable in v and in ``couplings``; ``Hadjoint_to_couplingsadjoint(v1, v2)`` is the hook for
+    ``setDominantSparseSymeig`` / ``setLowestSparseSymeig``: all 2 nb + L forms in one pass.  Both are re-entrant (H is linear
+    in the couplings), so second order works.  The state table and the two rank tables are built once per operator by the
+    library's kernels and kept alive by it.  ``embed`` / ``restrict`` convert to and from the 2^L space (L <= 30)."""
+
+    _native_methods = ("H", "__call__")
+
+    def __init__(self, L, bonds, couplings, ndown, device=None):
+        self.N, self.ndown, n = _check_sector(L, ndown)
+        self._bonds = _check_bonds(self.N, bonds)
+        self.nb = len(self._bonds)
+        self.nparam = 2 * self.nb + self.N
+        self.dim = self.n = n
+        if device is None:
+            device = couplings.device if torch.is_tensor(couplings) else "cuda"
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError("SpinSectorOperator is a device operator; use device='cuda'")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.Llo = (self.N + 1) // 2
+        states = torch.empty(n, dtype=torch.int64, device=self.device)
+        lo_rank = torch.empty(1 << self.Llo, dtype=torch.int32, device=self.device)
+        hi_base = torch.empty(1 << (self.N - self.Llo), dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            check(_lib.load().dsea_sector_build_tables(self.N, self.ndown, c_void_p(states.data_ptr()),
+                                                       c_void_p(lo_rank.data_ptr()), c_void_p(hi_base.data_ptr()),
+                                                       engine._stream(self.device)), "dsea_sector_build_tables")
+        self._tables = (states, lo_rank, hi_base)
+        self._c = None
+        self._H = None
+        self._grid_log2 = None
+        self.couplings = couplings
+
+    @property
+    def bonds(self):
+        """the bond list as a tuple of (a, b) pairs, in the order of the couplings (read-only)"""
+        return self._bonds
+
+    @property
+    def states(self):
+        """states[r] = the basis state of row r (int64 device tensor, increasing)"""
+        return self._tables[0]
+
+    @property
+    def couplings(self):
+        return self._c
+
+    @couplings.setter
+    def couplings(self, value):
+        if not torch.is_tensor(value):
+            value = torch.as_tensor(value, dtype=F64).to(self.device)
+        if value.device != self.device or value.dtype != F64:
+            raise ValueError("couplings must be a float64 tensor on %s" % self.device)
+        if tuple(value.shape) != (self.nparam,) or not value.is_contiguous():
+            raise ValueError("couplings must be a contiguous tensor of shape (%d,): Jxy(nb), Jz(nb), hz(L)" % self.nparam)
+        self._c = value
+        self._H = _sector_view(self, value)     # the kernels read the couplings through this tensor's pointer
+        if self._grid_log2 is not None:
+            _set_sector_grid(self._H, self._grid_log2)
+
+    def set_grid_log2(self, grid_log2):
+        """log2 of the most blocks a launch uses (6..12, default 12; measurement aid, dsea_op_set_tuning)"""
+        _set_sector_grid(self._H, grid_log2)
+        self._grid_log2 = int(grid_log2)
+
+    def pack(self, Jxy, Jz, hz):
+        """the three families (scalars, or one value per bond / per site) as one parameter tensor on the operator's device"""
+        parts = []
+        for value, size in zip((Jxy, Jz, hz), (self.nb, self.nb, self.N)):
+            t = torch.as_tensor(value, dtype=F64).to(self.device)
+            parts.append(t.expand(size) if t.dim() == 0 else t.reshape(size))
+        return torch.cat(parts).contiguous()
+
+    def unpack(self, t):
+        """views (Jxy, Jz, hz) of a parameter tensor"""
+        nb = self.nb
+        if tuple(t.shape) != (self.nparam,):
+            raise ValueError("expected a tensor of shape (%d,)" % self.nparam)
+        return t[:nb], t[nb:2 * nb], t[2 * nb:]
+
+    @property
+    def handle(self):
+        return self._H.handle
+
+    def H(self, v):
+        """H v, differentiable in v and in the couplings"""
+        return _SectorApply.apply(v, self._c, self, self._H)
+
+    __call__ = H
+
+    def Hadjoint_to_couplingsadjoint(self, v1, v2):
+        """adjoint hook: couplings-bar[t] = v1^T (dH/dp_t) v2, shape (2 nb + L,)"""
+        return _SectorForms.apply(v1, v2, self, self._H)
+
+    def rank(self, s):
+        """the row of every state in the int64 device tensor ``s`` (states of the sector only): the two-table lookup"""
+        _, lo_rank, hi_base = self._tables
+        return hi_base[s >> self.Llo].to(torch.int64) + lo_rank[s & ((1 << self.Llo) - 1)].to(torch.int64)
+
+    def embed(self, v):
+        """the sector vector v as a vector of the full 2^L space (zero outside the sector); L <= 30"""
+        if self.N > 30:
+            raise ValueError("embed / restrict need L <= 30")
+        w = torch.zeros(1 << self.N, dtype=v.dtype, device=v.device)
+        return w.index_put((self.states.to(v.device),), v)
+
+    def restrict(self, w):
+        """the sector part of a vector of the full 2^L space; L <= 30"""
+        if self.N > 30:
+            raise ValueError("embed / restrict need L <= 30")
+        return w[self.states.to(w.device)]
+
+    def to_csr(self, layout="sell", col16="auto", values="auto"):
+        """The sector matrix as an explicit device CSR operand: the diagonal, and for every distinct bond mask one entry in the
+        rows that the mask flips (bonds with equal masks are summed).  Built on the device with index arithmetic."""
+        n = self.n
+        jxy, jz, hz = self.unpack(self._c.detach())
+        s = self.states
+        rows = torch.arange(n, dtype=torch.int64, device=self.device)
+        z = [(1 - 2 * ((s >> i) & 1)).to(F64) for i in range(self.N)]
+        diag = torch.zeros(n, dtype=F64, device=self.device)
+        for i in range(self.N):
+            diag = diag + hz[i] * z[i]
+        by_mask = {}
+        for t, (a, b) in enumerate(self._bonds):
+            diag = diag + jz[t] * (z[a] * z[b])
+            m = (1 << a) | (1 << b)
+            by_mask[m] = by_mask[m] + 2.0 * jxy[t] if m in by_mask else 2.0 * jxy[t]
+        r_all, c_all, v_all = [rows], [rows], [diag]
+        for m, v in by_mask.items():
+            a, b = [i for i in range(self.N) if (m >> i) & 1]
+            flips = rows[((s >> a) ^ (s >> b)) & 1 == 1]
+            r_all.append(flips)
+            c_all.append(self.rank(s[flips] ^ m))
+            v_all.append(v.expand(flips.numel()))
+        r_all, c_all, v_all = torch.cat(r_all), torch.cat(c_all), torch.cat(v_all)
+        order = torch.argsort(r_all * n + c_all)
+        rowptr = torch.zeros(n + 1, dtype=torch.int64, device=self.device)
+        rowptr[1:] = torch.cumsum(torch.bincount(r_all, minlength=n), 0)
+        return CSROperator(rowptr, c_all[order], v_all[order].contiguous(), n, layout=layout, col16=col16, values=values)
+
+
+class _SectorApply(torch.autograd.Function):
+    """y = H[c] v.  Backward: H[c] gy (symmetric) and the forms(gy, v) -- both re-entrant."""
+
+    @staticmethod
+    def forward(ctx, v, c, op, view):
+        ctx.op, ctx.view = op, view
+        ctx.save_for_backward(v, c)
+        return engine.spmv(view, v.detach())
+
+    @staticmethod
+    def backward(ctx, gy):
+        v, c = ctx.saved_tensors
+        gv = _SectorApply.apply(gy, c, ctx.op, ctx.view) if ctx.needs_input_grad[0] else None
+        gc = _SectorForms.apply(gy, v, ctx.op, ctx.view).reshape(c.shape) if ctx.needs_input_grad[1] else None
+        return gv, gc, None, None
+
+
+class _SectorForms(torch.autograd.Function):
+    """out[t] = v1^T (dH/dp_t) v2, shape (2 nb + L,).  H is linear in the couplings, so with the incoming adjoint G as
+    couplings the backward is d/dv1 = H[G] v2 and d/dv2 = H[G] v1: a second handle on the same tables."""
+
+    @staticmethod
+    def forward(ctx, v1, v2, op, view):
+        ctx.op, ctx.view = op, view
+        ctx.save_for_backward(v1, v2)
+        return _sector_forms(view, op, v1.detach(), v2.detach())
+
+    @staticmethod
+    def backward(ctx, G):
+        v1, v2 = ctx.saved_tensors
+        g1 = g2 = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            G = G.reshape(ctx.op.nparam)
+            adj = _sector_view(ctx.op, G, like=ctx.view)      # the Hamiltonian whose couplings are the adjoint
+            if ctx.needs_input_grad[0]:
+                g1 = _SectorApply.apply(v2, G, ctx.op, adj)
+            if ctx.needs_input_grad[1]:
+                g2 = _SectorApply.apply(v1, G, ctx.op, adj)
         return g1, g2, None, None
 
 

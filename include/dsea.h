@@ -187,6 +187,38 @@ int dsea_op_create_lattice(int L, int nb, const int32_t *bonds_host, const doubl
 int dsea_op_lattice_forms_scratch_doubles(int L, int nb, int64_t *out);
 int dsea_op_lattice_forms(dsea_op_t op, const double *v1, const double *v2, double *out, double *scratch, void *stream);
 
+/* XXZ spins on a caller-given bond list in ONE MAGNETISATION SECTOR, matrix-free (docs/design/18-spin-sector.md): the sites,
+ * bits and bonds of dsea_op_create_lattice,
+ *     H = sum_t [ Jxy_t (X_a X_b + Y_a Y_b) + Jz_t Z_a Z_b ] + sum_i hz_i Z_i
+ * restricted to the states with exactly ndown set bits.  Row r is the r-th such state IN INCREASING INTEGER ORDER, s_r;
+ * n = C(L, ndown):
+ *     y[r] = ( sum_t Jz_t z_a z_b + sum_i hz_i z_i ) x[r] + sum_{t : bit_a(s_r) != bit_b(s_r)} 2 Jxy_t x[rank(s_r ^ m_t)]
+ *     rank(s) = hi_base[s >> Llo] + lo_rank[s & (2^Llo - 1)],   Llo = (L + 1) / 2,  Lhi = L - Llo
+ * dsea_sector_table_sizes: n, n_lo = 2^Llo, n_hi = 2^Lhi.  Host arithmetic only.  DSEA_ERR_ARG outside 2 <= L <= 40,
+ * 1 <= ndown <= L - 1, n <= 2^31 - 1 (ranks are 32-bit), and for a null pointer. */
+int dsea_sector_table_sizes(int L, int ndown, int64_t *n, int64_t *n_lo, int64_t *n_hi);
+/* Fills the caller's three device tables on `stream` (deterministic; once per (L, ndown), the tables hold no couplings):
+ * states int64 [n] = s_r (combinatorial unranking, one row per thread); lo_rank int32 [n_lo]: the rank of p among the Llo-bit
+ * words of its popcount; hi_base int32 [n_hi]: the number of sector states below h << Llo, 0 for an h no sector state has.
+ * The library allocates nothing. */
+int dsea_sector_build_tables(int L, int ndown, int64_t *states, int32_t *lo_rank, int32_t *hi_base, void *stream);
+/* The operator on filled tables (caller-owned, alive as long as the handle; several handles may share one set).
+ * bonds_host: as dsea_op_create_lattice, copied at creation.  couplings_dev: fp64 [2 nb + L] on the device in the order
+ * Jxy(nb), Jz(nb), hz(L); READ THROUGH THE POINTER ON EVERY LAUNCH (in-place updates are seen).  Checked on the host before any
+ * device work (DSEA_ERR_ARG): the limits of dsea_sector_table_sizes, 1 <= nb <= DSEA_LATTICE_MAX_BONDS, 0 <= a_t, b_t < L,
+ * a_t != b_t, non-null pointers.  Nothing is launched or allocated at creation.  For this kind dsea_op_set_tuning
+ * DSEA_TUNE_TFIM_TILE_LOG2 = log2 of the most blocks a launch uses (6..12, default 12; beyond the cap blocks walk ranges of
+ * 256 rows).  No fused Lanczos tail, no persistent forms, no row-partitioned slabs. */
+int dsea_op_create_sector(int L, int ndown, int nb, const int32_t *bonds_host, const double *couplings_dev,
+                          const int64_t *states, const int32_t *lo_rank, const int32_t *hi_base, dsea_op_t *out);
+/* The parameter adjoint of dsea_op_create_sector: out[t] = v1^T (dH/dp_t) v2 for all 2 nb + L couplings in the order of
+ * couplings_dev, in one pass over v1 and v2 (per-block partials in `scratch`, then a fixed-order reduction: no atomics,
+ * repeated calls return identical bits).  `scratch`: caller-owned, dsea_op_sector_forms_scratch_doubles(L, ndown, nb) =
+ * (2 nb + L) * min(4096, ceil(n / 256)) doubles (enough for every grid cap); the library allocates nothing.  DSEA_ERR_ARG for
+ * any other operator kind. */
+int dsea_op_sector_forms_scratch_doubles(int L, int ndown, int nb, int64_t *out);
+int dsea_op_sector_forms(dsea_op_t op, const double *v1, const double *v2, double *out, double *scratch, void *stream);
+
 /* CSR, caller-owned device arrays: rowptr int64 [n+1], colidx int32 [nnz], vals fp64 [nnz]. */
 int dsea_op_create_csr(int64_t n, int64_t nnz, const int64_t *rowptr, const int32_t *colidx,
                        const double *vals, dsea_op_t *out);
