@@ -81,6 +81,11 @@ _SIGNATURES = {
                                       POINTER(c_void_p)]),
     "dsea_op_sector_forms_scratch_doubles": (c_int, [c_int, c_int, c_int, POINTER(c_int64)]),
     "dsea_op_sector_forms": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dsea_hubbard_sizes": (c_int, [c_int, c_int, c_int, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)]),
+    "dsea_op_create_hubbard": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_int32), c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, POINTER(c_void_p)]),
+    "dsea_op_hubbard_forms_scratch_doubles": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_int64)]),
+    "dsea_op_hubbard_forms": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dsea_op_create_csr": (c_int, [c_int64, c_int64, c_void_p, c_void_p, c_void_p, POINTER(c_void_p)]),
     "dsea_op_create_sell": (c_int, [c_int64, c_int64, c_void_p, c_void_p, c_void_p, POINTER(c_void_p)]),
     "dsea_op_create_sell16": (c_int, [c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_void_p)]),

@@ -621,6 +621,60 @@ int dsea_op_sector_forms(dsea_op_t op, const double* v1, const double* v2, doubl
   return check_launch();
 }
 
+int dsea_hubbard_sizes(int L, int nup, int ndn, int64_t* n, int64_t* n_up, int64_t* n_dn) {
+  REQUIRE(n && n_up && n_dn && hubbard_sizes(L, nup, ndn, n, n_up, n_dn), DSEA_ERR_ARG);
+  return DSEA_OK;
+}
+
+int dsea_op_create_hubbard(int L, int nup, int ndn, int nb, const int32_t* bonds_host, const double* couplings_dev,
+                           const int64_t* up_states, const int32_t* up_lo_rank, const int32_t* up_hi_base,
+                           const int64_t* dn_states, const int32_t* dn_lo_rank, const int32_t* dn_hi_base, dsea_op_t* out) {
+  int64_t n, n_up, n_dn;
+  REQUIRE(out && hubbard_sizes(L, nup, ndn, &n, &n_up, &n_dn) && nb >= 1 && nb <= DSEA_LATTICE_MAX_BONDS && bonds_host &&
+              couplings_dev && up_states && up_lo_rank && up_hi_base && dn_states && dn_lo_rank && dn_hi_base,
+          DSEA_ERR_ARG);
+  for (int t = 0; t < nb; ++t) {
+    const int32_t a = bonds_host[2 * t], b = bonds_host[2 * t + 1];
+    REQUIRE(a >= 0 && a < L && b >= 0 && b < L && a != b, DSEA_ERR_ARG);
+  }
+  dsea_op_s* op = new (std::nothrow) dsea_op_s;
+  if (!op) return DSEA_ERR_ARG;
+  memset(&op->d, 0, sizeof(op->d));
+  op->d.tune_tile_log2 = 12;   // this kind: log2 of the grid cap (DSEA_MAX_TFIM_BLOCKS)
+  op->d.kind = OP_HUBBARD;
+  op->d.n = n;
+  op->d.hubbard.L = L;
+  op->d.hubbard.nup = nup;
+  op->d.hubbard.ndn = ndn;
+  op->d.hubbard.nb = nb;
+  op->d.hubbard.c = couplings_dev;
+  op->d.hubbard.up_states = reinterpret_cast<const uint64_t*>(up_states);
+  op->d.hubbard.up_lo = reinterpret_cast<const uint32_t*>(up_lo_rank);
+  op->d.hubbard.up_hi = reinterpret_cast<const uint32_t*>(up_hi_base);
+  op->d.hubbard.dn_states = reinterpret_cast<const uint64_t*>(dn_states);
+  op->d.hubbard.dn_lo = reinterpret_cast<const uint32_t*>(dn_lo_rank);
+  op->d.hubbard.dn_hi = reinterpret_cast<const uint32_t*>(dn_hi_base);
+  for (int t = 0; t < nb; ++t) {
+    op->d.hubbard.a[t] = (uint8_t)bonds_host[2 * t];
+    op->d.hubbard.b[t] = (uint8_t)bonds_host[2 * t + 1];
+  }
+  *out = op;
+  return DSEA_OK;
+}
+
+int dsea_op_hubbard_forms_scratch_doubles(int L, int nup, int ndn, int nb, int64_t* out) {
+  int64_t n, n_up, n_dn;
+  REQUIRE(out && hubbard_sizes(L, nup, ndn, &n, &n_up, &n_dn) && nb >= 1 && nb <= DSEA_LATTICE_MAX_BONDS, DSEA_ERR_ARG);
+  *out = hubbard_forms_scratch_doubles(n, L, nb);
+  return DSEA_OK;
+}
+
+int dsea_op_hubbard_forms(dsea_op_t op, const double* v1, const double* v2, double* out, double* scratch, void* stream) {
+  REQUIRE(op && op->d.kind == OP_HUBBARD && v1 && v2 && out && scratch, DSEA_ERR_ARG);
+  if (launch_hubbard_forms(op->d, v1, v2, out, scratch, static_cast<hipStream_t>(stream)) != 0) return DSEA_ERR_UNSUPPORTED;
+  return check_launch();
+}
+
 int dsea_op_create_csr(int64_t n, int64_t nnz, const int64_t* rowptr, const int32_t* colidx,
                        const double* vals, dsea_op_t* out) {
   REQUIRE(out && n >= 1 && nnz >= 0 && rowptr && (nnz == 0 || (colidx && vals)), DSEA_ERR_ARG);

@@ -132,12 +132,27 @@ struct SectorDesc {
   const uint32_t* hi_base;
   uint8_t a[DSEA_LATTICE_MAX_BONDS], b[DSEA_LATTICE_MAX_BONDS];
 };
+// The Hubbard model on a caller-given bond list at fixed (nup, ndn) (dsea_hubbard.hip): bond t joins sites a[t] != b[t] (host
+// copies, the caller's order); c = [t(nb), V(nb), U(L), eps(L)] on the device -- read through the pointer on every launch; per
+// species the caller's device tables of dsea_sector_build_tables at (L, nup) and (L, ndn): states (C(L, .) words), lo_rank
+// (2^Llo) and hi_base (2^Lhi), Llo = (L + 1) / 2.  The two triples may be the same pointers when nup == ndn.
+struct HubbardDesc {
+  int L, nup, ndn, nb;
+  const double* c;
+  const uint64_t* up_states;
+  const uint32_t* up_lo;
+  const uint32_t* up_hi;
+  const uint64_t* dn_states;
+  const uint32_t* dn_lo;
+  const uint32_t* dn_hi;
+  uint8_t a[DSEA_LATTICE_MAX_BONDS], b[DSEA_LATTICE_MAX_BONDS];
+};
 enum OpKind { OP_TFIM = 1, OP_CSR = 2, OP_STENCIL3 = 3, OP_SELL = 4, OP_DENSE = 5, OP_TRANSFER = 6, OP_SYMDENSE = 7, OP_CHAIN = 8,
-              OP_LATTICE = 9, OP_SECTOR = 10 };
+              OP_LATTICE = 9, OP_SECTOR = 10, OP_HUBBARD = 11 };
 struct OpDesc {
   OpKind kind;
   int64_t n;
-  int tune_tile_log2;  // TFIM, spin chain, spin lattice: log2 rows of x staged in LDS per block (6..12); spin sector: log2 of the grid cap
+  int tune_tile_log2;  // TFIM, spin chain, spin lattice: log2 rows of x staged in LDS per block (6..12); spin sector, Hubbard: log2 of the grid cap
   int tune_csr_group;  // CSR: lanes per row, 0 = automatic
   int tune_sell_unroll;  // SELL: slice-column pairs in flight per lane {0 = automatic, 2, 4, 6, 8}; 1 = the round-5 kernel (A/B)
   TfimParams tfim;
@@ -150,6 +165,7 @@ struct OpDesc {
   ChainParams chain;
   LatticeDesc lattice;
   SectorDesc sector;
+  HubbardDesc hubbard;
 };
 
 // One basis row's storage shadow as the writers see it: bf16 (h), e5m2 codes of q * S (b), or neither.  At most one of
@@ -434,6 +450,15 @@ int launch_spmv_sector(const OpDesc& op, const double* x, double* y, const doubl
                        hipStream_t st, EventPair* ev);
 int launch_sector_forms(const OpDesc& op, const double* v1, const double* v2, double* out, double* scratch, hipStream_t st);
 int64_t sector_forms_scratch_doubles(int64_t n, int L, int nb);
+// dsea_hubbard.hip (the Hubbard model on a bond list at fixed (nup, ndn)): the sizes n_up = C(L, nup), n_dn = C(L, ndn),
+// n = n_up n_dn (false when L, nup, ndn or n is out of range); the mat-vec of launch_spmv's OP_HUBBARD case; the 2 nb + 2 L
+// bilinear forms v1^T (dH/dp) v2 into out through per-block partials in the caller's scratch (hubbard_forms_scratch_doubles
+// doubles); the launchers return -1 when the descriptor is out of range
+bool hubbard_sizes(int L, int nup, int ndn, int64_t* n, int64_t* n_up, int64_t* n_dn);
+int launch_spmv_hubbard(const OpDesc& op, const double* x, double* y, const double* shift, const double* skip, double* P,
+                        hipStream_t st, EventPair* ev);
+int launch_hubbard_forms(const OpDesc& op, const double* v1, const double* v2, double* out, double* scratch, hipStream_t st);
+int64_t hubbard_forms_scratch_doubles(int64_t n, int L, int nb);
 // dsea_cg_persist_tfim_big.hip
 bool cg_persist_tfim_big_applicable(const OpDesc& op);
 size_t cg_persist_tfim_big_comm_bytes(int64_t n);

@@ -1176,6 +1176,8 @@ int launch_spmv(const OpDesc& op, const double* x, double* y, const double* shif
       return launch_spmv_lattice(op, x, y, shift, skip, P, st, ev);
     case OP_SECTOR:
       return launch_spmv_sector(op, x, y, shift, skip, P, st, ev);
+    case OP_HUBBARD:
+      return launch_spmv_hubbard(op, x, y, shift, skip, P, st, ev);
   }
   return -1;
 }

@@ -864,6 +864,266 @@ class _SectorForms(torch.autograd.Function):
         return g1, g2, None, None
 
 
+# ------------------------------------------------------------------------------------------ Hubbard model at fixed (N_up, N_dn)
+def hubbard_dim(L, nup, ndn):
+    """the dimension C(L, nup) C(L, ndn) of the Hubbard space of L sites with nup up and ndn down particles (pure Python)"""
+    return sector_dim(L, nup) * sector_dim(L, ndn)
+
+
+def _check_hubbard(L, nup, ndn):
+    """(L, nup, ndn, n_up, n_dn) as ints; ValueError for what dsea_hubbard_sizes refuses -- host arithmetic only"""
+    L, nup, ndn = int(L), int(nup), int(ndn)
+    if not 2 <= L <= _lib.SECTOR_MAX_L:
+        raise ValueError("HubbardOperator needs 2 <= L <= %d, got %d" % (_lib.SECTOR_MAX_L, L))
+    for name, k in (("nup", nup), ("ndn", ndn)):
+        if not 1 <= k <= L - 1:
+            raise ValueError("HubbardOperator needs 1 <= %s <= L - 1 = %d, got %d" % (name, L - 1, k))
+    n_up, n_dn = math.comb(L, nup), math.comb(L, ndn)
+    if n_up * n_dn > 2 ** 31 - 1:
+        raise ValueError("L = %d, nup = %d, ndn = %d has %d rows; rows are 32-bit: at most 2^31 - 1" % (L, nup, ndn, n_up * n_dn))
+    return L, nup, ndn, n_up, n_dn
+
+
+def _hubbard_view(op, couplings, like=None):
+    """(handle, n) of the Hubbard Hamiltonian of ``op`` (its bonds and its tables) whose couplings are the (2 nb + 2 L,) tensor
+    ``couplings``; ``like``: a view whose grid cap the new handle takes over."""
+    data = couplings.detach()
+    if data.dtype != F64 or not data.is_contiguous():
+        data = data.to(F64).contiguous()
+    bonds = op.bonds
+    flat = (c_int32 * (2 * len(bonds)))(*[s for bond in bonds for s in bond])
+    tables = op._up + op._dn
+    raw = c_void_p()
+    check(_lib.load().dsea_op_create_hubbard(op.N, op.nup, op.ndn, len(bonds), flat, c_void_p(data.data_ptr()),
+                                             *[c_void_p(t.data_ptr()) for t in tables], byref(raw)), "dsea_op_create_hubbard")
+    view = _NativeView(_Handle(raw, op.n, (data, tables)))
+    view.grid_log2 = None
+    if like is not None and like.grid_log2 is not None:
+        _set_sector_grid(view, like.grid_log2)
+    return view
+
+
+def _hubbard_forms(view, op, v1, v2):
+    """all 2 nb + 2 L bilinear forms v1^T (dH/dp) v2 (dsea_op_hubbard_forms: one pass, deterministic)"""
+    lib = _lib.load()
+    v1, v2 = engine.as_vector(v1, view.n), engine.as_vector(v2, view.n)
+    need = c_int64()
+    check(lib.dsea_op_hubbard_forms_scratch_doubles(op.N, op.nup, op.ndn, op.nb, byref(need)),
+          "dsea_op_hubbard_forms_scratch_doubles")
+    scratch = torch.empty(need.value, dtype=F64, device=v1.device)
+    out = torch.empty(op.nparam, dtype=F64, device=v1.device)
+    check(lib.dsea_op_hubbard_forms(view.handle, c_void_p(v1.data_ptr()), c_void_p(v2.data_ptr()), c_void_p(out.data_ptr()),
+                                    c_void_p(scratch.data_ptr()), engine._stream(v1.device)), "dsea_op_hubbard_forms")
+    return out
+
+
+class HubbardOperator:
+    """H = sum_t [-t_t sum_s (c+_{a s} c_{b s} + h.c.) + V_t n_a n_b] + sum_i U_i n_{i up} n_{i dn} + sum_i eps_i n_i on L sites
+    with exactly ``nup`` up and ``ndn`` down fermions, matrix-free (docs/design/19-hubbard.md).  ``bonds`` follows the rules of
+    ``SpinLatticeOperator``; 2 <= L <= 40, 1 <= nup, ndn <= L - 1 and n = C(L, nup) C(L, ndn) <= 2^31 - 1.  Bit i of the word u
+    is the occupation of (i, up), bit i of d that of (i, dn); |u, d> = (prod_{i in u, ascending} c+_{i up})
+    (prod_{j in d, ascending} c+_{j dn}) |0>.  Row r = ru * n_dn + rd (down fastest) with ru, rd the ranks of u, d among the words
+    of their popcount in increasing integer order: ``up_states`` / ``dn_states`` (int64, on the device),
+    ``sector_states(L, nup)`` / ``sector_states(L, ndn)`` on the host.
+
+    ``couplings`` is ONE contiguous float64 device tensor of length 2 nb + 2 L in the order [t(nb), V(nb), U(L), eps(L)] -- the
+    parameter (it may require grad; ``pack`` / ``unpack`` convert).  The kernels read it through its device pointer on every
+    launch: in-place optimiser steps are seen, binding another tensor makes a new handle on the same tables.  ``H(v)`` is
+    differentiable in v and in ``couplings``; ``Hadjoint_to_couplingsadjoint(v1, v2)`` is the hook for
+    ``setDominantSparseSymeig`` / ``setLowestSparseSymeig``: all 2 nb + 2 L forms in one pass.  Both are re-entrant (H is linear
+    in the couplings), so second order works.  The state and rank tables of each species are built once per operator by the
+    library's sector-table kernels and kept alive by it; with nup == ndn one set serves both species."""
+
+    _native_methods = ("H", "__call__")
+
+    def __init__(self, L, bonds, couplings, nup, ndn, device=None):
+        self.N, self.nup, self.ndn, self.n_up, self.n_dn = _check_hubbard(L, nup, ndn)
+        self._bonds = _check_bonds(self.N, bonds)
+        self.nb = len(self._bonds)
+        self.nparam = 2 * self.nb + 2 * self.N
+        self.dim = self.n = self.n_up * self.n_dn
+        if device is None:
+            device = couplings.device if torch.is_tensor(couplings) else "cuda"
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError("HubbardOperator is a device operator; use device='cuda'")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.Llo = (self.N + 1) // 2
+        self._up = self._build_tables(self.nup, self.n_up)
+        self._dn = self._up if self.ndn == self.nup else self._build_tables(self.ndn, self.n_dn)
+        self._c = None
+        self._H = None
+        self._grid_log2 = None
+        self.couplings = couplings
+
+    def _build_tables(self, count, rows):
+        """(states, lo_rank, hi_base) of the L-bit words with ``count`` set bits: dsea_sector_build_tables"""
+        states = torch.empty(rows, dtype=torch.int64, device=self.device)
+        lo_rank = torch.empty(1 << self.Llo, dtype=torch.int32, device=self.device)
+        hi_base = torch.empty(1 << (self.N - self.Llo), dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            check(_lib.load().dsea_sector_build_tables(self.N, count, c_void_p(states.data_ptr()), c_void_p(lo_rank.data_ptr()),
+                                                       c_void_p(hi_base.data_ptr()), engine._stream(self.device)),
+                  "dsea_sector_build_tables")
+        return (states, lo_rank, hi_base)
+
+    @property
+    def bonds(self):
+        """the bond list as a tuple of (a, b) pairs, in the order of the couplings (read-only)"""
+        return self._bonds
+
+    @property
+    def up_states(self):
+        """up_states[ru] = the up word of the rows ru * n_dn .. ru * n_dn + n_dn - 1 (int64 device tensor, increasing)"""
+        return self._up[0]
+
+    @property
+    def dn_states(self):
+        """dn_states[rd] = the down word of the rows rd, n_dn + rd, ... (int64 device tensor, increasing)"""
+        return self._dn[0]
+
+    @property
+    def couplings(self):
+        return self._c
+
+    @couplings.setter
+    def couplings(self, value):
+        if not torch.is_tensor(value):
+            value = torch.as_tensor(value, dtype=F64).to(self.device)
+        if value.device != self.device or value.dtype != F64:
+            raise ValueError("couplings must be a float64 tensor on %s" % self.device)
+        if tuple(value.shape) != (self.nparam,) or not value.is_contiguous():
+            raise ValueError("couplings must be a contiguous tensor of shape (%d,): t(nb), V(nb), U(L), eps(L)" % self.nparam)
+        self._c = value
+        self._H = _hubbard_view(self, value)     # the kernels read the couplings through this tensor's pointer
+        if self._grid_log2 is not None:
+            _set_sector_grid(self._H, self._grid_log2)
+
+    def set_grid_log2(self, grid_log2):
+        """log2 of the most blocks a launch uses (6..12, default 12; measurement aid, dsea_op_set_tuning)"""
+        _set_sector_grid(self._H, grid_log2)
+        self._grid_log2 = int(grid_log2)
+
+    def pack(self, t, V, U, eps):
+        """the four families (scalars, or one value per bond / per site) as one parameter tensor on the operator's device"""
+        parts = []
+        for value, size in zip((t, V, U, eps), (self.nb, self.nb, self.N, self.N)):
+            x = torch.as_tensor(value, dtype=F64).to(self.device)
+            parts.append(x.expand(size) if x.dim() == 0 else x.reshape(size))
+        return torch.cat(parts).contiguous()
+
+    def unpack(self, p):
+        """views (t, V, U, eps) of a parameter tensor"""
+        nb, L = self.nb, self.N
+        if tuple(p.shape) != (self.nparam,):
+            raise ValueError("expected a tensor of shape (%d,)" % self.nparam)
+        return p[:nb], p[nb:2 * nb], p[2 * nb:2 * nb + L], p[2 * nb + L:]
+
+    @property
+    def handle(self):
+        return self._H.handle
+
+    def H(self, v):
+        """H v, differentiable in v and in the couplings"""
+        return _HubbardApply.apply(v, self._c, self, self._H)
+
+    __call__ = H
+
+    def Hadjoint_to_couplingsadjoint(self, v1, v2):
+        """adjoint hook: couplings-bar[p] = v1^T (dH/dp) v2, shape (2 nb + 2 L,)"""
+        return _HubbardForms.apply(v1, v2, self, self._H)
+
+    def _species_rank(self, tables, w):
+        _, lo_rank, hi_base = tables
+        return hi_base[w >> self.Llo].to(torch.int64) + lo_rank[w & ((1 << self.Llo) - 1)].to(torch.int64)
+
+    def rank(self, u, d):
+        """the row of every pair of words in the int64 device tensors ``u`` (nup set bits) and ``d`` (ndn set bits)"""
+        return self._species_rank(self._up, u) * self.n_dn + self._species_rank(self._dn, d)
+
+    def to_csr(self, layout="sell", col16="auto", values="auto"):
+        """The matrix as an explicit device CSR operand: the diagonal, and one entry per (row, species, distinct bond mask that
+        moves a particle of that species in the row); bonds with equal masks are summed.  Built on the device with index
+        arithmetic."""
+        n, n_dn, L = self.n, self.n_dn, self.N
+        t, V, U, eps = self.unpack(self._c.detach())
+        rows = torch.arange(n, dtype=torch.int64, device=self.device)
+        ru, rd = rows // n_dn, rows % n_dn
+        u, d = self.up_states[ru], self.dn_states[rd]
+        occ = [((u >> i) & 1) + ((d >> i) & 1) for i in range(L)]
+        diag = torch.zeros(n, dtype=F64, device=self.device)
+        for i in range(L):
+            diag = diag + U[i] * ((u >> i) & (d >> i) & 1).to(F64) + eps[i] * occ[i].to(F64)
+        by_mask = {}
+        for k, (a, b) in enumerate(self._bonds):
+            diag = diag + V[k] * (occ[a] * occ[b]).to(F64)
+            m = (1 << a) | (1 << b)
+            by_mask[m] = by_mask[m] - t[k] if m in by_mask else -t[k]
+        r_all, c_all, v_all = [rows], [rows], [diag]
+        for m, amp in by_mask.items():
+            lo, hi = [i for i in range(L) if (m >> i) & 1]
+            between = ((1 << hi) - 1) & ~((1 << (lo + 1)) - 1)
+            for up in (True, False):
+                w = u if up else d
+                moved = rows[((w >> lo) ^ (w >> hi)) & 1 == 1]
+                wm = w[moved]
+                partner = self._species_rank(self._up if up else self._dn, wm ^ m)
+                # sgn = (-1)^popcount(w & between): the parity by folding the word onto its lowest bit
+                par = wm & between
+                for shift in (32, 16, 8, 4, 2, 1):
+                    par = par ^ (par >> shift)
+                r_all.append(moved)
+                c_all.append(partner * n_dn + rd[moved] if up else ru[moved] * n_dn + partner)
+                v_all.append(amp * (1 - 2 * (par & 1)).to(F64))
+        r_all, c_all, v_all = torch.cat(r_all), torch.cat(c_all), torch.cat(v_all)
+        order = torch.argsort(r_all * n + c_all)
+        rowptr = torch.zeros(n + 1, dtype=torch.int64, device=self.device)
+        rowptr[1:] = torch.cumsum(torch.bincount(r_all, minlength=n), 0)
+        return CSROperator(rowptr, c_all[order], v_all[order].contiguous(), n, layout=layout, col16=col16, values=values)
+
+
+class _HubbardApply(torch.autograd.Function):
+    """y = H[c] v.  Backward: H[c] gy (symmetric) and the forms(gy, v) -- both re-entrant."""
+
+    @staticmethod
+    def forward(ctx, v, c, op, view):
+        ctx.op, ctx.view = op, view
+        ctx.save_for_backward(v, c)
+        return engine.spmv(view, v.detach())
+
+    @staticmethod
+    def backward(ctx, gy):
+        v, c = ctx.saved_tensors
+        gv = _HubbardApply.apply(gy, c, ctx.op, ctx.view) if ctx.needs_input_grad[0] else None
+        gc = _HubbardForms.apply(gy, v, ctx.op, ctx.view).reshape(c.shape) if ctx.needs_input_grad[1] else None
+        return gv, gc, None, None
+
+
+class _HubbardForms(torch.autograd.Function):
+    """out[p] = v1^T (dH/dp) v2, shape (2 nb + 2 L,).  H is linear in the couplings, so with the incoming adjoint G as
+    couplings the backward is d/dv1 = H[G] v2 and d/dv2 = H[G] v1: a second handle on the same tables."""
+
+    @staticmethod
+    def forward(ctx, v1, v2, op, view):
+        ctx.op, ctx.view = op, view
+        ctx.save_for_backward(v1, v2)
+        return _hubbard_forms(view, op, v1.detach(), v2.detach())
+
+    @staticmethod
+    def backward(ctx, G):
+        v1, v2 = ctx.saved_tensors
+        g1 = g2 = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            G = G.reshape(ctx.op.nparam)
+            adj = _hubbard_view(ctx.op, G, like=ctx.view)      # the Hamiltonian whose couplings are the adjoint
+            if ctx.needs_input_grad[0]:
+                g1 = _HubbardApply.apply(v2, G, ctx.op, adj)
+            if ctx.needs_input_grad[1]:
+                g2 = _HubbardApply.apply(v1, G, ctx.op, adj)
+        return g1, g2, None, None
+
+
 # ------------------------------------------------------------------------------------------ stencil
 class Stencil3Operator:
     """H v = coef (-2 v + v_{+1} + v_{-1}) + V o v, Dirichlet ends (reference examples/schrodinger1D.py:18-27

@@ -219,6 +219,39 @@ int dsea_op_create_sector(int L, int ndown, int nb, const int32_t *bonds_host, c
 int dsea_op_sector_forms_scratch_doubles(int L, int ndown, int nb, int64_t *out);
 int dsea_op_sector_forms(dsea_op_t op, const double *v1, const double *v2, double *out, double *scratch, void *stream);
 
+/* THE HUBBARD MODEL of spinful fermions on a caller-given bond list at fixed particle numbers (nup, ndn), matrix-free
+ * (docs/design/19-hubbard.md): the sites and bonds of dsea_op_create_lattice,
+ *     H = sum_t [ -t_t sum_s (c+_{a s} c_{b s} + h.c.) + V_t n_a n_b ] + sum_i U_i n_{i up} n_{i dn} + sum_i eps_i n_i
+ * Bit i of the word u is the occupation of (i, up), bit i of d that of (i, dn);
+ * |u, d> = (prod_{i in u, ascending} c+_{i up}) (prod_{j in d, ascending} c+_{j dn}) |0>.  Row r = ru * n_dn + rd (down
+ * fastest), ru the rank of u among the L-bit words of nup set bits IN INCREASING INTEGER ORDER, rd likewise for d.  With
+ * m_t = (1 << a_t) | (1 << b_t) and sgn_t(w) = (-1)^(number of set bits of w strictly between a_t and b_t):
+ *     y[r] = diag(u, d) x[r] - sum_{t : bit_a(u) != bit_b(u)} t_t sgn_t(u) x[rank_u(u ^ m_t) n_dn + rd]
+ *                            - sum_{t : bit_a(d) != bit_b(d)} t_t sgn_t(d) x[ru n_dn + rank_d(d ^ m_t)]
+ *     diag(u, d) = sum_i U_i bit_i(u) bit_i(d) + sum_i eps_i (bit_i(u) + bit_i(d)) + sum_t V_t n_a n_b
+ * dsea_hubbard_sizes: n = n_up n_dn, n_up = C(L, nup), n_dn = C(L, ndn).  Host arithmetic only.  DSEA_ERR_ARG outside
+ * 2 <= L <= 40, 1 <= nup <= L - 1, 1 <= ndn <= L - 1, n <= 2^31 - 1 (rows are 32-bit), and for a null pointer. */
+int dsea_hubbard_sizes(int L, int nup, int ndn, int64_t *n, int64_t *n_up, int64_t *n_dn);
+/* The operator on filled tables (caller-owned, alive as long as the handle; several handles may share them).  Each triple
+ * (states, lo_rank, hi_base) is what dsea_sector_table_sizes / dsea_sector_build_tables give at (L, nup) and at (L, ndn); the
+ * two triples may be the same pointers when nup == ndn.  bonds_host: as dsea_op_create_lattice, copied at creation.
+ * couplings_dev: fp64 [2 nb + 2 L] on the device in the order t(nb), V(nb), U(L), eps(L); READ THROUGH THE POINTER ON EVERY
+ * LAUNCH (in-place updates are seen).  Checked on the host before any device work (DSEA_ERR_ARG): the limits of
+ * dsea_hubbard_sizes, 1 <= nb <= DSEA_LATTICE_MAX_BONDS, 0 <= a_t, b_t < L, a_t != b_t, non-null pointers.  Nothing is
+ * launched or allocated at creation.  For this kind dsea_op_set_tuning DSEA_TUNE_TFIM_TILE_LOG2 = log2 of the most blocks a
+ * launch uses (6..12, default 12; beyond the cap blocks walk ranges of 256 rows).  No fused Lanczos tail, no persistent
+ * forms, no row-partitioned slabs. */
+int dsea_op_create_hubbard(int L, int nup, int ndn, int nb, const int32_t *bonds_host, const double *couplings_dev,
+                           const int64_t *up_states, const int32_t *up_lo_rank, const int32_t *up_hi_base,
+                           const int64_t *dn_states, const int32_t *dn_lo_rank, const int32_t *dn_hi_base, dsea_op_t *out);
+/* The parameter adjoint of dsea_op_create_hubbard: out[p] = v1^T (dH/dp) v2 for all 2 nb + 2 L couplings in the order of
+ * couplings_dev, in one pass over v1 and v2 (per-block partials in `scratch`, then a fixed-order reduction: no atomics,
+ * repeated calls return identical bits).  `scratch`: caller-owned, dsea_op_hubbard_forms_scratch_doubles(L, nup, ndn, nb) =
+ * (2 nb + 2 L) * min(4096, ceil(n / 256)) doubles (enough for every grid cap); the library allocates nothing.  DSEA_ERR_ARG
+ * for any other operator kind. */
+int dsea_op_hubbard_forms_scratch_doubles(int L, int nup, int ndn, int nb, int64_t *out);
+int dsea_op_hubbard_forms(dsea_op_t op, const double *v1, const double *v2, double *out, double *scratch, void *stream);
+
 /* CSR, caller-owned device arrays: rowptr int64 [n+1], colidx int32 [nnz], vals fp64 [nnz]. */
 int dsea_op_create_csr(int64_t n, int64_t nnz, const int64_t *rowptr, const int32_t *colidx,
                        const double *vals, dsea_op_t *out);
