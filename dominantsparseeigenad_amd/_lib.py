@@ -28,6 +28,7 @@ ERR_UNSUPPORTED = -6
 MAX_NEV = 8            # DSEA_MAX_NEV
 LATTICE_MAX_BONDS = 128  # DSEA_LATTICE_MAX_BONDS
 SECTOR_MAX_L = 40        # the spin-sector operator: 2 <= L <= 40, C(L, ndown) <= 2^31 - 1
+SYMSECTOR_MAX_GROUP = 128  # DSEA_SYMSECTOR_MAX_GROUP
 COMM_ID_BYTES = 128
 TUNE_TFIM_TILE_LOG2, TUNE_CSR_GROUP, TUNE_SELL_UNROLL, TUNE_SELL_XCD_MAP, TUNE_SELL_NT = 1, 2, 3, 4, 5
 TUNE_SELL_MAX_WIDTH = 6
@@ -81,6 +82,14 @@ _SIGNATURES = {
                                       POINTER(c_void_p)]),
     "dsea_op_sector_forms_scratch_doubles": (c_int, [c_int, c_int, c_int, POINTER(c_int64)]),
     "dsea_op_sector_forms": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dsea_symsector_sizes": (c_int, [c_int, c_int, c_int, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)]),
+    "dsea_symsector_fill_perm": (c_int, [c_int, c_int, POINTER(c_int32), c_void_p, c_void_p]),
+    "dsea_symsector_classify": (c_int, [c_int, c_int, c_int, POINTER(c_int32), c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
+    "dsea_symsector_fill_buckets": (c_int, [c_int, c_int64, c_void_p, c_void_p, c_void_p]),
+    "dsea_op_create_symsector": (c_int, [c_int, c_int, c_int, POINTER(c_int32), c_void_p, c_int, POINTER(c_int32),
+                                         POINTER(c_int32), c_int64, c_void_p, c_void_p, c_void_p, POINTER(c_void_p)]),
+    "dsea_op_symsector_forms_scratch_doubles": (c_int, [c_int64, c_int, c_int, POINTER(c_int64)]),
+    "dsea_op_symsector_forms": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dsea_hubbard_sizes": (c_int, [c_int, c_int, c_int, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)]),
     "dsea_op_create_hubbard": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_int32), c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_void_p, c_void_p, POINTER(c_void_p)]),

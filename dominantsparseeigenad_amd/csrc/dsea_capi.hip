@@ -621,6 +621,108 @@ int dsea_op_sector_forms(dsea_op_t op, const double* v1, const double* v2, doubl
   return check_launch();
 }
 
+int dsea_symsector_sizes(int L, int ndown, int ng, int64_t* n_sector, int64_t* n_bucket, int64_t* n_perm) {
+  REQUIRE(n_sector && n_bucket && n_perm && symsector_sizes(L, ndown, ng, n_sector, n_bucket, n_perm), DSEA_ERR_ARG);
+  return DSEA_OK;
+}
+
+// bit g of neg = (chars_host[g] == -1); false unless every character is +1 or -1
+static bool symsector_chars(int ng, const int32_t* chars_host, uint64_t neg[2]) {
+  neg[0] = neg[1] = 0;
+  for (int g = 0; g < ng; ++g) {
+    if (chars_host[g] != 1 && chars_host[g] != -1) return false;
+    if (chars_host[g] == -1) neg[g >> 6] |= 1ull << (g & 63);
+  }
+  return true;
+}
+
+int dsea_symsector_fill_perm(int L, int ng, const int32_t* perms_host, int64_t* perm_tab, void* stream) {
+  int64_t n_sector, n_bucket, n_perm;
+  REQUIRE(perms_host && perm_tab && symsector_sizes(L, 1, ng, &n_sector, &n_bucket, &n_perm), DSEA_ERR_ARG);
+  for (int g = 0; g < ng; ++g) {
+    uint64_t seen = 0;
+    for (int i = 0; i < L; ++i) {
+      const int32_t to = perms_host[g * L + i];
+      REQUIRE(to >= 0 && to < L && !((seen >> to) & 1ull), DSEA_ERR_ARG);
+      seen |= 1ull << to;
+    }
+  }
+  launch_symsector_fill_perm(L, ng, perms_host, reinterpret_cast<uint64_t*>(perm_tab), static_cast<hipStream_t>(stream));
+  return check_launch();
+}
+
+int dsea_symsector_classify(int L, int ndown, int ng, const int32_t* chars_host, const int64_t* perm_tab, int64_t first,
+                            int64_t count, int64_t* slab, void* stream) {
+  int64_t n_sector, n_bucket, n_perm;
+  uint64_t neg[2];
+  REQUIRE(chars_host && perm_tab && slab && symsector_sizes(L, ndown, ng, &n_sector, &n_bucket, &n_perm), DSEA_ERR_ARG);
+  REQUIRE(first >= 0 && count >= 1 && first <= n_sector - count && symsector_chars(ng, chars_host, neg), DSEA_ERR_ARG);
+  launch_symsector_classify(L, ndown, ng, neg, reinterpret_cast<const uint64_t*>(perm_tab), first, count,
+                            reinterpret_cast<uint64_t*>(slab), static_cast<hipStream_t>(stream));
+  return check_launch();
+}
+
+int dsea_symsector_fill_buckets(int L, int64_t n_rep, const int64_t* reps, int32_t* bucket, void* stream) {
+  REQUIRE(reps && bucket && L >= 2 && L <= DSEA_SECTOR_MAX_L && n_rep >= 1 && n_rep <= 0x7FFFFFFFll, DSEA_ERR_ARG);
+  launch_symsector_fill_buckets(L, n_rep, reinterpret_cast<const uint64_t*>(reps), reinterpret_cast<uint32_t*>(bucket),
+                                static_cast<hipStream_t>(stream));
+  return check_launch();
+}
+
+int dsea_op_create_symsector(int L, int ndown, int nb, const int32_t* bonds_host, const double* couplings_dev, int ng,
+                             const int32_t* chars_host, const int32_t* orbits_host, int64_t n_rep, const int64_t* reps,
+                             const int32_t* bucket, const int64_t* perm_tab, dsea_op_t* out) {
+  int64_t n_sector, n_bucket, n_perm;
+  uint64_t neg[2];
+  REQUIRE(out && symsector_sizes(L, ndown, ng, &n_sector, &n_bucket, &n_perm) && nb >= 1 && nb <= DSEA_LATTICE_MAX_BONDS &&
+              bonds_host && couplings_dev && chars_host && orbits_host && reps && bucket && perm_tab,
+          DSEA_ERR_ARG);
+  REQUIRE(n_rep >= 1 && n_rep <= n_sector && symsector_chars(ng, chars_host, neg), DSEA_ERR_ARG);
+  for (int t = 0; t < nb; ++t) {
+    const int32_t a = bonds_host[2 * t], b = bonds_host[2 * t + 1];
+    REQUIRE(a >= 0 && a < L && b >= 0 && b < L && a != b, DSEA_ERR_ARG);
+  }
+  for (int c = 0; c < 2 * nb + L; ++c) REQUIRE(orbits_host[c] >= 0 && orbits_host[c] < 2 * nb + L, DSEA_ERR_ARG);
+  dsea_op_s* op = new (std::nothrow) dsea_op_s;
+  if (!op) return DSEA_ERR_ARG;
+  memset(&op->d, 0, sizeof(op->d));
+  op->d.tune_tile_log2 = 12;   // this kind: log2 of the grid cap (DSEA_MAX_TFIM_BLOCKS)
+  op->d.kind = OP_SYMSECTOR;
+  op->d.n = n_rep;
+  SymSectorDesc& d = op->d.symsector;
+  d.L = L;
+  d.ndown = ndown;
+  d.nb = nb;
+  d.ng = ng;
+  d.c = couplings_dev;
+  d.reps = reinterpret_cast<const uint64_t*>(reps);
+  d.bucket = reinterpret_cast<const uint32_t*>(bucket);
+  d.perm_tab = reinterpret_cast<const uint64_t*>(perm_tab);
+  d.neg[0] = neg[0];
+  d.neg[1] = neg[1];
+  for (int t = 0; t < nb; ++t) {
+    d.a[t] = (uint8_t)bonds_host[2 * t];
+    d.b[t] = (uint8_t)bonds_host[2 * t + 1];
+  }
+  for (int c = 0; c < 2 * nb + L; ++c) d.orb[c] = (uint16_t)orbits_host[c];
+  *out = op;
+  return DSEA_OK;
+}
+
+int dsea_op_symsector_forms_scratch_doubles(int64_t n_rep, int L, int nb, int64_t* out) {
+  REQUIRE(out && n_rep >= 1 && n_rep <= 0x7FFFFFFFll && L >= 2 && L <= DSEA_SECTOR_MAX_L && nb >= 1 &&
+              nb <= DSEA_LATTICE_MAX_BONDS,
+          DSEA_ERR_ARG);
+  *out = symsector_forms_scratch_doubles(n_rep, L, nb);
+  return DSEA_OK;
+}
+
+int dsea_op_symsector_forms(dsea_op_t op, const double* v1, const double* v2, double* out, double* scratch, void* stream) {
+  REQUIRE(op && op->d.kind == OP_SYMSECTOR && v1 && v2 && out && scratch, DSEA_ERR_ARG);
+  if (launch_symsector_forms(op->d, v1, v2, out, scratch, static_cast<hipStream_t>(stream)) != 0) return DSEA_ERR_UNSUPPORTED;
+  return check_launch();
+}
+
 int dsea_hubbard_sizes(int L, int nup, int ndn, int64_t* n, int64_t* n_up, int64_t* n_dn) {
   REQUIRE(n && n_up && n_dn && hubbard_sizes(L, nup, ndn, n, n_up, n_dn), DSEA_ERR_ARG);
   return DSEA_OK;

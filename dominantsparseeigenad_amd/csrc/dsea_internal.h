@@ -147,12 +147,26 @@ struct HubbardDesc {
   const uint32_t* dn_hi;
   uint8_t a[DSEA_LATTICE_MAX_BONDS], b[DSEA_LATTICE_MAX_BONDS];
 };
+// XXZ spins in one magnetisation sector reduced by a lattice-symmetry group with a real one-dimensional character
+// (dsea_symsector.hip): bonds and couplings as SectorDesc; ng group elements, bit g of neg set when chi(g) = -1; orb[c] the orbit
+// id of parameter c (the couplings are averaged over their orbits); reps (n_rep words s | sigma << 48, increasing), bucket
+// (2^Lhi + 1) and perm_tab (ng * ceil(L / 8) * 256): the caller's device tables
+struct SymSectorDesc {
+  int L, ndown, nb, ng;
+  const double* c;
+  const uint64_t* reps;
+  const uint32_t* bucket;
+  const uint64_t* perm_tab;
+  uint64_t neg[2];
+  uint8_t a[DSEA_LATTICE_MAX_BONDS], b[DSEA_LATTICE_MAX_BONDS];
+  uint16_t orb[2 * DSEA_LATTICE_MAX_BONDS + DSEA_SECTOR_MAX_L];
+};
 enum OpKind { OP_TFIM = 1, OP_CSR = 2, OP_STENCIL3 = 3, OP_SELL = 4, OP_DENSE = 5, OP_TRANSFER = 6, OP_SYMDENSE = 7, OP_CHAIN = 8,
-              OP_LATTICE = 9, OP_SECTOR = 10, OP_HUBBARD = 11 };
+              OP_LATTICE = 9, OP_SECTOR = 10, OP_HUBBARD = 11, OP_SYMSECTOR = 12 };
 struct OpDesc {
   OpKind kind;
   int64_t n;
-  int tune_tile_log2;  // TFIM, spin chain, spin lattice: log2 rows of x staged in LDS per block (6..12); spin sector, Hubbard: log2 of the grid cap
+  int tune_tile_log2;  // TFIM, spin chain, spin lattice: log2 rows of x staged in LDS per block (6..12); spin sector, Hubbard, symmetry sector: log2 of the grid cap
   int tune_csr_group;  // CSR: lanes per row, 0 = automatic
   int tune_sell_unroll;  // SELL: slice-column pairs in flight per lane {0 = automatic, 2, 4, 6, 8}; 1 = the round-5 kernel (A/B)
   TfimParams tfim;
@@ -166,6 +180,7 @@ struct OpDesc {
   LatticeDesc lattice;
   SectorDesc sector;
   HubbardDesc hubbard;
+  SymSectorDesc symsector;
 };
 
 // One basis row's storage shadow as the writers see it: bf16 (h), e5m2 codes of q * S (b), or neither.  At most one of
@@ -459,6 +474,19 @@ int launch_spmv_hubbard(const OpDesc& op, const double* x, double* y, const doub
                         hipStream_t st, EventPair* ev);
 int launch_hubbard_forms(const OpDesc& op, const double* v1, const double* v2, double* out, double* scratch, hipStream_t st);
 int64_t hubbard_forms_scratch_doubles(int64_t n, int L, int nb);
+// dsea_symsector.hip (the spin sector reduced by a lattice-symmetry group): the sizes n_sector = C(L, ndown), 2^Lhi + 1 buckets
+// and the words of perm_tab (false when L, ndown, n_sector or ng is out of range); the table fills; the mat-vec of launch_spmv's
+// OP_SYMSECTOR case; the 2 nb + L orbit-averaged bilinear forms into out through per-block partials in the caller's scratch
+// (symsector_forms_scratch_doubles doubles); the op launchers return -1 when the descriptor is out of range
+bool symsector_sizes(int L, int ndown, int ng, int64_t* n_sector, int64_t* n_bucket, int64_t* n_perm);
+int launch_symsector_fill_perm(int L, int ng, const int32_t* perms_host, uint64_t* perm_tab, hipStream_t st);
+int launch_symsector_classify(int L, int ndown, int ng, const uint64_t neg[2], const uint64_t* perm_tab, int64_t first,
+                              int64_t count, uint64_t* slab, hipStream_t st);
+int launch_symsector_fill_buckets(int L, int64_t n_rep, const uint64_t* reps, uint32_t* bucket, hipStream_t st);
+int launch_spmv_symsector(const OpDesc& op, const double* x, double* y, const double* shift, const double* skip, double* P,
+                          hipStream_t st, EventPair* ev);
+int launch_symsector_forms(const OpDesc& op, const double* v1, const double* v2, double* out, double* scratch, hipStream_t st);
+int64_t symsector_forms_scratch_doubles(int64_t n, int L, int nb);
 // dsea_cg_persist_tfim_big.hip
 bool cg_persist_tfim_big_applicable(const OpDesc& op);
 size_t cg_persist_tfim_big_comm_bytes(int64_t n);

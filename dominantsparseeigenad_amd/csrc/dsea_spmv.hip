@@ -1178,6 +1178,8 @@ int launch_spmv(const OpDesc& op, const double* x, double* y, const double* shif
       return launch_spmv_sector(op, x, y, shift, skip, P, st, ev);
     case OP_HUBBARD:
       return launch_spmv_hubbard(op, x, y, shift, skip, P, st, ev);
+    case OP_SYMSECTOR:
+      return launch_spmv_symsector(op, x, y, shift, skip, P, st, ev);
   }
   return -1;
 }

@@ -864,6 +864,403 @@ class _SectorForms(torch.autograd.Function):
         return g1, g2, None, None
 
 
+# ------------------------------------------------------------------------------------------ XXZ spins in a lattice-symmetry sector
+def ring_symmetries(L, momentum=0, parity=None):
+    """generators of the symmetry group of an L-site ring as (perm, char) pairs: the translation i -> i + 1 with character +1
+    (momentum 0) or -1 (momentum "pi"), and with ``parity`` = +1 / -1 the reflection i -> L - 1 - i with that character"""
+    L = int(L)
+    if momentum not in (0, "pi"):
+        raise ValueError("ring_symmetries: momentum is 0 or 'pi' (complex characters are out of scope)")
+    if parity not in (None, 1, -1):
+        raise ValueError("ring_symmetries: parity is None, +1 or -1")
+    gens = [(tuple((i + 1) % L for i in range(L)), 1 if momentum == 0 else -1)]
+    if parity is not None:
+        gens.append((tuple(L - 1 - i for i in range(L)), int(parity)))
+    return gens
+
+
+def torus_symmetries(Lx, Ly, kx=0, ky=0):
+    """generators of the translation group of the Lx x Ly torus of ``square_bonds`` (site = y * Lx + x): the x translation with
+    character +1 (kx = 0) or -1 (kx = "pi"), and the y translation likewise"""
+    Lx, Ly = int(Lx), int(Ly)
+    if kx not in (0, "pi") or ky not in (0, "pi"):
+        raise ValueError("torus_symmetries: kx and ky are 0 or 'pi' (complex characters are out of scope)")
+    tx = tuple(y * Lx + (x + 1) % Lx for y in range(Ly) for x in range(Lx))
+    ty = tuple(((y + 1) % Ly) * Lx + x for y in range(Ly) for x in range(Lx))
+    return [(tx, 1 if kx == 0 else -1), (ty, 1 if ky == 0 else -1)]
+
+
+def _close_group(L, generators):
+    """the group generated by ``generators`` as a list of (perm, char), the identity first, in breadth-first order; ValueError
+    for a perm that is no permutation of 0 .. L - 1, a character other than +-1 or one that is not consistent, and for more
+    than DSEA_SYMSECTOR_MAX_GROUP elements -- host arithmetic only"""
+    gens = []
+    for perm, char in generators:
+        perm = tuple(int(v) for v in perm)
+        if sorted(perm) != list(range(L)):
+            raise ValueError("a generator's perm must be a permutation of 0 .. %d" % (L - 1))
+        if char not in (1, -1):
+            raise ValueError("a generator's character must be +1 or -1 (real one-dimensional irreps only)")
+        gens.append((perm, int(char)))
+    ident = tuple(range(L))
+    chars = {ident: 1}
+    order, frontier = [ident], [ident]
+    while frontier:
+        new = []
+        for p in frontier:
+            for q, d in gens:
+                r = tuple(q[p[i]] for i in range(L))            # p first, then q
+                e = chars[p] * d
+                if r not in chars:
+                    if len(order) >= _lib.SYMSECTOR_MAX_GROUP:
+                        raise ValueError("the symmetry group has more than %d elements" % _lib.SYMSECTOR_MAX_GROUP)
+                    chars[r] = e
+                    order.append(r)
+                    new.append(r)
+                elif chars[r] != e:
+                    raise ValueError("the character is not consistent: one group element is reached with both signs")
+        frontier = new
+    return [(p, chars[p]) for p in order]
+
+
+def _orbit_ids(L, bonds, group):
+    """orbit id per parameter [Jxy(nb), Jz(nb), hz(L)], numbered by first appearance inside each family; ValueError when a group
+    element does not map the bond set onto itself or a pair is listed twice"""
+    pairs = [frozenset(b) for b in bonds]
+    index = {}
+    for t, pair in enumerate(pairs):
+        if pair in index:
+            raise ValueError("bond (%d, %d) is listed twice: SpinSymmetrySectorOperator refuses repeated bonds" % bonds[t])
+        index[pair] = t
+    low_b, low_s = list(range(len(bonds))), list(range(L))
+    for perm, _ in group:
+        for t, (a, b) in enumerate(bonds):
+            image = index.get(frozenset((perm[a], perm[b])))
+            if image is None:
+                raise ValueError("a group element maps bond (%d, %d) off the bond list" % (a, b))
+            low_b[t] = min(low_b[t], image)
+        for i in range(L):
+            low_s[i] = min(low_s[i], perm[i])
+    # the smallest image is a canonical label because G is a group; closing it transitively keeps that true for any input
+    for low in (low_b, low_s):
+        for i in range(len(low)):
+            while low[low[i]] != low[i]:
+                low[i] = low[low[i]]
+    def number(low):
+        ids = {}
+        return [ids.setdefault(v, len(ids)) for v in low]
+    ob, os_ = number(low_b), number(low_s)
+    nob = max(ob) + 1
+    return ob + [nob + v for v in ob] + [2 * nob + v for v in os_]
+
+
+def _apply_perm(perm, s):
+    t = 0
+    for i, to in enumerate(perm):
+        if (s >> i) & 1:
+            t |= 1 << to
+    return t
+
+
+def symmetry_sector_dim(L, ndown, generators):
+    """the number of rows of ``SpinSymmetrySectorOperator``: the orbits of the sector under the generated group whose
+    sigma = sum over the stabiliser of chi is not 0 (pure Python, for small L)"""
+    L, ndown = int(L), int(ndown)
+    group = _close_group(L, generators)
+    count = 0
+    for s in sector_states(L, ndown):
+        images = [_apply_perm(perm, s) for perm, _ in group]
+        if min(images) == s and sum(c for (_, c), im in zip(group, images) if im == s) != 0:
+            count += 1
+    return count
+
+
+def _symsector_view(op, couplings, like=None):
+    """(handle, n) of the symmetry-sector Hamiltonian of ``op`` (its bonds, group and tables) whose couplings are the
+    (2 nb + L,) tensor ``couplings``; ``like``: a view whose grid cap the new handle takes over."""
+    data = couplings.detach()
+    if data.dtype != F64 or not data.is_contiguous():
+        data = data.to(F64).contiguous()
+    bonds = op.bonds
+    flat = (c_int32 * (2 * len(bonds)))(*[s for bond in bonds for s in bond])
+    chars = (c_int32 * op.ng)(*[c for _, c in op.group])
+    orbits = (c_int32 * op.nparam)(*op.orbits)
+    reps, bucket, perm_tab = op._tables
+    raw = c_void_p()
+    check(_lib.load().dsea_op_create_symsector(op.N, op.ndown, len(bonds), flat, c_void_p(data.data_ptr()), op.ng, chars, orbits,
+                                               op.n, c_void_p(reps.data_ptr()), c_void_p(bucket.data_ptr()),
+                                               c_void_p(perm_tab.data_ptr()), byref(raw)), "dsea_op_create_symsector")
+    view = _NativeView(_Handle(raw, op.n, (data, op._tables)))
+    view.grid_log2 = None
+    if like is not None and like.grid_log2 is not None:
+        _set_sector_grid(view, like.grid_log2)
+    return view
+
+
+def _symsector_forms(view, op, v1, v2):
+    """all 2 nb + L orbit-averaged bilinear forms (dsea_op_symsector_forms: one pass, deterministic)"""
+    lib = _lib.load()
+    v1, v2 = engine.as_vector(v1, view.n), engine.as_vector(v2, view.n)
+    need = c_int64()
+    check(lib.dsea_op_symsector_forms_scratch_doubles(op.n, op.N, op.nb, byref(need)), "dsea_op_symsector_forms_scratch_doubles")
+    scratch = torch.empty(need.value, dtype=F64, device=v1.device)
+    out = torch.empty(op.nparam, dtype=F64, device=v1.device)
+    check(lib.dsea_op_symsector_forms(view.handle, c_void_p(v1.data_ptr()), c_void_p(v2.data_ptr()), c_void_p(out.data_ptr()),
+                                      c_void_p(scratch.data_ptr()), engine._stream(v1.device)), "dsea_op_symsector_forms")
+    return out
+
+
+class SpinSymmetrySectorOperator:
+    """The Hamiltonian of ``SpinSectorOperator`` (same bits, bonds and parameter tensor [Jxy(nb), Jz(nb), hz(L)]) restricted
+    further to one sector of a lattice-symmetry group G with a real one-dimensional character, matrix-free
+    (docs/design/20-symmetry-sector.md).  ``generators`` is a list of (perm, char): perm[i] is the site that site i is sent to,
+    char is +1 or -1 (``ring_symmetries`` / ``torus_symmetries`` build the usual ones).  The host closes the group and raises
+    ValueError, before anything touches the device, for a perm that is no permutation, an inconsistent character, more than 128
+    elements, a group element that does not map the bond set onto itself, and a bond listed twice.
+
+    Row r is the r-th orbit representative (the smallest state of its orbit) with sigma_r = sum over its stabiliser of chi != 0,
+    in increasing integer order: ``states`` and ``norms`` on the device.  The matrix is B^T H_sector(p) B with
+    |r> = (|G| sigma_r)^(-1/2) sum_g chi(g) |g s_r>, for any couplings: they enter through their orbit means (``symmetrise``).
+    ``H(v)`` is differentiable in v and in ``couplings``; ``Hadjoint_to_couplingsadjoint(v1, v2)`` returns all 2 nb + L entries in
+    one pass; both are re-entrant (second order works).  The couplings are read through the tensor's pointer on every launch;
+    binding another tensor makes a new handle on the same tables."""
+
+    _native_methods = ("H", "__call__")
+    SLAB_ROWS = 1 << 26
+
+    def __init__(self, L, bonds, couplings, ndown, generators, device=None):
+        self.N, self.ndown, self.n_sector = _check_sector(L, ndown)
+        self._bonds = _check_bonds(self.N, bonds)
+        self.nb = len(self._bonds)
+        self.nparam = 2 * self.nb + self.N
+        self._group = tuple(_close_group(self.N, generators))
+        self.ng = len(self._group)
+        self._orbits = tuple(_orbit_ids(self.N, self._bonds, self._group))
+        if device is None:
+            device = couplings.device if torch.is_tensor(couplings) else "cuda"
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError("SpinSymmetrySectorOperator is a device operator; use device='cuda'")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.Llo = (self.N + 1) // 2
+        self.nsl = (self.N + 7) // 8
+        lib = _lib.load()
+        stream = engine._stream(self.device)
+        chars = (c_int32 * self.ng)(*[c for _, c in self._group])
+        perms = (c_int32 * (self.ng * self.N))(*[v for perm, _ in self._group for v in perm])
+        perm_tab = torch.empty(self.ng * self.nsl * 256, dtype=torch.int64, device=self.device)
+        kept = []
+        with torch.cuda.device(self.device):
+            check(lib.dsea_symsector_fill_perm(self.N, self.ng, perms, c_void_p(perm_tab.data_ptr()), stream),
+                  "dsea_symsector_fill_perm")
+            for first in range(0, self.n_sector, self.SLAB_ROWS):
+                count = min(self.SLAB_ROWS, self.n_sector - first)
+                slab = torch.empty(count, dtype=torch.int64, device=self.device)
+                check(lib.dsea_symsector_classify(self.N, self.ndown, self.ng, chars, c_void_p(perm_tab.data_ptr()), first, count,
+                                                  c_void_p(slab.data_ptr()), stream), "dsea_symsector_classify")
+                kept.append(slab[slab != 0])
+            reps = torch.cat(kept).contiguous()
+            del kept
+            self.dim = self.n = int(reps.numel())
+            if self.n < 1:
+                raise ValueError("the symmetry sector is empty: every orbit has sigma = 0")
+            bucket = torch.empty((1 << (self.N - self.Llo)) + 1, dtype=torch.int32, device=self.device)
+            check(lib.dsea_symsector_fill_buckets(self.N, self.n, c_void_p(reps.data_ptr()), c_void_p(bucket.data_ptr()), stream),
+                  "dsea_symsector_fill_buckets")
+        self._tables = (reps, bucket, perm_tab)
+        self._states = reps & ((1 << 48) - 1)
+        self._norms = reps >> 48
+        self._orbit_index = torch.tensor(self._orbits, dtype=torch.int64, device=self.device)
+        self._chars = torch.tensor([c for _, c in self._group], dtype=F64, device=self.device)
+        self._sector_tables = None
+        self._c = None
+        self._H = None
+        self._grid_log2 = None
+        self.couplings = couplings
+
+    @property
+    def bonds(self):
+        """the bond list as a tuple of (a, b) pairs, in the order of the couplings (read-only)"""
+        return self._bonds
+
+    @property
+    def group(self):
+        """the closed group as a tuple of (perm, char), the identity first"""
+        return self._group
+
+    @property
+    def orbits(self):
+        """orbit id per parameter, in the order of the couplings: equal ids = one orbit under the group"""
+        return self._orbits
+
+    @property
+    def states(self):
+        """states[r] = the representative of row r (int64 device tensor, increasing)"""
+        return self._states
+
+    @property
+    def norms(self):
+        """norms[r] = sigma_r, the size of the representative's stabiliser (int64 device tensor)"""
+        return self._norms
+
+    @property
+    def couplings(self):
+        return self._c
+
+    @couplings.setter
+    def couplings(self, value):
+        if not torch.is_tensor(value):
+            value = torch.as_tensor(value, dtype=F64).to(self.device)
+        if value.device != self.device or value.dtype != F64:
+            raise ValueError("couplings must be a float64 tensor on %s" % self.device)
+        if tuple(value.shape) != (self.nparam,) or not value.is_contiguous():
+            raise ValueError("couplings must be a contiguous tensor of shape (%d,): Jxy(nb), Jz(nb), hz(L)" % self.nparam)
+        self._c = value
+        self._H = _symsector_view(self, value)     # the kernels read the couplings through this tensor's pointer
+        if self._grid_log2 is not None:
+            _set_sector_grid(self._H, self._grid_log2)
+
+    def set_grid_log2(self, grid_log2):
+        """log2 of the most blocks a launch uses (6..12, default 12; measurement aid, dsea_op_set_tuning)"""
+        _set_sector_grid(self._H, grid_log2)
+        self._grid_log2 = int(grid_log2)
+
+    pack = SpinSectorOperator.pack
+    unpack = SpinSectorOperator.unpack
+
+    @property
+    def handle(self):
+        return self._H.handle
+
+    def H(self, v):
+        """H v, differentiable in v and in the couplings"""
+        return _SymSectorApply.apply(v, self._c, self, self._H)
+
+    __call__ = H
+
+    def Hadjoint_to_couplingsadjoint(self, v1, v2):
+        """adjoint hook: couplings-bar = S raw, raw[t] = v1^T A_t v2, shape (2 nb + L,)"""
+        return _SymSectorForms.apply(v1, v2, self, self._H)
+
+    def symmetrise(self, p):
+        """S p: every coupling replaced by the mean over its orbit (torch, differentiable)"""
+        idx = self._orbit_index.to(p.device)
+        size = int(idx.max()) + 1
+        sums = torch.zeros(size, dtype=p.dtype, device=p.device).index_add(0, idx, p)
+        counts = torch.zeros(size, dtype=p.dtype, device=p.device).index_add(0, idx, torch.ones_like(p))
+        return (sums / counts)[idx]
+
+    def row_of(self, s):
+        """the row of every state in the int64 device tensor ``s``, -1 for a state that is no stored representative"""
+        s = torch.as_tensor(s, dtype=torch.int64, device=self.device)
+        pos = torch.searchsorted(self._states, s).clamp(max=self.n - 1)
+        return torch.where(self._states[pos] == s, pos, torch.full_like(pos, -1))
+
+    def _images(self, s):
+        """g(s) for every group element: an (|G|, len(s)) int64 tensor, from perm_tab by torch indexing"""
+        tab = self._tables[2].view(self.ng, self.nsl, 256)
+        out = torch.zeros((self.ng, s.numel()), dtype=torch.int64, device=self.device)
+        for sl in range(self.nsl):
+            out |= tab[:, sl, :][:, (s >> (8 * sl)) & 255]
+        return out
+
+    def expand(self, v):
+        """B v: the vector in the row order of ``SpinSectorOperator`` (torch indexing; for tests, n_sector <= 2^27)"""
+        if self.n_sector > 1 << 27:
+            raise ValueError("expand needs n_sector <= 2^27")
+        if self._sector_tables is None:
+            states = torch.empty(self.n_sector, dtype=torch.int64, device=self.device)
+            lo_rank = torch.empty(1 << self.Llo, dtype=torch.int32, device=self.device)
+            hi_base = torch.empty(1 << (self.N - self.Llo), dtype=torch.int32, device=self.device)
+            with torch.cuda.device(self.device):
+                check(_lib.load().dsea_sector_build_tables(self.N, self.ndown, c_void_p(states.data_ptr()),
+                                                           c_void_p(lo_rank.data_ptr()), c_void_p(hi_base.data_ptr()),
+                                                           engine._stream(self.device)), "dsea_sector_build_tables")
+            self._sector_tables = (lo_rank.to(torch.int64), hi_base.to(torch.int64))
+        lo_rank, hi_base = self._sector_tables
+        coef = v / torch.sqrt(float(self.ng) * self._norms.to(v.dtype))
+        images = self._images(self._states)
+        w = torch.zeros(self.n_sector, dtype=v.dtype, device=v.device)
+        for g in range(self.ng):
+            rows = hi_base[images[g] >> self.Llo] + lo_rank[images[g] & ((1 << self.Llo) - 1)]
+            w = w.index_add(0, rows, self._chars[g] * coef)
+        return w
+
+    def to_csr(self, layout="sell", col16="auto", values="auto"):
+        """The symmetry-sector matrix as an explicit device CSR operand (entries that share a row and a column are summed).
+        Built on the device with index arithmetic."""
+        n = self.n
+        jxy, jz, hz = self.unpack(self.symmetrise(self._c.detach()))
+        s, sigma = self._states, self._norms.to(F64)
+        rows = torch.arange(n, dtype=torch.int64, device=self.device)
+        z = [(1 - 2 * ((s >> i) & 1)).to(F64) for i in range(self.N)]
+        diag = torch.zeros(n, dtype=F64, device=self.device)
+        for i in range(self.N):
+            diag = diag + hz[i] * z[i]
+        r_all, c_all, v_all = [rows], [rows], []
+        for t, (a, b) in enumerate(self._bonds):
+            diag = diag + jz[t] * (z[a] * z[b])
+            flips = rows[((s >> a) ^ (s >> b)) & 1 == 1]
+            images = self._images(s[flips] ^ ((1 << a) | (1 << b)))
+            best, which = images.min(dim=0)
+            col = self.row_of(best)
+            keep = col >= 0
+            flips, col, which = flips[keep], col[keep], which[keep]
+            r_all.append(flips)
+            c_all.append(col)
+            v_all.append(2.0 * jxy[t] * self._chars[which] * torch.sqrt(sigma[col] / sigma[flips]))
+        key = torch.cat(r_all) * n + torch.cat(c_all)
+        uniq, inverse = torch.unique(key, sorted=True, return_inverse=True)
+        vals = torch.zeros(uniq.numel(), dtype=F64, device=self.device).index_add(0, inverse, torch.cat([diag] + v_all))
+        r_u = torch.div(uniq, n, rounding_mode="floor")
+        rowptr = torch.zeros(n + 1, dtype=torch.int64, device=self.device)
+        rowptr[1:] = torch.cumsum(torch.bincount(r_u, minlength=n), 0)
+        return CSROperator(rowptr, uniq - r_u * n, vals.contiguous(), n, layout=layout, col16=col16, values=values)
+
+
+class _SymSectorApply(torch.autograd.Function):
+    """y = H_sym[c] v.  Backward: H_sym[c] gy (symmetric) and the forms(gy, v) -- both re-entrant."""
+
+    @staticmethod
+    def forward(ctx, v, c, op, view):
+        ctx.op, ctx.view = op, view
+        ctx.save_for_backward(v, c)
+        return engine.spmv(view, v.detach())
+
+    @staticmethod
+    def backward(ctx, gy):
+        v, c = ctx.saved_tensors
+        gv = _SymSectorApply.apply(gy, c, ctx.op, ctx.view) if ctx.needs_input_grad[0] else None
+        gc = _SymSectorForms.apply(gy, v, ctx.op, ctx.view).reshape(c.shape) if ctx.needs_input_grad[1] else None
+        return gv, gc, None, None
+
+
+class _SymSectorForms(torch.autograd.Function):
+    """out = S raw(v1, v2), shape (2 nb + L,).  H_sym is linear in the couplings and sees them through S, which is symmetric: with
+    the incoming adjoint G as couplings the backward is d/dv1 = H_sym[G] v2 and d/dv2 = H_sym[G] v1 -- a second handle on the same
+    tables."""
+
+    @staticmethod
+    def forward(ctx, v1, v2, op, view):
+        ctx.op, ctx.view = op, view
+        ctx.save_for_backward(v1, v2)
+        return _symsector_forms(view, op, v1.detach(), v2.detach())
+
+    @staticmethod
+    def backward(ctx, G):
+        v1, v2 = ctx.saved_tensors
+        g1 = g2 = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            G = G.reshape(ctx.op.nparam)
+            adj = _symsector_view(ctx.op, G, like=ctx.view)      # the Hamiltonian whose couplings are the adjoint
+            if ctx.needs_input_grad[0]:
+                g1 = _SymSectorApply.apply(v2, G, ctx.op, adj)
+            if ctx.needs_input_grad[1]:
+                g2 = _SymSectorApply.apply(v1, G, ctx.op, adj)
+        return g1, g2, None, None
+
+
 # ------------------------------------------------------------------------------------------ Hubbard model at fixed (N_up, N_dn)
 def hubbard_dim(L, nup, ndn):
     """the dimension C(L, nup) C(L, ndn) of the Hubbard space of L sites with nup up and ndn down particles (pure Python)"""

@@ -252,6 +252,48 @@ int dsea_op_create_hubbard(int L, int nup, int ndn, int nb, const int32_t *bonds
 int dsea_op_hubbard_forms_scratch_doubles(int L, int nup, int ndn, int nb, int64_t *out);
 int dsea_op_hubbard_forms(dsea_op_t op, const double *v1, const double *v2, double *out, double *scratch, void *stream);
 
+/* XXZ spins of dsea_op_create_sector reduced further by a LATTICE-SYMMETRY GROUP G with a real one-dimensional character chi,
+ * matrix-free (docs/design/20-symmetry-sector.md).  g in G is a permutation of the sites: g(s) has bit perm_g[i] set iff s has
+ * bit i; chi(g) = +1 or -1.  rep(s) = min_g g(s); sigma(s) = sum_{g : g(s) = s} chi(g) (|Stab(s)| or 0).  Row r is the r-th
+ * representative with sigma != 0 IN INCREASING INTEGER ORDER; basis vector |r> = (|G| sigma_r)^(-1/2) sum_g chi(g) |g s_r>.  With
+ * pbar the couplings averaged over their orbits under G (bond orbits for Jxy and Jz, site orbits for hz; ascending index order):
+ *     y[r] = ( sum_t Jzbar_t z_a z_b + sum_i hzbar_i z_i ) x[r]
+ *          + sum_{t : bit_a(s_r) != bit_b(s_r)} 2 Jxybar_t chi(g*) sqrt(sigma_j / sigma_r) x[j]
+ * g* attains min_g g(s_r ^ m_t), j is the row of that minimum; the term is dropped when the minimum is no stored row.
+ * dsea_symsector_sizes: n_sector = C(L, ndown), n_bucket = 2^Lhi + 1 (Lhi = L - (L + 1) / 2), n_perm = ng ceil(L / 8) 256.
+ * Host arithmetic only.  DSEA_ERR_ARG outside the limits of dsea_sector_table_sizes, outside 1 <= ng <=
+ * DSEA_SYMSECTOR_MAX_GROUP, and for a null pointer. */
+#define DSEA_SYMSECTOR_MAX_GROUP 128 /* most group elements (the space group of the 4 x 4 torus has 128) */
+int dsea_symsector_sizes(int L, int ndown, int ng, int64_t *n_sector, int64_t *n_bucket, int64_t *n_perm);
+/* perm_tab int64 [n_perm] on the device, filled on `stream`: entry (g, slice, byte) = the image under g of the state whose byte
+ * `slice` is `byte` and whose other bits are 0, so g(s) is the OR of ceil(L / 8) entries.  perms_host: int32 [ng * L],
+ * perms_host[g * L + i] = the site that g sends site i to; DSEA_ERR_ARG unless every row is a permutation of 0 .. L - 1. */
+int dsea_symsector_fill_perm(int L, int ng, const int32_t *perms_host, int64_t *perm_tab, void *stream);
+/* Rows [first, first + count) of the full sector (unranked in the kernel): slab[i] = s | sigma << 48 when the state s of row
+ * first + i is the smallest of its orbit and sigma != 0, and 0 otherwise.  chars_host: int32 [ng], +1 or -1.  slab: int64
+ * [count] on the device.  The non-zero entries of all slabs in order are the table `reps`. */
+int dsea_symsector_classify(int L, int ndown, int ng, const int32_t *chars_host, const int64_t *perm_tab, int64_t first,
+                            int64_t count, int64_t *slab, void *stream);
+/* bucket int32 [n_bucket] on the device: bucket[h] = the first row whose state >> Llo is >= h, Llo = (L + 1) / 2. */
+int dsea_symsector_fill_buckets(int L, int64_t n_rep, const int64_t *reps, int32_t *bucket, void *stream);
+/* The operator on filled tables (caller-owned, alive as long as the handle; several handles may share one set); n = n_rep rows.
+ * bonds_host, couplings_dev: as dsea_op_create_sector (READ THROUGH THE POINTER ON EVERY LAUNCH).  orbits_host: int32
+ * [2 nb + L], the orbit id of every parameter (equal ids inside one family = one orbit), 0 <= id < 2 nb + L.  Checked on the
+ * host before any device work (DSEA_ERR_ARG): the limits of dsea_symsector_sizes, 1 <= n_rep <= n_sector, the bond rules of
+ * dsea_op_create_sector, chars of +-1, orbit ids in range, non-null pointers.  Nothing is launched or allocated at creation.
+ * DSEA_TUNE_TFIM_TILE_LOG2 = log2 of the most blocks a launch uses (6..12, default 12; a block takes 16 rows at a time and
+ * walks beyond the cap).  No fused Lanczos tail, no persistent forms, no row-partitioned slabs. */
+int dsea_op_create_symsector(int L, int ndown, int nb, const int32_t *bonds_host, const double *couplings_dev, int ng,
+                             const int32_t *chars_host, const int32_t *orbits_host, int64_t n_rep, const int64_t *reps,
+                             const int32_t *bucket, const int64_t *perm_tab, dsea_op_t *out);
+/* The parameter adjoint of dsea_op_create_symsector: out = S raw, raw[t] = v1^T A_t v2 with A_t the coefficient matrix of
+ * pbar_t in the row formula and S the orbit mean, for all 2 nb + L couplings in one pass (per-block partials in `scratch`, then
+ * a fixed-order reduction over the members of each orbit: no atomics, repeated calls return identical bits, the members of an
+ * orbit receive identical bits).  `scratch`: caller-owned, dsea_op_symsector_forms_scratch_doubles(n_rep, L, nb) =
+ * (2 nb + L) * min(4096, ceil(n_rep / 8)) doubles (enough for every grid cap).  DSEA_ERR_ARG for any other operator kind. */
+int dsea_op_symsector_forms_scratch_doubles(int64_t n_rep, int L, int nb, int64_t *out);
+int dsea_op_symsector_forms(dsea_op_t op, const double *v1, const double *v2, double *out, double *scratch, void *stream);
+
 /* CSR, caller-owned device arrays: rowptr int64 [n+1], colidx int32 [nnz], vals fp64 [nnz]. */
 int dsea_op_create_csr(int64_t n, int64_t nnz, const int64_t *rowptr, const int32_t *colidx,
                        const double *vals, dsea_op_t *out);
