@@ -8,6 +8,7 @@ empty; users import sub-modules by name):
     dominantsparseeigenad_amd.symeig    DominantSymeig, setDominantSparseSymeig
     dominantsparseeigenad_amd.eig       DominantEig, setDominantSparseEig
     dominantsparseeigenad_amd.operators TFIMOperator, CSROperator, Stencil3Operator (native mat-vecs)
+                                        Bipartition (reduced density matrices and entanglement entropies of their vectors)
 
 The top-level ``DominantSparseEigenAD`` package in this repository re-exports the same modules
 under the reference's import names.

@@ -29,6 +29,8 @@ MAX_NEV = 8            # DSEA_MAX_NEV
 LATTICE_MAX_BONDS = 128  # DSEA_LATTICE_MAX_BONDS
 SECTOR_MAX_L = 40        # the spin-sector operator: 2 <= L <= 40, C(L, ndown) <= 2^31 - 1
 SYMSECTOR_MAX_GROUP = 128  # DSEA_SYMSECTOR_MAX_GROUP
+RDM_MAX_SITES = 16         # DSEA_RDM_MAX_SITES
+RDM_MAX_BLOCKS = 17        # DSEA_RDM_MAX_BLOCKS
 COMM_ID_BYTES = 128
 TUNE_TFIM_TILE_LOG2, TUNE_CSR_GROUP, TUNE_SELL_UNROLL, TUNE_SELL_XCD_MAP, TUNE_SELL_NT = 1, 2, 3, 4, 5
 TUNE_SELL_MAX_WIDTH = 6
@@ -90,6 +92,14 @@ _SIGNATURES = {
                                          POINTER(c_int32), c_int64, c_void_p, c_void_p, c_void_p, POINTER(c_void_p)]),
     "dsea_op_symsector_forms_scratch_doubles": (c_int, [c_int64, c_int, c_int, POINTER(c_int64)]),
     "dsea_op_symsector_forms": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dsea_rdm_sizes": (c_int, [c_int, c_int, c_int, POINTER(c_int32), POINTER(c_int64), POINTER(c_int), POINTER(c_int64),
+                               POINTER(c_int64)]),
+    "dsea_rdm_build_index_sector": (c_int, [c_int, c_int, c_int, POINTER(c_int32), c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dsea_rdm_build_index_full": (c_int, [c_int, c_int, POINTER(c_int32), c_void_p, c_void_p]),
+    "dsea_rdm_scratch_doubles": (c_int, [c_int, c_int, c_int, POINTER(c_int32), POINTER(c_int64)]),
+    "dsea_rdm_cross": (c_int, [c_int, c_int, c_int, POINTER(c_int32), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                               c_void_p]),
+    "dsea_rdm_pull": (c_int, [c_int, c_int, c_int, POINTER(c_int32), c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "dsea_hubbard_sizes": (c_int, [c_int, c_int, c_int, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)]),
     "dsea_op_create_hubbard": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_int32), c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_void_p, c_void_p, POINTER(c_void_p)]),

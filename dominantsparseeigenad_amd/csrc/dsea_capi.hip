@@ -1912,4 +1912,67 @@ int dsea_cg_run_deflated(dsea_op_t op, dsea_ws_t ws, const double* shift, const 
   return cg_result(hs, iters_out, resnorm_out);
 }
 
+int dsea_rdm_sizes(int L, int ndown, int LA, const int32_t* sites_host, int64_t* n, int* nblocks, int64_t* blocks,
+                   int64_t* out_len) {
+  RdmGeom g;
+  REQUIRE(n && nblocks && blocks && out_len && (ndown >= 1 || ndown == -1) && rdm_geometry(L, ndown, LA, sites_host, &g),
+          DSEA_ERR_ARG);
+  *n = g.n;
+  *nblocks = g.blk.nblk;
+  *out_len = g.out_len;
+  for (int c = 0; c < g.blk.nblk; ++c) {
+    blocks[5 * c] = g.blk.m0 + c;
+    blocks[5 * c + 1] = g.blk.dA[c];
+    blocks[5 * c + 2] = g.blk.dB[c];
+    blocks[5 * c + 3] = g.blk.off[c];
+    blocks[5 * c + 4] = g.blk.ooff[c];
+  }
+  return DSEA_OK;
+}
+
+int dsea_rdm_build_index_sector(int L, int ndown, int LA, const int32_t* sites_host, const int32_t* lo_rank,
+                                const int32_t* hi_base, int32_t* idx, void* stream) {
+  RdmGeom g;
+  REQUIRE(lo_rank && hi_base && idx && ndown >= 1 && rdm_geometry(L, ndown, LA, sites_host, &g), DSEA_ERR_ARG);
+  if (launch_rdm_index(g, reinterpret_cast<const uint32_t*>(lo_rank), reinterpret_cast<const uint32_t*>(hi_base), idx,
+                       static_cast<hipStream_t>(stream)) != 0)
+    return DSEA_ERR_ARG;
+  return check_launch();
+}
+
+int dsea_rdm_build_index_full(int L, int LA, const int32_t* sites_host, int32_t* idx, void* stream) {
+  RdmGeom g;
+  REQUIRE(idx && rdm_geometry(L, -1, LA, sites_host, &g), DSEA_ERR_ARG);
+  if (launch_rdm_index(g, nullptr, nullptr, idx, static_cast<hipStream_t>(stream)) != 0) return DSEA_ERR_ARG;
+  return check_launch();
+}
+
+int dsea_rdm_scratch_doubles(int L, int ndown, int LA, const int32_t* sites_host, int64_t* out) {
+  RdmGeom g;
+  REQUIRE(out && (ndown >= 1 || ndown == -1) && rdm_geometry(L, ndown, LA, sites_host, &g), DSEA_ERR_ARG);
+  const int64_t need = rdm_scratch_doubles(g);
+  REQUIRE(need >= 0, DSEA_ERR_UNSUPPORTED);
+  *out = need;
+  return DSEA_OK;
+}
+
+int dsea_rdm_cross(int L, int ndown, int LA, const int32_t* sites_host, const int32_t* idx, const double* x, const double* y,
+                   double* out, double* scratch, int tile, void* stream) {
+  RdmGeom g;
+  REQUIRE(idx && x && y && out && scratch && tile >= 0 && tile <= 2 && (ndown >= 1 || ndown == -1) &&
+              rdm_geometry(L, ndown, LA, sites_host, &g),
+          DSEA_ERR_ARG);
+  if (launch_rdm_cross(g, idx, x, y, out, scratch, tile, static_cast<hipStream_t>(stream)) != 0) return DSEA_ERR_UNSUPPORTED;
+  return check_launch();
+}
+
+int dsea_rdm_pull(int L, int ndown, int LA, const int32_t* sites_host, const int32_t* idx, const double* G, const double* y,
+                  double* out, int transpose, void* stream) {
+  RdmGeom g;
+  REQUIRE(idx && G && y && out && out != y && (ndown >= 1 || ndown == -1) && rdm_geometry(L, ndown, LA, sites_host, &g),
+          DSEA_ERR_ARG);
+  if (launch_rdm_pull(g, idx, G, y, out, transpose != 0, static_cast<hipStream_t>(stream)) != 0) return DSEA_ERR_UNSUPPORTED;
+  return check_launch();
+}
+
 }  // extern "C"

@@ -487,6 +487,33 @@ int launch_spmv_symsector(const OpDesc& op, const double* x, double* y, const do
                           hipStream_t st, EventPair* ev);
 int launch_symsector_forms(const OpDesc& op, const double* v1, const double* v2, double* out, double* scratch, hipStream_t st);
 int64_t symsector_forms_scratch_doubles(int64_t n, int L, int nb);
+// dsea_rdm.hip (reduced density matrices of a bipartition of the sites, docs/design/21-reduced-density-matrix.md).  RdmSites:
+// a[k] the site of bit k of the A-word (the caller's order), b[k] that of the B-word (the other sites, increasing).  RdmBlocks:
+// block c holds m0 + c set bits in A; off = its offset into idx, ooff = into the flat output (ooff[nblk] = the output length),
+// dA x dB its slice.  rdm_geometry fills them on the host (ndown < 0: the full 2^L space) and is false for every argument the
+// ABI refuses; the launchers return -1 when a work list does not fit 31 bits.
+#define DSEA_RDM_MAX_LA DSEA_RDM_MAX_SITES      /* (DSEA_RDM_MAX_BLOCKS = DSEA_RDM_MAX_SITES + 1: include/dsea.h) */
+struct RdmSites {
+  int L, LA;
+  uint8_t a[DSEA_RDM_MAX_LA], b[DSEA_SECTOR_MAX_L];
+};
+struct RdmBlocks {
+  int nblk, m0;
+  int32_t off[DSEA_RDM_MAX_BLOCKS], dA[DSEA_RDM_MAX_BLOCKS], dB[DSEA_RDM_MAX_BLOCKS], ooff[DSEA_RDM_MAX_BLOCKS + 1];
+};
+struct RdmGeom {
+  int L, ndown;
+  int64_t n, out_len;
+  RdmSites sites;
+  RdmBlocks blk;
+};
+bool rdm_geometry(int L, int ndown, int LA, const int32_t* sites, RdmGeom* g);
+int64_t rdm_scratch_doubles(const RdmGeom& g);
+int launch_rdm_index(const RdmGeom& g, const uint32_t* lo_rank, const uint32_t* hi_base, int32_t* idx, hipStream_t st);
+int launch_rdm_cross(const RdmGeom& g, const int32_t* idx, const double* x, const double* y, double* out, double* scratch,
+                     int tile, hipStream_t st);
+int launch_rdm_pull(const RdmGeom& g, const int32_t* idx, const double* G, const double* y, double* out, int transpose,
+                    hipStream_t st);
 // dsea_cg_persist_tfim_big.hip
 bool cg_persist_tfim_big_applicable(const OpDesc& op);
 size_t cg_persist_tfim_big_comm_bytes(int64_t n);

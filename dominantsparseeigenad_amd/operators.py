@@ -12,7 +12,7 @@ Each operator is
 from __future__ import annotations
 
 import math
-from ctypes import byref, c_int32, c_int64, c_void_p
+from ctypes import byref, c_int, c_int32, c_int64, c_void_p
 
 import torch
 
@@ -793,6 +793,10 @@ class SpinSectorOperator:
             raise ValueError("embed / restrict need L <= 30")
         return w[self.states.to(w.device)]
 
+    def bipartition(self, sites):
+        """the ``Bipartition`` of this sector into the sites ``sites`` and the rest, on the operator's rank tables"""
+        return Bipartition(self.N, sites, ndown=self.ndown, device=self.device, _tables=self._tables[1:])
+
     def to_csr(self, layout="sell", col16="auto", values="auto"):
         """The sector matrix as an explicit device CSR operand: the diagonal, and for every distinct bond mask one entry in the
         rows that the mask flips (bonds with equal masks are summed).  Built on the device with index arithmetic."""
@@ -862,6 +866,241 @@ class _SectorForms(torch.autograd.Function):
             if ctx.needs_input_grad[1]:
                 g2 = _SectorApply.apply(v1, G, ctx.op, adj)
         return g1, g2, None, None
+
+
+# ------------------------------------------------------------------------------------------ reduced density matrices
+RDM_DENSE_MAX_SITES = 12   # dense(): the 2^LA x 2^LA matrix is for tests and small cases
+
+
+class Bipartition:
+    """The sites ``sites`` (A, in the caller's order) against the rest (B) for the vectors of a spin operator on L sites
+    (docs/design/21-reduced-density-matrix.md).  ``ndown`` = the sector of ``SpinSectorOperator`` (row r = the r-th state with
+    ndown set bits); ``ndown=None`` = the full 2^L space of ``TFIMOperator`` / ``SpinChainOperator`` / ``SpinLatticeOperator``
+    (L <= 30).  1 <= len(sites) <= min(L - 1, 16): for a larger A take the complement, it has the same non-zero spectrum.
+
+    Bit k of the A-word a is the bit of site sites[k]; bit k of the B-word b is the bit of the k-th other site.  In a sector
+    the reduced density matrix is block diagonal in the number m of set bits inside A: ``blocks`` is the tuple of
+    (m, dA, dB), row i of block m the i-th LA-bit word with m set bits in increasing order, column j the j-th LB-bit word with
+    ndown - m set bits.  With M_m(x)[i, j] = x[row(a_i, b_j)]:
+        cross(x, y)_m = M_m(x) M_m(y)^T        rdm(psi)_m = cross(psi, psi)_m        (psi as given: Tr rho = |psi|^2)
+    ``idx`` (int32, n entries, on the device) holds row(a_i, b_j) block after block, j fastest; it is built once here by the
+    library's kernel, so build the object once and reuse it.  Everything is differentiable to any order: the forward
+    (k_rdm_cross) and its adjoint (k_rdm_pull) are bilinear and each is the other's derivative.  ``ValueError`` for every
+    argument the C ABI refuses."""
+
+    def __init__(self, L, sites, ndown=None, device=None, _tables=None):
+        L = int(L)
+        sites = [int(s) for s in sites]
+        LA = len(sites)
+        full = ndown is None
+        if full:
+            if not 2 <= L <= 30:
+                raise ValueError("a Bipartition of the full 2^L space needs 2 <= L <= 30, got %d" % L)
+        else:
+            L, ndown, _ = _check_sector(L, ndown)
+        if not 1 <= LA <= min(L - 1, _lib.RDM_MAX_SITES):
+            raise ValueError("a Bipartition needs 1 <= len(sites) <= min(L - 1, %d), got %d" % (_lib.RDM_MAX_SITES, LA))
+        if len(set(sites)) != LA or min(sites) < 0 or max(sites) >= L:
+            raise ValueError("sites must be distinct and in 0 .. L - 1 = %d, got %r" % (L - 1, sites))
+        self.N, self.ndown, self.sites = L, (None if full else ndown), tuple(sites)
+        self._nd = -1 if full else ndown
+        self._sites = (c_int32 * LA)(*sites)
+        if device is None:
+            device = "cuda"
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError("Bipartition is a device object; use device='cuda'")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        lib = _lib.load()
+        n, nblk, out_len = c_int64(), c_int(), c_int64()
+        table = (c_int64 * (5 * _lib.RDM_MAX_BLOCKS))()
+        status = lib.dsea_rdm_sizes(L, self._nd, LA, self._sites, byref(n), byref(nblk), table, byref(out_len))
+        if status == _lib.ERR_ARG:
+            raise ValueError("the reduced density matrix of %d sites at L = %d, ndown = %r has 2^31 elements or more"
+                             % (LA, L, ndown))
+        check(status, "dsea_rdm_sizes")
+        self.n = self.dim = n.value
+        self.out_len = out_len.value
+        rows = [tuple(table[5 * c + e] for e in range(5)) for c in range(nblk.value)]
+        self.blocks = tuple((m, dA, dB) for m, dA, dB, _, _ in rows)
+        self._idx_off = tuple(r[3] for r in rows)
+        self._out_off = tuple(r[4] for r in rows)
+        need = c_int64()
+        status = lib.dsea_rdm_scratch_doubles(L, self._nd, LA, self._sites, byref(need))
+        if status == _lib.ERR_UNSUPPORTED:
+            raise ValueError("the work list of this Bipartition does not fit 31 bits")
+        check(status, "dsea_rdm_scratch_doubles")
+        self._scratch_doubles = need.value
+        self.idx = torch.empty(self.n, dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            if full:
+                check(lib.dsea_rdm_build_index_full(L, LA, self._sites, c_void_p(self.idx.data_ptr()),
+                                                    engine._stream(self.device)), "dsea_rdm_build_index_full")
+            else:
+                if _tables is None:
+                    Llo = (L + 1) // 2
+                    states = torch.empty(self.n, dtype=torch.int64, device=self.device)
+                    lo_rank = torch.empty(1 << Llo, dtype=torch.int32, device=self.device)
+                    hi_base = torch.empty(1 << (L - Llo), dtype=torch.int32, device=self.device)
+                    check(lib.dsea_sector_build_tables(L, ndown, c_void_p(states.data_ptr()), c_void_p(lo_rank.data_ptr()),
+                                                       c_void_p(hi_base.data_ptr()), engine._stream(self.device)),
+                          "dsea_sector_build_tables")
+                    _tables = (lo_rank, hi_base)
+                lo_rank, hi_base = _tables
+                check(lib.dsea_rdm_build_index_sector(L, ndown, LA, self._sites, c_void_p(lo_rank.data_ptr()),
+                                                      c_void_p(hi_base.data_ptr()), c_void_p(self.idx.data_ptr()),
+                                                      engine._stream(self.device)), "dsea_rdm_build_index_sector")
+        self._tile = 0
+
+    def set_tile(self, tile):
+        """the tile edge of the forward: 0 = the library's choice, 1 = 16, 2 = 32 (measurement aid)"""
+        if int(tile) not in (0, 1, 2):
+            raise ValueError("tile must be 0, 1 or 2")
+        self._tile = int(tile)
+
+    # ---- the two kernels on flat tensors
+    def _vector(self, v):
+        if not torch.is_tensor(v) or not v.is_cuda:
+            raise ValueError("Bipartition works on device vectors; got %s" % (v.device if torch.is_tensor(v) else type(v)))
+        if v.dim() != 1 or v.numel() != self.n:
+            raise ValueError("expected a vector of %d elements, got shape %r" % (self.n, tuple(v.shape)))
+        if v.dtype != F64:
+            raise ValueError("Bipartition works on float64 vectors, got %s" % v.dtype)
+        return engine.as_vector(v, self.n)
+
+    def _flat(self, G):
+        if not torch.is_tensor(G) or not G.is_cuda:
+            raise ValueError("Bipartition works on device tensors")
+        if G.numel() != self.out_len:
+            raise ValueError("expected %d elements (the blocks, flat), got %d" % (self.out_len, G.numel()))
+        if G.dtype != F64:
+            raise ValueError("Bipartition works on float64 tensors, got %s" % G.dtype)
+        return G.reshape(-1).contiguous()
+
+    def _cross_raw(self, x, y):
+        same = x is y or (x.data_ptr() == y.data_ptr() and x.dtype == y.dtype == F64 and x.is_contiguous() and y.is_contiguous())
+        x = self._vector(x)
+        y = x if same else self._vector(y)
+        out = torch.empty(self.out_len, dtype=F64, device=x.device)
+        scratch = torch.empty(self._scratch_doubles, dtype=F64, device=x.device)
+        check(_lib.load().dsea_rdm_cross(self.N, self._nd, len(self.sites), self._sites, c_void_p(self.idx.data_ptr()),
+                                         c_void_p(x.data_ptr()), c_void_p(y.data_ptr()), c_void_p(out.data_ptr()),
+                                         c_void_p(scratch.data_ptr()), self._tile, engine._stream(x.device)), "dsea_rdm_cross")
+        return out
+
+    def _pull_raw(self, G, y, transpose):
+        G, y = self._flat(G), self._vector(y)
+        out = torch.empty(self.n, dtype=F64, device=y.device)
+        check(_lib.load().dsea_rdm_pull(self.N, self._nd, len(self.sites), self._sites, c_void_p(self.idx.data_ptr()),
+                                        c_void_p(G.data_ptr()), c_void_p(y.data_ptr()), c_void_p(out.data_ptr()),
+                                        1 if transpose else 0, engine._stream(y.device)), "dsea_rdm_pull")
+        return out
+
+    # ---- the public, differentiable interface
+    def views(self, flat):
+        """the blocks of a flat tensor of ``out_len`` elements as a tuple of (dA, dA) views"""
+        return tuple(flat[o:o + dA * dA].view(dA, dA) for o, (_, dA, _) in zip(self._out_off, self.blocks))
+
+    def flatten(self, blocks):
+        """one flat tensor from a sequence of (dA, dA) blocks (the layout ``pull`` takes)"""
+        return torch.cat([b.reshape(-1) for b in blocks])
+
+    def cross_flat(self, x, y):
+        self._vector(x), self._vector(y)
+        return _RdmCross.apply(x, y, self)
+
+    def cross(self, x, y):
+        """(M_m(x) M_m(y)^T for every block m): 2-D views into one flat float64 tensor"""
+        return self.views(self.cross_flat(x, y))
+
+    def rdm_flat(self, psi):
+        return self.cross_flat(psi, psi)
+
+    def rdm(self, psi):
+        """the blocks rho_m of the reduced density matrix of psi (bitwise symmetric; Tr rho = |psi|^2)"""
+        return self.views(self.rdm_flat(psi))
+
+    def pull(self, G, y, transpose=False):
+        """the vector whose slices are G_m M_m(y) (G_m^T when ``transpose``); G flat or a sequence of blocks"""
+        if not torch.is_tensor(G):
+            G = self.flatten(G)
+        self._flat(G), self._vector(y)
+        return _RdmPull.apply(G, y, self, bool(transpose))
+
+    def _trace(self, flat):
+        return sum(torch.diagonal(b).sum() for b in self.views(flat))
+
+    def renyi2(self, psi):
+        """S_2 = -log( sum_m |rho_m|_F^2 / (Tr rho)^2 ): no eigendecomposition, smooth"""
+        flat = self.rdm_flat(psi)
+        return -torch.log((flat * flat).sum() / self._trace(flat) ** 2)
+
+    def spectrum(self, psi):
+        """the eigenvalues of rho (not normalised), block after block, ascending inside a block"""
+        return torch.cat([torch.linalg.eigvalsh(b) for b in self.rdm(psi)])
+
+    def entropy(self, psi, floor=1e-14):
+        """S = -sum lambda log lambda over the eigenvalues of rho / Tr rho above ``floor``; the others contribute neither value
+        nor gradient"""
+        lam = self.spectrum(psi)
+        lam = lam / lam.sum()
+        lam = lam[lam.detach() > floor]
+        return -(lam * torch.log(lam)).sum()
+
+    def dense(self, psi):
+        """the 2^LA x 2^LA reduced density matrix in the basis of the A-words (len(sites) <= 12): the blocks placed by torch"""
+        LA = len(self.sites)
+        if LA > RDM_DENSE_MAX_SITES:
+            raise ValueError("dense() is for len(sites) <= %d" % RDM_DENSE_MAX_SITES)
+        blocks = self.rdm(psi)
+        if self.ndown is None:
+            return blocks[0]
+        out = torch.zeros((1 << LA, 1 << LA), dtype=F64, device=blocks[0].device)
+        for (m, _, _), b in zip(self.blocks, blocks):
+            rows = torch.tensor([a for a in range(1 << LA) if bin(a).count("1") == m], dtype=torch.int64, device=out.device)
+            out = out.index_put((rows[:, None], rows[None, :]), b)
+        return out
+
+
+class _RdmCross(torch.autograd.Function):
+    """flat = (M_m(x) M_m(y)^T)_m.  Bilinear: with the cotangent G the slices of x-bar are G M(y) and those of y-bar G^T M(x),
+    both pulls -- re-entrant."""
+
+    @staticmethod
+    def forward(ctx, x, y, part):
+        ctx.part = part
+        ctx.save_for_backward(x, y)
+        return part._cross_raw(x.detach(), y.detach())
+
+    @staticmethod
+    def backward(ctx, G):
+        x, y = ctx.saved_tensors
+        gx = _RdmPull.apply(G, y, ctx.part, False) if ctx.needs_input_grad[0] else None
+        gy = _RdmPull.apply(G, x, ctx.part, True) if ctx.needs_input_grad[1] else None
+        return gx, gy, None
+
+
+class _RdmPull(torch.autograd.Function):
+    """out with slices G_m M_m(y) (G_m^T M_m(y) when transposed).  Bilinear in (G, y): with the cotangent w, G-bar =
+    cross(w, y) (cross(y, w), its transpose, when transposed) and y-bar = pull of w with the other transpose setting."""
+
+    @staticmethod
+    def forward(ctx, G, y, part, transpose):
+        ctx.part, ctx.transpose = part, transpose
+        ctx.save_for_backward(G, y)
+        return part._pull_raw(G.detach(), y.detach(), transpose)
+
+    @staticmethod
+    def backward(ctx, w):
+        G, y = ctx.saved_tensors
+        gG = gy = None
+        if ctx.needs_input_grad[0]:
+            gG = _RdmCross.apply(y, w, ctx.part) if ctx.transpose else _RdmCross.apply(w, y, ctx.part)
+            gG = gG.reshape(G.shape)
+        if ctx.needs_input_grad[1]:
+            gy = _RdmPull.apply(G, w, ctx.part, not ctx.transpose)
+        return gG, gy, None, None
 
 
 # ------------------------------------------------------------------------------------------ XXZ spins in a lattice-symmetry sector

@@ -855,6 +855,45 @@ int dsea_cg_deflated_step(dsea_ws_t ws, double *x, double *r, double *d, double 
                           const double *Psi, int64_t ldpsi, int m, double *state, double eps, int64_t iteration,
                           int64_t n, void *stream);
 
+/* ------------------------------------------------------------------ reduced density matrices (docs/design/21-reduced-density-matrix.md)
+ * A bipartition A | B of the L sites of a spin operator.  sites_host: int32 [LA], the sites of A in the caller's order,
+ * distinct, 1 <= LA <= min(L - 1, 16): bit k of the A-word a is the bit of site sites_host[k]; B is the other LB = L - LA sites
+ * in increasing order, bit k of the B-word b the bit of site B[k].  ndown >= 1: vectors of dsea_op_create_sector at (L, ndown)
+ * (row r = the r-th state with ndown set bits); the reduced density matrix is block diagonal in the number m of set bits
+ * inside A, m = max(0, ndown - LB) .. min(LA, ndown): row i of block m is the i-th LA-bit word with m set bits in increasing
+ * integer order, column j the j-th LB-bit word with ndown - m set bits, dA_m = C(LA, m), dB_m = C(LB, ndown - m).  ndown = -1:
+ * vectors of the full 2^L space (L <= 30, row = state), one block with dA = 2^LA, dB = 2^LB.
+ *     M_m(x)[i, j] = x[row(dep_A(a_i) | dep_B(b_j))]     cross(x, y)_m = M_m(x) M_m(y)^T     rho_m = cross(psi, psi)_m
+ * Every function takes the same (L, ndown, LA, sites_host) and refuses, by host arithmetic before any device work
+ * (DSEA_ERR_ARG): a site repeated or out of range, LA outside its limits, the limits of dsea_sector_table_sizes, the full
+ * space with L > 30, a flat output sum_m dA_m^2 of 2^31 elements or more, a null pointer. */
+#define DSEA_RDM_MAX_SITES 16  /* most sites of A (take the complement of a larger A: the same non-zero spectrum) */
+#define DSEA_RDM_MAX_BLOCKS 17
+/* dsea_rdm_sizes: n (the vector length), nblocks, out_len = sum_m dA_m^2, and blocks [5 * nblocks] (room for
+ * 5 * DSEA_RDM_MAX_BLOCKS): per block m, dA_m, dB_m, its offset into idx and its offset into the flat output. */
+int dsea_rdm_sizes(int L, int ndown, int LA, const int32_t *sites_host, int64_t *n, int *nblocks, int64_t *blocks,
+                   int64_t *out_len);
+/* The index table, int32 [n] on the device, filled on `stream` once per (L, ndown, sites): block after block, j fastest,
+ * idx[off_m + i dB_m + j] = the row of (a_i, b_j); a permutation of 0 .. n - 1.  The sector form unranks (m, i, j), deposits
+ * and ranks through lo_rank / hi_base of dsea_sector_build_tables at (L, ndown); the full-space form (ndown = -1) deposits
+ * only.  The library allocates nothing. */
+int dsea_rdm_build_index_sector(int L, int ndown, int LA, const int32_t *sites_host, const int32_t *lo_rank,
+                                const int32_t *hi_base, int32_t *idx, void *stream);
+int dsea_rdm_build_index_full(int L, int LA, const int32_t *sites_host, int32_t *idx, void *stream);
+/* dsea_rdm_cross: out [out_len] = cross(x, y), block after block, each block row-major, all blocks in one launch on
+ * v_mfma_f64_16x16x4_f64 with the inner dimension split over waves (partial tiles in `scratch`), then a fixed-order reduction:
+ * no atomics, repeated calls return identical bits.  x == y (the same pointer): only tiles on or below the diagonal are
+ * computed and the result is bitwise symmetric.  `scratch`: caller-owned, dsea_rdm_scratch_doubles doubles (enough for every
+ * `tile`).  tile: 0 = the library's choice of the tile edge, 1 = 16, 2 = 32 (measurement aid).  x, y: fp64 [n]. */
+int dsea_rdm_scratch_doubles(int L, int ndown, int LA, const int32_t *sites_host, int64_t *out);
+int dsea_rdm_cross(int L, int ndown, int LA, const int32_t *sites_host, const int32_t *idx, const double *x, const double *y,
+                   double *out, double *scratch, int tile, void *stream);
+/* dsea_rdm_pull: the adjoint of cross in one launch.  out[idx[off_m + i dB_m + j]] = sum_i' G_m[i, i'] y[idx[off_m + i' dB_m + j]]
+ * (transpose != 0: G_m[i', i]); G [out_len] in the layout of dsea_rdm_cross's output, out fp64 [n], not y.  idx is a
+ * permutation, so every element of out is written exactly once: no atomics, no scratch. */
+int dsea_rdm_pull(int L, int ndown, int LA, const int32_t *sites_host, const int32_t *idx, const double *G, const double *y,
+                  double *out, int transpose, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
