@@ -84,6 +84,9 @@ _SIGNATURES = {
                                       POINTER(c_void_p)]),
     "dsea_op_sector_forms_scratch_doubles": (c_int, [c_int, c_int, c_int, POINTER(c_int64)]),
     "dsea_op_sector_forms": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dsea_op_create_pairsector": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_void_p)]),
+    "dsea_op_pairsector_forms_scratch_doubles": (c_int, [c_int, c_int, POINTER(c_int64)]),
+    "dsea_op_pairsector_forms": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dsea_symsector_sizes": (c_int, [c_int, c_int, c_int, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)]),
     "dsea_symsector_fill_perm": (c_int, [c_int, c_int, POINTER(c_int32), c_void_p, c_void_p]),
     "dsea_symsector_classify": (c_int, [c_int, c_int, c_int, POINTER(c_int32), c_void_p, c_int64, c_int64, c_void_p, c_void_p]),

@@ -621,6 +621,39 @@ int dsea_op_sector_forms(dsea_op_t op, const double* v1, const double* v2, doubl
   return check_launch();
 }
 
+int dsea_op_create_pairsector(int L, int ndown, const double* couplings_dev, const int64_t* states, const int32_t* lo_rank,
+                              const int32_t* hi_base, dsea_op_t* out) {
+  int64_t n, n_lo, n_hi;
+  REQUIRE(out && sector_sizes(L, ndown, &n, &n_lo, &n_hi) && couplings_dev && states && lo_rank && hi_base, DSEA_ERR_ARG);
+  dsea_op_s* op = new (std::nothrow) dsea_op_s;
+  if (!op) return DSEA_ERR_ARG;
+  memset(&op->d, 0, sizeof(op->d));
+  op->d.tune_tile_log2 = 12;   // this kind: log2 of the grid cap (DSEA_MAX_TFIM_BLOCKS)
+  op->d.kind = OP_PAIRSECTOR;
+  op->d.n = n;
+  op->d.pairsector.L = L;
+  op->d.pairsector.ndown = ndown;
+  op->d.pairsector.c = couplings_dev;
+  op->d.pairsector.states = reinterpret_cast<const uint64_t*>(states);
+  op->d.pairsector.lo_rank = reinterpret_cast<const uint32_t*>(lo_rank);
+  op->d.pairsector.hi_base = reinterpret_cast<const uint32_t*>(hi_base);
+  *out = op;
+  return DSEA_OK;
+}
+
+int dsea_op_pairsector_forms_scratch_doubles(int L, int ndown, int64_t* out) {
+  int64_t n, n_lo, n_hi;
+  REQUIRE(out && sector_sizes(L, ndown, &n, &n_lo, &n_hi), DSEA_ERR_ARG);
+  *out = pairsector_forms_scratch_doubles(n, L);
+  return DSEA_OK;
+}
+
+int dsea_op_pairsector_forms(dsea_op_t op, const double* v1, const double* v2, double* out, double* scratch, void* stream) {
+  REQUIRE(op && op->d.kind == OP_PAIRSECTOR && v1 && v2 && out && scratch, DSEA_ERR_ARG);
+  if (launch_pairsector_forms(op->d, v1, v2, out, scratch, static_cast<hipStream_t>(stream)) != 0) return DSEA_ERR_UNSUPPORTED;
+  return check_launch();
+}
+
 int dsea_symsector_sizes(int L, int ndown, int ng, int64_t* n_sector, int64_t* n_bucket, int64_t* n_perm) {
   REQUIRE(n_sector && n_bucket && n_perm && symsector_sizes(L, ndown, ng, n_sector, n_bucket, n_perm), DSEA_ERR_ARG);
   return DSEA_OK;

@@ -161,12 +161,22 @@ struct SymSectorDesc {
   uint8_t a[DSEA_LATTICE_MAX_BONDS], b[DSEA_LATTICE_MAX_BONDS];
   uint16_t orb[2 * DSEA_LATTICE_MAX_BONDS + DSEA_SECTOR_MAX_L];
 };
+// XXZ spins with a coupling on every pair of sites in the sector of ndown set bits (dsea_pairsector.hip): the pairs are
+// implicit (lexicographic, i < j); c = [Jxy(P), Jz(P), hz(L)], P = L (L - 1) / 2, on the device -- read through the pointer on
+// every launch; states, lo_rank, hi_base: the caller's device tables as in SectorDesc
+struct PairSectorDesc {
+  int L, ndown;
+  const double* c;
+  const uint64_t* states;
+  const uint32_t* lo_rank;
+  const uint32_t* hi_base;
+};
 enum OpKind { OP_TFIM = 1, OP_CSR = 2, OP_STENCIL3 = 3, OP_SELL = 4, OP_DENSE = 5, OP_TRANSFER = 6, OP_SYMDENSE = 7, OP_CHAIN = 8,
-              OP_LATTICE = 9, OP_SECTOR = 10, OP_HUBBARD = 11, OP_SYMSECTOR = 12 };
+              OP_LATTICE = 9, OP_SECTOR = 10, OP_HUBBARD = 11, OP_SYMSECTOR = 12, OP_PAIRSECTOR = 13 };
 struct OpDesc {
   OpKind kind;
   int64_t n;
-  int tune_tile_log2;  // TFIM, spin chain, spin lattice: log2 rows of x staged in LDS per block (6..12); spin sector, Hubbard, symmetry sector: log2 of the grid cap
+  int tune_tile_log2;  // TFIM, spin chain, spin lattice: log2 rows of x staged in LDS per block (6..12); spin sector, Hubbard, symmetry sector, pair sector: log2 of the grid cap
   int tune_csr_group;  // CSR: lanes per row, 0 = automatic
   int tune_sell_unroll;  // SELL: slice-column pairs in flight per lane {0 = automatic, 2, 4, 6, 8}; 1 = the round-5 kernel (A/B)
   TfimParams tfim;
@@ -181,6 +191,7 @@ struct OpDesc {
   SectorDesc sector;
   HubbardDesc hubbard;
   SymSectorDesc symsector;
+  PairSectorDesc pairsector;
 };
 
 // One basis row's storage shadow as the writers see it: bf16 (h), e5m2 codes of q * S (b), or neither.  At most one of
@@ -487,6 +498,14 @@ int launch_spmv_symsector(const OpDesc& op, const double* x, double* y, const do
                           hipStream_t st, EventPair* ev);
 int launch_symsector_forms(const OpDesc& op, const double* v1, const double* v2, double* out, double* scratch, hipStream_t st);
 int64_t symsector_forms_scratch_doubles(int64_t n, int L, int nb);
+// dsea_pairsector.hip (XXZ spins with all-pair couplings in one magnetisation sector, on the tables of dsea_sector.hip): the
+// mat-vec of launch_spmv's OP_PAIRSECTOR case; the 2 P + L bilinear forms v1^T (dH/dp) v2 into out (the xy forms by gathers,
+// the zz and z forms by a Gram product on the matrix cores) through partials in the caller's scratch
+// (pairsector_forms_scratch_doubles doubles); the launchers return -1 when the descriptor is out of range
+int launch_spmv_pairsector(const OpDesc& op, const double* x, double* y, const double* shift, const double* skip, double* P,
+                           hipStream_t st, EventPair* ev);
+int launch_pairsector_forms(const OpDesc& op, const double* v1, const double* v2, double* out, double* scratch, hipStream_t st);
+int64_t pairsector_forms_scratch_doubles(int64_t n, int L);
 // dsea_rdm.hip (reduced density matrices of a bipartition of the sites, docs/design/21-reduced-density-matrix.md).  RdmSites:
 // a[k] the site of bit k of the A-word (the caller's order), b[k] that of the B-word (the other sites, increasing).  RdmBlocks:
 // block c holds m0 + c set bits in A; off = its offset into idx, ooff = into the flat output (ooff[nblk] = the output length),

@@ -1180,6 +1180,8 @@ int launch_spmv(const OpDesc& op, const double* x, double* y, const double* shif
       return launch_spmv_hubbard(op, x, y, shift, skip, P, st, ev);
     case OP_SYMSECTOR:
       return launch_spmv_symsector(op, x, y, shift, skip, P, st, ev);
+    case OP_PAIRSECTOR:
+      return launch_spmv_pairsector(op, x, y, shift, skip, P, st, ev);
   }
   return -1;
 }

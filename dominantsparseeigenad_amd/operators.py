@@ -797,6 +797,16 @@ class SpinSectorOperator:
         """the ``Bipartition`` of this sector into the sites ``sites`` and the rest, on the operator's rank tables"""
         return Bipartition(self.N, sites, ndown=self.ndown, device=self.device, _tables=self._tables[1:])
 
+    def pair_operator(self, couplings=None):
+        """the ``SpinSectorPairOperator`` of this sector on the operator's tables; ``couplings=None``: zeros, the correlator
+        of a state of this (or any other) Hamiltonian of the sector"""
+        return SpinSectorPairOperator(self.N, couplings, self.ndown, device=self.device, _tables=self._tables)
+
+    def correlations(self, psi):
+        """(xy, zz, z) of the state psi: <X_i X_j + Y_i Y_j> and <Z_i Z_j> for ALL pairs of sites as L x L matrices, and
+        <Z_i> (``SpinSectorPairOperator.correlations``); differentiable in psi"""
+        return self.pair_operator().correlations(psi)
+
     def to_csr(self, layout="sell", col16="auto", values="auto"):
         """The sector matrix as an explicit device CSR operand: the diagonal, and for every distinct bond mask one entry in the
         rows that the mask flips (bonds with equal masks are summed).  Built on the device with index arithmetic."""
@@ -865,6 +875,316 @@ class _SectorForms(torch.autograd.Function):
                 g1 = _SectorApply.apply(v2, G, ctx.op, adj)
             if ctx.needs_input_grad[1]:
                 g2 = _SectorApply.apply(v1, G, ctx.op, adj)
+        return g1, g2, None, None
+
+
+# ------------------------------------------------------------------------------------------ all-pair XXZ couplings in one S^z sector
+def pair_count(L):
+    """P = L (L - 1) / 2, the number of site pairs i < j"""
+    L = int(L)
+    return L * (L - 1) // 2
+
+
+def pair_index(L, i, j):
+    """the position of the pair {i, j}, i != j, in the lexicographic list (0,1), (0,2), ..., (0,L-1), (1,2), ...:
+    p = i (2 L - i - 1) / 2 + (j - i - 1) for i < j (pure Python)"""
+    L, i, j = int(L), int(i), int(j)
+    if i > j:
+        i, j = j, i
+    if not 0 <= i < j < L:
+        raise ValueError("pair_index needs two different sites in 0 .. L - 1 = %d, got %d and %d" % (L - 1, i, j))
+    return i * (2 * L - i - 1) // 2 + (j - i - 1)
+
+
+def power_law_couplings(L, alpha, periodic=False):
+    """the strict upper triangle of 1 / d(i, j)^alpha as an L x L float64 matrix, d = |i - j| on the open chain and
+    min(|i - j|, L - |i - j|) on the ring; differentiable in ``alpha`` (a tensor, on whose device the matrix lives); pure torch"""
+    L = int(L)
+    if L < 2:
+        raise ValueError("power_law_couplings needs L >= 2")
+    alpha = torch.as_tensor(alpha, dtype=F64) if not torch.is_tensor(alpha) else alpha.to(F64)
+    idx = torch.arange(L, device=alpha.device)
+    d = (idx[:, None] - idx[None, :]).abs()
+    if periodic:
+        d = torch.minimum(d, L - d)
+    d = d.clamp(min=1).to(F64)                 # (the diagonal is cut off below; 1 keeps its gradient finite)
+    return torch.triu(torch.exp(-alpha * torch.log(d)), diagonal=1)
+
+
+def ring_structure_factor(C):
+    """S[k] = (1 / L) sum_ij cos(2 pi k (i - j) / L) C[i, j] for k = 0 .. L - 1, of an L x L correlation matrix; pure torch"""
+    if C.dim() != 2 or C.shape[0] != C.shape[1]:
+        raise ValueError("ring_structure_factor needs a square matrix")
+    L = C.shape[0]
+    idx = torch.arange(L, device=C.device)
+    diff = (idx[:, None] - idx[None, :]).to(C.dtype)
+    k = idx.to(C.dtype)
+    phase = torch.cos((2.0 * math.pi / L) * k[:, None, None] * diff[None, :, :])
+    return (phase * C[None, :, :]).sum(dim=(1, 2)) / L
+
+
+def _pairsector_view(op, couplings, like=None):
+    """(handle, n) of the all-pair sector Hamiltonian on the tables of ``op`` whose couplings are the (2 P + L,) tensor
+    ``couplings``; ``like``: a view whose grid cap the new handle takes over."""
+    data = couplings.detach()
+    if data.dtype != F64 or not data.is_contiguous():
+        data = data.to(F64).contiguous()
+    states, lo_rank, hi_base = op._tables
+    raw = c_void_p()
+    check(_lib.load().dsea_op_create_pairsector(op.N, op.ndown, c_void_p(data.data_ptr()), c_void_p(states.data_ptr()),
+                                                c_void_p(lo_rank.data_ptr()), c_void_p(hi_base.data_ptr()), byref(raw)),
+          "dsea_op_create_pairsector")
+    view = _NativeView(_Handle(raw, op.n, (data, op._tables)))
+    view.grid_log2 = None
+    if like is not None and like.grid_log2 is not None:
+        _set_sector_grid(view, like.grid_log2)
+    return view
+
+
+def _pairsector_forms(view, op, v1, v2):
+    """all 2 P + L bilinear forms v1^T (dH/dp) v2 (dsea_op_pairsector_forms: deterministic)"""
+    lib = _lib.load()
+    v1, v2 = engine.as_vector(v1, view.n), engine.as_vector(v2, view.n)
+    need = c_int64()
+    check(lib.dsea_op_pairsector_forms_scratch_doubles(op.N, op.ndown, byref(need)), "dsea_op_pairsector_forms_scratch_doubles")
+    scratch = torch.empty(need.value, dtype=F64, device=v1.device)
+    out = torch.empty(op.nparam, dtype=F64, device=v1.device)
+    check(lib.dsea_op_pairsector_forms(view.handle, c_void_p(v1.data_ptr()), c_void_p(v2.data_ptr()), c_void_p(out.data_ptr()),
+                                       c_void_p(scratch.data_ptr()), engine._stream(v1.device)), "dsea_op_pairsector_forms")
+    return out
+
+
+class SpinSectorPairOperator:
+    """H = sum_{i<j} [Jxy_ij (X_i X_j + Y_i Y_j) + Jz_ij Z_i Z_j] + sum_i hz_i Z_i on L sites with a coupling on EVERY pair of
+    sites, restricted to the states with exactly ``ndown`` set bits, matrix-free (docs/design/22-pair-sector.md).  Rows, bits,
+    ``states``, the two rank tables and the limits are those of ``SpinSectorOperator``: 2 <= L <= 40, 1 <= ndown <= L - 1,
+    n = C(L, ndown) <= 2^31 - 1.  There is no bond list and no cap on the number of bonds: long-range models (power-law,
+    Haldane-Shastry, all-to-all) fit in one handle at every L.
+
+    ``couplings`` is ONE contiguous float64 device tensor of length 2 P + L, P = L (L - 1) / 2, in the order
+    [Jxy(P), Jz(P), hz(L)] with the pairs in lexicographic order (0,1), (0,2), ..., (0,L-1), (1,2), ... (``pairs``,
+    ``pair_index``); ``pack`` takes scalars, length-P vectors or L x L matrices (strict upper triangle).  ``None`` = zeros: the
+    operator is then the correlator of a state.  The kernels read the tensor through its device pointer on every launch:
+    in-place optimiser steps are seen, binding another tensor makes a new handle on the same tables.  ``H(v)`` is differentiable
+    in v and in ``couplings``; ``Hadjoint_to_couplingsadjoint(v1, v2)`` gives all 2 P + L forms and is the hook for
+    ``setDominantSparseSymeig`` / ``setLowestSparseSymeig``.  Both are re-entrant, so second order works.
+    ``correlations(v1, v2)`` arranges the forms as the L x L matrices of v1^T (X_i X_j + Y_i Y_j) v2 and v1^T Z_i Z_j v2 and
+    the vector v1^T Z_i v2."""
+
+    _native_methods = ("H", "__call__")
+
+    def __init__(self, L, couplings, ndown, device=None, _tables=None):
+        self.N, self.ndown, n = _check_sector(L, ndown)
+        self.npair = pair_count(self.N)
+        self.nparam = 2 * self.npair + self.N
+        self.dim = self.n = n
+        if device is None:
+            device = couplings.device if torch.is_tensor(couplings) else "cuda"
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError("SpinSectorPairOperator is a device operator; use device='cuda'")
+        if torch.is_tensor(couplings) and tuple(couplings.shape) != (self.nparam,):
+            raise ValueError("couplings must have shape (%d,): Jxy(P), Jz(P), hz(L) with P = %d" % (self.nparam, self.npair))
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.Llo = (self.N + 1) // 2
+        if _tables is None:
+            states = torch.empty(n, dtype=torch.int64, device=self.device)
+            lo_rank = torch.empty(1 << self.Llo, dtype=torch.int32, device=self.device)
+            hi_base = torch.empty(1 << (self.N - self.Llo), dtype=torch.int32, device=self.device)
+            with torch.cuda.device(self.device):
+                check(_lib.load().dsea_sector_build_tables(self.N, self.ndown, c_void_p(states.data_ptr()),
+                                                           c_void_p(lo_rank.data_ptr()), c_void_p(hi_base.data_ptr()),
+                                                           engine._stream(self.device)), "dsea_sector_build_tables")
+            _tables = (states, lo_rank, hi_base)
+        self._tables = tuple(_tables)
+        self._pairs = tuple((i, j) for i in range(self.N) for j in range(i + 1, self.N))
+        self._upper = None
+        self._c = None
+        self._H = None
+        self._grid_log2 = None
+        self.couplings = torch.zeros(self.nparam, dtype=F64, device=self.device) if couplings is None else couplings
+
+    @property
+    def pairs(self):
+        """the P pairs (i, j), i < j, as a tuple in the order of the couplings (read-only)"""
+        return self._pairs
+
+    def pair_index(self, i, j):
+        """the position of the pair {i, j} in ``pairs``"""
+        return pair_index(self.N, i, j)
+
+    def _upper_index(self):
+        """(rows, columns) of the strict upper triangle in pair order, on the device"""
+        if self._upper is None:
+            iu = torch.tensor([p[0] for p in self._pairs], dtype=torch.int64, device=self.device)
+            ju = torch.tensor([p[1] for p in self._pairs], dtype=torch.int64, device=self.device)
+            self._upper = (iu, ju)
+        return self._upper
+
+    @property
+    def states(self):
+        """states[r] = the basis state of row r (int64 device tensor, increasing)"""
+        return self._tables[0]
+
+    @property
+    def couplings(self):
+        return self._c
+
+    @couplings.setter
+    def couplings(self, value):
+        if not torch.is_tensor(value):
+            value = torch.as_tensor(value, dtype=F64).to(self.device)
+        if value.device != self.device or value.dtype != F64:
+            raise ValueError("couplings must be a float64 tensor on %s" % self.device)
+        if tuple(value.shape) != (self.nparam,) or not value.is_contiguous():
+            raise ValueError("couplings must be a contiguous tensor of shape (%d,): Jxy(P), Jz(P), hz(L)" % self.nparam)
+        self._c = value
+        self._H = _pairsector_view(self, value)     # the kernels read the couplings through this tensor's pointer
+        if self._grid_log2 is not None:
+            _set_sector_grid(self._H, self._grid_log2)
+
+    def set_grid_log2(self, grid_log2):
+        """log2 of the most blocks a launch uses (6..12, default 12; measurement aid, dsea_op_set_tuning)"""
+        _set_sector_grid(self._H, grid_log2)
+        self._grid_log2 = int(grid_log2)
+
+    def pack(self, Jxy, Jz, hz):
+        """the three families as one parameter tensor on the operator's device.  Jxy and Jz: a scalar, one value per pair, or
+        an L x L matrix of which the strict upper triangle is read; hz: a scalar or one value per site.  Differentiable."""
+        parts = []
+        for value, size in zip((Jxy, Jz, hz), (self.npair, self.npair, self.N)):
+            t = torch.as_tensor(value, dtype=F64).to(self.device)
+            if t.dim() == 2 and size == self.npair:
+                if tuple(t.shape) != (self.N, self.N):
+                    raise ValueError("a coupling matrix must have shape (%d, %d)" % (self.N, self.N))
+                t = t[self._upper_index()]
+            parts.append(t.expand(size) if t.dim() == 0 else t.reshape(size))
+        return torch.cat(parts).contiguous()
+
+    def unpack(self, t):
+        """views (Jxy, Jz, hz) of a parameter tensor"""
+        P = self.npair
+        if tuple(t.shape) != (self.nparam,):
+            raise ValueError("expected a tensor of shape (%d,)" % self.nparam)
+        return t[:P], t[P:2 * P], t[2 * P:]
+
+    @property
+    def handle(self):
+        return self._H.handle
+
+    def H(self, v):
+        """H v, differentiable in v and in the couplings"""
+        return _PairSectorApply.apply(v, self._c, self, self._H)
+
+    __call__ = H
+
+    def Hadjoint_to_couplingsadjoint(self, v1, v2):
+        """adjoint hook: couplings-bar[t] = v1^T (dH/dp_t) v2, shape (2 P + L,)"""
+        return _PairSectorForms.apply(v1, v2, self, self._H)
+
+    def correlations(self, v1, v2=None):
+        """(xy, zz, z): xy[i, j] = v1^T (X_i X_j + Y_i Y_j) v2 and zz[i, j] = v1^T Z_i Z_j v2 as symmetric L x L matrices (their
+        diagonals are 2 v1.v2 and v1.v2), z[i] = v1^T Z_i v2; ``v2=None``: the expectation values of v1.  One forms call, then
+        torch indexing; differentiable in v1 and v2."""
+        if v2 is None:
+            v2 = v1
+        f = self.Hadjoint_to_couplingsadjoint(v1, v2)
+        fxy, fzz, z = self.unpack(f)
+        index = self._upper_index()
+        eye = torch.eye(self.N, dtype=F64, device=f.device) * torch.dot(v1.to(F64), v2.to(F64))
+        out = []
+        for part, weight in ((fxy, 2.0), (fzz, 1.0)):
+            upper = torch.zeros((self.N, self.N), dtype=F64, device=f.device).index_put(index, part)
+            out.append(upper + upper.t() + weight * eye)      # (x + 0 and 0 + x: the two triangles carry the same bits)
+        return out[0], out[1], z
+
+    def rank(self, s):
+        """the row of every state in the int64 device tensor ``s`` (states of the sector only): the two-table lookup"""
+        _, lo_rank, hi_base = self._tables
+        return hi_base[s >> self.Llo].to(torch.int64) + lo_rank[s & ((1 << self.Llo) - 1)].to(torch.int64)
+
+    def embed(self, v):
+        """the sector vector v as a vector of the full 2^L space (zero outside the sector); L <= 30"""
+        if self.N > 30:
+            raise ValueError("embed / restrict need L <= 30")
+        w = torch.zeros(1 << self.N, dtype=v.dtype, device=v.device)
+        return w.index_put((self.states.to(v.device),), v)
+
+    def restrict(self, w):
+        """the sector part of a vector of the full 2^L space; L <= 30"""
+        if self.N > 30:
+            raise ValueError("embed / restrict need L <= 30")
+        return w[self.states.to(w.device)]
+
+    def bipartition(self, sites):
+        """the ``Bipartition`` of this sector into the sites ``sites`` and the rest, on the operator's rank tables"""
+        return Bipartition(self.N, sites, ndown=self.ndown, device=self.device, _tables=self._tables[1:])
+
+    def to_csr(self, layout="sell", col16="auto", values="auto"):
+        """The sector matrix as an explicit device CSR operand: the diagonal, and for every pair one entry in the rows that
+        the pair flips.  Built on the device with index arithmetic."""
+        n = self.n
+        jxy, jz, hz = self.unpack(self._c.detach())
+        s = self.states
+        rows = torch.arange(n, dtype=torch.int64, device=self.device)
+        z = [(1 - 2 * ((s >> i) & 1)).to(F64) for i in range(self.N)]
+        diag = torch.zeros(n, dtype=F64, device=self.device)
+        for i in range(self.N):
+            diag = diag + hz[i] * z[i]
+        r_all, c_all, off = [rows], [rows], []
+        for t, (a, b) in enumerate(self._pairs):
+            diag = diag + jz[t] * (z[a] * z[b])
+            flips = rows[((s >> a) ^ (s >> b)) & 1 == 1]
+            r_all.append(flips)
+            c_all.append(self.rank(s[flips] ^ ((1 << a) | (1 << b))))
+            off.append((2.0 * jxy[t]).expand(flips.numel()))
+        v_all = [diag] + off
+        r_all, c_all, v_all = torch.cat(r_all), torch.cat(c_all), torch.cat(v_all)
+        order = torch.argsort(r_all * n + c_all)
+        rowptr = torch.zeros(n + 1, dtype=torch.int64, device=self.device)
+        rowptr[1:] = torch.cumsum(torch.bincount(r_all, minlength=n), 0)
+        return CSROperator(rowptr, c_all[order], v_all[order].contiguous(), n, layout=layout, col16=col16, values=values)
+
+
+class _PairSectorApply(torch.autograd.Function):
+    """y = H[c] v.  Backward: H[c] gy (symmetric) and the forms(gy, v) -- both re-entrant."""
+
+    @staticmethod
+    def forward(ctx, v, c, op, view):
+        ctx.op, ctx.view = op, view
+        ctx.save_for_backward(v, c)
+        return engine.spmv(view, v.detach())
+
+    @staticmethod
+    def backward(ctx, gy):
+        v, c = ctx.saved_tensors
+        gv = _PairSectorApply.apply(gy, c, ctx.op, ctx.view) if ctx.needs_input_grad[0] else None
+        gc = _PairSectorForms.apply(gy, v, ctx.op, ctx.view).reshape(c.shape) if ctx.needs_input_grad[1] else None
+        return gv, gc, None, None
+
+
+class _PairSectorForms(torch.autograd.Function):
+    """out[t] = v1^T (dH/dp_t) v2, shape (2 P + L,).  H is linear in the couplings, so with the incoming adjoint G as
+    couplings the backward is d/dv1 = H[G] v2 and d/dv2 = H[G] v1: a second handle on the same tables."""
+
+    @staticmethod
+    def forward(ctx, v1, v2, op, view):
+        ctx.op, ctx.view = op, view
+        ctx.save_for_backward(v1, v2)
+        return _pairsector_forms(view, op, v1.detach(), v2.detach())
+
+    @staticmethod
+    def backward(ctx, G):
+        v1, v2 = ctx.saved_tensors
+        g1 = g2 = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            G = G.reshape(ctx.op.nparam).contiguous()
+            adj = _pairsector_view(ctx.op, G, like=ctx.view)      # the Hamiltonian whose couplings are the adjoint
+            if ctx.needs_input_grad[0]:
+                g1 = _PairSectorApply.apply(v2, G, ctx.op, adj)
+            if ctx.needs_input_grad[1]:
+                g2 = _PairSectorApply.apply(v1, G, ctx.op, adj)
         return g1, g2, None, None
 
 

@@ -219,6 +219,27 @@ int dsea_op_create_sector(int L, int ndown, int nb, const int32_t *bonds_host, c
 int dsea_op_sector_forms_scratch_doubles(int L, int ndown, int nb, int64_t *out);
 int dsea_op_sector_forms(dsea_op_t op, const double *v1, const double *v2, double *out, double *scratch, void *stream);
 
+/* XXZ spins with a coupling on EVERY PAIR OF SITES in one magnetisation sector, matrix-free (docs/design/22-pair-sector.md):
+ *     H = sum_{i<j} [ Jxy_ij (X_i X_j + Y_i Y_j) + Jz_ij Z_i Z_j ] + sum_i hz_i Z_i
+ * on the rows, bits and tables of dsea_op_create_sector (dsea_sector_table_sizes / dsea_sector_build_tables; several handles
+ * of either kind may share one set).  The pairs are implicit, P = L (L - 1) / 2 of them in lexicographic order (0,1), (0,2),
+ * ..., (0,L-1), (1,2), ...: p(i, j) = i (2 L - i - 1) / 2 + (j - i - 1); no bond list and no 128-bond cap.  couplings_dev: fp64
+ * [2 P + L] on the device in the order Jxy(P), Jz(P), hz(L); READ THROUGH THE POINTER ON EVERY LAUNCH (in-place updates are
+ * seen).  Checked on the host before any device work (DSEA_ERR_ARG): the limits of dsea_sector_table_sizes, non-null
+ * pointers.  Nothing is launched or allocated at creation.  DSEA_TUNE_TFIM_TILE_LOG2 as for dsea_op_create_sector.  No fused
+ * Lanczos tail, no persistent forms, no row-partitioned slabs. */
+int dsea_op_create_pairsector(int L, int ndown, const double *couplings_dev, const int64_t *states, const int32_t *lo_rank,
+                              const int32_t *hi_base, dsea_op_t *out);
+/* The parameter adjoint of dsea_op_create_pairsector: out[t] = v1^T (dH/dp_t) v2 for all 2 P + L couplings in the order of
+ * couplings_dev.  With v1 = v2 = psi these are the two-point correlation matrices <X_i X_j + Y_i Y_j>, <Z_i Z_j> and <Z_i> of
+ * psi.  The xy forms come from one pass of gathers, the zz and z forms from a Gram product over the rows on the fp64 matrix
+ * cores; partials in `scratch`, then fixed-order reductions: no atomics, repeated calls return identical bits.  `scratch`:
+ * caller-owned, dsea_op_pairsector_forms_scratch_doubles(L, ndown) = P min(4096, ceil(n / 256)) + 4 (P + L) min(256,
+ * ceil(n / 256)) doubles (enough for every grid cap); the library allocates nothing.  DSEA_ERR_ARG for any other operator
+ * kind. */
+int dsea_op_pairsector_forms_scratch_doubles(int L, int ndown, int64_t *out);
+int dsea_op_pairsector_forms(dsea_op_t op, const double *v1, const double *v2, double *out, double *scratch, void *stream);
+
 /* THE HUBBARD MODEL of spinful fermions on a caller-given bond list at fixed particle numbers (nup, ndn), matrix-free
  * (docs/design/19-hubbard.md): the sites and bonds of dsea_op_create_lattice,
  *     H = sum_t [ -t_t sum_s (c+_{a s} c_{b s} + h.c.) + V_t n_a n_b ] + sum_i U_i n_{i up} n_{i dn} + sum_i eps_i n_i
