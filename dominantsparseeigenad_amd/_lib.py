@@ -95,6 +95,11 @@ _SIGNATURES = {
                                          POINTER(c_int32), c_int64, c_void_p, c_void_p, c_void_p, POINTER(c_void_p)]),
     "dsea_op_symsector_forms_scratch_doubles": (c_int, [c_int64, c_int, c_int, POINTER(c_int64)]),
     "dsea_op_symsector_forms": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dsea_symsector_classify_flip": (c_int, [c_int, c_int, c_int, POINTER(c_int32), POINTER(c_int32), c_void_p, c_int64, c_int64,
+                                             c_void_p, c_void_p]),
+    "dsea_op_create_symsector_flip": (c_int, [c_int, c_int, c_int, POINTER(c_int32), c_void_p, c_int, POINTER(c_int32),
+                                              POINTER(c_int32), POINTER(c_int32), POINTER(c_int32), c_int64, c_void_p, c_void_p,
+                                              c_void_p, POINTER(c_void_p)]),
     "dsea_rdm_sizes": (c_int, [c_int, c_int, c_int, POINTER(c_int32), POINTER(c_int64), POINTER(c_int), POINTER(c_int64),
                                POINTER(c_int64)]),
     "dsea_rdm_build_index_sector": (c_int, [c_int, c_int, c_int, POINTER(c_int32), c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -695,6 +695,34 @@ int dsea_symsector_classify(int L, int ndown, int ng, const int32_t* chars_host,
   return check_launch();
 }
 
+// bit g of flip = flips_host[g]; false unless every entry is 0 or 1 and a set flip comes with 2 ndown = L
+static bool symsector_flips(int L, int ndown, int ng, const int32_t* flips_host, uint32_t flip[4]) {
+  flip[0] = flip[1] = flip[2] = flip[3] = 0;
+  for (int g = 0; g < ng; ++g) {
+    if (flips_host[g] != 0 && flips_host[g] != 1) return false;
+    if (flips_host[g] == 1) {
+      if (2 * ndown != L) return false;
+      flip[g >> 5] |= 1u << (g & 31);
+    }
+  }
+  return true;
+}
+
+int dsea_symsector_classify_flip(int L, int ndown, int ng, const int32_t* chars_host, const int32_t* flips_host,
+                                 const int64_t* perm_tab, int64_t first, int64_t count, int64_t* slab, void* stream) {
+  int64_t n_sector, n_bucket, n_perm;
+  uint64_t neg[2];
+  uint32_t flip[4];
+  REQUIRE(chars_host && flips_host && perm_tab && slab && symsector_sizes(L, ndown, ng, &n_sector, &n_bucket, &n_perm),
+          DSEA_ERR_ARG);
+  REQUIRE(first >= 0 && count >= 1 && first <= n_sector - count && symsector_chars(ng, chars_host, neg) &&
+              symsector_flips(L, ndown, ng, flips_host, flip),
+          DSEA_ERR_ARG);
+  launch_symsector_classify_flip(L, ndown, ng, neg, flip, reinterpret_cast<const uint64_t*>(perm_tab), first, count,
+                                 reinterpret_cast<uint64_t*>(slab), static_cast<hipStream_t>(stream));
+  return check_launch();
+}
+
 int dsea_symsector_fill_buckets(int L, int64_t n_rep, const int64_t* reps, int32_t* bucket, void* stream) {
   REQUIRE(reps && bucket && L >= 2 && L <= DSEA_SECTOR_MAX_L && n_rep >= 1 && n_rep <= 0x7FFFFFFFll, DSEA_ERR_ARG);
   launch_symsector_fill_buckets(L, n_rep, reinterpret_cast<const uint64_t*>(reps), reinterpret_cast<uint32_t*>(bucket),
@@ -739,6 +767,26 @@ int dsea_op_create_symsector(int L, int ndown, int nb, const int32_t* bonds_host
   }
   for (int c = 0; c < 2 * nb + L; ++c) d.orb[c] = (uint16_t)orbits_host[c];
   *out = op;
+  return DSEA_OK;
+}
+
+int dsea_op_create_symsector_flip(int L, int ndown, int nb, const int32_t* bonds_host, const double* couplings_dev, int ng,
+                                  const int32_t* chars_host, const int32_t* flips_host, const int32_t* site_signs_host,
+                                  const int32_t* orbits_host, int64_t n_rep, const int64_t* reps, const int32_t* bucket,
+                                  const int64_t* perm_tab, dsea_op_t* out) {
+  int64_t n_sector, n_bucket, n_perm;
+  uint32_t flip[4];
+  REQUIRE(out && flips_host && site_signs_host && symsector_sizes(L, ndown, ng, &n_sector, &n_bucket, &n_perm) &&
+              symsector_flips(L, ndown, ng, flips_host, flip),
+          DSEA_ERR_ARG);
+  for (int i = 0; i < L; ++i) REQUIRE(site_signs_host[i] >= -1 && site_signs_host[i] <= 1, DSEA_ERR_ARG);
+  const int rc = dsea_op_create_symsector(L, ndown, nb, bonds_host, couplings_dev, ng, chars_host, orbits_host, n_rep, reps, bucket,
+                                          perm_tab, out);
+  if (rc != DSEA_OK) return rc;
+  SymSectorDesc& d = (*out)->d.symsector;
+  d.has_flip = 1;
+  for (int w = 0; w < 4; ++w) d.flip[w] = flip[w];
+  for (int i = 0; i < L; ++i) d.eps[i] = (int8_t)site_signs_host[i];
   return DSEA_OK;
 }
 

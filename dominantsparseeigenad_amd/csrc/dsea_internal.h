@@ -160,6 +160,11 @@ struct SymSectorDesc {
   uint64_t neg[2];
   uint8_t a[DSEA_LATTICE_MAX_BONDS], b[DSEA_LATTICE_MAX_BONDS];
   uint16_t orb[2 * DSEA_LATTICE_MAX_BONDS + DSEA_SECTOR_MAX_L];
+  // spin inversion (dsea_op_create_symsector_flip; all zero otherwise): bit g of flip set when g also flips every spin, eps[i] the
+  // sign of site i in the signed orbit mean of hz; has_flip selects the *_flip kernels
+  int has_flip;
+  uint32_t flip[4];
+  int8_t eps[DSEA_SECTOR_MAX_L];
 };
 // XXZ spins with a coupling on every pair of sites in the sector of ndown set bits (dsea_pairsector.hip): the pairs are
 // implicit (lexicographic, i < j); c = [Jxy(P), Jz(P), hz(L)], P = L (L - 1) / 2, on the device -- read through the pointer on
@@ -493,6 +498,8 @@ bool symsector_sizes(int L, int ndown, int ng, int64_t* n_sector, int64_t* n_buc
 int launch_symsector_fill_perm(int L, int ng, const int32_t* perms_host, uint64_t* perm_tab, hipStream_t st);
 int launch_symsector_classify(int L, int ndown, int ng, const uint64_t neg[2], const uint64_t* perm_tab, int64_t first,
                               int64_t count, uint64_t* slab, hipStream_t st);
+int launch_symsector_classify_flip(int L, int ndown, int ng, const uint64_t neg[2], const uint32_t flip[4], const uint64_t* perm_tab,
+                                   int64_t first, int64_t count, uint64_t* slab, hipStream_t st);
 int launch_symsector_fill_buckets(int L, int64_t n_rep, const uint64_t* reps, uint32_t* bucket, hipStream_t st);
 int launch_spmv_symsector(const OpDesc& op, const double* x, double* y, const double* shift, const double* skip, double* P,
                           hipStream_t st, EventPair* ev);

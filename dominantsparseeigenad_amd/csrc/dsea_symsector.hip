@@ -15,6 +15,10 @@
 // perm_tab (the image of every byte slice under every g), the hops only XOR the image of the bond mask onto them.
 // j is found by a bounded binary search of reps inside [bucket[h], bucket[h + 1]), h = rep >> Llo, Llo = (L + 1) / 2.
 // A row belongs to a team of 16 lanes; lane l owns the group elements l, l + 16, ...
+// Spin inversion (docs/design/23-spin-inversion.md): an element may also flip every spin, g(s) = perm_g(s) ^ (2^L - 1); the flip
+// cancels in g(s ^ m) = g(s) ^ perm_g(m), so only the row's own images and the mean of hz (signed) change.  The bodies of the
+// classification, the mat-vec and the forms are written once with a compile-time FLIP flag: the kernels named above instantiate
+// them without it, k_symsector_classify_flip / k_spmv_symsector_flip / k_symsector_forms_flip (+ k_symsector_forms_reduce_flip) with.
 // Nothing here is shared with dsea_sector.hip: the file has its own helpers.
 
 #include <hip/hip_runtime.h>
@@ -47,6 +51,16 @@ struct SymOrbits {
 struct SymPerm {
   uint8_t p[DSEA_SECTOR_MAX_L];
 };
+// Spin inversion (docs/design/23-spin-inversion.md): bit g of flip set when g(s) = perm_g(s) ^ full, full = 2^L - 1; eps[i] in
+// {+1, -1, 0}, the sign of site i in the signed orbit mean of hz.  Only the *_flip kernels take it.
+struct SymFlip {
+  uint32_t flip[4];
+  uint64_t full;
+  int8_t eps[DSEA_SECTOR_MAX_L];
+};
+__device__ __forceinline__ uint64_t sym_flip_mask(const SymFlip& f, int g) {
+  return ((f.flip[g >> 5] >> (g & 31)) & 1u) ? f.full : 0ull;
+}
 
 __device__ __forceinline__ double sym_signed(double v, uint64_t bit) {
   return __longlong_as_double(__double_as_longlong(v) ^ (long long)(bit << 63));
@@ -84,9 +98,11 @@ __global__ __launch_bounds__(256) void k_symsector_fill_perm(SymPerm pm, int L, 
 #define DSEA_SYM_PASCAL (DSEA_SECTOR_MAX_L + 1)
 // slab[i] = s | sigma << 48 for row first + i of the full sector when its state s is the smallest of its orbit and sigma != 0,
 // and 0 otherwise.  The state is unranked in the kernel (the combinatorial number system, as k_sector_fill_states).
-__global__ __launch_bounds__(256) void k_symsector_classify(int L, int ndown, int ng, int nsl, uint64_t neg0, uint64_t neg1,
-                                                            const uint64_t* __restrict__ perm_tab, int64_t first, int64_t count,
-                                                            uint64_t* __restrict__ slab) {
+// (FLIP: the images of flipped elements are XORed with the full mask)
+template <bool FLIP>
+__device__ __forceinline__ void sym_classify(const SymFlip& fl, int L, int ndown, int ng, int nsl, uint64_t neg0, uint64_t neg1,
+                                             const uint64_t* __restrict__ perm_tab, int64_t first, int64_t count,
+                                             uint64_t* __restrict__ slab) {
   __shared__ uint64_t C[DSEA_SYM_PASCAL][DSEA_SYM_PASCAL];
   for (int c = threadIdx.x; c < DSEA_SYM_PASCAL * DSEA_SYM_PASCAL; c += 256) (&C[0][0])[c] = 0;
   __syncthreads();
@@ -109,13 +125,24 @@ __global__ __launch_bounds__(256) void k_symsector_classify(int L, int ndown, in
     bool smallest = true;
     int sigma = 0;
     for (int g = 0; g < ng && smallest; ++g) {
-      const uint64_t im = sym_image(perm_tab + (int64_t)g * nsl * 256, nsl, s);
+      uint64_t im = sym_image(perm_tab + (int64_t)g * nsl * 256, nsl, s);
+      if (FLIP) im ^= sym_flip_mask(fl, g);
       const uint64_t ngb = ((g < 64 ? neg0 >> g : neg1 >> (g - 64)) & 1ull);
       if (im < s) smallest = false;
       if (im == s) sigma += ngb ? -1 : 1;
     }
     slab[i] = (smallest && sigma > 0) ? (s | ((uint64_t)sigma << 48)) : 0ull;
   }
+}
+__global__ __launch_bounds__(256) void k_symsector_classify(int L, int ndown, int ng, int nsl, uint64_t neg0, uint64_t neg1,
+                                                            const uint64_t* __restrict__ perm_tab, int64_t first, int64_t count,
+                                                            uint64_t* __restrict__ slab) {
+  sym_classify<false>(SymFlip(), L, ndown, ng, nsl, neg0, neg1, perm_tab, first, count, slab);
+}
+__global__ __launch_bounds__(256) void k_symsector_classify_flip(SymFlip fl, int L, int ndown, int ng, int nsl, uint64_t neg0,
+                                                                 uint64_t neg1, const uint64_t* __restrict__ perm_tab,
+                                                                 int64_t first, int64_t count, uint64_t* __restrict__ slab) {
+  sym_classify<true>(fl, L, ndown, ng, nsl, neg0, neg1, perm_tab, first, count, slab);
 }
 
 // bucket[h], 0 <= h <= 2^Lhi: the first row whose state >> Llo is >= h (lower bound in the sorted reps)
@@ -155,9 +182,9 @@ __device__ __forceinline__ void sym_stage_group(const SymSectorParams& p, int ng
 
 // The images of the row's state under the lane's NGL group elements (all ones for a slot past ng: its keys never win), and the
 // lane's character bits.
-template <int NGL>
-__device__ __forceinline__ void sym_images(const SymSectorParams& p, uint64_t st, int lane16, uint64_t (&img)[NGL],
-                                           uint64_t (&ngb)[NGL]) {
+template <int NGL, bool FLIP>
+__device__ __forceinline__ void sym_images(const SymSectorParams& p, const SymFlip& fl, uint64_t st, int lane16,
+                                           uint64_t (&img)[NGL], uint64_t (&ngb)[NGL]) {
 #pragma unroll
   for (int k = 0; k < NGL; ++k) {
     const int g = lane16 + DSEA_SYM_TEAM * k;
@@ -165,6 +192,7 @@ __device__ __forceinline__ void sym_images(const SymSectorParams& p, uint64_t st
     ngb[k] = 0;
     if (g < p.ng) {
       img[k] = sym_image(p.perm_tab + (int64_t)g * p.nsl * 256, p.nsl, st);
+      if (FLIP) img[k] ^= sym_flip_mask(fl, g);     // (< 2^L: a padding slot's all-ones image still never wins)
       ngb[k] = (g < 64 ? p.neg[0] >> g : p.neg[1] >> (g - 64)) & 1ull;
     }
   }
@@ -250,10 +278,13 @@ __device__ __forceinline__ double sym_team_sum(double v) {
 // y = H x - shift x ; partial x.y per block.  256 threads = 16 teams = 16 rows per range; a block walks the ranges blockIdx.x,
 // + gridDim.x, ...  Every block first averages the couplings over their orbits (ascending index order) into LDS.  A team past
 // the last row reads row n - 1 and writes nothing.  NGL = group elements per lane (|G| <= 16 NGL).
-template <int NGL>
-__global__ __launch_bounds__(256) void k_spmv_symsector(SymSectorParams p, const double* __restrict__ x, double* __restrict__ y,
-                                                        const double* __restrict__ shift, const double* __restrict__ skip,
-                                                        double* __restrict__ P) {
+// FLIP (k_spmv_symsector_flip): the row's images carry the flips and the mean of hz is the signed one, eps_i times the mean of
+// eps_j hz_j over the site orbit (0 on an orbit with eps = 0).  Each instantiation is inlined into exactly one kernel, which so
+// owns the LDS arrays declared here.
+template <int NGL, bool FLIP>
+__device__ __forceinline__ void sym_spmv(const SymSectorParams& p, const SymFlip& fl, const double* __restrict__ x,
+                                         double* __restrict__ y, const double* __restrict__ shift,
+                                         const double* __restrict__ skip, double* __restrict__ P) {
   __shared__ double raw[DSEA_SYM_MAX_PARAMS];
   __shared__ double cp[DSEA_SYM_MAX_PARAMS];
   __shared__ uint16_t orb[DSEA_SYM_MAX_PARAMS];
@@ -273,6 +304,15 @@ __global__ __launch_bounds__(256) void k_spmv_symsector(SymSectorParams p, const
     int f0, f1, cnt = 0;
     sym_family(c, nb, L, &f0, &f1);
     double sum = 0.0;
+    if (FLIP && c >= 2 * nb) {
+      for (int m = f0; m < f1; ++m)
+        if (orb[m] == orb[c]) {
+          sum += (double)fl.eps[m - 2 * nb] * raw[m];
+          ++cnt;
+        }
+      cp[c] = (double)fl.eps[c - 2 * nb] * (sum / (double)cnt);
+      continue;
+    }
     for (int m = f0; m < f1; ++m)
       if (orb[m] == orb[c]) {
         sum += raw[m];
@@ -295,7 +335,7 @@ __global__ __launch_bounds__(256) void k_spmv_symsector(SymSectorParams p, const
     const double sr = (double)(entry >> 48);
     const double xr = x[have ? r : n - 1];
     uint64_t img[NGL], ngb[NGL];
-    sym_images<NGL>(p, st, lane16, img, ngb);
+    sym_images<NGL, FLIP>(p, fl, st, lane16, img, ngb);
     double diag = 0.0, sum = 0.0;
     for (int k0 = 0; k0 < nb; k0 += DSEA_SYM_TEAM) {
       uint32_t j = 0;
@@ -319,15 +359,26 @@ __global__ __launch_bounds__(256) void k_spmv_symsector(SymSectorParams p, const
     if (threadIdx.x == 0) P[blockIdx.x] = tot;
   }
 }
+template <int NGL>
+__global__ __launch_bounds__(256) void k_spmv_symsector(SymSectorParams p, const double* __restrict__ x, double* __restrict__ y,
+                                                        const double* __restrict__ shift, const double* __restrict__ skip,
+                                                        double* __restrict__ P) {
+  sym_spmv<NGL, false>(p, SymFlip(), x, y, shift, skip, P);
+}
+template <int NGL>
+__global__ __launch_bounds__(256) void k_spmv_symsector_flip(SymSectorParams p, SymFlip fl, const double* __restrict__ x,
+                                                             double* __restrict__ y, const double* __restrict__ shift,
+                                                             const double* __restrict__ skip, double* __restrict__ P) {
+  sym_spmv<NGL, true>(p, fl, x, y, shift, skip, P);
+}
 
 // The raw forms: raw[t] = v1^T A_t v2 with A_t the coefficient matrix of pbar_t in the row formula,
 //   Jxy_t: sum_{r : hop} 2 chi sqrt(sigma_j / sigma_r) v1[r] v2[j]     Jz_t: sum_r zz_t v1[r] v2[r]     hz_i: sum_r z_i v1[r] v2[r]
 // Same row walk, 128 threads = 8 teams.  Every (team, term) accumulator in LDS has exactly one owning lane (bond t: lane t mod 16,
 // site i: lane i mod 16), so there are no atomics; the 8 rows are added in fixed order into scratch[t * gridDim.x + block].
-template <int NGL>
-__global__ __launch_bounds__(DSEA_SYM_FORMS_THREADS) void k_symsector_forms(SymSectorParams p, const double* __restrict__ v1,
-                                                                            const double* __restrict__ v2,
-                                                                            double* __restrict__ scratch) {
+template <int NGL, bool FLIP>
+__device__ __forceinline__ void sym_forms(const SymSectorParams& p, const SymFlip& fl, const double* __restrict__ v1,
+                                          const double* __restrict__ v2, double* __restrict__ scratch) {
   constexpr int TEAMS = DSEA_SYM_FORMS_THREADS / DSEA_SYM_TEAM;
   __shared__ double accs[TEAMS][DSEA_SYM_MAX_PARAMS];
   __shared__ uint16_t tb[DSEA_LATTICE_MAX_BONDS];
@@ -348,7 +399,7 @@ __global__ __launch_bounds__(DSEA_SYM_FORMS_THREADS) void k_symsector_forms(SymS
     const double a = have ? v1[r] : 0.0;
     const double d = a * v2[have ? r : n - 1];
     uint64_t img[NGL], ngb[NGL];
-    sym_images<NGL>(p, st, lane16, img, ngb);
+    sym_images<NGL, FLIP>(p, fl, st, lane16, img, ngb);
     for (int k0 = 0; k0 < nb; k0 += DSEA_SYM_TEAM) {
       uint32_t j = 0;
       uint64_t sj = 1, neg = 0;
@@ -366,6 +417,19 @@ __global__ __launch_bounds__(DSEA_SYM_FORMS_THREADS) void k_symsector_forms(SymS
     for (int w = 1; w < TEAMS; ++w) tot += accs[w][c];
     scratch[(int64_t)c * gridDim.x + blockIdx.x] = tot;
   }
+}
+template <int NGL>
+__global__ __launch_bounds__(DSEA_SYM_FORMS_THREADS) void k_symsector_forms(SymSectorParams p, const double* __restrict__ v1,
+                                                                            const double* __restrict__ v2,
+                                                                            double* __restrict__ scratch) {
+  sym_forms<NGL, false>(p, SymFlip(), v1, v2, scratch);
+}
+template <int NGL>
+__global__ __launch_bounds__(DSEA_SYM_FORMS_THREADS) void k_symsector_forms_flip(SymSectorParams p, SymFlip fl,
+                                                                                 const double* __restrict__ v1,
+                                                                                 const double* __restrict__ v2,
+                                                                                 double* __restrict__ scratch) {
+  sym_forms<NGL, true>(p, fl, v1, v2, scratch);
 }
 
 // second stage: out[t] = the mean over t's orbit of the raw forms (that is S): the per-block partials of every member of the
@@ -386,6 +450,30 @@ __global__ __launch_bounds__(256) void k_symsector_forms_reduce(SymOrbits o, int
     }
   if (threadIdx.x == 0) out[c] = tot / (double)cnt;
 }
+// the same with the signed sum for the hz outputs: eps_c / |orbit| times the sum of eps_m raw_m, so the members of an orbit get
+// bits that are identical up to the sign and an eps = 0 output is exactly 0.0
+__global__ __launch_bounds__(256) void k_symsector_forms_reduce_flip(SymOrbits o, SymFlip fl, int L, int nb,
+                                                                     const double* __restrict__ scratch, int count,
+                                                                     double* __restrict__ out) {
+  __shared__ double sm5[5];
+  const int c = blockIdx.x;
+  int f0, f1, cnt = 0;
+  sym_family(c, nb, L, &f0, &f1);
+  const uint16_t mine = o.orb[c];
+  const bool site = c >= 2 * nb;
+  double tot = 0.0;
+  for (int m = f0; m < f1; ++m)
+    if (o.orb[m] == mine) {
+      const double part = sum_partials_block(scratch + (int64_t)m * count, count, sm5);
+      tot += site ? (double)fl.eps[m - 2 * nb] * part : part;
+      ++cnt;
+    }
+  if (threadIdx.x == 0) {
+    const double mean = tot / (double)cnt;
+    const int e = site ? fl.eps[c - 2 * nb] : 1;
+    out[c] = e == 0 ? 0.0 : (double)e * mean;
+  }
+}
 
 // n_sector = C(L, ndown), the bucket count 2^Lhi + 1 and the words of perm_tab; false outside the limits of sector_sizes or
 // 1 <= ng <= DSEA_SYMSECTOR_MAX_GROUP (host arithmetic only)
@@ -396,6 +484,15 @@ bool symsector_sizes(int L, int ndown, int ng, int64_t* n_sector, int64_t* n_buc
   *n_bucket = n_hi + 1;
   *n_perm = (int64_t)ng * ((L + 7) / 8) * 256;
   return true;
+}
+
+// the flips and the site signs of a handle made by dsea_op_create_symsector_flip
+static SymFlip sym_flip(const SymSectorDesc& d) {
+  SymFlip fl = {};
+  for (int w = 0; w < 4; ++w) fl.flip[w] = d.flip[w];
+  fl.full = (1ull << d.L) - 1ull;
+  for (int i = 0; i < d.L; ++i) fl.eps[i] = d.eps[i];
+  return fl;
 }
 
 static inline int sym_ngl(int ng) { return ng <= 16 ? 1 : ng <= 32 ? 2 : ng <= 64 ? 4 : 8; }
@@ -458,6 +555,16 @@ int launch_symsector_classify(int L, int ndown, int ng, const uint64_t neg[2], c
   return 0;
 }
 
+int launch_symsector_classify_flip(int L, int ndown, int ng, const uint64_t neg[2], const uint32_t flip[4], const uint64_t* perm_tab,
+                                   int64_t first, int64_t count, uint64_t* slab, hipStream_t st) {
+  SymFlip fl = {};
+  for (int w = 0; w < 4; ++w) fl.flip[w] = flip[w];
+  fl.full = (1ull << L) - 1ull;
+  hipLaunchKernelGGL(k_symsector_classify_flip, dim3((unsigned)ew_blocks(count * 8)), dim3(256), 0, st, fl, L, ndown, ng,
+                     (L + 7) / 8, neg[0], neg[1], perm_tab, first, count, slab);
+  return 0;
+}
+
 int launch_symsector_fill_buckets(int L, int64_t n_rep, const uint64_t* reps, uint32_t* bucket, hipStream_t st) {
   const int Llo = (L + 1) / 2;
   const int64_t nh = (int64_t)1 << (L - Llo);
@@ -471,10 +578,13 @@ int launch_spmv_symsector(const OpDesc& op, const double* x, double* y, const do
   SymSectorParams p;
   if (!sym_params(op, &p)) return -1;
   const int nblk = sym_blocks(op, 256 / DSEA_SYM_TEAM);
+  const bool flipped = op.symsector.has_flip != 0;
+  const SymFlip fl = sym_flip(op.symsector);
   dispatch_int<1, 2, 4, 8>(sym_ngl(p.ng), [&](auto ngl) {
     constexpr int NGL = decltype(ngl)::value;
-    klaunch(ev, k_spmv_symsector<NGL>, nblk, 256, (size_t)p.nb * NGL * DSEA_SYM_TEAM * sizeof(uint16_t), st, p, x, y, shift, skip,
-            P);
+    const size_t lds = (size_t)p.nb * NGL * DSEA_SYM_TEAM * sizeof(uint16_t);
+    if (flipped) klaunch(ev, k_spmv_symsector_flip<NGL>, nblk, 256, lds, st, p, fl, x, y, shift, skip, P);
+    else klaunch(ev, k_spmv_symsector<NGL>, nblk, 256, lds, st, p, x, y, shift, skip, P);
   });
   return nblk;
 }
@@ -483,14 +593,20 @@ int launch_symsector_forms(const OpDesc& op, const double* v1, const double* v2,
   SymSectorParams p;
   if (!sym_params(op, &p)) return -1;
   const int nblk = sym_blocks(op, DSEA_SYM_FORMS_THREADS / DSEA_SYM_TEAM);
+  const bool flipped = op.symsector.has_flip != 0;
+  const SymFlip fl = sym_flip(op.symsector);
   dispatch_int<1, 2, 4, 8>(sym_ngl(p.ng), [&](auto ngl) {
     constexpr int NGL = decltype(ngl)::value;
-    klaunch(nullptr, k_symsector_forms<NGL>, nblk, DSEA_SYM_FORMS_THREADS, (size_t)p.nb * NGL * DSEA_SYM_TEAM * sizeof(uint16_t),
-            st, p, v1, v2, scratch);
+    const size_t lds = (size_t)p.nb * NGL * DSEA_SYM_TEAM * sizeof(uint16_t);
+    if (flipped) klaunch(nullptr, k_symsector_forms_flip<NGL>, nblk, DSEA_SYM_FORMS_THREADS, lds, st, p, fl, v1, v2, scratch);
+    else klaunch(nullptr, k_symsector_forms<NGL>, nblk, DSEA_SYM_FORMS_THREADS, lds, st, p, v1, v2, scratch);
   });
   SymOrbits o;
   for (int c = 0; c < DSEA_SYM_MAX_PARAMS; ++c) o.orb[c] = p.orb[c];
-  hipLaunchKernelGGL(k_symsector_forms_reduce, dim3(2 * p.nb + p.L), dim3(256), 0, st, o, p.L, p.nb, scratch, nblk, out);
+  if (flipped)
+    hipLaunchKernelGGL(k_symsector_forms_reduce_flip, dim3(2 * p.nb + p.L), dim3(256), 0, st, o, fl, p.L, p.nb, scratch, nblk, out);
+  else
+    hipLaunchKernelGGL(k_symsector_forms_reduce, dim3(2 * p.nb + p.L), dim3(256), 0, st, o, p.L, p.nb, scratch, nblk, out);
   return 0;
 }
 

@@ -1424,10 +1424,21 @@ class _RdmPull(torch.autograd.Function):
 
 
 # ------------------------------------------------------------------------------------------ XXZ spins in a lattice-symmetry sector
-def ring_symmetries(L, momentum=0, parity=None):
+def spin_inversion(L, char):
+    """the generator (identity, char, True) of the global spin flip s -> s ^ (2^L - 1) with character ``char`` = +1 / -1 (it needs
+    ndown = L / 2 and hz-free or staggered couplings to be a symmetry; docs/design/23-spin-inversion.md)"""
+    if char not in (1, -1):
+        raise ValueError("spin_inversion: char is +1 or -1")
+    return (tuple(range(int(L))), int(char), True)
+
+
+def ring_symmetries(L, momentum=0, parity=None, spin_flip=None):
     """generators of the symmetry group of an L-site ring as (perm, char) pairs: the translation i -> i + 1 with character +1
-    (momentum 0) or -1 (momentum "pi"), and with ``parity`` = +1 / -1 the reflection i -> L - 1 - i with that character"""
+    (momentum 0) or -1 (momentum "pi"), and with ``parity`` = +1 / -1 the reflection i -> L - 1 - i with that character; with
+    ``spin_flip`` = +1 / -1 also ``spin_inversion(L, spin_flip)``"""
     L = int(L)
+    if spin_flip not in (None, 1, -1):
+        raise ValueError("ring_symmetries: spin_flip is None, +1 or -1")
     if momentum not in (0, "pi"):
         raise ValueError("ring_symmetries: momentum is 0 or 'pi' (complex characters are out of scope)")
     if parity not in (None, 1, -1):
@@ -1435,40 +1446,56 @@ def ring_symmetries(L, momentum=0, parity=None):
     gens = [(tuple((i + 1) % L for i in range(L)), 1 if momentum == 0 else -1)]
     if parity is not None:
         gens.append((tuple(L - 1 - i for i in range(L)), int(parity)))
+    if spin_flip is not None:
+        gens.append(spin_inversion(L, spin_flip))
     return gens
 
 
-def torus_symmetries(Lx, Ly, kx=0, ky=0):
+def torus_symmetries(Lx, Ly, kx=0, ky=0, spin_flip=None):
     """generators of the translation group of the Lx x Ly torus of ``square_bonds`` (site = y * Lx + x): the x translation with
-    character +1 (kx = 0) or -1 (kx = "pi"), and the y translation likewise"""
+    character +1 (kx = 0) or -1 (kx = "pi"), and the y translation likewise; with ``spin_flip`` = +1 / -1 also
+    ``spin_inversion(Lx * Ly, spin_flip)``"""
     Lx, Ly = int(Lx), int(Ly)
+    if spin_flip not in (None, 1, -1):
+        raise ValueError("torus_symmetries: spin_flip is None, +1 or -1")
     if kx not in (0, "pi") or ky not in (0, "pi"):
         raise ValueError("torus_symmetries: kx and ky are 0 or 'pi' (complex characters are out of scope)")
     tx = tuple(y * Lx + (x + 1) % Lx for y in range(Ly) for x in range(Lx))
     ty = tuple(((y + 1) % Ly) * Lx + x for y in range(Ly) for x in range(Lx))
-    return [(tx, 1 if kx == 0 else -1), (ty, 1 if ky == 0 else -1)]
+    gens = [(tx, 1 if kx == 0 else -1), (ty, 1 if ky == 0 else -1)]
+    if spin_flip is not None:
+        gens.append(spin_inversion(Lx * Ly, spin_flip))
+    return gens
 
 
-def _close_group(L, generators):
-    """the group generated by ``generators`` as a list of (perm, char), the identity first, in breadth-first order; ValueError
-    for a perm that is no permutation of 0 .. L - 1, a character other than +-1 or one that is not consistent, and for more
-    than DSEA_SYMSECTOR_MAX_GROUP elements -- host arithmetic only"""
+def _close_group(L, generators, flips=False):
+    """the group generated by ``generators`` as a list of (perm, char), the identity first, in breadth-first order; with
+    ``flips`` the pair (that list, the list of the elements' flip bits).  A generator is (perm, char) or (perm, char, flip); an
+    element is a permutation together with its flip bit, composition multiplies the characters and XORs the flips.  ValueError
+    for a generator of another length, a perm that is no permutation of 0 .. L - 1, a flip other than a bool / 0 / 1, a character
+    other than +-1 or one that is not consistent, and for more than DSEA_SYMSECTOR_MAX_GROUP elements -- host arithmetic only"""
     gens = []
-    for perm, char in generators:
+    for gen in generators:
+        gen = tuple(gen)
+        if len(gen) not in (2, 3):
+            raise ValueError("a generator is (perm, char) or (perm, char, flip)")
+        perm, char, flip = gen if len(gen) == 3 else gen + (False,)
         perm = tuple(int(v) for v in perm)
         if sorted(perm) != list(range(L)):
             raise ValueError("a generator's perm must be a permutation of 0 .. %d" % (L - 1))
         if char not in (1, -1):
             raise ValueError("a generator's character must be +1 or -1 (real one-dimensional irreps only)")
-        gens.append((perm, int(char)))
-    ident = tuple(range(L))
+        if isinstance(flip, (float, str, bytes)) or not any(flip is v or flip == v for v in (False, True)):
+            raise ValueError("a generator's flip must be a bool (or 0 / 1)")
+        gens.append(((perm, bool(flip)), int(char)))
+    ident = (tuple(range(L)), False)
     chars = {ident: 1}
     order, frontier = [ident], [ident]
     while frontier:
         new = []
         for p in frontier:
             for q, d in gens:
-                r = tuple(q[p[i]] for i in range(L))            # p first, then q
+                r = (tuple(q[0][p[0][i]] for i in range(L)), p[1] != q[1])            # p first, then q
                 e = chars[p] * d
                 if r not in chars:
                     if len(order) >= _lib.SYMSECTOR_MAX_GROUP:
@@ -1479,7 +1506,28 @@ def _close_group(L, generators):
                 elif chars[r] != e:
                     raise ValueError("the character is not consistent: one group element is reached with both signs")
         frontier = new
-    return [(p, chars[p]) for p in order]
+    group = [(p[0], chars[p]) for p in order]
+    return (group, [p[1] for p in order]) if flips else group
+
+
+def _check_flips(L, ndown, flips):
+    """ValueError when an element flips the spins outside the sector that the flip maps onto itself"""
+    if any(flips) and 2 * ndown != L:
+        raise ValueError("a group element with a spin flip needs ndown = L / 2 (got L = %d, ndown = %d)" % (L, ndown))
+
+
+def _site_signs(L, group, flips):
+    """eps_i in {+1, -1, 0} of the signed orbit mean of hz: 0 on a site orbit one of whose sites is fixed by a flipped element,
+    otherwise +1 on the orbit's lowest site i0 and sgn(g) = -1 (flipped) / +1 on perm_g[i0] (path independent: two elements that
+    carry i0 to the same site with different flips would compose to a flipped element fixing i0)"""
+    low = [min(perm[i] for perm, _ in group) for i in range(L)]
+    dead = {low[i] for (perm, _), flip in zip(group, flips) if flip for i in range(L) if perm[i] == i}
+    eps = [0] * L
+    for i0 in range(L):
+        if low[i0] == i0 and i0 not in dead:
+            for (perm, _), flip in zip(group, flips):
+                eps[perm[i0]] = -1 if flip else 1
+    return eps
 
 
 def _orbit_ids(L, bonds, group):
@@ -1525,10 +1573,12 @@ def symmetry_sector_dim(L, ndown, generators):
     """the number of rows of ``SpinSymmetrySectorOperator``: the orbits of the sector under the generated group whose
     sigma = sum over the stabiliser of chi is not 0 (pure Python, for small L)"""
     L, ndown = int(L), int(ndown)
-    group = _close_group(L, generators)
+    group, flips = _close_group(L, generators, flips=True)
+    _check_flips(L, ndown, flips)
+    full = (1 << L) - 1
     count = 0
     for s in sector_states(L, ndown):
-        images = [_apply_perm(perm, s) for perm, _ in group]
+        images = [_apply_perm(perm, s) ^ (full if flip else 0) for (perm, _), flip in zip(group, flips)]
         if min(images) == s and sum(c for (_, c), im in zip(group, images) if im == s) != 0:
             count += 1
     return count
@@ -1546,9 +1596,17 @@ def _symsector_view(op, couplings, like=None):
     orbits = (c_int32 * op.nparam)(*op.orbits)
     reps, bucket, perm_tab = op._tables
     raw = c_void_p()
-    check(_lib.load().dsea_op_create_symsector(op.N, op.ndown, len(bonds), flat, c_void_p(data.data_ptr()), op.ng, chars, orbits,
-                                               op.n, c_void_p(reps.data_ptr()), c_void_p(bucket.data_ptr()),
-                                               c_void_p(perm_tab.data_ptr()), byref(raw)), "dsea_op_create_symsector")
+    if any(op.flips):
+        flips = (c_int32 * op.ng)(*[int(f) for f in op.flips])
+        signs = (c_int32 * op.N)(*op.site_signs)
+        check(_lib.load().dsea_op_create_symsector_flip(op.N, op.ndown, len(bonds), flat, c_void_p(data.data_ptr()), op.ng, chars,
+                                                        flips, signs, orbits, op.n, c_void_p(reps.data_ptr()),
+                                                        c_void_p(bucket.data_ptr()), c_void_p(perm_tab.data_ptr()), byref(raw)),
+              "dsea_op_create_symsector_flip")
+    else:
+        check(_lib.load().dsea_op_create_symsector(op.N, op.ndown, len(bonds), flat, c_void_p(data.data_ptr()), op.ng, chars,
+                                                   orbits, op.n, c_void_p(reps.data_ptr()), c_void_p(bucket.data_ptr()),
+                                                   c_void_p(perm_tab.data_ptr()), byref(raw)), "dsea_op_create_symsector")
     view = _NativeView(_Handle(raw, op.n, (data, op._tables)))
     view.grid_log2 = None
     if like is not None and like.grid_log2 is not None:
@@ -1582,7 +1640,12 @@ class SpinSymmetrySectorOperator:
     |r> = (|G| sigma_r)^(-1/2) sum_g chi(g) |g s_r>, for any couplings: they enter through their orbit means (``symmetrise``).
     ``H(v)`` is differentiable in v and in ``couplings``; ``Hadjoint_to_couplingsadjoint(v1, v2)`` returns all 2 nb + L entries in
     one pass; both are re-entrant (second order works).  The couplings are read through the tensor's pointer on every launch;
-    binding another tensor makes a new handle on the same tables."""
+    binding another tensor makes a new handle on the same tables.
+
+    Spin inversion (docs/design/23-spin-inversion.md): a generator may also be (perm, char, flip); with ``flip`` the element acts
+    as g(s) = perm(s) ^ (2^L - 1) (``spin_inversion``, or ``spin_flip=`` of the builders).  It needs ndown = L / 2 (ValueError
+    otherwise).  ``flips`` holds the flip bit of every element of ``group``; hz then enters through the signed orbit mean with the
+    signs ``site_signs``.  Without a flipped generator the operator is exactly the one above."""
 
     _native_methods = ("H", "__call__")
     SLAB_ROWS = 1 << 26
@@ -1592,9 +1655,13 @@ class SpinSymmetrySectorOperator:
         self._bonds = _check_bonds(self.N, bonds)
         self.nb = len(self._bonds)
         self.nparam = 2 * self.nb + self.N
-        self._group = tuple(_close_group(self.N, generators))
+        group, flips = _close_group(self.N, generators, flips=True)
+        _check_flips(self.N, self.ndown, flips)
+        self._group, self._flips = tuple(group), tuple(flips)
         self.ng = len(self._group)
         self._orbits = tuple(_orbit_ids(self.N, self._bonds, self._group))
+        self._site_signs = tuple(_site_signs(self.N, self._group, self._flips))
+        self._has_flip = any(self._flips)
         if device is None:
             device = couplings.device if torch.is_tensor(couplings) else "cuda"
         self.device = torch.device(device)
@@ -1616,8 +1683,14 @@ class SpinSymmetrySectorOperator:
             for first in range(0, self.n_sector, self.SLAB_ROWS):
                 count = min(self.SLAB_ROWS, self.n_sector - first)
                 slab = torch.empty(count, dtype=torch.int64, device=self.device)
-                check(lib.dsea_symsector_classify(self.N, self.ndown, self.ng, chars, c_void_p(perm_tab.data_ptr()), first, count,
-                                                  c_void_p(slab.data_ptr()), stream), "dsea_symsector_classify")
+                if self._has_flip:
+                    flipbits = (c_int32 * self.ng)(*[int(f) for f in self._flips])
+                    check(lib.dsea_symsector_classify_flip(self.N, self.ndown, self.ng, chars, flipbits,
+                                                           c_void_p(perm_tab.data_ptr()), first, count, c_void_p(slab.data_ptr()),
+                                                           stream), "dsea_symsector_classify_flip")
+                else:
+                    check(lib.dsea_symsector_classify(self.N, self.ndown, self.ng, chars, c_void_p(perm_tab.data_ptr()), first,
+                                                      count, c_void_p(slab.data_ptr()), stream), "dsea_symsector_classify")
                 kept.append(slab[slab != 0])
             reps = torch.cat(kept).contiguous()
             del kept
@@ -1632,6 +1705,10 @@ class SpinSymmetrySectorOperator:
         self._norms = reps >> 48
         self._orbit_index = torch.tensor(self._orbits, dtype=torch.int64, device=self.device)
         self._chars = torch.tensor([c for _, c in self._group], dtype=F64, device=self.device)
+        full = (1 << self.N) - 1
+        self._flip_masks = torch.tensor([full if f else 0 for f in self._flips], dtype=torch.int64, device=self.device)
+        self._param_signs = torch.tensor([1.0] * (2 * self.nb) + [float(e) for e in self._site_signs], dtype=F64,
+                                         device=self.device)
         self._sector_tables = None
         self._c = None
         self._H = None
@@ -1647,6 +1724,17 @@ class SpinSymmetrySectorOperator:
     def group(self):
         """the closed group as a tuple of (perm, char), the identity first"""
         return self._group
+
+    @property
+    def flips(self):
+        """flips[g]: whether element g of ``group`` also flips every spin (a tuple of bools)"""
+        return self._flips
+
+    @property
+    def site_signs(self):
+        """eps_i in {+1, -1, 0}: the signed orbit mean of hz is eps_i times the mean of eps_j hz_j over the orbit of site i (all +1
+        without a flipped element)"""
+        return self._site_signs
 
     @property
     def orbits(self):
@@ -1703,7 +1791,15 @@ class SpinSymmetrySectorOperator:
         return _SymSectorForms.apply(v1, v2, self, self._H)
 
     def symmetrise(self, p):
-        """S p: every coupling replaced by the mean over its orbit (torch, differentiable)"""
+        """S p: every coupling replaced by the mean over its orbit, for hz under flipped elements the signed mean
+        eps_i mean(eps_j hz_j) (torch, differentiable)"""
+        if self._has_flip:
+            sign = self._param_signs.to(device=p.device, dtype=p.dtype)
+            idx = self._orbit_index.to(p.device)
+            size = int(idx.max()) + 1
+            sums = torch.zeros(size, dtype=p.dtype, device=p.device).index_add(0, idx, sign * p)
+            counts = torch.zeros(size, dtype=p.dtype, device=p.device).index_add(0, idx, torch.ones_like(p))
+            return sign * (sums / counts)[idx]
         idx = self._orbit_index.to(p.device)
         size = int(idx.max()) + 1
         sums = torch.zeros(size, dtype=p.dtype, device=p.device).index_add(0, idx, p)
@@ -1717,11 +1813,13 @@ class SpinSymmetrySectorOperator:
         return torch.where(self._states[pos] == s, pos, torch.full_like(pos, -1))
 
     def _images(self, s):
-        """g(s) for every group element: an (|G|, len(s)) int64 tensor, from perm_tab by torch indexing"""
+        """g(s) for every group element: an (|G|, len(s)) int64 tensor, from perm_tab by torch indexing (and the flips)"""
         tab = self._tables[2].view(self.ng, self.nsl, 256)
         out = torch.zeros((self.ng, s.numel()), dtype=torch.int64, device=self.device)
         for sl in range(self.nsl):
             out |= tab[:, sl, :][:, (s >> (8 * sl)) & 255]
+        if self._has_flip:
+            out ^= self._flip_masks[:, None]
         return out
 
     def expand(self, v):

@@ -314,6 +314,23 @@ int dsea_op_create_symsector(int L, int ndown, int nb, const int32_t *bonds_host
  * (2 nb + L) * min(4096, ceil(n_rep / 8)) doubles (enough for every grid cap).  DSEA_ERR_ARG for any other operator kind. */
 int dsea_op_symsector_forms_scratch_doubles(int64_t n_rep, int L, int nb, int64_t *out);
 int dsea_op_symsector_forms(dsea_op_t op, const double *v1, const double *v2, double *out, double *scratch, void *stream);
+/* Spin inversion: a group element may also flip every spin, g(s) = perm_g(s) ^ (flip_g ? 2^L - 1 : 0); composition multiplies
+ * the characters and XORs the flips.  rep, sigma, the row order, |r> and the dropped hops are defined as above with this g.
+ * flips_host: int32 [ng], 0 or 1.  perm_tab keeps its meaning (the permutation alone); dsea_symsector_sizes, _fill_perm and
+ * _fill_buckets serve both kinds.  Jxy and Jz enter through their orbit means as before; hz through the SIGNED mean
+ *     hzbar_i = eps_i * mean_{j in the site orbit of i} (eps_j hz_j)
+ * site_signs_host: int32 [L], eps_i in {+1, -1, 0}: 0 on an orbit one of whose sites is fixed by a flipped element, otherwise
+ * the relative sign sgn(g) = -1 (flipped) / +1 of the elements that carry the orbit's first site to i.
+ * dsea_symsector_classify_flip: as dsea_symsector_classify with the flipped images.
+ * dsea_op_create_symsector_flip: as dsea_op_create_symsector; dsea_op_symsector_forms works on its handles (the hz outputs of an
+ * orbit are then identical up to the sign bit for bit, and exactly 0.0 where eps = 0).  Further host checks (DSEA_ERR_ARG, before
+ * any device work): flips of 0 or 1, a set flip only with 2 ndown = L, signs in {-1, 0, +1}. */
+int dsea_symsector_classify_flip(int L, int ndown, int ng, const int32_t *chars_host, const int32_t *flips_host,
+                                 const int64_t *perm_tab, int64_t first, int64_t count, int64_t *slab, void *stream);
+int dsea_op_create_symsector_flip(int L, int ndown, int nb, const int32_t *bonds_host, const double *couplings_dev, int ng,
+                                  const int32_t *chars_host, const int32_t *flips_host, const int32_t *site_signs_host,
+                                  const int32_t *orbits_host, int64_t n_rep, const int64_t *reps, const int32_t *bucket,
+                                  const int64_t *perm_tab, dsea_op_t *out);
 
 /* CSR, caller-owned device arrays: rowptr int64 [n+1], colidx int32 [nnz], vals fp64 [nnz]. */
 int dsea_op_create_csr(int64_t n, int64_t nnz, const int64_t *rowptr, const int32_t *colidx,
