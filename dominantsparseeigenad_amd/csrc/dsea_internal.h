@@ -540,6 +540,19 @@ int launch_rdm_cross(const RdmGeom& g, const int32_t* idx, const double* x, cons
                      int tile, hipStream_t st);
 int launch_rdm_pull(const RdmGeom& g, const int32_t* idx, const double* G, const double* y, double* out, int transpose,
                     hipStream_t st);
+// dsea_ladder.hip (linear maps between two magnetisation sectors, docs/design/24-dynamics.md): sigma^-(c) (step +1), Z(c)
+// (step 0) and sigma^+(c) (step -1) from the sector (L, ndown_src) to (L, ndown_src + step) as gathers over the destination
+// rows, on the state table of the destination and the two rank tables of the source; the L site forms v1^T (dS/dc_i) v2 into
+// out through per-block partials in the caller's scratch (ladder_forms_scratch_doubles doubles).  ladder_sizes is false, and
+// the launchers return -1, for a step outside -1 .. 1, a sector outside the limits of sector_sizes, a grid_log2 other than 0
+// (= 12) or 6 .. 12, or a null table.
+bool ladder_sizes(int L, int ndown_src, int step, int64_t* n_src, int64_t* n_dst);
+int64_t ladder_forms_scratch_doubles(int64_t n_dst, int L);
+int launch_sector_ladder(int L, int ndown_src, int step, const double* c, const uint64_t* states_dst, const uint32_t* lo_rank_src,
+                         const uint32_t* hi_base_src, const double* x, double* y, int grid_log2, hipStream_t st);
+int launch_sector_ladder_forms(int L, int ndown_src, int step, const uint64_t* states_dst, const uint32_t* lo_rank_src,
+                               const uint32_t* hi_base_src, const double* v1, const double* v2, double* out, double* scratch,
+                               int grid_log2, hipStream_t st);
 // dsea_cg_persist_tfim_big.hip
 bool cg_persist_tfim_big_applicable(const OpDesc& op);
 size_t cg_persist_tfim_big_comm_bytes(int64_t n);

@@ -797,6 +797,11 @@ class SpinSectorOperator:
         """the ``Bipartition`` of this sector into the sites ``sites`` and the rest, on the operator's rank tables"""
         return Bipartition(self.N, sites, ndown=self.ndown, device=self.device, _tables=self._tables[1:])
 
+    def ladder(self, dst):
+        """the ``SpinSectorLadder`` from this sector to the sector of ``dst`` (ndown + 1, ndown or ndown - 1; ``dst`` may be
+        this operator), on the two operators' tables"""
+        return SpinSectorLadder(self, dst)
+
     def pair_operator(self, couplings=None):
         """the ``SpinSectorPairOperator`` of this sector on the operator's tables; ``couplings=None``: zeros, the correlator
         of a state of this (or any other) Hamiltonian of the sector"""
@@ -1099,6 +1104,11 @@ class SpinSectorPairOperator:
             out.append(upper + upper.t() + weight * eye)      # (x + 0 and 0 + x: the two triangles carry the same bits)
         return out[0], out[1], z
 
+    def ladder(self, dst):
+        """the ``SpinSectorLadder`` from this sector to the sector of ``dst`` (ndown + 1, ndown or ndown - 1; ``dst`` may be
+        this operator), on the two operators' tables"""
+        return SpinSectorLadder(self, dst)
+
     def rank(self, s):
         """the row of every state in the int64 device tensor ``s`` (states of the sector only): the two-table lookup"""
         _, lo_rank, hi_base = self._tables
@@ -1186,6 +1196,172 @@ class _PairSectorForms(torch.autograd.Function):
             if ctx.needs_input_grad[1]:
                 g2 = _PairSectorApply.apply(v1, G, ctx.op, adj)
         return g1, g2, None, None
+
+
+# ------------------------------------------------------------------------------------------ ladder maps between two S^z sectors
+def ring_momentum_weights(L, m):
+    """(cos(2 pi m j / L), sin(2 pi m j / L)) / sqrt(L) for j = 0 .. L - 1 as two float64 host tensors: the real and the
+    imaginary part of the site weights of the momentum q = 2 pi m / L on a ring (pure torch, no device)"""
+    L, m = int(L), int(m)
+    if L < 1:
+        raise ValueError("ring_momentum_weights needs L >= 1")
+    angle = (2.0 * math.pi / L) * ((m * torch.arange(L, dtype=torch.int64)) % L).to(F64)
+    return torch.cos(angle) / math.sqrt(L), torch.sin(angle) / math.sqrt(L)
+
+
+class SpinSectorLadder:
+    """The site-weighted ladder operators between two magnetisation sectors of the same L sites, matrix-free
+    (docs/design/24-dynamics.md).  ``src`` and ``dst`` are ``SpinSectorOperator`` or ``SpinSectorPairOperator`` objects
+    (anything that carries the sector tables: ``N``, ``ndown``, ``device``, ``_tables``) with the same L on the same device and
+    ``step = dst.ndown - src.ndown`` in {+1, 0, -1}.  Site i is bit i, a set bit is a down spin, z_i = 1 - 2 bit_i; sigma^+- =
+    (X +- iY) / 2 have matrix elements 1, sigma^- sets a bit and sigma^+ clears it.  For site weights c (float64 [L]):
+
+        step = +1:  lad(c, x) = sum_i c_i sigma^-_i x        step = -1:  sum_i c_i sigma^+_i x        step = 0:  sum_i c_i Z_i x
+
+    as a vector of the destination sector (``n_dst`` rows) from one of the source sector (``n_src`` rows).  The object builds no
+    tables: it reads the two operators' tables and keeps them alive.  ``lad.T`` is the ladder dst -> src on the same tables and
+    ``lad.T(c, .)`` the exact transpose of ``lad(c, .)``.  ``lad.forms(v1, v2)[i] = v1^T (d lad / d c_i) v2`` for all sites in
+    one pass (v1 on the destination, v2 on the source; deterministic).  Both are differentiable to any order in c and in the
+    vectors: the map is bilinear and each of the two ``autograd.Function``s is the other's derivative.  ``dense(c)`` is the
+    n_dst x n_src matrix, a test aid for small sectors.  Every argument check is host arithmetic before the device is touched
+    and raises ``ValueError``."""
+
+    def __init__(self, src, dst, _transpose=None):
+        for name, op in (("src", src), ("dst", dst)):
+            for attr in ("N", "ndown", "device", "_tables"):
+                if not hasattr(op, attr):
+                    raise ValueError("%s carries no sector tables (no attribute %r): a SpinSectorOperator or a "
+                                     "SpinSectorPairOperator is needed" % (name, attr))
+            _check_sector(op.N, op.ndown)
+            if len(op._tables) != 3:
+                raise ValueError("%s._tables must be (states, lo_rank, hi_base)" % name)
+        if int(src.N) != int(dst.N):
+            raise ValueError("the two sectors must have the same number of sites, got L = %d and L = %d" % (src.N, dst.N))
+        if torch.device(src.device) != torch.device(dst.device):
+            raise ValueError("the two sectors must live on the same device, got %s and %s" % (src.device, dst.device))
+        step = int(dst.ndown) - int(src.ndown)
+        if step not in (-1, 0, 1):
+            raise ValueError("a ladder changes ndown by +1, 0 or -1, got %d -> %d" % (src.ndown, dst.ndown))
+        self.src, self.dst = src, dst
+        self.L = self.N = int(src.N)
+        self.step = step
+        self.device = torch.device(src.device)
+        self.n_src, self.n_dst = math.comb(self.L, int(src.ndown)), math.comb(self.L, int(dst.ndown))
+        self._tables = (dst._tables[0], src._tables[1], src._tables[2])     # states of dst, rank tables of src: kept alive
+        self._T = _transpose
+        self._grid = _transpose._grid if _transpose is not None else [0]    # one setting for the ladder and its transpose
+
+    @property
+    def T(self):
+        """the ladder dst -> src on the same tables: ``lad.T(c, .)`` is the transpose of ``lad(c, .)``"""
+        if self._T is None:
+            self._T = SpinSectorLadder(self.dst, self.src, _transpose=self)
+        return self._T
+
+    def set_grid_log2(self, grid_log2):
+        """log2 of the most blocks a launch uses (6..12, 0 = the default 12; measurement aid), for the ladder and ``T``"""
+        g = int(grid_log2)
+        if g != 0 and not 6 <= g <= 12:
+            raise ValueError("grid_log2 must be 0 or 6 .. 12, got %d" % g)
+        self._grid[0] = g
+
+    def _weights(self, c):
+        if not torch.is_tensor(c):
+            c = torch.as_tensor(c, dtype=F64)
+        if c.dim() != 1 or c.numel() != self.L:
+            raise ValueError("expected %d site weights, got shape %r" % (self.L, tuple(c.shape)))
+        if c.is_complex():
+            raise ValueError("the site weights must be real: apply the real and the imaginary part one after the other")
+        if c.dtype != F64 or c.device != self.device:
+            c = c.to(device=self.device, dtype=F64)
+        return c
+
+    def _vector(self, v, n, what):
+        if not torch.is_tensor(v) or v.dim() != 1 or v.numel() != n:
+            raise ValueError("%s must be a vector of %d elements, got %s" % (what, n, tuple(v.shape) if torch.is_tensor(v) else type(v)))
+        if v.device != self.device:
+            raise ValueError("%s must live on %s, got %s" % (what, self.device, v.device))
+        return v
+
+    def _apply_raw(self, c, x):
+        c, x = engine.as_vector(c, self.L), engine.as_vector(x, self.n_src)
+        states, lo_rank, hi_base = self._tables
+        y = torch.empty(self.n_dst, dtype=F64, device=x.device)
+        with torch.cuda.device(self.device):
+            check(_lib.load().dsea_sector_ladder_apply(self.L, int(self.src.ndown), self.step, c_void_p(c.data_ptr()),
+                                                       c_void_p(states.data_ptr()), c_void_p(lo_rank.data_ptr()),
+                                                       c_void_p(hi_base.data_ptr()), c_void_p(x.data_ptr()),
+                                                       c_void_p(y.data_ptr()), self._grid[0], engine._stream(self.device)),
+                  "dsea_sector_ladder_apply")
+        return y
+
+    def _forms_raw(self, v1, v2):
+        lib = _lib.load()
+        v1, v2 = engine.as_vector(v1, self.n_dst), engine.as_vector(v2, self.n_src)
+        states, lo_rank, hi_base = self._tables
+        need = c_int64()
+        check(lib.dsea_sector_ladder_forms_scratch_doubles(self.L, int(self.src.ndown), self.step, byref(need)),
+              "dsea_sector_ladder_forms_scratch_doubles")
+        scratch = torch.empty(need.value, dtype=F64, device=v1.device)
+        out = torch.empty(self.L, dtype=F64, device=v1.device)
+        with torch.cuda.device(self.device):
+            check(lib.dsea_sector_ladder_forms(self.L, int(self.src.ndown), self.step, c_void_p(states.data_ptr()),
+                                               c_void_p(lo_rank.data_ptr()), c_void_p(hi_base.data_ptr()),
+                                               c_void_p(v1.data_ptr()), c_void_p(v2.data_ptr()), c_void_p(out.data_ptr()),
+                                               c_void_p(scratch.data_ptr()), self._grid[0], engine._stream(self.device)),
+                  "dsea_sector_ladder_forms")
+        return out
+
+    def __call__(self, c, x):
+        """the vector sum_i c_i O_i x of the destination sector, differentiable in c and in x"""
+        return _LadderApply.apply(self._weights(c), self._vector(x, self.n_src, "x"), self)
+
+    def forms(self, v1, v2):
+        """out[i] = v1^T O_i v2 for every site i, shape (L,): v1 on the destination, v2 on the source; differentiable"""
+        return _LadderForms.apply(self._vector(v1, self.n_dst, "v1"), self._vector(v2, self.n_src, "v2"), self)
+
+    def dense(self, c):
+        """the n_dst x n_src matrix of ``lad(c, .)``, by applying the map to the columns of the identity (small sectors)"""
+        c = self._weights(c)
+        eye = torch.eye(self.n_src, dtype=F64, device=self.device)
+        return torch.stack([self(c, eye[j]) for j in range(self.n_src)], dim=1)
+
+
+class _LadderApply(torch.autograd.Function):
+    """y = S(c) x.  Bilinear: with the cotangent gy, c-bar = forms(gy, x) and x-bar = S(c)^T gy, the transposed ladder on the
+    same tables -- both re-entrant."""
+
+    @staticmethod
+    def forward(ctx, c, x, lad):
+        ctx.lad = lad
+        ctx.save_for_backward(c, x)
+        return lad._apply_raw(c.detach(), x.detach())
+
+    @staticmethod
+    def backward(ctx, gy):
+        c, x = ctx.saved_tensors
+        gc = _LadderForms.apply(gy, x, ctx.lad).reshape(c.shape) if ctx.needs_input_grad[0] else None
+        gx = _LadderApply.apply(c, gy, ctx.lad.T) if ctx.needs_input_grad[1] else None
+        return gc, gx, None
+
+
+class _LadderForms(torch.autograd.Function):
+    """out[i] = v1^T (dS/dc_i) v2, shape (L,).  S is linear in the weights, so with the cotangent G as weights
+    v1-bar = S(G) v2 and v2-bar = S(G)^T v1."""
+
+    @staticmethod
+    def forward(ctx, v1, v2, lad):
+        ctx.lad = lad
+        ctx.save_for_backward(v1, v2)
+        return lad._forms_raw(v1.detach(), v2.detach())
+
+    @staticmethod
+    def backward(ctx, G):
+        v1, v2 = ctx.saved_tensors
+        G = G.reshape(ctx.lad.L)
+        g1 = _LadderApply.apply(G, v2, ctx.lad) if ctx.needs_input_grad[0] else None
+        g2 = _LadderApply.apply(G, v1, ctx.lad.T) if ctx.needs_input_grad[1] else None
+        return g1, g2, None
 
 
 # ------------------------------------------------------------------------------------------ reduced density matrices

@@ -1,0 +1,156 @@
+"""Zero-temperature spectral functions by the Lanczos continued fraction (docs/design/24-dynamics.md).
+
+    S_O(omega) = sum_n |<n| O |psi0>|^2 delta(omega - (E_n - E_0))
+
+For a vector phi = O psi0 the k-step Lanczos run of H from phi / |phi| gives a k x k tridiagonal matrix T = S diag(theta) S^T,
+and the measure sum_j w_j delta(E - theta_j) with w_j = |phi|^2 S_{0j}^2 has the first 2 k moments phi^T H^m phi of the exact
+one.  The run is ``engine.lanczos`` on a native operator (full re-orthogonalisation, the kernels of the eigenvalue solvers); the
+k x k eigenproblem is solved on the host.
+
+    lanczos_measure(op, phi, k)                                   the measure of phi under the operator ``op``
+    SpectralMeasure                                               poles and weights: greens(z), __call__(omega, eta), moment(m)
+    dynamical_structure_factor(op0, psi0, E0, weights, channel)   S^{zz}, S^{-}, S^{+} of a sector state through SpinSectorLadder
+
+A ``SpectralMeasure`` holds host float64 tensors and is NOT differentiable: derivatives of poles and weights are out of scope.
+Static quantities built on the ladder itself (|sigma^-_q psi0|^2, matrix elements) are differentiable through
+``SpinSectorLadder``.
+"""
+from __future__ import annotations
+
+import math
+import warnings
+
+import torch
+
+from . import engine
+
+F64 = torch.float64
+
+
+class SpectralMeasure:
+    """sum_j weights[j] delta(E - poles[j]): ``poles`` and ``weights`` are host float64 tensors of the same length, ``norm2`` =
+    |phi|^2 of the vector(s) it was built from (= the sum of the weights up to rounding) and ``steps`` the number of Lanczos
+    steps that entered it (fewer than asked for when the Krylov space of phi was exhausted).  The sum of two measures
+    concatenates them (``norm2`` and ``steps`` add).  Plain numbers: nothing here is differentiable."""
+
+    def __init__(self, poles, weights, norm2, steps):
+        self.poles = torch.as_tensor(poles, dtype=F64).detach().cpu().reshape(-1)
+        self.weights = torch.as_tensor(weights, dtype=F64).detach().cpu().reshape(-1)
+        if self.poles.numel() != self.weights.numel():
+            raise ValueError("poles and weights must have the same length")
+        self.norm2 = float(norm2)
+        self.steps = int(steps)
+
+    def __len__(self):
+        return self.poles.numel()
+
+    def greens(self, z):
+        """G(z) = sum_j w_j / (z - theta_j) for a complex tensor (or number) z, on the device of z"""
+        z = torch.as_tensor(z).to(torch.complex128)
+        poles, weights = self.poles.to(z.device), self.weights.to(z.device)
+        return (weights / (z.unsqueeze(-1) - poles)).sum(dim=-1)
+
+    def __call__(self, omega, eta):
+        """the Lorentzian-broadened spectral function -Im G(omega + i eta) / pi"""
+        omega = torch.as_tensor(omega, dtype=F64)
+        return -self.greens(torch.complex(omega, torch.full_like(omega, float(eta)))).imag / math.pi
+
+    def moment(self, m):
+        """sum_j w_j theta_j^m as a float"""
+        return float((self.weights * self.poles ** int(m)).sum())
+
+    def shifted(self, E0):
+        """the same weights at the poles theta - E0"""
+        return SpectralMeasure(self.poles - float(E0), self.weights, self.norm2, self.steps)
+
+    def __add__(self, other):
+        if not isinstance(other, SpectralMeasure):
+            return NotImplemented
+        return SpectralMeasure(torch.cat([self.poles, other.poles]), torch.cat([self.weights, other.weights]),
+                               self.norm2 + other.norm2, self.steps + other.steps)
+
+    def __repr__(self):
+        return "SpectralMeasure(%d poles, norm2 = %.6g, steps = %d)" % (len(self), self.norm2, self.steps)
+
+
+def lanczos_measure(op, phi, k):
+    """The spectral measure of the vector ``phi`` under the native symmetric operator ``op`` (``op.handle``, ``op.n``) from
+    min(k, n) Lanczos steps with the module defaults of ``engine`` (full re-orthogonalisation).  When the run meets beta ~ 0
+    at step s (``engine.last_break``: the Krylov space of phi has dimension s), the tridiagonal matrix is cut there, the
+    engine's ``RuntimeWarning`` is not passed on and the measure reports ``steps = s``; its poles are then exact eigenvalues.
+    phi = 0 gives the empty measure.  Not differentiable: phi is detached."""
+    n = int(op.n)
+    phi = phi.detach()
+    if phi.dim() != 1 or phi.numel() != n:
+        raise ValueError("expected a vector of %d elements, got shape %r" % (n, tuple(phi.shape)))
+    k = min(int(k), n)
+    if k < 1:
+        raise ValueError("lanczos_measure needs k >= 1")
+    norm2 = float(torch.dot(phi, phi))
+    if not norm2 > 0.0:
+        return SpectralMeasure(torch.empty(0, dtype=F64), torch.empty(0, dtype=F64), 0.0, 0)
+    q0 = phi / math.sqrt(norm2)
+    with warnings.catch_warnings(record=True) as caught:
+        warnings.simplefilter("always")
+        _, _, alphas, betas = engine.lanczos(None, k, n, phi.device, q0, native=op)
+        steps = engine.last_break or k
+    for w in caught:            # the breakdown is reported as ``steps``; anything else goes on to the caller
+        if not (issubclass(w.category, RuntimeWarning) and "Lanczos breakdown" in str(w.message)):
+            warnings.warn_explicit(w.message, w.category, w.filename, w.lineno)
+    a = alphas[:steps].cpu()
+    b = betas[:steps - 1].cpu()
+    T = torch.diag(a)
+    if steps > 1:
+        T = T + torch.diag(b, 1) + torch.diag(b, -1)
+    theta, S = torch.linalg.eigh(T)
+    return SpectralMeasure(theta, norm2 * S[0] ** 2, norm2, steps)
+
+
+def _weight_parts(weights):
+    """the real site-weight vectors whose measures add up: [c] for a real vector, [re, im] for a (re, im) pair or a complex
+    tensor"""
+    if torch.is_tensor(weights) and weights.is_complex():
+        return [weights.real.to(F64), weights.imag.to(F64)]
+    if isinstance(weights, (tuple, list)) and len(weights) == 2 and all(torch.as_tensor(w).dim() == 1 for w in weights):
+        return [torch.as_tensor(w, dtype=F64) for w in weights]
+    t = torch.as_tensor(weights)
+    if t.is_complex():
+        return [t.real.to(F64), t.imag.to(F64)]
+    return [t.to(F64)]
+
+
+def dynamical_structure_factor(op0, psi0, E0, weights, channel, k=200, target=None):
+    """The spectral measure of O psi0 as a function of the excitation energy E - E0, for the eigenstate (psi0, E0) of the sector
+    operator ``op0`` (``SpinSectorOperator`` or ``SpinSectorPairOperator``) and the site-weighted operator
+
+        channel "zz": O = sum_i c_i Z_i            (stays in the sector; ``target`` = op0)
+        channel "-":  O = sum_i c_i sigma^-_i      (lands in ndown + 1)
+        channel "+":  O = sum_i c_i sigma^+_i      (lands in ndown - 1)
+
+    in the Pauli convention of the operators (Z = 2 S^z, sigma^+- = S^+-).  ``weights``: a real vector [L], a ``(re, im)``
+    pair (``ring_momentum_weights``) or a complex tensor.  For complex weights the result is the sum of the measures of the real
+    and of the imaginary part: H is real symmetric, so the cross terms of <a + ib| f(H) |a + ib> cancel.  ``target`` is the
+    Hamiltonian of the destination sector; ``None`` builds it from the bonds and couplings of ``op0`` at the new ndown, on new
+    tables.  ``k`` Lanczos steps per real vector.  Plain numbers: not differentiable."""
+    from .operators import SpinSectorLadder, SpinSectorOperator, SpinSectorPairOperator
+    step = {"zz": 0, "-": 1, "+": -1}.get(channel)
+    if step is None:
+        raise ValueError("channel must be 'zz', '-' or '+', got %r" % (channel,))
+    if target is None:
+        if step == 0:
+            target = op0
+        else:
+            couplings = op0.couplings.detach()
+            if hasattr(op0, "bonds"):
+                target = SpinSectorOperator(op0.N, op0.bonds, couplings, op0.ndown + step, op0.device)
+            else:
+                target = SpinSectorPairOperator(op0.N, couplings, op0.ndown + step, op0.device)
+    lad = SpinSectorLadder(op0, target)
+    if lad.step != step:
+        raise ValueError("channel %r needs a target at ndown = %d, got %d" % (channel, op0.ndown + step, target.ndown))
+    psi0 = psi0.detach()
+    total = None
+    for c in _weight_parts(weights):
+        part = lanczos_measure(target, lad(c, psi0), k)
+        total = part if total is None else total + part
+    return total.shifted(float(E0))

@@ -932,6 +932,34 @@ int dsea_rdm_cross(int L, int ndown, int LA, const int32_t *sites_host, const in
 int dsea_rdm_pull(int L, int ndown, int LA, const int32_t *sites_host, const int32_t *idx, const double *G, const double *y,
                   double *out, int transpose, void *stream);
 
+/* ------------------------------------------------------------------ sector ladder maps (docs/design/24-dynamics.md)
+ * Linear maps from the sector (L, ndown_src) of dsea_op_create_sector to the sector (L, ndown_src + step) of the same L sites
+ * (site i = bit i, a set bit = a down spin, z_i = 1 - 2 bit_i).  weights_dev: fp64 [L] on the device, one weight c_i per site,
+ * READ THROUGH THE POINTER ON EVERY LAUNCH.  With r' a row of the destination and s' its state:
+ *     step = +1, sigma^-(c):  y[r'] = sum_{i : bit_i(s') = 1} c_i x[rank_src(s' ^ (1 << i))]     (sigma^- sets a bit)
+ *     step = -1, sigma^+(c):  y[r'] = sum_{i : bit_i(s') = 0} c_i x[rank_src(s' | (1 << i))]     (sigma^+ clears a bit)
+ *     step =  0, Z(c):        y[r'] = (sum_i c_i z_i(s')) x[r']
+ * sigma^+- = (X +- iY) / 2 have matrix elements 1, and sigma^+(c) is the transpose of sigma^-(c).  All three are gathers over
+ * the destination rows (no atomics).  states_dst: the state table of the DESTINATION sector; lo_rank_src, hi_base_src: the two
+ * rank tables of the SOURCE sector (dsea_sector_build_tables at the two sectors; for step = 0 they are one sector's).  x fp64
+ * [n_src], y fp64 [n_dst].  grid_log2: log2 of the most blocks of a launch, 6 .. 12, 0 = the default 12.  The library allocates
+ * nothing.  Refused by host arithmetic before any device work (DSEA_ERR_ARG): step outside {-1, 0, 1}; either sector outside
+ * the limits of dsea_sector_table_sizes (so a destination with ndown = 0 or ndown = L); grid_log2 outside {0, 6 .. 12}; a
+ * null pointer; x == y when step != 0. */
+int dsea_sector_ladder_apply(int L, int ndown_src, int step, const double *weights_dev, const int64_t *states_dst,
+                             const int32_t *lo_rank_src, const int32_t *hi_base_src, const double *x, double *y,
+                             int grid_log2 /* 0 = default */, void *stream);
+/* dsea_sector_ladder_forms: out [L] on the device, out[i] = v1^T (dS/dc_i) v2 for every site in one pass, v1 fp64 [n_dst] on
+ * the destination and v2 fp64 [n_src] on the source: sum_{r' : bit_i qualifies} v1[r'] v2[rank_src(...)] for step = +-1,
+ * sum_r z_i v1[r] v2[r] for step = 0.  Wave and block reductions in fixed order into per-block partials in `scratch`, then one
+ * block per form: no floating-point atomics, repeated calls return identical bits.  `scratch`: caller-owned,
+ * dsea_sector_ladder_forms_scratch_doubles = L * min(4096, ceil(n_dst / 256)) doubles (enough for every grid cap).  The same
+ * argument checks as dsea_sector_ladder_apply. */
+int dsea_sector_ladder_forms_scratch_doubles(int L, int ndown_src, int step, int64_t *out);
+int dsea_sector_ladder_forms(int L, int ndown_src, int step, const int64_t *states_dst, const int32_t *lo_rank_src,
+                             const int32_t *hi_base_src, const double *v1, const double *v2, double *out, double *scratch,
+                             int grid_log2, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
