@@ -10,7 +10,9 @@ empty; users import sub-modules by name):
     dominantsparseeigenad_amd.operators TFIMOperator, CSROperator, Stencil3Operator (native mat-vecs)
                                         Bipartition (reduced density matrices and entanglement entropies of their vectors)
                                         SpinSectorLadder (sigma^-, sigma^+ and Z maps between magnetisation sectors)
-    dominantsparseeigenad_amd.spectral  lanczos_measure, SpectralMeasure, dynamical_structure_factor (re-exported here)
+                                        HubbardLadder (c+, c and n maps between Hubbard sectors), one_body_density_matrix
+    dominantsparseeigenad_amd.spectral  lanczos_measure, SpectralMeasure, dynamical_structure_factor,
+                                        hubbard_spectral_function (re-exported here)
 
 The top-level ``DominantSparseEigenAD`` package in this repository re-exports the same modules
 under the reference's import names.
@@ -20,7 +22,8 @@ __version__ = "0.1.0"
 
 def __getattr__(name):
     # the spectral functions under the package's own name, resolved on first use (the module imports torch and the engine)
-    if name in ("spectral", "lanczos_measure", "SpectralMeasure", "dynamical_structure_factor"):
+    if name in ("spectral", "lanczos_measure", "SpectralMeasure", "dynamical_structure_factor",
+                "hubbard_spectral_function"):
         import importlib
         mod = importlib.import_module(__name__ + ".spectral")
         return mod if name == "spectral" else getattr(mod, name)

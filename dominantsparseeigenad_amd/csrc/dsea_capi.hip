@@ -2091,4 +2091,41 @@ int dsea_sector_ladder_forms(int L, int ndown_src, int step, const int64_t* stat
   return check_launch();
 }
 
+int dsea_hubbard_ladder_apply(int L, int nup_src, int ndn_src, int species, int step, const double* weights_dev,
+                              const int64_t* states_dst, const int32_t* lo_rank_src, const int32_t* hi_base_src, const double* x,
+                              double* y, int grid_log2, void* stream) {
+  int64_t n_src, n_dst, n_dn_src, n_dn_dst;
+  REQUIRE(hubbard_ladder_sizes(L, nup_src, ndn_src, species, step, &n_src, &n_dst, &n_dn_src, &n_dn_dst) &&
+              (grid_log2 == 0 || (grid_log2 >= 6 && grid_log2 <= 12)) && weights_dev && states_dst && lo_rank_src &&
+              hi_base_src && x && y && (step == 0 || x != y),
+          DSEA_ERR_ARG);
+  if (launch_hubbard_ladder(L, nup_src, ndn_src, species, step, weights_dev, reinterpret_cast<const uint64_t*>(states_dst),
+                            reinterpret_cast<const uint32_t*>(lo_rank_src), reinterpret_cast<const uint32_t*>(hi_base_src), x, y,
+                            grid_log2, static_cast<hipStream_t>(stream)) != 0)
+    return DSEA_ERR_ARG;
+  return check_launch();
+}
+
+int dsea_hubbard_ladder_forms_scratch_doubles(int L, int nup_src, int ndn_src, int species, int step, int64_t* out) {
+  int64_t n_src, n_dst, n_dn_src, n_dn_dst;
+  REQUIRE(out && hubbard_ladder_sizes(L, nup_src, ndn_src, species, step, &n_src, &n_dst, &n_dn_src, &n_dn_dst), DSEA_ERR_ARG);
+  *out = hubbard_ladder_forms_scratch_doubles(n_dst, L);
+  return DSEA_OK;
+}
+
+int dsea_hubbard_ladder_forms(int L, int nup_src, int ndn_src, int species, int step, const int64_t* states_dst,
+                              const int32_t* lo_rank_src, const int32_t* hi_base_src, const double* v1, const double* v2,
+                              double* out, double* scratch, int grid_log2, void* stream) {
+  int64_t n_src, n_dst, n_dn_src, n_dn_dst;
+  REQUIRE(hubbard_ladder_sizes(L, nup_src, ndn_src, species, step, &n_src, &n_dst, &n_dn_src, &n_dn_dst) &&
+              (grid_log2 == 0 || (grid_log2 >= 6 && grid_log2 <= 12)) && states_dst && lo_rank_src && hi_base_src && v1 && v2 &&
+              out && scratch,
+          DSEA_ERR_ARG);
+  if (launch_hubbard_ladder_forms(L, nup_src, ndn_src, species, step, reinterpret_cast<const uint64_t*>(states_dst),
+                                  reinterpret_cast<const uint32_t*>(lo_rank_src), reinterpret_cast<const uint32_t*>(hi_base_src),
+                                  v1, v2, out, scratch, grid_log2, static_cast<hipStream_t>(stream)) != 0)
+    return DSEA_ERR_ARG;
+  return check_launch();
+}
+
 }  // extern "C"

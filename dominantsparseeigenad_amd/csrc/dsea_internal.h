@@ -553,6 +553,23 @@ int launch_sector_ladder(int L, int ndown_src, int step, const double* c, const 
 int launch_sector_ladder_forms(int L, int ndown_src, int step, const uint64_t* states_dst, const uint32_t* lo_rank_src,
                                const uint32_t* hi_base_src, const double* v1, const double* v2, double* out, double* scratch,
                                int grid_log2, hipStream_t st);
+// dsea_hubbard_ladder.hip (linear maps between two particle-number sectors of the Hubbard space,
+// docs/design/25-hubbard-ladder.md): sum_i c_i c+_{i s} (step +1), sum_i c_i n_{i s} (step 0) and sum_i c_i c_{i s} (step -1) of the
+// species s (0 up, 1 dn) from (L, nup_src, ndn_src) to the sector with that species' count changed by step, as gathers over
+// the destination rows, on the state table of the moving species at its destination count and its two rank tables at its source
+// count; the L site forms v1^T (dS/dc_i) v2 into out through per-block partials in the caller's scratch
+// (hubbard_ladder_forms_scratch_doubles doubles).  hubbard_ladder_sizes is false, and the launchers return -1, for a species
+// outside {0, 1}, a step outside -1 .. 1, a sector outside the limits of hubbard_sizes, a grid_log2 other than 0 (= 12) or
+// 6 .. 12, or a null table.
+bool hubbard_ladder_sizes(int L, int nup_src, int ndn_src, int species, int step, int64_t* n_src, int64_t* n_dst,
+                          int64_t* n_dn_src, int64_t* n_dn_dst);
+int64_t hubbard_ladder_forms_scratch_doubles(int64_t n_dst, int L);
+int launch_hubbard_ladder(int L, int nup_src, int ndn_src, int species, int step, const double* c, const uint64_t* states_dst,
+                          const uint32_t* lo_rank_src, const uint32_t* hi_base_src, const double* x, double* y, int grid_log2,
+                          hipStream_t st);
+int launch_hubbard_ladder_forms(int L, int nup_src, int ndn_src, int species, int step, const uint64_t* states_dst,
+                                const uint32_t* lo_rank_src, const uint32_t* hi_base_src, const double* v1, const double* v2,
+                                double* out, double* scratch, int grid_log2, hipStream_t st);
 // dsea_cg_persist_tfim_big.hip
 bool cg_persist_tfim_big_applicable(const OpDesc& op);
 size_t cg_persist_tfim_big_comm_bytes(int64_t n);

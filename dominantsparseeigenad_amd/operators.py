@@ -1209,7 +1209,51 @@ def ring_momentum_weights(L, m):
     return torch.cos(angle) / math.sqrt(L), torch.sin(angle) / math.sqrt(L)
 
 
-class SpinSectorLadder:
+class _SectorLadderBase:
+    """What ``SpinSectorLadder`` and ``HubbardLadder`` share: a subclass sets ``L``, ``device``, ``n_src``, ``n_dst`` and ``_grid``
+    (one list for the ladder and its transpose) and provides ``T``, ``_apply_raw(c, x)`` and ``_forms_raw(v1, v2)``."""
+
+    def set_grid_log2(self, grid_log2):
+        """log2 of the most blocks a launch uses (6..12, 0 = the default 12; measurement aid), for the ladder and ``T``"""
+        g = int(grid_log2)
+        if g != 0 and not 6 <= g <= 12:
+            raise ValueError("grid_log2 must be 0 or 6 .. 12, got %d" % g)
+        self._grid[0] = g
+
+    def _weights(self, c):
+        if not torch.is_tensor(c):
+            c = torch.as_tensor(c, dtype=F64)
+        if c.dim() != 1 or c.numel() != self.L:
+            raise ValueError("expected %d site weights, got shape %r" % (self.L, tuple(c.shape)))
+        if c.is_complex():
+            raise ValueError("the site weights must be real: apply the real and the imaginary part one after the other")
+        if c.dtype != F64 or c.device != self.device:
+            c = c.to(device=self.device, dtype=F64)
+        return c
+
+    def _vector(self, v, n, what):
+        if not torch.is_tensor(v) or v.dim() != 1 or v.numel() != n:
+            raise ValueError("%s must be a vector of %d elements, got %s" % (what, n, tuple(v.shape) if torch.is_tensor(v) else type(v)))
+        if v.device != self.device:
+            raise ValueError("%s must live on %s, got %s" % (what, self.device, v.device))
+        return v
+
+    def __call__(self, c, x):
+        """the vector sum_i c_i O_i x of the destination sector, differentiable in c and in x"""
+        return _LadderApply.apply(self._weights(c), self._vector(x, self.n_src, "x"), self)
+
+    def forms(self, v1, v2):
+        """out[i] = v1^T O_i v2 for every site i, shape (L,): v1 on the destination, v2 on the source; differentiable"""
+        return _LadderForms.apply(self._vector(v1, self.n_dst, "v1"), self._vector(v2, self.n_src, "v2"), self)
+
+    def dense(self, c):
+        """the n_dst x n_src matrix of ``lad(c, .)``, by applying the map to the columns of the identity (small sectors)"""
+        c = self._weights(c)
+        eye = torch.eye(self.n_src, dtype=F64, device=self.device)
+        return torch.stack([self(c, eye[j]) for j in range(self.n_src)], dim=1)
+
+
+class SpinSectorLadder(_SectorLadderBase):
     """The site-weighted ladder operators between two magnetisation sectors of the same L sites, matrix-free
     (docs/design/24-dynamics.md).  ``src`` and ``dst`` are ``SpinSectorOperator`` or ``SpinSectorPairOperator`` objects
     (anything that carries the sector tables: ``N``, ``ndown``, ``device``, ``_tables``) with the same L on the same device and
@@ -1258,31 +1302,6 @@ class SpinSectorLadder:
             self._T = SpinSectorLadder(self.dst, self.src, _transpose=self)
         return self._T
 
-    def set_grid_log2(self, grid_log2):
-        """log2 of the most blocks a launch uses (6..12, 0 = the default 12; measurement aid), for the ladder and ``T``"""
-        g = int(grid_log2)
-        if g != 0 and not 6 <= g <= 12:
-            raise ValueError("grid_log2 must be 0 or 6 .. 12, got %d" % g)
-        self._grid[0] = g
-
-    def _weights(self, c):
-        if not torch.is_tensor(c):
-            c = torch.as_tensor(c, dtype=F64)
-        if c.dim() != 1 or c.numel() != self.L:
-            raise ValueError("expected %d site weights, got shape %r" % (self.L, tuple(c.shape)))
-        if c.is_complex():
-            raise ValueError("the site weights must be real: apply the real and the imaginary part one after the other")
-        if c.dtype != F64 or c.device != self.device:
-            c = c.to(device=self.device, dtype=F64)
-        return c
-
-    def _vector(self, v, n, what):
-        if not torch.is_tensor(v) or v.dim() != 1 or v.numel() != n:
-            raise ValueError("%s must be a vector of %d elements, got %s" % (what, n, tuple(v.shape) if torch.is_tensor(v) else type(v)))
-        if v.device != self.device:
-            raise ValueError("%s must live on %s, got %s" % (what, self.device, v.device))
-        return v
-
     def _apply_raw(self, c, x):
         c, x = engine.as_vector(c, self.L), engine.as_vector(x, self.n_src)
         states, lo_rank, hi_base = self._tables
@@ -1311,20 +1330,6 @@ class SpinSectorLadder:
                                                c_void_p(scratch.data_ptr()), self._grid[0], engine._stream(self.device)),
                   "dsea_sector_ladder_forms")
         return out
-
-    def __call__(self, c, x):
-        """the vector sum_i c_i O_i x of the destination sector, differentiable in c and in x"""
-        return _LadderApply.apply(self._weights(c), self._vector(x, self.n_src, "x"), self)
-
-    def forms(self, v1, v2):
-        """out[i] = v1^T O_i v2 for every site i, shape (L,): v1 on the destination, v2 on the source; differentiable"""
-        return _LadderForms.apply(self._vector(v1, self.n_dst, "v1"), self._vector(v2, self.n_src, "v2"), self)
-
-    def dense(self, c):
-        """the n_dst x n_src matrix of ``lad(c, .)``, by applying the map to the columns of the identity (small sectors)"""
-        c = self._weights(c)
-        eye = torch.eye(self.n_src, dtype=F64, device=self.device)
-        return torch.stack([self(c, eye[j]) for j in range(self.n_src)], dim=1)
 
 
 class _LadderApply(torch.autograd.Function):
@@ -2272,6 +2277,10 @@ class HubbardOperator:
         """the row of every pair of words in the int64 device tensors ``u`` (nup set bits) and ``d`` (ndn set bits)"""
         return self._species_rank(self._up, u) * self.n_dn + self._species_rank(self._dn, d)
 
+    def ladder(self, dst, species=None):
+        """the site-weighted c+ / c / n maps of one species from this sector into the sector of ``dst`` (``HubbardLadder``)"""
+        return HubbardLadder(self, dst, species)
+
     def to_csr(self, layout="sell", col16="auto", values="auto"):
         """The matrix as an explicit device CSR operand: the diagonal, and one entry per (row, species, distinct bond mask that
         moves a particle of that species in the row); bonds with equal masks are summed.  Built on the device with index
@@ -2352,6 +2361,128 @@ class _HubbardForms(torch.autograd.Function):
             if ctx.needs_input_grad[1]:
                 g2 = _HubbardApply.apply(v1, G, ctx.op, adj)
         return g1, g2, None, None
+
+
+# ------------------------------------------------------------------------------------------ c / c+ between two Hubbard sectors
+_HUBBARD_SPECIES = {"up": 0, "dn": 1}
+
+
+class HubbardLadder(_SectorLadderBase):
+    """The site-weighted creation, annihilation and density operators of one species between two particle-number sectors of
+    the Hubbard space of the same L sites, matrix-free (docs/design/25-hubbard-ladder.md).  ``src`` and ``dst`` are
+    ``HubbardOperator`` objects (anything that carries the species tables: ``N``, ``nup``, ``ndn``, ``device``, ``_up``, ``_dn``)
+    with the same L on the same device.  (dst.nup - src.nup, dst.ndn - src.ndn) fixes the species and the step: (+-1, 0) is the
+    up species, (0, +-1) the down species; (0, 0) needs ``species="up"`` or ``"dn"``.  With the ordering convention of
+    ``HubbardOperator`` and site weights w (float64 [L]):
+
+        step = +1:  lad(w, x) = sum_i w_i c+_{i s} x      step = -1:  sum_i w_i c_{i s} x      step = 0:  sum_i w_i n_{i s} x
+
+    as a vector of the destination sector (``n_dst`` rows) from one of the source sector (``n_src`` rows), fermion signs
+    included (a down operator passes all nup up operators).  The object builds no tables: it reads the two operators' tables and
+    keeps them alive.  ``lad.T`` is the ladder dst -> src on the same tables and ``lad.T(w, .)`` the exact transpose of
+    ``lad(w, .)``.  ``lad.forms(v1, v2)[i] = v1^T (d lad / d w_i) v2`` for all sites in one pass (v1 on the destination, v2 on
+    the source; deterministic).  Both are differentiable to any order in w and in the vectors: the map is bilinear and each of
+    the two ``autograd.Function``s is the other's derivative.  ``dense(w)`` is the n_dst x n_src matrix, a test aid for small
+    sectors.  Every argument check is host arithmetic before the device is touched and raises ``ValueError``."""
+
+    def __init__(self, src, dst, species=None, _transpose=None):
+        for name, op in (("src", src), ("dst", dst)):
+            for attr in ("N", "nup", "ndn", "device", "_up", "_dn"):
+                if not hasattr(op, attr):
+                    raise ValueError("%s carries no species tables (no attribute %r): a HubbardOperator is needed" % (name, attr))
+            _check_hubbard(op.N, op.nup, op.ndn)
+            if len(op._up) != 3 or len(op._dn) != 3:
+                raise ValueError("%s._up and %s._dn must be (states, lo_rank, hi_base)" % (name, name))
+        if int(src.N) != int(dst.N):
+            raise ValueError("the two sectors must have the same number of sites, got L = %d and L = %d" % (src.N, dst.N))
+        if torch.device(src.device) != torch.device(dst.device):
+            raise ValueError("the two sectors must live on the same device, got %s and %s" % (src.device, dst.device))
+        if species is not None and species not in _HUBBARD_SPECIES:
+            raise ValueError("species must be 'up', 'dn' or None, got %r" % (species,))
+        dup, ddn = int(dst.nup) - int(src.nup), int(dst.ndn) - int(src.ndn)
+        if (dup, ddn) == (0, 0):
+            if species is None:
+                raise ValueError("src and dst are the same sector: species='up' or 'dn' picks sum_i w_i n_{i s}")
+            step = 0
+        elif ddn == 0 and dup in (-1, 1):
+            implied, step = "up", dup
+        elif dup == 0 and ddn in (-1, 1):
+            implied, step = "dn", ddn
+        else:
+            raise ValueError("a ladder changes the count of one species by +1, 0 or -1, got (nup, ndn) = (%d, %d) -> (%d, %d)"
+                             % (src.nup, src.ndn, dst.nup, dst.ndn))
+        if step != 0:
+            if species is not None and species != implied:
+                raise ValueError("species=%r contradicts the sectors (%d, %d) -> (%d, %d), which move the %s species"
+                                 % (species, src.nup, src.ndn, dst.nup, dst.ndn, implied))
+            species = implied
+        self.src, self.dst = src, dst
+        self.L = self.N = int(src.N)
+        self.species, self.step = species, step
+        self._species = _HUBBARD_SPECIES[species]
+        self.device = torch.device(src.device)
+        self.n_src = math.comb(self.L, int(src.nup)) * math.comb(self.L, int(src.ndn))
+        self.n_dst = math.comb(self.L, int(dst.nup)) * math.comb(self.L, int(dst.ndn))
+        moving_src, moving_dst = (src._up, dst._up) if species == "up" else (src._dn, dst._dn)
+        self._tables = (moving_dst[0], moving_src[1], moving_src[2])    # states of dst, rank tables of src: kept alive
+        self._T = _transpose
+        self._grid = _transpose._grid if _transpose is not None else [0]    # one setting for the ladder and its transpose
+
+    @property
+    def T(self):
+        """the ladder dst -> src on the same tables: ``lad.T(w, .)`` is the transpose of ``lad(w, .)``"""
+        if self._T is None:
+            self._T = HubbardLadder(self.dst, self.src, self.species, _transpose=self)
+        return self._T
+
+    def _sector_args(self):
+        return self.L, int(self.src.nup), int(self.src.ndn), self._species, self.step
+
+    def _apply_raw(self, w, x):
+        w, x = engine.as_vector(w, self.L), engine.as_vector(x, self.n_src)
+        states, lo_rank, hi_base = self._tables
+        y = torch.empty(self.n_dst, dtype=F64, device=x.device)
+        with torch.cuda.device(self.device):
+            check(_lib.load().dsea_hubbard_ladder_apply(*self._sector_args(), c_void_p(w.data_ptr()), c_void_p(states.data_ptr()),
+                                                        c_void_p(lo_rank.data_ptr()), c_void_p(hi_base.data_ptr()),
+                                                        c_void_p(x.data_ptr()), c_void_p(y.data_ptr()), self._grid[0],
+                                                        engine._stream(self.device)), "dsea_hubbard_ladder_apply")
+        return y
+
+    def _forms_raw(self, v1, v2):
+        lib = _lib.load()
+        v1, v2 = engine.as_vector(v1, self.n_dst), engine.as_vector(v2, self.n_src)
+        states, lo_rank, hi_base = self._tables
+        need = c_int64()
+        check(lib.dsea_hubbard_ladder_forms_scratch_doubles(*self._sector_args(), byref(need)),
+              "dsea_hubbard_ladder_forms_scratch_doubles")
+        scratch = torch.empty(need.value, dtype=F64, device=v1.device)
+        out = torch.empty(self.L, dtype=F64, device=v1.device)
+        with torch.cuda.device(self.device):
+            check(lib.dsea_hubbard_ladder_forms(*self._sector_args(), c_void_p(states.data_ptr()), c_void_p(lo_rank.data_ptr()),
+                                                c_void_p(hi_base.data_ptr()), c_void_p(v1.data_ptr()), c_void_p(v2.data_ptr()),
+                                                c_void_p(out.data_ptr()), c_void_p(scratch.data_ptr()), self._grid[0],
+                                                engine._stream(self.device)), "dsea_hubbard_ladder_forms")
+        return out
+
+
+def one_body_density_matrix(op, psi, species, target=None):
+    """rho[i, j] = <psi| c+_{i s} c_{j s} |psi> for the species ``"up"`` or ``"dn"`` of the Hubbard sector of ``op``, shape
+    (L, L): rho_ij = (c_{i s} psi) . (c_{j s} psi) from L applications of the annihilation ladder with one-hot weights and one
+    Gram matrix.  Differentiable in psi (hence through ``DominantSparseSymeig``).  ``target`` carries the tables of the sector
+    with one particle of that species less; ``None`` builds them (zero couplings on the bonds of ``op``)."""
+    if species not in _HUBBARD_SPECIES:
+        raise ValueError("species must be 'up' or 'dn', got %r" % (species,))
+    if target is None:
+        nup, ndn = (op.nup - 1, op.ndn) if species == "up" else (op.nup, op.ndn - 1)
+        _check_hubbard(op.N, nup, ndn)
+        target = HubbardOperator(op.N, op.bonds, torch.zeros(op.nparam, dtype=F64, device=op.device), nup, ndn, op.device)
+    lad = HubbardLadder(op, target, species)
+    if lad.step != -1:
+        raise ValueError("one_body_density_matrix needs a target with one %s particle less than op" % species)
+    eye = torch.eye(lad.L, dtype=F64, device=lad.device)
+    C = torch.stack([lad(eye[i], psi) for i in range(lad.L)])
+    return C @ C.T
 
 
 # ------------------------------------------------------------------------------------------ stencil

@@ -10,6 +10,7 @@ k x k eigenproblem is solved on the host.
     lanczos_measure(op, phi, k)                                   the measure of phi under the operator ``op``
     SpectralMeasure                                               poles and weights: greens(z), __call__(omega, eta), moment(m)
     dynamical_structure_factor(op0, psi0, E0, weights, channel)   S^{zz}, S^{-}, S^{+} of a sector state through SpinSectorLadder
+    hubbard_spectral_function(op0, psi0, E0, weights, channel)    c, c+, charge and spin channels of a Hubbard state (HubbardLadder)
 
 A ``SpectralMeasure`` holds host float64 tensors and is NOT differentiable: derivatives of poles and weights are out of scope.
 Static quantities built on the ladder itself (|sigma^-_q psi0|^2, matrix elements) are differentiable through
@@ -62,6 +63,10 @@ class SpectralMeasure:
     def shifted(self, E0):
         """the same weights at the poles theta - E0"""
         return SpectralMeasure(self.poles - float(E0), self.weights, self.norm2, self.steps)
+
+    def reflected(self):
+        """the same weights at the poles -theta: a removal measure in E_n - E0 placed at omega = E0 - E_n"""
+        return SpectralMeasure(-self.poles, self.weights, self.norm2, self.steps)
 
     def __add__(self, other):
         if not isinstance(other, SpectralMeasure):
@@ -152,5 +157,53 @@ def dynamical_structure_factor(op0, psi0, E0, weights, channel, k=200, target=No
     total = None
     for c in _weight_parts(weights):
         part = lanczos_measure(target, lad(c, psi0), k)
+        total = part if total is None else total + part
+    return total.shifted(float(E0))
+
+
+_HUBBARD_CHANNELS = {"c_up": ("up", -1), "c_dn": ("dn", -1), "cdag_up": ("up", 1), "cdag_dn": ("dn", 1), "n": (None, 0),
+                     "sz": (None, 0)}
+
+
+def hubbard_spectral_function(op0, psi0, E0, weights, channel, k=200, target=None):
+    """The spectral measure of O psi0 as a function of the excitation energy E - E0, for the eigenstate (psi0, E0) of the
+    ``HubbardOperator`` ``op0`` and the site-weighted operator (docs/design/25-hubbard-ladder.md)
+
+        channel "c_up", "c_dn":        O = sum_i w_i c_{i s}        (photoemission; lands in the sector with one s particle less)
+        channel "cdag_up", "cdag_dn":  O = sum_i w_i c+_{i s}       (inverse photoemission; one s particle more)
+        channel "n":                   O = sum_i w_i (n_{i up} + n_{i dn})     (charge; stays in the sector, ``target`` = op0)
+        channel "sz":                  O = sum_i w_i (n_{i up} - n_{i dn})     (2 S^z; stays in the sector)
+
+    ``weights``: a real vector [L], a ``(re, im)`` pair (``ring_momentum_weights``) or a complex tensor.  For complex weights
+    the result is the sum of the measures of the real and of the imaginary part: H is real symmetric, so the cross terms of
+    <a + ib| f(H) |a + ib> cancel.  ``target`` is the Hamiltonian of the destination sector; ``None`` builds it from the bonds
+    and couplings of ``op0`` at the new particle numbers, on new tables.  ``k`` Lanczos steps per real vector.  A removal
+    measure comes out in E_n - E0 >= 0 like every other; ``reflected()`` places it at omega = E0 - E_n, so that
+    ``cdag + c.reflected()`` is the one-particle spectral function A(omega).  Plain numbers: not differentiable."""
+    from .operators import HubbardLadder, HubbardOperator
+    if channel not in _HUBBARD_CHANNELS:
+        raise ValueError("channel must be one of %s, got %r" % (", ".join(repr(c) for c in _HUBBARD_CHANNELS), channel))
+    species, step = _HUBBARD_CHANNELS[channel]
+    if target is None:
+        if step == 0:
+            target = op0
+        else:
+            nup, ndn = (op0.nup + step, op0.ndn) if species == "up" else (op0.nup, op0.ndn + step)
+            target = HubbardOperator(op0.N, op0.bonds, op0.couplings.detach(), nup, ndn, op0.device)
+    if step == 0:
+        ladders = [HubbardLadder(op0, target, "up"), HubbardLadder(op0, target, "dn")]
+        sign = 1.0 if channel == "n" else -1.0
+    else:
+        ladders = [HubbardLadder(op0, target, species)]
+    if ladders[0].step != step:
+        raise ValueError("channel %r needs a target with the %s count changed by %d, got (nup, ndn) = (%d, %d)"
+                         % (channel, species or "no", step, target.nup, target.ndn))
+    psi0 = psi0.detach()
+    total = None
+    for w in _weight_parts(weights):
+        phi = ladders[0](w, psi0)
+        if step == 0:
+            phi = phi + sign * ladders[1](w, psi0)
+        part = lanczos_measure(target, phi, k)
         total = part if total is None else total + part
     return total.shifted(float(E0))

@@ -960,6 +960,36 @@ int dsea_sector_ladder_forms(int L, int ndown_src, int step, const int64_t *stat
                              const int32_t *hi_base_src, const double *v1, const double *v2, double *out, double *scratch,
                              int grid_log2, void *stream);
 
+/* ------------------------------------------------------------------ Hubbard ladder maps (docs/design/25-hubbard-ladder.md)
+ * Linear maps from the Hubbard sector (L, nup_src, ndn_src) of dsea_op_create_hubbard to the sector of the same L sites in which
+ * the count of one species (species: 0 up, 1 dn) is changed by step; conventions and row order r = ru * n_dn + rd of
+ * dsea_op_create_hubbard.  weights_dev: fp64 [L] on the device, one weight c_i per site, READ THROUGH THE POINTER ON EVERY
+ * LAUNCH.  With w' the word of the moving species in a row of the destination, below_i = (1 << i) - 1, par = popcount & 1:
+ *     step = +1, sum_i c_i c+_{i s}:  y[row] = g sum_{i : bit_i(w') = 1} c_i (-1)^par(w' & below_i) x[row with rank_src(w' ^ (1 << i))]
+ *     step = -1, sum_i c_i c_{i s}:   y[row] = g sum_{i : bit_i(w') = 0} c_i (-1)^par(w' & below_i) x[row with rank_src(w' | (1 << i))]
+ *     step =  0, sum_i c_i n_{i s}:   y[row] = (sum_i c_i bit_i(w')) x[row]
+ * g = 1 for the up species and (-1)^nup_src for the down species (every down operator stands right of all up operators).  The
+ * other species keeps its rank; the row stride is C(L, ndn) of the destination for y and of the source for x.  The map with the
+ * two sectors exchanged and step negated is the exact transpose.  All are gathers over the destination rows (no atomics).
+ * states_dst: the state table of the MOVING species at its DESTINATION count; lo_rank_src, hi_base_src: its two rank tables at
+ * its SOURCE count (dsea_sector_build_tables; for step = 0 they are one count's).  x fp64 [n_src], y fp64 [n_dst].  grid_log2:
+ * log2 of the most blocks of a launch, 6 .. 12, 0 = the default 12.  The library allocates nothing.  Refused by host arithmetic
+ * before any device work (DSEA_ERR_ARG): species outside {0, 1}; step outside {-1, 0, 1}; the source or the destination
+ * outside the limits of dsea_hubbard_sizes (so a destination count of 0 or L); grid_log2 outside {0, 6 .. 12}; a null pointer;
+ * x == y when step != 0. */
+int dsea_hubbard_ladder_apply(int L, int nup_src, int ndn_src, int species /* 0 up, 1 dn */, int step, const double *weights_dev,
+                              const int64_t *states_dst, const int32_t *lo_rank_src, const int32_t *hi_base_src, const double *x,
+                              double *y, int grid_log2 /* 0 = default */, void *stream);
+/* dsea_hubbard_ladder_forms: out [L] on the device, out[i] = v1^T (dS/dc_i) v2 for every site in one pass, v1 fp64 [n_dst] on
+ * the destination and v2 fp64 [n_src] on the source.  Wave and block reductions in fixed order into per-block partials in
+ * `scratch`, then one block per form: no floating-point atomics, repeated calls return identical bits.  `scratch`: caller-owned,
+ * dsea_hubbard_ladder_forms_scratch_doubles = L * min(4096, ceil(n_dst / 256)) doubles (enough for every grid cap).  The same
+ * argument checks as dsea_hubbard_ladder_apply. */
+int dsea_hubbard_ladder_forms_scratch_doubles(int L, int nup_src, int ndn_src, int species, int step, int64_t *out);
+int dsea_hubbard_ladder_forms(int L, int nup_src, int ndn_src, int species, int step, const int64_t *states_dst,
+                              const int32_t *lo_rank_src, const int32_t *hi_base_src, const double *v1, const double *v2,
+                              double *out, double *scratch, int grid_log2, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
