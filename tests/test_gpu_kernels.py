@@ -1,7 +1,11 @@
 """Kernel-level parity on the MI355X: every C-ABI phase against a plain fp64 torch/numpy evaluation of
 the same reference expression, on ragged sizes (odd n, n < one wave tile, n not a multiple of anything)
 and every rows-per-lane variant of the basis-streaming kernels.  Tolerance: 1e-13 relative to the
-operand norms (sum-order differences only)."""
+operand norms (sum-order differences only).
+
+The conjugate-gradient entries (dsea_shift_dot, the CG phases, dsea_cg_step) are judged one call at a time, bit for bit on exact
+inputs and to operation-count bounds on random ones, in tests/test_gpu_cg_stages.py; the dsea_cg_step test here compares whole
+solves."""
 from ctypes import byref, c_void_p
 
 import numpy as np

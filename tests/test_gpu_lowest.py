@@ -1,6 +1,10 @@
 """The nev lowest eigenpairs on the MI355X (docs/design/13-lowest-eigenpairs.md): the block Ritz combine against
 dsea_ritz_combine bit for bit, the block projection and the deflated CG against torch fp64, and the primitives
-(LowestSymeig / LowestSparseSymeig) against torch.linalg.eigh autograd."""
+(LowestSymeig / LowestSparseSymeig) against torch.linalg.eigh autograd.
+
+dsea_block_project_out, dsea_cg_deflated_init and dsea_cg_deflated_step are judged one call at a time (odd n, n below a tile
+and above 2^21 rows, m = 1 ... DSEA_MAX_NEV, a padded ldpsi) in tests/test_gpu_cg_stages.py; the deflated tests here go
+through the restarting driver."""
 import os
 import subprocess
 import sys
