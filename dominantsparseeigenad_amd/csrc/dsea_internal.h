@@ -570,6 +570,15 @@ int launch_hubbard_ladder(int L, int nup_src, int ndn_src, int species, int step
 int launch_hubbard_ladder_forms(int L, int nup_src, int ndn_src, int species, int step, const uint64_t* states_dst,
                                 const uint32_t* lo_rank_src, const uint32_t* hi_base_src, const double* v1, const double* v2,
                                 double* out, double* scratch, int grid_log2, hipStream_t st);
+// dsea_sector_block.hip (the bond-list sector Hamiltonian on a block of R vectors, docs/design/27-finite-temperature.md): a block is
+// fp64 [n, R] row-major, R in {1, 2, 4, 8}.  launch_sector_block_apply: Y = H X (column j bit for bit the single-vector mat-vec).
+// launch_sector_block_lanczos: the start and k steps of the basis-free block recurrence with the per-column break record, three
+// launches per step, nothing read back; scratch of sector_block_lanczos_scratch_doubles(n, R) doubles (enough for every grid
+// cap).  The launchers return -1 when the descriptor is out of range; the callers check R.
+int64_t sector_block_lanczos_scratch_doubles(int64_t n, int R);
+int launch_sector_block_apply(const OpDesc& op, int R, const double* X, double* Y, hipStream_t st);
+int launch_sector_block_lanczos(const OpDesc& op, int R, int k, double* Q, double* W, double* norm2, double* alphas, double* betas,
+                                int32_t* steps, double* scratch, hipStream_t st);
 // dsea_cg_persist_tfim_big.hip
 bool cg_persist_tfim_big_applicable(const OpDesc& op);
 size_t cg_persist_tfim_big_comm_bytes(int64_t n);

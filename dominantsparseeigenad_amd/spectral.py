@@ -124,7 +124,7 @@ def _weight_parts(weights):
     return [t.to(F64)]
 
 
-def dynamical_structure_factor(op0, psi0, E0, weights, channel, k=200, target=None):
+def dynamical_structure_factor(op0, psi0, E0, weights, channel, k=200, target=None, basis_free=False):
     """The spectral measure of O psi0 as a function of the excitation energy E - E0, for the eigenstate (psi0, E0) of the sector
     operator ``op0`` (``SpinSectorOperator`` or ``SpinSectorPairOperator``) and the site-weighted operator
 
@@ -136,11 +136,15 @@ def dynamical_structure_factor(op0, psi0, E0, weights, channel, k=200, target=No
     pair (``ring_momentum_weights``) or a complex tensor.  For complex weights the result is the sum of the measures of the real
     and of the imaginary part: H is real symmetric, so the cross terms of <a + ib| f(H) |a + ib> cancel.  ``target`` is the
     Hamiltonian of the destination sector; ``None`` builds it from the bonds and couplings of ``op0`` at the new ndown, on new
-    tables.  ``k`` Lanczos steps per real vector.  Plain numbers: not differentiable."""
+    tables.  ``k`` Lanczos steps per real vector.  ``basis_free=True`` (bond-list ``SpinSectorOperator`` only): the real and the
+    imaginary part run as one block of 1 or 2 columns through ``thermal.block_lanczos_measures`` -- no stored basis, no
+    re-orthogonalisation, memory independent of k (docs/design/27-finite-temperature.md).  Plain numbers: not differentiable."""
     from .operators import SpinSectorLadder, SpinSectorOperator, SpinSectorPairOperator
     step = {"zz": 0, "-": 1, "+": -1}.get(channel)
     if step is None:
         raise ValueError("channel must be 'zz', '-' or '+', got %r" % (channel,))
+    if basis_free and not (isinstance(op0, SpinSectorOperator) and (target is None or isinstance(target, SpinSectorOperator))):
+        raise ValueError("basis_free=True works on the bond-list SpinSectorOperator only")
     if target is None:
         if step == 0:
             target = op0
@@ -154,6 +158,12 @@ def dynamical_structure_factor(op0, psi0, E0, weights, channel, k=200, target=No
     if lad.step != step:
         raise ValueError("channel %r needs a target at ndown = %d, got %d" % (channel, op0.ndown + step, target.ndown))
     psi0 = psi0.detach()
+    if basis_free:
+        from .thermal import block_lanczos_measures
+        Phi = torch.stack([lad(c, psi0).detach() for c in _weight_parts(weights)], dim=1)
+        parts = block_lanczos_measures(target, Phi, k)
+        total = parts[0] if len(parts) == 1 else parts[0] + parts[1]
+        return total.shifted(float(E0))
     total = None
     for c in _weight_parts(weights):
         part = lanczos_measure(target, lad(c, psi0), k)

@@ -1,0 +1,255 @@
+"""Finite temperature by the finite-temperature Lanczos method (docs/design/27-finite-temperature.md).
+
+    tr f(H) in a sector of dimension n  ~=  (n / R) sum_r <r| f(H) |r>     over R random unit vectors r
+
+and every <r| f(H) |r> is the Gauss quadrature sum_j S_{0j}^2 f(theta_j) of the k x k Lanczos matrix T = S diag(theta) S^T of r:
+a ``SpectralMeasure``.  The runs keep NO basis and do not re-orthogonalise (the quadrature does not need it): all R vectors go
+through the three-term recurrence at once as one [n, R] block, on the block mat-vec of ``SpinSectorOperator``; the k x k
+eigenproblems are solved on the host.
+
+    block_lanczos_coefficients(op, Phi, k)  norm2, alphas, betas and steps of the R columns of Phi, basis-free
+    block_lanczos_measures(op, Phi, k)      their measures
+    sector_trace_measure(op, R, k, seed)    a measure with sum_j w_j f(theta_j) ~= tr f(H_sector); exact for small sectors
+    ThermalEnsemble(entries)                ln Z, E, C, S and chi of a list of (measure, m) over a tensor of inverse temperatures
+    spin_thermodynamics(L, bonds, couplings, ...)   the ensemble over all magnetisation sectors of a bond-list XXZ model
+
+Plain host float64 numbers: nothing here is differentiable.
+"""
+from __future__ import annotations
+
+from ctypes import byref, c_int64, c_void_p
+
+import torch
+
+from . import _lib, engine
+from ._lib import check
+from .spectral import SpectralMeasure
+
+F64 = torch.float64
+BLOCK_WIDTHS = (8, 4, 2, 1)
+
+
+def block_pieces(R):
+    """[(first column, width)] of the split of R >= 1 columns into blocks the kernels take: widths 8, 4, 2 and 1, widest first"""
+    R = int(R)
+    if R < 1:
+        raise ValueError("a block needs at least one column, got %d" % R)
+    out, first = [], 0
+    for w in BLOCK_WIDTHS:
+        while R - first >= w:
+            out.append((first, w))
+            first += w
+    return out
+
+
+def _sector_operator(op, what):
+    from .operators import SpinSectorOperator
+    if not isinstance(op, SpinSectorOperator):
+        raise ValueError("%s works on the bond-list SpinSectorOperator only, got %s" % (what, type(op).__name__))
+    return op
+
+
+def _as_block(op, X, what):
+    if not torch.is_tensor(X) or X.dim() != 2 or X.shape[0] != op.n or X.shape[1] < 1:
+        raise ValueError("%s expects a tensor of shape (%d, R) with R >= 1, got %r"
+                         % (what, op.n, tuple(X.shape) if torch.is_tensor(X) else type(X).__name__))
+    if not X.is_cuda:
+        raise ValueError("%s expects a block on %s, got a %s tensor" % (what, op.device, X.device))
+    return X.detach()
+
+
+def _empty_measure(norm2=0.0):
+    return SpectralMeasure(torch.empty(0, dtype=F64), torch.empty(0, dtype=F64), norm2, 0)
+
+
+def _tridiagonal_measure(alphas, betas, norm2):
+    """the measure norm2 sum_j S_{0j}^2 delta(E - theta_j) of the tridiagonal matrix with diagonal alphas (s) and off-diagonal
+    betas (s - 1), host tensors"""
+    s = alphas.numel()
+    T = torch.diag(alphas)
+    if s > 1:
+        T = T + torch.diag(betas, 1) + torch.diag(betas, -1)
+    theta, S = torch.linalg.eigh(T)
+    return SpectralMeasure(theta, norm2 * S[0] ** 2, norm2, s)
+
+
+def block_lanczos_coefficients(op, Phi, k):
+    """(norm2 [R], alphas [k, R], betas [k, R], steps [R]) of the basis-free recurrence for the R columns of ``Phi`` as host
+    tensors, k cut to n: norm2[j] = |Phi[:, j]|^2, alphas[i, j] = alpha_i and betas[i, j] = beta_{i+1} of column j, steps[j] = k or
+    the step at which column j broke (dsea_op_sector_block_lanczos, in blocks of 8, 4, 2 and 1 columns)."""
+    op = _sector_operator(op, "block_lanczos_coefficients")
+    k = min(int(k), int(op.n))
+    if k < 1:
+        raise ValueError("the block Lanczos run needs k >= 1")
+    Phi = _as_block(op, Phi, "block_lanczos_coefficients")
+    lib = _lib.load()
+    dev = Phi.device
+    out = []
+    for first, w in block_pieces(Phi.shape[1]):
+        Q = Phi[:, first:first + w].to(F64).clone(memory_format=torch.contiguous_format)   # (overwritten by the run)
+        W = torch.empty_like(Q)
+        need = c_int64()
+        check(lib.dsea_op_sector_block_lanczos_scratch_doubles(op.N, op.ndown, w, byref(need)),
+              "dsea_op_sector_block_lanczos_scratch_doubles")
+        scratch = torch.empty(need.value, dtype=F64, device=dev)
+        norm2 = torch.empty(w, dtype=F64, device=dev)
+        alphas = torch.empty((k, w), dtype=F64, device=dev)
+        betas = torch.empty((k, w), dtype=F64, device=dev)
+        steps = torch.empty(w, dtype=torch.int32, device=dev)
+        check(lib.dsea_op_sector_block_lanczos(op.handle, w, k, c_void_p(Q.data_ptr()), c_void_p(W.data_ptr()),
+                                               c_void_p(norm2.data_ptr()), c_void_p(alphas.data_ptr()), c_void_p(betas.data_ptr()),
+                                               c_void_p(steps.data_ptr()), c_void_p(scratch.data_ptr()), engine._stream(dev)),
+              "dsea_op_sector_block_lanczos")
+        out.append((norm2.cpu(), alphas.cpu(), betas.cpu(), steps.cpu()))
+    return tuple(torch.cat([piece[i] for piece in out], dim=-1) for i in range(4))
+
+
+def block_lanczos_measures(op, Phi, k):
+    """The spectral measures of the R columns of ``Phi`` (a device tensor (n, R), any R >= 1, any norms) under the
+    ``SpinSectorOperator`` ``op``, from min(k, n) steps of the three-term recurrence WITHOUT a stored basis and without
+    re-orthogonalisation: memory is two blocks plus scratch whatever k is.  Columns go through the kernels in blocks of 8, 4, 2
+    and 1.  A column whose Krylov space is exhausted at step s reports ``steps = s`` (its poles are then exact eigenvalues)
+    while the other columns go on; a zero column gives the empty measure.  Returns a list of R ``SpectralMeasure``.  Not
+    differentiable: Phi is detached."""
+    norm2, alphas, betas, steps = block_lanczos_coefficients(_sector_operator(op, "block_lanczos_measures"), Phi, k)
+    out = []
+    for j in range(steps.numel()):
+        s = int(steps[j])
+        if s == 0:
+            out.append(_empty_measure(float(norm2[j])))
+        else:
+            out.append(_tridiagonal_measure(alphas[:s, j].contiguous(), betas[:s - 1, j].contiguous(), float(norm2[j])))
+    return out
+
+
+def sector_trace_measure(op, R=8, k=100, seed=0, dense_below=256):
+    """A ``SpectralMeasure`` with sum_j w_j f(theta_j) ~= tr f(H) over the sector of the ``SpinSectorOperator`` ``op``.
+
+    n <= ``dense_below``: EXACT -- H is formed by ``op.apply_block`` on the identity columns, eight at a time, its eigenvalues
+    (``torch.linalg.eigvalsh`` on the host) are the poles and the weights are 1.  Otherwise the R start vectors are
+    ``synthetic.normal_vector(n, seed + j)`` (deterministic; the torch generators are not touched), each runs min(k, n)
+    basis-free Lanczos steps in one block, and the weights are (n / R) S_{0j}^2: a stochastic estimate whose error is the
+    sampling error of R vectors."""
+    op = _sector_operator(op, "sector_trace_measure")
+    n = int(op.n)
+    R, k = int(R), int(k)
+    if R < 1 or k < 1:
+        raise ValueError("sector_trace_measure needs R >= 1 and k >= 1")
+    if n <= int(dense_below):
+        H = torch.empty((n, n), dtype=F64, device=op.device)
+        for first in range(0, n, 8):
+            w = min(8, n - first)
+            X = torch.zeros((n, w), dtype=F64, device=op.device)
+            X[first:first + w] = torch.eye(w, dtype=F64, device=op.device)
+            H[:, first:first + w] = op.apply_block(X)
+        poles = torch.linalg.eigvalsh(H.cpu())
+        return SpectralMeasure(poles, torch.ones(n, dtype=F64), float(n), n)
+    from .synthetic import normal_vector
+    Phi = torch.stack([torch.from_numpy(normal_vector(n, int(seed) + j)) for j in range(R)], dim=1).to(op.device)
+    parts = block_lanczos_measures(op, Phi, k)
+    poles = torch.cat([m.poles for m in parts])
+    weights = torch.cat([m.weights * (n / (R * m.norm2)) for m in parts if len(m)] or [torch.empty(0, dtype=F64)])
+    return SpectralMeasure(poles, weights, float(n), sum(m.steps for m in parts))
+
+
+class ThermalEnsemble:
+    """Canonical averages over a list of ``(measure, m)``: ``measure`` a ``SpectralMeasure`` with sum_j w_j f(theta_j) = tr f(H)
+    of one sector (``sector_trace_measure``) and ``m`` the magnetisation S^z_total = L / 2 - ndown of that sector.  With
+    p_j = w_j exp(-beta theta_j) / Z over all poles of all entries:
+
+        logZ(beta)            ln sum_j w_j exp(-beta theta_j)     (log-sum-exp shifted by the lowest pole)
+        energy(beta)          E = sum_j p_j theta_j
+        specific_heat(beta)   C = beta^2 sum_j p_j (theta_j - E)^2
+        entropy(beta)         S = ln Z + beta E
+        susceptibility(beta)  chi = beta sum_j p_j (m_j - <m>)^2
+        moment(p)             sum_j w_j theta_j^p = tr H^p
+
+    ``beta`` >= 0 is a number or a tensor; the results are host float64 tensors of its shape.  The variances are sums of squared
+    deviations, not differences of two means.  Plain numbers: not differentiable."""
+
+    def __init__(self, entries):
+        entries = list(entries)
+        if not entries:
+            raise ValueError("ThermalEnsemble needs at least one (measure, m) entry")
+        poles, weights, ms = [], [], []
+        for entry in entries:
+            if not (isinstance(entry, (tuple, list)) and len(entry) == 2 and isinstance(entry[0], SpectralMeasure)):
+                raise ValueError("every entry must be a (SpectralMeasure, m) pair, got %r" % (entry,))
+            measure, m = entry
+            poles.append(measure.poles)
+            weights.append(measure.weights)
+            ms.append(torch.full((len(measure),), float(m), dtype=F64))
+        self.entries = [(e[0], float(e[1])) for e in entries]
+        self.poles, self.weights, self.m = torch.cat(poles), torch.cat(weights), torch.cat(ms)
+        if self.poles.numel() == 0:
+            raise ValueError("ThermalEnsemble needs at least one pole")
+        if bool((self.weights < 0).any()):
+            raise ValueError("the weights of a trace measure must not be negative")
+        self.lowest = float(self.poles.min())
+
+    def _boltzmann(self, beta):
+        """(beta as a host fp64 tensor, sum_j w_j exp(-beta (theta_j - lowest)) [...], the probabilities p [..., poles])"""
+        beta = torch.as_tensor(beta, dtype=F64).detach().cpu()
+        if bool((beta < 0).any()):
+            raise ValueError("ThermalEnsemble works at inverse temperatures beta >= 0")
+        terms = self.weights * torch.exp(-beta.unsqueeze(-1) * (self.poles - self.lowest))
+        total = terms.sum(dim=-1)
+        return beta, total, terms / total.unsqueeze(-1)
+
+    def logZ(self, beta):
+        beta, total, _ = self._boltzmann(beta)
+        return torch.log(total) - beta * self.lowest
+
+    def energy(self, beta):
+        _, _, p = self._boltzmann(beta)
+        return (p * self.poles).sum(dim=-1)
+
+    def specific_heat(self, beta):
+        beta, _, p = self._boltzmann(beta)
+        E = (p * self.poles).sum(dim=-1)
+        return beta ** 2 * (p * (self.poles - E.unsqueeze(-1)) ** 2).sum(dim=-1)
+
+    def entropy(self, beta):
+        beta, total, p = self._boltzmann(beta)
+        return torch.log(total) - beta * self.lowest + beta * (p * self.poles).sum(dim=-1)
+
+    def susceptibility(self, beta):
+        beta, _, p = self._boltzmann(beta)
+        mean = (p * self.m).sum(dim=-1)
+        return beta * (p * (self.m - mean.unsqueeze(-1)) ** 2).sum(dim=-1)
+
+    def moment(self, p):
+        return float((self.weights * self.poles ** int(p)).sum())
+
+
+def spin_thermodynamics(L, bonds, couplings, R=8, k=100, seed=0, dense_below=256, sectors=None, device=None):
+    """The ``ThermalEnsemble`` of H = sum_t [Jxy_t (X_a X_b + Y_a Y_b) + Jz_t Z_a Z_b] + sum_i hz_i Z_i (the Hamiltonian and the
+    parameter order [Jxy(nb), Jz(nb), hz(L)] of ``SpinSectorOperator``) over the sectors ndown = 0 .. L, or over the list
+    ``sectors``.  Every sector contributes ``sector_trace_measure(op, R, k, seed, dense_below)`` at m = L / 2 - ndown; the two
+    one-state sectors ndown = 0 and ndown = L, which the operator refuses, contribute their energy sum_t Jz_t +- sum_i hz_i from
+    host arithmetic.  One sector's tables are released before the next sector is built."""
+    from .operators import SpinSectorOperator, _check_bonds
+    L = int(L)
+    bonds = _check_bonds(L, bonds)
+    nb = len(bonds)
+    c = torch.as_tensor(couplings, dtype=F64).detach()
+    if tuple(c.shape) != (2 * nb + L,):
+        raise ValueError("couplings must have shape (%d,): Jxy(nb), Jz(nb), hz(L)" % (2 * nb + L))
+    sectors = list(range(L + 1)) if sectors is None else [int(s) for s in sectors]
+    if not sectors or any(not 0 <= s <= L for s in sectors) or len(set(sectors)) != len(sectors):
+        raise ValueError("sectors must be distinct values of ndown in 0 .. %d" % L)
+    host = c.cpu()
+    jz_sum, hz_sum = float(host[nb:2 * nb].sum()), float(host[2 * nb:].sum())
+    if device is None:
+        device = c.device if c.is_cuda else "cuda"
+    entries = []
+    for ndown in sectors:
+        m = 0.5 * L - ndown
+        if ndown in (0, L):
+            energy = jz_sum + (hz_sum if ndown == 0 else -hz_sum)
+            entries.append((SpectralMeasure(torch.tensor([energy], dtype=F64), torch.ones(1, dtype=F64), 1.0, 1), m))
+            continue
+        op = SpinSectorOperator(L, bonds, c.to(device), ndown, device)
+        entries.append((sector_trace_measure(op, R=R, k=k, seed=seed, dense_below=dense_below), m))
+        del op
+    return ThermalEnsemble(entries)

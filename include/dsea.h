@@ -990,6 +990,29 @@ int dsea_hubbard_ladder_forms(int L, int nup_src, int ndn_src, int species, int 
                               const int32_t *lo_rank_src, const int32_t *hi_base_src, const double *v1, const double *v2,
                               double *out, double *scratch, int grid_log2, void *stream);
 
+/* ------------------------------------------------------------------ block sector mat-vec, block Lanczos (docs/design/27-finite-temperature.md)
+ * The operator of dsea_op_create_sector applied to R vectors at once, and the basis-free Lanczos recurrence on it.  A block is fp64
+ * [n, R] row-major (element (r, j) at r * R + j), 16-byte aligned (DSEA_ERR_ALIGN otherwise), R in {1, 2, 4, 8}.  The library
+ * allocates nothing; every check is host arithmetic before any device work.  DSEA_ERR_ARG: any other operator kind, R outside
+ * {1, 2, 4, 8}, k < 1, a null pointer, X == Y, Q == W.  DSEA_TUNE_TFIM_TILE_LOG2 of the handle caps the grid as for its mat-vec.
+ * dsea_op_sector_block_apply: Y = H X; column j of Y equals the single-vector mat-vec of column j of X bit for bit.
+ * dsea_op_sector_block_lanczos: k steps of the three-term recurrence for every column, WITHOUT a stored basis and without
+ * re-orthogonalisation; nothing is read back during the run and the call does not synchronise.  Q [n, R]: the start block, any
+ * norms (normalised on the device), overwritten; W [n, R]: work; on return both hold the last two Lanczos blocks.  norm2 [R]:
+ * |start column|^2.  alphas [k, R], betas [k, R] row-major: alphas[i, j] = alpha_i, betas[i, j] = beta_{i+1} of column j.  steps
+ * [R]: column j breaks at the first s with beta_s <= 1e-13 max(its earlier |alpha|, |beta|) (the rule of dsea_lanczos_status;
+ * a start column of norm 0 breaks at s = 0): steps[j] = s, its leading s x s block of T holds exact eigenvalues, the column is
+ * zeroed, its entries alphas[i >= s, j] and betas[i >= s - 1, j] are 0, and the other columns go on; steps[j] = k otherwise.
+ * Every reduction runs in fixed order (no floating-point atomics): identical calls return identical bits.  scratch:
+ * caller-owned, dsea_op_sector_block_lanczos_scratch_doubles(L, ndown, R) = 64 + 2 R min(4096, ceil(n / 256)) doubles (enough
+ * for every grid cap). */
+int dsea_op_sector_block_apply(dsea_op_t op, int R, const double *X, double *Y, void *stream);
+int dsea_op_sector_block_lanczos_scratch_doubles(int L, int ndown, int R, int64_t *out);
+int dsea_op_sector_block_lanczos(dsea_op_t op, int R, int k, double *Q /* [n,R] in: start block, any norms; overwritten */,
+                                 double *W /* [n,R] work */, double *norm2 /* [R] out: |start column|^2 */,
+                                 double *alphas /* [k,R] */, double *betas /* [k,R]: betas[i,j] = beta_{i+1} */,
+                                 int32_t *steps /* [R]: k, or the break step */, double *scratch, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
