@@ -13,8 +13,8 @@ empty; users import sub-modules by name):
                                         HubbardLadder (c+, c and n maps between Hubbard sectors), one_body_density_matrix
     dominantsparseeigenad_amd.spectral  lanczos_measure, SpectralMeasure, dynamical_structure_factor,
                                         hubbard_spectral_function (re-exported here)
-    dominantsparseeigenad_amd.thermal   block_lanczos_measures, sector_trace_measure, ThermalEnsemble, spin_thermodynamics
-                                        (finite temperature; re-exported here)
+    dominantsparseeigenad_amd.thermal   block_lanczos_measures, sector_trace_measure, ThermalEnsemble, spin_thermodynamics,
+                                        GrandCanonicalEnsemble, hubbard_thermodynamics (finite temperature; re-exported here)
 
 The top-level ``DominantSparseEigenAD`` package in this repository re-exports the same modules
 under the reference's import names.
@@ -29,7 +29,8 @@ def __getattr__(name):
         import importlib
         mod = importlib.import_module(__name__ + ".spectral")
         return mod if name == "spectral" else getattr(mod, name)
-    if name in ("thermal", "block_lanczos_measures", "sector_trace_measure", "ThermalEnsemble", "spin_thermodynamics"):
+    if name in ("thermal", "block_lanczos_measures", "sector_trace_measure", "ThermalEnsemble", "spin_thermodynamics",
+                "GrandCanonicalEnsemble", "hubbard_thermodynamics"):
         import importlib
         mod = importlib.import_module(__name__ + ".thermal")
         return mod if name == "thermal" else getattr(mod, name)

@@ -2118,6 +2118,31 @@ int dsea_op_sector_block_lanczos(dsea_op_t op, int R, int k, double* Q, double* 
   return check_launch();
 }
 
+int dsea_op_hubbard_block_apply(dsea_op_t op, int R, const double* X, double* Y, void* stream) {
+  REQUIRE(op && op->d.kind == OP_HUBBARD && block_width_ok(R) && X && Y && X != Y, DSEA_ERR_ARG);
+  REQUIRE(aligned16(X) && aligned16(Y), DSEA_ERR_ALIGN);
+  if (launch_hubbard_block_apply(op->d, R, X, Y, static_cast<hipStream_t>(stream)) < 0) return DSEA_ERR_UNSUPPORTED;
+  return check_launch();
+}
+
+int dsea_op_hubbard_block_lanczos_scratch_doubles(int L, int nup, int ndn, int R, int64_t* out) {
+  int64_t n, n_up, n_dn;
+  REQUIRE(out && hubbard_sizes(L, nup, ndn, &n, &n_up, &n_dn) && block_width_ok(R), DSEA_ERR_ARG);
+  *out = sector_block_lanczos_scratch_doubles(n, R);   // (the layout is the recurrence driver's, whatever the operator)
+  return DSEA_OK;
+}
+
+int dsea_op_hubbard_block_lanczos(dsea_op_t op, int R, int k, double* Q, double* W, double* norm2, double* alphas, double* betas,
+                                  int32_t* steps, double* scratch, void* stream) {
+  REQUIRE(op && op->d.kind == OP_HUBBARD && block_width_ok(R) && k >= 1 && Q && W && Q != W && norm2 && alphas && betas && steps &&
+              scratch,
+          DSEA_ERR_ARG);
+  REQUIRE(aligned16(Q) && aligned16(W), DSEA_ERR_ALIGN);
+  if (launch_hubbard_block_lanczos(op->d, R, k, Q, W, norm2, alphas, betas, steps, scratch, static_cast<hipStream_t>(stream)) != 0)
+    return DSEA_ERR_UNSUPPORTED;
+  return check_launch();
+}
+
 int dsea_hubbard_ladder_apply(int L, int nup_src, int ndn_src, int species, int step, const double* weights_dev,
                               const int64_t* states_dst, const int32_t* lo_rank_src, const int32_t* hi_base_src, const double* x,
                               double* y, int grid_log2, void* stream) {

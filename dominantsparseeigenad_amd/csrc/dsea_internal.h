@@ -579,6 +579,19 @@ int64_t sector_block_lanczos_scratch_doubles(int64_t n, int R);
 int launch_sector_block_apply(const OpDesc& op, int R, const double* X, double* Y, hipStream_t st);
 int launch_sector_block_lanczos(const OpDesc& op, int R, int k, double* Q, double* W, double* norm2, double* alphas, double* betas,
                                 int32_t* steps, double* scratch, hipStream_t st);
+// The driver of that recurrence for any operator (defined in dsea_sector_block.hip, beside the recurrence kernels it launches):
+// the start and k steps on nblk blocks of 256 rows, the mat-vec of a step being the caller's step(q, w, state, first, PA), which
+// launches W = H q - w diag(state[0 .. R)) over w (first != 0: W = H q, w is not read) with the partials of q_j . W_j in
+// PA[j * nblk + block].  Scratch as sector_block_lanczos_scratch_doubles(n, R).  Returns 0.
+typedef std::function<void(const double* q, double* w, const double* state, int first, double* PA)> BlockLanczosStep;
+int block_lanczos_drive(int64_t n, int nblk, int R, int k, double* Q, double* W, double* norm2, double* alphas, double* betas,
+                        int32_t* steps, double* scratch, hipStream_t st, const BlockLanczosStep& step);
+// dsea_hubbard_block.hip (the Hubbard Hamiltonian on a block of R vectors, docs/design/28-hubbard-finite-temperature.md): the twins
+// of launch_sector_block_apply and launch_sector_block_lanczos for an OP_HUBBARD descriptor; column j of Y = H X is bit for bit
+// the single-vector mat-vec without a shift.  -1 when the descriptor is out of range; the callers check R.
+int launch_hubbard_block_apply(const OpDesc& op, int R, const double* X, double* Y, hipStream_t st);
+int launch_hubbard_block_lanczos(const OpDesc& op, int R, int k, double* Q, double* W, double* norm2, double* alphas, double* betas,
+                                 int32_t* steps, double* scratch, hipStream_t st);
 // dsea_cg_persist_tfim_big.hip
 bool cg_persist_tfim_big_applicable(const OpDesc& op);
 size_t cg_persist_tfim_big_comm_bytes(int64_t n);

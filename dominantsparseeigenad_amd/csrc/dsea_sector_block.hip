@@ -1,6 +1,8 @@
 // dsea_sector_block.hip -- the bond-list sector Hamiltonian of dsea_sector.hip applied to a BLOCK of R vectors at once, and the
 // basis-free block Lanczos recurrence built on it (docs/design/27-finite-temperature.md): k_spmv_sector_block<R, LZ>,
-// k_sblock_norm<R>, k_sblock_update<R>, k_sblock_finish<R>, and their launchers.
+// k_sblock_norm<R>, k_sblock_update<R>, k_sblock_finish<R>, and their launchers.  The recurrence kernels know nothing about the
+// operator: block_lanczos_drive runs them around a caller's mat-vec step, for this file's kernel and for the Hubbard block
+// kernel of dsea_hubbard_block.hip alike.
 //
 // A block is an fp64 array [n, R], row-major (element (r, j) at r * R + j), 16-byte aligned, R in {1, 2, 4, 8}.  One row per
 // thread: the row's state word and the two table reads of a flipped bond are paid once for all R columns, and every gather
@@ -363,13 +365,12 @@ int launch_sector_block_apply(const OpDesc& op, int R, const double* X, double* 
   return nblk;
 }
 
-// start (norm, finish) and k steps of three launches each; nothing is read back.  Q and W change roles from step to step.
-int launch_sector_block_lanczos(const OpDesc& op, int R, int k, double* Q, double* W, double* norm2, double* alphas, double* betas,
-                                int32_t* steps, double* scratch, hipStream_t st) {
-  SectorBlockParams p;
-  if (!sector_block_params(op, &p)) return -1;
-  const int nblk = sector_block_blocks(op);
-  const int64_t n = op.n;
+// The recurrence for any operator: start (norm, finish) and k steps of three launches each -- the caller's mat-vec step, update,
+// finish; nothing is read back.  Q and W change roles from step to step.  step(q, w, state, first, PA) launches, on st and with
+// nblk blocks, W = H q - w diag(state[0 .. R)) over w (first: W = H q, w not read) and the partials PA[j * nblk + block] of
+// q_j . W_j.
+int block_lanczos_drive(int64_t n, int nblk, int R, int k, double* Q, double* W, double* norm2, double* alphas, double* betas,
+                        int32_t* steps, double* scratch, hipStream_t st, const BlockLanczosStep& step) {
   double* state[2] = {scratch, scratch + DSEA_SBLOCK_STATE};
   double* PA = scratch + 2 * DSEA_SBLOCK_STATE;
   double* PB = PA + (int64_t)R * nblk;
@@ -380,7 +381,7 @@ int launch_sector_block_lanczos(const OpDesc& op, int R, int k, double* Q, doubl
     double* q = Q;
     double* w = W;
     for (int i = 0; i < k; ++i) {
-      klaunch(nullptr, k_spmv_sector_block<RR, true>, nblk, 256, 0, st, p, q, w, state[i & 1], i == 0 ? 1 : 0, PA);
+      step(q, w, state[i & 1], i == 0 ? 1 : 0, PA);
       klaunch(nullptr, k_sblock_update<RR>, nblk, 256, 0, st, q, w, n, PA, nblk, alphas + (int64_t)i * RR, PB);
       klaunch(nullptr, k_sblock_finish<RR>, nblk, 256, 0, st, w, q, n, PB, nblk, alphas + (int64_t)i * RR, betas + (int64_t)i * RR,
               state[i & 1], state[(i + 1) & 1], steps, i + 1, k);
@@ -390,6 +391,21 @@ int launch_sector_block_lanczos(const OpDesc& op, int R, int k, double* Q, doubl
     }
   });
   return 0;
+}
+
+// the recurrence with this file's mat-vec as the step
+int launch_sector_block_lanczos(const OpDesc& op, int R, int k, double* Q, double* W, double* norm2, double* alphas, double* betas,
+                                int32_t* steps, double* scratch, hipStream_t st) {
+  SectorBlockParams p;
+  if (!sector_block_params(op, &p)) return -1;
+  const int nblk = sector_block_blocks(op);
+  return block_lanczos_drive(op.n, nblk, R, k, Q, W, norm2, alphas, betas, steps, scratch, st,
+                             [&](const double* q, double* w, const double* state, int first, double* PA) {
+                               dispatch_block_width(R, [&](auto r) {
+                                 klaunch(nullptr, k_spmv_sector_block<decltype(r)::value, true>, nblk, 256, 0, st, p, q, w, state,
+                                         first, PA);
+                               });
+                             });
 }
 
 }  // namespace dsea

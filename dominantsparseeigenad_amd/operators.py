@@ -2283,6 +2283,24 @@ class HubbardOperator:
 
     __call__ = H
 
+    def apply_block(self, X):
+        """H X for a device tensor X of shape (n, R), any R >= 1: all columns in one pass over the rows per block of 8, 4, 2 or
+        1 columns (dsea_op_hubbard_block_apply, docs/design/28-hubbard-finite-temperature.md); column j equals ``H(X[:, j])`` bit
+        for bit.  Plain, not differentiable: X is detached."""
+        from .thermal import _as_block, block_pieces
+        X = _as_block(self, X, "apply_block")
+        lib = _lib.load()
+        out = []
+        for first, w in block_pieces(X.shape[1]):
+            Xp = X[:, first:first + w].to(F64).contiguous()
+            if Xp.data_ptr() % 16:
+                Xp = Xp.clone()
+            Yp = torch.empty_like(Xp)
+            check(lib.dsea_op_hubbard_block_apply(self.handle, w, c_void_p(Xp.data_ptr()), c_void_p(Yp.data_ptr()),
+                                                  engine._stream(Xp.device)), "dsea_op_hubbard_block_apply")
+            out.append(Yp)
+        return out[0] if len(out) == 1 else torch.cat(out, dim=1)
+
     def Hadjoint_to_couplingsadjoint(self, v1, v2):
         """adjoint hook: couplings-bar[p] = v1^T (dH/dp) v2, shape (2 nb + 2 L,)"""
         return _HubbardForms.apply(v1, v2, self, self._H)

@@ -175,7 +175,7 @@ _HUBBARD_CHANNELS = {"c_up": ("up", -1), "c_dn": ("dn", -1), "cdag_up": ("up", 1
                      "sz": (None, 0)}
 
 
-def hubbard_spectral_function(op0, psi0, E0, weights, channel, k=200, target=None):
+def hubbard_spectral_function(op0, psi0, E0, weights, channel, k=200, target=None, basis_free=False):
     """The spectral measure of O psi0 as a function of the excitation energy E - E0, for the eigenstate (psi0, E0) of the
     ``HubbardOperator`` ``op0`` and the site-weighted operator (docs/design/25-hubbard-ladder.md)
 
@@ -189,7 +189,10 @@ def hubbard_spectral_function(op0, psi0, E0, weights, channel, k=200, target=Non
     <a + ib| f(H) |a + ib> cancel.  ``target`` is the Hamiltonian of the destination sector; ``None`` builds it from the bonds
     and couplings of ``op0`` at the new particle numbers, on new tables.  ``k`` Lanczos steps per real vector.  A removal
     measure comes out in E_n - E0 >= 0 like every other; ``reflected()`` places it at omega = E0 - E_n, so that
-    ``cdag + c.reflected()`` is the one-particle spectral function A(omega).  Plain numbers: not differentiable."""
+    ``cdag + c.reflected()`` is the one-particle spectral function A(omega).  ``basis_free=True``: the real and the imaginary
+    part run as one block of 1 or 2 columns through ``thermal.block_lanczos_measures`` -- no stored basis, no
+    re-orthogonalisation, memory independent of k (docs/design/28-hubbard-finite-temperature.md).  Plain numbers: not
+    differentiable."""
     from .operators import HubbardLadder, HubbardOperator
     if channel not in _HUBBARD_CHANNELS:
         raise ValueError("channel must be one of %s, got %r" % (", ".join(repr(c) for c in _HUBBARD_CHANNELS), channel))
@@ -209,11 +212,19 @@ def hubbard_spectral_function(op0, psi0, E0, weights, channel, k=200, target=Non
         raise ValueError("channel %r needs a target with the %s count changed by %d, got (nup, ndn) = (%d, %d)"
                          % (channel, species or "no", step, target.nup, target.ndn))
     psi0 = psi0.detach()
+
+    def excited(w):
+        phi = ladders[0](w, psi0)
+        return phi + sign * ladders[1](w, psi0) if step == 0 else phi
+
+    if basis_free:
+        from .thermal import block_lanczos_measures
+        Phi = torch.stack([excited(w).detach() for w in _weight_parts(weights)], dim=1)
+        parts = block_lanczos_measures(target, Phi, k)
+        total = parts[0] if len(parts) == 1 else parts[0] + parts[1]
+        return total.shifted(float(E0))
     total = None
     for w in _weight_parts(weights):
-        phi = ladders[0](w, psi0)
-        if step == 0:
-            phi = phi + sign * ladders[1](w, psi0)
-        part = lanczos_measure(target, phi, k)
+        part = lanczos_measure(target, excited(w), k)
         total = part if total is None else total + part
     return total.shifted(float(E0))

@@ -1,22 +1,26 @@
-"""Finite temperature by the finite-temperature Lanczos method (docs/design/27-finite-temperature.md).
+"""Finite temperature by the finite-temperature Lanczos method (docs/design/27-finite-temperature.md for spins,
+docs/design/28-hubbard-finite-temperature.md for the Hubbard model).
 
     tr f(H) in a sector of dimension n  ~=  (n / R) sum_r <r| f(H) |r>     over R random unit vectors r
 
 and every <r| f(H) |r> is the Gauss quadrature sum_j S_{0j}^2 f(theta_j) of the k x k Lanczos matrix T = S diag(theta) S^T of r:
 a ``SpectralMeasure``.  The runs keep NO basis and do not re-orthogonalise (the quadrature does not need it): all R vectors go
-through the three-term recurrence at once as one [n, R] block, on the block mat-vec of ``SpinSectorOperator``; the k x k
-eigenproblems are solved on the host.
+through the three-term recurrence at once as one [n, R] block, on the block mat-vec of ``SpinSectorOperator`` or of
+``HubbardOperator``; the k x k eigenproblems are solved on the host.
 
     block_lanczos_coefficients(op, Phi, k)  norm2, alphas, betas and steps of the R columns of Phi, basis-free
     block_lanczos_measures(op, Phi, k)      their measures
     sector_trace_measure(op, R, k, seed)    a measure with sum_j w_j f(theta_j) ~= tr f(H_sector); exact for small sectors
     ThermalEnsemble(entries)                ln Z, E, C, S and chi of a list of (measure, m) over a tensor of inverse temperatures
     spin_thermodynamics(L, bonds, couplings, ...)   the ensemble over all magnetisation sectors of a bond-list XXZ model
+    GrandCanonicalEnsemble(entries)         ln Xi, <H>, <N>, kappa, chi_s, C and S of a list of (measure, nup, ndn) over (beta, mu)
+    hubbard_thermodynamics(L, bonds, couplings, ...)   that ensemble over all (nup, ndn) sectors of a Hubbard model
 
 Plain host float64 numbers: nothing here is differentiable.
 """
 from __future__ import annotations
 
+import math
 from ctypes import byref, c_int64, c_void_p
 
 import torch
@@ -43,10 +47,21 @@ def block_pieces(R):
 
 
 def _sector_operator(op, what):
-    from .operators import SpinSectorOperator
-    if not isinstance(op, SpinSectorOperator):
-        raise ValueError("%s works on the bond-list SpinSectorOperator only, got %s" % (what, type(op).__name__))
+    from .operators import HubbardOperator, SpinSectorOperator
+    if not isinstance(op, (SpinSectorOperator, HubbardOperator)):
+        raise ValueError("%s works on the bond-list SpinSectorOperator and on the HubbardOperator only, got %s"
+                         % (what, type(op).__name__))
     return op
+
+
+def _block_lanczos_entries(op, lib):
+    """(scratch query with the sector's sizes bound, run, the run's name) of the operator's kind: the pair of ABI entries"""
+    from .operators import HubbardOperator
+    if isinstance(op, HubbardOperator):
+        return (lambda w, out: lib.dsea_op_hubbard_block_lanczos_scratch_doubles(op.N, op.nup, op.ndn, w, out),
+                lib.dsea_op_hubbard_block_lanczos, "dsea_op_hubbard_block_lanczos")
+    return (lambda w, out: lib.dsea_op_sector_block_lanczos_scratch_doubles(op.N, op.ndown, w, out),
+            lib.dsea_op_sector_block_lanczos, "dsea_op_sector_block_lanczos")
 
 
 def _as_block(op, X, what):
@@ -76,38 +91,38 @@ def _tridiagonal_measure(alphas, betas, norm2):
 def block_lanczos_coefficients(op, Phi, k):
     """(norm2 [R], alphas [k, R], betas [k, R], steps [R]) of the basis-free recurrence for the R columns of ``Phi`` as host
     tensors, k cut to n: norm2[j] = |Phi[:, j]|^2, alphas[i, j] = alpha_i and betas[i, j] = beta_{i+1} of column j, steps[j] = k or
-    the step at which column j broke (dsea_op_sector_block_lanczos, in blocks of 8, 4, 2 and 1 columns)."""
+    the step at which column j broke (dsea_op_sector_block_lanczos, or dsea_op_hubbard_block_lanczos for a ``HubbardOperator``, in
+    blocks of 8, 4, 2 and 1 columns)."""
     op = _sector_operator(op, "block_lanczos_coefficients")
     k = min(int(k), int(op.n))
     if k < 1:
         raise ValueError("the block Lanczos run needs k >= 1")
     Phi = _as_block(op, Phi, "block_lanczos_coefficients")
     lib = _lib.load()
+    scratch_doubles, run, name = _block_lanczos_entries(op, lib)
     dev = Phi.device
     out = []
     for first, w in block_pieces(Phi.shape[1]):
         Q = Phi[:, first:first + w].to(F64).clone(memory_format=torch.contiguous_format)   # (overwritten by the run)
         W = torch.empty_like(Q)
         need = c_int64()
-        check(lib.dsea_op_sector_block_lanczos_scratch_doubles(op.N, op.ndown, w, byref(need)),
-              "dsea_op_sector_block_lanczos_scratch_doubles")
+        check(scratch_doubles(w, byref(need)), name + "_scratch_doubles")
         scratch = torch.empty(need.value, dtype=F64, device=dev)
         norm2 = torch.empty(w, dtype=F64, device=dev)
         alphas = torch.empty((k, w), dtype=F64, device=dev)
         betas = torch.empty((k, w), dtype=F64, device=dev)
         steps = torch.empty(w, dtype=torch.int32, device=dev)
-        check(lib.dsea_op_sector_block_lanczos(op.handle, w, k, c_void_p(Q.data_ptr()), c_void_p(W.data_ptr()),
-                                               c_void_p(norm2.data_ptr()), c_void_p(alphas.data_ptr()), c_void_p(betas.data_ptr()),
-                                               c_void_p(steps.data_ptr()), c_void_p(scratch.data_ptr()), engine._stream(dev)),
-              "dsea_op_sector_block_lanczos")
+        check(run(op.handle, w, k, c_void_p(Q.data_ptr()), c_void_p(W.data_ptr()), c_void_p(norm2.data_ptr()),
+                  c_void_p(alphas.data_ptr()), c_void_p(betas.data_ptr()), c_void_p(steps.data_ptr()),
+                  c_void_p(scratch.data_ptr()), engine._stream(dev)), name)
         out.append((norm2.cpu(), alphas.cpu(), betas.cpu(), steps.cpu()))
     return tuple(torch.cat([piece[i] for piece in out], dim=-1) for i in range(4))
 
 
 def block_lanczos_measures(op, Phi, k):
     """The spectral measures of the R columns of ``Phi`` (a device tensor (n, R), any R >= 1, any norms) under the
-    ``SpinSectorOperator`` ``op``, from min(k, n) steps of the three-term recurrence WITHOUT a stored basis and without
-    re-orthogonalisation: memory is two blocks plus scratch whatever k is.  Columns go through the kernels in blocks of 8, 4, 2
+    ``SpinSectorOperator`` or ``HubbardOperator`` ``op``, from min(k, n) steps of the three-term recurrence WITHOUT a stored
+    basis and without re-orthogonalisation: memory is two blocks plus scratch whatever k is.  Columns go through the kernels in blocks of 8, 4, 2
     and 1.  A column whose Krylov space is exhausted at step s reports ``steps = s`` (its poles are then exact eigenvalues)
     while the other columns go on; a zero column gives the empty measure.  Returns a list of R ``SpectralMeasure``.  Not
     differentiable: Phi is detached."""
@@ -123,7 +138,8 @@ def block_lanczos_measures(op, Phi, k):
 
 
 def sector_trace_measure(op, R=8, k=100, seed=0, dense_below=256):
-    """A ``SpectralMeasure`` with sum_j w_j f(theta_j) ~= tr f(H) over the sector of the ``SpinSectorOperator`` ``op``.
+    """A ``SpectralMeasure`` with sum_j w_j f(theta_j) ~= tr f(H) over the sector of ``op``, a ``SpinSectorOperator`` or a
+    ``HubbardOperator``.
 
     n <= ``dense_below``: EXACT -- H is formed by ``op.apply_block`` on the identity columns, eight at a time, its eigenvalues
     (``torch.linalg.eigvalsh`` on the host) are the poles and the weights are 1.  Otherwise the R start vectors are
@@ -253,3 +269,192 @@ def spin_thermodynamics(L, bonds, couplings, R=8, k=100, seed=0, dense_below=256
         entries.append((sector_trace_measure(op, R=R, k=k, seed=seed, dense_below=dense_below), m))
         del op
     return ThermalEnsemble(entries)
+
+
+class GrandCanonicalEnsemble:
+    """Grand-canonical averages over a list of ``(measure, nup, ndn)``: ``measure`` a ``SpectralMeasure`` with
+    sum_j w_j f(theta_j) = tr f(H) of the sector with ``nup`` up and ``ndn`` down particles (``sector_trace_measure`` on a
+    ``HubbardOperator``).  Per pole N = nup + ndn, Sz = (nup - ndn) / 2 and K = theta - mu N; with
+    p_j = w_j exp(-beta K_j) / Xi over all poles of all entries:
+
+        logZ(beta, mu)                 ln Xi = ln sum_j w_j exp(-beta K_j)     (log-sum-exp shifted by the lowest K per (beta, mu))
+        energy(beta, mu)               <H> = sum_j p_j theta_j
+        density(beta, mu)              <N> = sum_j p_j N_j
+        compressibility(beta, mu)      beta sum_j p_j (N_j - <N>)^2 = d<N> / d mu
+        spin_susceptibility(beta, mu)  beta sum_j p_j (Sz_j - <Sz>)^2
+        specific_heat(beta, mu)        beta^2 sum_j p_j (K_j - <K>)^2: the specific heat at FIXED mu, not at fixed <N>
+        entropy(beta, mu)              ln Xi + beta (<H> - mu <N>)
+        moment(p)                      sum_j w_j theta_j^p = tr H^p
+
+    ``beta`` >= 0 and ``mu`` are numbers or tensors that broadcast against each other; the results are host float64 tensors of
+    the broadcast shape.  The variances are sums of squared deviations, not differences of two means.  A list of sectors that all
+    share N is the canonical ensemble: mu then only shifts ln Xi by beta mu N.  Plain numbers: not differentiable."""
+
+    def __init__(self, entries):
+        entries = list(entries)
+        if not entries:
+            raise ValueError("GrandCanonicalEnsemble needs at least one (measure, nup, ndn) entry")
+        poles, weights, ns, szs = [], [], [], []
+        for entry in entries:
+            if not (isinstance(entry, (tuple, list)) and len(entry) == 3 and isinstance(entry[0], SpectralMeasure)):
+                raise ValueError("every entry must be a (SpectralMeasure, nup, ndn) triple, got %r" % (entry,))
+            measure, nup, ndn = entry
+            poles.append(measure.poles)
+            weights.append(measure.weights)
+            ns.append(torch.full((len(measure),), float(nup) + float(ndn), dtype=F64))
+            szs.append(torch.full((len(measure),), 0.5 * (float(nup) - float(ndn)), dtype=F64))
+        self.entries = [(e[0], int(e[1]), int(e[2])) for e in entries]
+        self.poles, self.weights = torch.cat(poles), torch.cat(weights)
+        self.N, self.Sz = torch.cat(ns), torch.cat(szs)
+        if self.poles.numel() == 0:
+            raise ValueError("GrandCanonicalEnsemble needs at least one pole")
+        if bool((self.weights < 0).any()):
+            raise ValueError("the weights of a trace measure must not be negative")
+
+    def _boltzmann(self, beta, mu):
+        """(beta [...], mu [...], K [..., poles], its lowest value [...], sum_j w_j exp(-beta (K_j - lowest)) [...], p [..., poles])"""
+        beta = torch.as_tensor(beta, dtype=F64).detach().cpu()
+        mu = torch.as_tensor(mu, dtype=F64).detach().cpu()
+        if bool((beta < 0).any()):
+            raise ValueError("GrandCanonicalEnsemble works at inverse temperatures beta >= 0")
+        beta, mu = torch.broadcast_tensors(beta, mu)
+        K = self.poles - mu.unsqueeze(-1) * self.N
+        lowest = K.min(dim=-1).values
+        terms = self.weights * torch.exp(-beta.unsqueeze(-1) * (K - lowest.unsqueeze(-1)))
+        total = terms.sum(dim=-1)
+        return beta, mu, K, lowest, total, terms / total.unsqueeze(-1)
+
+    @staticmethod
+    def _variance(p, values):
+        mean = (p * values).sum(dim=-1)
+        return (p * (values - mean.unsqueeze(-1)) ** 2).sum(dim=-1)
+
+    def logZ(self, beta, mu):
+        beta, _, _, lowest, total, _ = self._boltzmann(beta, mu)
+        return torch.log(total) - beta * lowest
+
+    def energy(self, beta, mu):
+        p = self._boltzmann(beta, mu)[-1]
+        return (p * self.poles).sum(dim=-1)
+
+    def density(self, beta, mu):
+        p = self._boltzmann(beta, mu)[-1]
+        return (p * self.N).sum(dim=-1)
+
+    def compressibility(self, beta, mu):
+        beta, _, _, _, _, p = self._boltzmann(beta, mu)
+        return beta * self._variance(p, self.N)
+
+    def spin_susceptibility(self, beta, mu):
+        beta, _, _, _, _, p = self._boltzmann(beta, mu)
+        return beta * self._variance(p, self.Sz)
+
+    def specific_heat(self, beta, mu):
+        """beta^2 (<K^2> - <K>^2) with K = H - mu N: the specific heat at fixed chemical potential"""
+        beta, _, K, _, _, p = self._boltzmann(beta, mu)
+        return beta ** 2 * self._variance(p, K)
+
+    def entropy(self, beta, mu):
+        beta, _, K, lowest, total, p = self._boltzmann(beta, mu)
+        return torch.log(total) - beta * lowest + beta * (p * K).sum(dim=-1)
+
+    def moment(self, p):
+        return float((self.weights * self.poles ** int(p)).sum())
+
+
+def one_species_matrix(L, bonds, couplings, count, other_full):
+    """The dense Hamiltonian (host float64, rows in the order of ``sector_states(L, count)``) that one species of the Hubbard
+    model of ``HubbardOperator`` sees when it has ``count`` particles and the OTHER species is empty (``other_full`` False) or
+    full: the in-species hops -t_t (-1)^(particles strictly between a_t and b_t), and the diagonal of the full model with the
+    other species' bits all 0 or all 1.  ``couplings`` = [t(nb), V(nb), U(L), eps(L)] as a host tensor."""
+    from .operators import sector_states
+    nb = len(bonds)
+    c = torch.as_tensor(couplings, dtype=F64).detach().cpu()
+    t, V, U, eps = c[:nb], c[nb:2 * nb], c[2 * nb:2 * nb + L], c[2 * nb + L:]
+    states = torch.tensor(sector_states(L, count), dtype=torch.int64)
+    n = states.numel()
+    f = 1 if other_full else 0
+    occ = [((states >> i) & 1) + f for i in range(L)]
+    diag = torch.zeros(n, dtype=F64)
+    for i in range(L):
+        diag = diag + U[i] * (((states >> i) & 1) * f).to(F64) + eps[i] * occ[i].to(F64)
+    H = torch.zeros((n, n), dtype=F64)
+    rows = torch.arange(n)
+    for k, (a, b) in enumerate(bonds):
+        diag = diag + V[k] * (occ[a] * occ[b]).to(F64)
+        lo, hi = min(a, b), max(a, b)
+        moves = (((states >> a) ^ (states >> b)) & 1).bool()
+        src = rows[moves]
+        w = states[moves]
+        jumped = torch.zeros_like(w)
+        for i in range(lo + 1, hi):
+            jumped = jumped + ((w >> i) & 1)
+        amp = -t[k] * (1.0 - 2.0 * (jumped & 1).to(F64))
+        dst = torch.searchsorted(states, w ^ ((1 << a) | (1 << b)))
+        H.index_put_((dst, src), amp, accumulate=True)
+    H[rows, rows] += diag
+    return H
+
+
+def hubbard_thermodynamics(L, bonds, couplings, R=8, k=100, seed=0, dense_below=256, sectors=None, spin_symmetric=True,
+                           edge_dense_max=4096, device=None):
+    """The ``GrandCanonicalEnsemble`` of the Hubbard model of ``HubbardOperator`` (its Hamiltonian and its parameter order
+    [t(nb), V(nb), U(L), eps(L)]) over all sectors (nup, ndn) in {0 .. L}^2, or over the list ``sectors`` of distinct pairs.
+
+    A bulk sector, 1 <= nup, ndn <= L - 1, contributes ``sector_trace_measure(op, R, k, seed, dense_below)`` of its
+    ``HubbardOperator``; one sector's operator and tables are released before the next is built.  An edge sector -- a species
+    empty or full, which the operator refuses -- is always exact: the other species sees ``one_species_matrix``, whose
+    eigenvalues (host ``eigvalsh``) enter with weight 1; a one-species dimension above ``edge_dense_max`` raises ``ValueError``;
+    both species frozen is one state from host arithmetic.  ``spin_symmetric=True``: H has no spin-dependent term, so the
+    sectors (a, b) and (b, a) share a spectrum; only nup >= ndn is computed and the measure is entered for both."""
+    from .operators import HubbardOperator, _check_bonds
+    L = int(L)
+    if not 2 <= L <= _lib.SECTOR_MAX_L:
+        raise ValueError("hubbard_thermodynamics needs 2 <= L <= %d, got %d" % (_lib.SECTOR_MAX_L, L))
+    bonds = _check_bonds(L, bonds)
+    nb = len(bonds)
+    c = torch.as_tensor(couplings, dtype=F64).detach()
+    if tuple(c.shape) != (2 * nb + 2 * L,):
+        raise ValueError("couplings must have shape (%d,): t(nb), V(nb), U(L), eps(L)" % (2 * nb + 2 * L))
+    if sectors is None:
+        sectors = [(a, b) for a in range(L + 1) for b in range(L + 1)]
+    else:
+        sectors = [(int(a), int(b)) for a, b in sectors]
+    if not sectors or any(not (0 <= a <= L and 0 <= b <= L) for a, b in sectors) or len(set(sectors)) != len(sectors):
+        raise ValueError("sectors must be distinct pairs (nup, ndn) with both counts in 0 .. %d" % L)
+    for nup, ndn in sectors:                                    # (refused before any sector is computed)
+        if (nup in (0, L)) != (ndn in (0, L)):
+            n = math.comb(L, ndn if nup in (0, L) else nup)
+            if n > int(edge_dense_max):
+                raise ValueError("the edge sector (nup, ndn) = (%d, %d) has a one-species dimension of %d, above edge_dense_max = %d"
+                                 % (nup, ndn, n, int(edge_dense_max)))
+    host = c.cpu()
+    if device is None:
+        device = c.device if c.is_cuda else "cuda"
+    on_device = None
+
+    def measure(nup, ndn):
+        nonlocal on_device
+        frozen = [s for s in (nup, ndn) if s in (0, L)]
+        if len(frozen) == 2:
+            energy = one_species_matrix(L, bonds, host, nup, ndn == L)
+            return SpectralMeasure(energy.reshape(1), torch.ones(1, dtype=F64), 1.0, 1)
+        if frozen:
+            count, other = (ndn, nup) if nup in (0, L) else (nup, ndn)
+            n = math.comb(L, count)
+            poles = torch.linalg.eigvalsh(one_species_matrix(L, bonds, host, count, other == L))
+            return SpectralMeasure(poles, torch.ones(n, dtype=F64), float(n), n)
+        if on_device is None:
+            on_device = c.to(device)
+        op = HubbardOperator(L, bonds, on_device, nup, ndn, device)
+        out = sector_trace_measure(op, R=R, k=k, seed=seed, dense_below=dense_below)
+        del op
+        return out
+
+    entries, done = [], {}
+    for nup, ndn in sectors:
+        key = (max(nup, ndn), min(nup, ndn)) if spin_symmetric else (nup, ndn)
+        if key not in done:
+            done[key] = measure(*key)
+        entries.append((done[key], nup, ndn))
+    return GrandCanonicalEnsemble(entries)

@@ -1013,6 +1013,23 @@ int dsea_op_sector_block_lanczos(dsea_op_t op, int R, int k, double *Q /* [n,R] 
                                  double *alphas /* [k,R] */, double *betas /* [k,R]: betas[i,j] = beta_{i+1} */,
                                  int32_t *steps /* [R]: k, or the break step */, double *scratch, void *stream);
 
+/* ------------------------------------------------------------------ block Hubbard mat-vec, block Lanczos (docs/design/28-hubbard-finite-temperature.md)
+ * The operator of dsea_op_create_hubbard applied to R vectors at once, and the same basis-free Lanczos recurrence on it: the twins
+ * of the three entries above, with the same blocks (fp64 [n, R] row-major, 16-byte aligned, DSEA_ERR_ALIGN otherwise, R in
+ * {1, 2, 4, 8}), the same outputs, break rule and scratch layout.  The library allocates nothing; every check is host
+ * arithmetic before any device work.  DSEA_ERR_ARG: any other operator kind, R outside {1, 2, 4, 8}, k < 1, a null pointer,
+ * X == Y, Q == W, and in the scratch query (L, nup, ndn) outside the limits of dsea_hubbard_sizes.
+ * dsea_op_hubbard_block_apply: Y = H X; column j of Y equals dsea_op_apply without a shift on column j of X bit for bit.
+ * dsea_op_hubbard_block_lanczos: as dsea_op_sector_block_lanczos.  scratch: caller-owned,
+ * dsea_op_hubbard_block_lanczos_scratch_doubles(L, nup, ndn, R) = 64 + 2 R min(4096, ceil(n / 256)) doubles (enough for every
+ * grid cap). */
+int dsea_op_hubbard_block_apply(dsea_op_t op, int R, const double *X, double *Y, void *stream);
+int dsea_op_hubbard_block_lanczos_scratch_doubles(int L, int nup, int ndn, int R, int64_t *out);
+int dsea_op_hubbard_block_lanczos(dsea_op_t op, int R, int k, double *Q /* [n,R] in: start block, any norms; overwritten */,
+                                  double *W /* [n,R] work */, double *norm2 /* [R] out: |start column|^2 */,
+                                  double *alphas /* [k,R] */, double *betas /* [k,R]: betas[i,j] = beta_{i+1} */,
+                                  int32_t *steps /* [R]: k, or the break step */, double *scratch, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
