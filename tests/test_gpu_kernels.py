@@ -5,7 +5,8 @@ operand norms (sum-order differences only).
 
 The conjugate-gradient entries (dsea_shift_dot, the CG phases, dsea_cg_step) are judged one call at a time, bit for bit on exact
 inputs and to operation-count bounds on random ones, in tests/test_gpu_cg_stages.py; the dsea_cg_step test here compares whole
-solves."""
+solves.  The symmetric Lanczos step entries (dsea_lanczos_rdots, dsea_lanczos_axpy_norm, dsea_ritz_combine, the stores, the
+callable step and dsea_lanczos_partial_step) are judged the same way, in every kernel geometry, in tests/test_gpu_lanczos_stages.py."""
 from ctypes import byref, c_void_p
 
 import numpy as np
