@@ -56,6 +56,37 @@ class _SymmetricApply(torch.autograd.Function):
         return _SymmetricApply.apply(gy, ctx.view), None
 
 
+def _cuda_device(name, device, couplings=None, what="operator", index=True):
+    """the device of the device object ``name``: ``device``, else the device of the tensor ``couplings``, else "cuda";
+    ValueError for a host device.  With ``index``, "cuda" becomes "cuda:<current>", so that tensors on the device compare
+    equal (this asks the runtime: host checks that must come first pass ``index=False`` and call again)."""
+    if device is None:
+        device = couplings.device if torch.is_tensor(couplings) else "cuda"
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise ValueError("%s is a device %s; use device='cuda'" % (name, what))
+    if index and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    return device
+
+
+def _csr_regular(cols, vals, n, layout, col16, values):
+    """the CSR operand of (n, per) column and value tensors with ``per`` distinct columns in every row, sorted row by row"""
+    order = torch.argsort(cols, dim=1)
+    cols, vals = torch.gather(cols, 1, order), torch.gather(vals, 1, order)
+    rowptr = torch.arange(n + 1, dtype=torch.int64, device=cols.device) * cols.shape[1]
+    return CSROperator(rowptr, cols.reshape(-1), vals.reshape(-1).contiguous(), n, layout=layout, col16=col16, values=values)
+
+
+def _csr_from_coo(rows, cols, vals, n, layout, col16, values):
+    """the CSR operand of the entries (rows[k], cols[k], vals[k]), each a list of tensors; no (row, column) is listed twice"""
+    rows, cols, vals = torch.cat(rows), torch.cat(cols), torch.cat(vals)
+    order = torch.argsort(rows * n + cols)
+    rowptr = torch.zeros(n + 1, dtype=torch.int64, device=rows.device)
+    rowptr[1:] = torch.cumsum(torch.bincount(rows, minlength=n), 0)
+    return CSROperator(rowptr, cols[order], vals[order].contiguous(), n, layout=layout, col16=col16, values=values)
+
+
 # ------------------------------------------------------------------------------------------ TFIM
 class TFIMOperator:
     """H = -sum_i (g sx_i + sz_i sz_{i+1}) on a periodic chain of L sites, dimension 2^L, matrix-free.
@@ -76,11 +107,7 @@ class TFIMOperator:
         self.row_offset = int(row_offset)
         self.dim = 1 << self.N
         self.n = 1 << self.L_local
-        self.device = torch.device(device if device is not None else "cuda")
-        if self.device.type != "cuda":
-            raise ValueError("TFIMOperator is a device operator; use device='cuda'")
-        if self.device.index is None:   # "cuda" -> "cuda:<current>", so that tensors on the device compare equal
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = _cuda_device("TFIMOperator", device)
         self._g = None
         self._H = None
         lib = _lib.load()
@@ -135,11 +162,7 @@ class TFIMOperator:
         for j in range(L):
             cols[:, j + 1] = idx ^ (1 << j)
             vals[:, j + 1] = -self._g.detach()
-        order = torch.argsort(cols, dim=1)
-        cols = torch.gather(cols, 1, order)
-        vals = torch.gather(vals, 1, order)
-        rowptr = torch.arange(n + 1, dtype=torch.int64, device=self.device) * (L + 1)
-        return CSROperator(rowptr, cols.reshape(-1), vals.reshape(-1), n, layout=layout, col16=col16, values=values)
+        return _csr_regular(cols, vals, n, layout, col16, values)
 
     def pHpg(self, v):
         """dH/dg v = -sum_j v[i xor (1<<j)]   (TFIM.py:58-65)"""
@@ -174,42 +197,197 @@ class _TFIMApply(torch.autograd.Function):
         return gv, gg, None
 
 
+# ------------------------------------------------------------------------------------------ operators linear in a couplings tensor
+def _set_tuning(view, log2):
+    check(_lib.load().dsea_op_set_tuning(view.handle, _lib.TUNE_TFIM_TILE_LOG2, int(log2)), "dsea_op_set_tuning")
+    view.tune_log2 = int(log2)
+
+
+def _flat_bonds(bonds):
+    """the bond list as the flat c_int32 array a0, b0, a1, b1, ... of the create calls"""
+    return (c_int32 * (2 * len(bonds)))(*[s for bond in bonds for s in bond])
+
+
+def _pack(device, values, sizes):
+    """coupling families (each a scalar, or ``size`` values) as one contiguous float64 parameter tensor on ``device``"""
+    parts = []
+    for value, size in zip(values, sizes):
+        t = torch.as_tensor(value, dtype=F64).to(device)
+        parts.append(t.expand(size) if t.dim() == 0 else t.reshape(size))
+    return torch.cat(parts).contiguous()
+
+
+def _build_sector_tables(L, count, rows, device):
+    """(states, lo_rank, hi_base) of the ``rows`` L-bit words with ``count`` set bits, on ``device``: dsea_sector_build_tables"""
+    Llo = (L + 1) // 2
+    states = torch.empty(rows, dtype=torch.int64, device=device)
+    lo_rank = torch.empty(1 << Llo, dtype=torch.int32, device=device)
+    hi_base = torch.empty(1 << (L - Llo), dtype=torch.int32, device=device)
+    with torch.cuda.device(device):
+        check(_lib.load().dsea_sector_build_tables(L, count, c_void_p(states.data_ptr()), c_void_p(lo_rank.data_ptr()),
+                                                   c_void_p(hi_base.data_ptr()), engine._stream(device)),
+              "dsea_sector_build_tables")
+    return states, lo_rank, hi_base
+
+
+def _table_rank(tables, Llo, s):
+    """the rank of every word in the int64 device tensor ``s`` among the words of its popcount: the two-table lookup"""
+    _, lo_rank, hi_base = tables
+    return hi_base[s >> Llo].to(torch.int64) + lo_rank[s & ((1 << Llo) - 1)].to(torch.int64)
+
+
+def _apply_block(op, X, entry):
+    """H X for a device tensor X of shape (n, R) by the block mat-vec ``entry`` of the library, per block of 8, 4, 2 or 1 columns"""
+    from .thermal import _as_block, block_pieces
+    X = _as_block(op, X, "apply_block")
+    apply = getattr(_lib.load(), entry)
+    out = []
+    for first, w in block_pieces(X.shape[1]):
+        Xp = X[:, first:first + w].to(F64).contiguous()
+        if Xp.data_ptr() % 16:
+            Xp = Xp.clone()
+        Yp = torch.empty_like(Xp)
+        check(apply(op.handle, w, c_void_p(Xp.data_ptr()), c_void_p(Yp.data_ptr()), engine._stream(Xp.device)), entry)
+        out.append(Yp)
+    return out[0] if len(out) == 1 else torch.cat(out, dim=1)
+
+
+class _CouplingsOperator:
+    """What the six matrix-free Hamiltonians that are LINEAR in one float64 couplings tensor share
+    (docs/design/30-couplings-operator-base.md): the ``couplings`` binding, the handle, the differentiable ``H`` and its adjoint
+    hook, and the tuning that a rebinding and an adjoint handle carry over.
+
+    A subclass sets, with host arithmetic first, ``N``, ``n``, ``dim``, ``device`` and whatever its create call reads, then calls
+    ``_bind(couplings)``.  It provides
+      * ``_families``: the coupling families in the order of the tensor, for the error message;
+      * ``_shape``: the shape of the couplings tensor, ``(nparam,)`` unless overridden;
+      * ``_create(data) -> (raw, keepalive)``: the library handle whose kernels read the prepared (detached, float64,
+        contiguous) tensor ``data`` through its pointer, and what that handle needs alive -- ``data`` itself and the tables;
+      * ``_forms_stem`` and ``_forms_sizes``: ``<stem>_forms`` is the library's forms call and ``_forms_sizes`` the integers its
+        ``<stem>_forms_scratch_doubles`` takes;
+      * ``set_tile_log2`` or ``set_grid_log2`` on ``_set_tune_log2``."""
+
+    _native_methods = ("H", "__call__")
+
+    def _bind(self, couplings):
+        self._c = None
+        self._H = None
+        self._tune_log2 = None
+        self.couplings = couplings
+
+    @property
+    def _shape(self):
+        return (self.nparam,)
+
+    @property
+    def couplings(self):
+        return self._c
+
+    @couplings.setter
+    def couplings(self, value):
+        if not torch.is_tensor(value):
+            value = torch.as_tensor(value, dtype=F64).to(self.device)
+        if value.device != self.device or value.dtype != F64:
+            raise ValueError("couplings must be a float64 tensor on %s" % self.device)
+        if tuple(value.shape) != self._shape or not value.is_contiguous():
+            raise ValueError("couplings must be a contiguous tensor of shape %s: %s" % (self._shape, self._families))
+        self._c = value
+        self._H = self._view(value)          # the kernels read the couplings through this tensor's pointer
+        if self._tune_log2 is not None:
+            _set_tuning(self._H, self._tune_log2)
+
+    def _view(self, couplings, like=None):
+        """(handle, n) of this Hamiltonian (its geometry and its tables) with the tensor ``couplings`` as couplings; ``like``: a
+        view whose tuning the new handle takes over."""
+        data = couplings.detach()
+        if data.dtype != F64 or not data.is_contiguous():
+            data = data.to(F64).contiguous()
+        raw, keepalive = self._create(data)
+        view = _NativeView(_Handle(raw, self.n, keepalive))
+        view.tune_log2 = None
+        if like is not None and like.tune_log2 is not None:
+            _set_tuning(view, like.tune_log2)
+        return view
+
+    def _forms(self, view, v1, v2):
+        """all bilinear forms v1^T (dH/dp) v2 in the shape of the couplings (<stem>_forms: one pass, deterministic)"""
+        lib = _lib.load()
+        v1, v2 = engine.as_vector(v1, view.n), engine.as_vector(v2, view.n)
+        need = c_int64()
+        sizer = self._forms_stem + "_forms_scratch_doubles"
+        check(getattr(lib, sizer)(*self._forms_sizes, byref(need)), sizer)
+        scratch = torch.empty(need.value, dtype=F64, device=v1.device)
+        out = torch.empty(self._shape, dtype=F64, device=v1.device)
+        check(getattr(lib, self._forms_stem + "_forms")(view.handle, c_void_p(v1.data_ptr()), c_void_p(v2.data_ptr()),
+                                                        c_void_p(out.data_ptr()), c_void_p(scratch.data_ptr()),
+                                                        engine._stream(v1.device)), self._forms_stem + "_forms")
+        return out
+
+    def _set_tune_log2(self, log2):
+        """the one tuning integer of a handle (DSEA_TUNE_TFIM_TILE_LOG2: the tile of the full-space kernels, the grid cap of the
+        sector kernels), kept for the handles of later bindings"""
+        _set_tuning(self._H, log2)
+        self._tune_log2 = int(log2)
+
+    @property
+    def handle(self):
+        return self._H.handle
+
+    def H(self, v):
+        """H v, differentiable in v and in the couplings"""
+        return _CouplingsApply.apply(v, self._c, self, self._H)
+
+    __call__ = H
+
+    def Hadjoint_to_couplingsadjoint(self, v1, v2):
+        """adjoint hook: couplings-bar[t] = v1^T (dH/dp_t) v2, in the shape of the couplings"""
+        return _CouplingsForms.apply(v1, v2, self, self._H)
+
+
+class _CouplingsApply(torch.autograd.Function):
+    """y = H[c] v of a ``_CouplingsOperator``.  Backward: H[c] gy (symmetric) and the forms(gy, v) -- both re-entrant."""
+
+    @staticmethod
+    def forward(ctx, v, c, op, view):
+        ctx.op, ctx.view = op, view
+        ctx.save_for_backward(v, c)
+        return engine.spmv(view, v.detach())
+
+    @staticmethod
+    def backward(ctx, gy):
+        v, c = ctx.saved_tensors
+        gv = _CouplingsApply.apply(gy, c, ctx.op, ctx.view) if ctx.needs_input_grad[0] else None
+        gc = _CouplingsForms.apply(gy, v, ctx.op, ctx.view).reshape(c.shape) if ctx.needs_input_grad[1] else None
+        return gv, gc, None, None
+
+
+class _CouplingsForms(torch.autograd.Function):
+    """out[t] = v1^T (dH/dp_t) v2 in the shape of the couplings.  H is linear in the couplings, so with the incoming adjoint G as
+    couplings the backward is d/dv1 = H[G] v2 and d/dv2 = H[G] v1: the same mat-vec kernel through a second handle on the same
+    geometry and tables, which both products share."""
+
+    @staticmethod
+    def forward(ctx, v1, v2, op, view):
+        ctx.op, ctx.view = op, view
+        ctx.save_for_backward(v1, v2)
+        return op._forms(view, v1.detach(), v2.detach())
+
+    @staticmethod
+    def backward(ctx, G):
+        v1, v2 = ctx.saved_tensors
+        g1 = g2 = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            G = G.reshape(ctx.op._shape)
+            adj = ctx.op._view(G, like=ctx.view)      # the Hamiltonian whose couplings are the adjoint
+            if ctx.needs_input_grad[0]:
+                g1 = _CouplingsApply.apply(v2, G, ctx.op, adj)
+            if ctx.needs_input_grad[1]:
+                g2 = _CouplingsApply.apply(v1, G, ctx.op, adj)
+        return g1, g2, None, None
+
+
 # ------------------------------------------------------------------------------------------ XYZ spin chain
-def _chain_view(L, couplings, like=None):
-    """(handle, n) of the chain Hamiltonian whose couplings are the (5, L) tensor ``couplings``; ``like``: a view whose tile
-    tuning the new handle takes over."""
-    data = couplings.detach()
-    if data.dtype != F64 or not data.is_contiguous():
-        data = data.to(F64).contiguous()
-    raw = c_void_p()
-    check(_lib.load().dsea_op_create_chain(int(L), c_void_p(data.data_ptr()), byref(raw)), "dsea_op_create_chain")
-    view = _NativeView(_Handle(raw, 1 << int(L), data))
-    view.tile_log2 = None
-    if like is not None and like.tile_log2 is not None:
-        _set_chain_tile(view, like.tile_log2)
-    return view
-
-
-def _set_chain_tile(view, tile_log2):
-    check(_lib.load().dsea_op_set_tuning(view.handle, _lib.TUNE_TFIM_TILE_LOG2, int(tile_log2)), "dsea_op_set_tuning")
-    view.tile_log2 = int(tile_log2)
-
-
-def _chain_forms(view, L, v1, v2):
-    """all 5 L bilinear forms v1^T (dH/dp) v2 as a (5, L) tensor (dsea_op_chain_forms: one pass, deterministic)"""
-    lib = _lib.load()
-    n = view.n
-    v1, v2 = engine.as_vector(v1, n), engine.as_vector(v2, n)
-    need = c_int64()
-    check(lib.dsea_op_chain_forms_scratch_doubles(int(L), byref(need)), "dsea_op_chain_forms_scratch_doubles")
-    scratch = torch.empty(need.value, dtype=F64, device=v1.device)
-    out = torch.empty((5, int(L)), dtype=F64, device=v1.device)
-    check(lib.dsea_op_chain_forms(view.handle, c_void_p(v1.data_ptr()), c_void_p(v2.data_ptr()), c_void_p(out.data_ptr()),
-                                  c_void_p(scratch.data_ptr()), engine._stream(v1.device)), "dsea_op_chain_forms")
-    return out
-
-
-class SpinChainOperator:
+class SpinChainOperator(_CouplingsOperator):
     """H = sum_b [Jx_b X_b X_b+1 + Jy_b Y_b Y_b+1 + Jz_b Z_b Z_b+1] + sum_i [hx_i X_i + hz_i Z_i] on a periodic chain of L
     sites, dimension 2^L, matrix-free (docs/design/14-spin-chain.md).  Site i is bit i of the row index, bond b joins sites
     b and (b + 1) mod L; an open chain is J_{L-1} = 0; at L = 2 bonds 0 and 1 join the same two sites and both count.
@@ -222,46 +400,30 @@ class SpinChainOperator:
     mat-vec with the incoming (5, L) adjoint as couplings), so second order works as for ``TFIMOperator``.
     Row-partitioned slabs, a fused Lanczos tail and the persistent single-launch forms do not exist for this operator."""
 
-    _native_methods = ("H", "__call__")
+    _families = "rows Jx, Jy, Jz, hx, hz"
+    _forms_stem = "dsea_op_chain"
 
     def __init__(self, L, couplings, device=None):
         self.N = int(L)
         if not 2 <= self.N <= 62:
             raise ValueError("SpinChainOperator needs 2 <= L <= 62, got %d" % self.N)
         self.dim = self.n = 1 << self.N
-        if device is None:
-            device = couplings.device if torch.is_tensor(couplings) else "cuda"
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError("SpinChainOperator is a device operator; use device='cuda'")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        self._c = None
-        self._H = None
-        self._tile_log2 = None
-        self.couplings = couplings
+        self.device = _cuda_device("SpinChainOperator", device, couplings)
+        self._forms_sizes = (self.N,)
+        self._bind(couplings)
 
     @property
-    def couplings(self):
-        return self._c
+    def _shape(self):
+        return (5, self.N)
 
-    @couplings.setter
-    def couplings(self, value):
-        if not torch.is_tensor(value):
-            value = torch.as_tensor(value, dtype=F64).to(self.device)
-        if value.device != self.device or value.dtype != F64:
-            raise ValueError("couplings must be a float64 tensor on %s" % self.device)
-        if tuple(value.shape) != (5, self.N) or not value.is_contiguous():
-            raise ValueError("couplings must be a contiguous tensor of shape (5, %d): rows Jx, Jy, Jz, hx, hz" % self.N)
-        self._c = value
-        self._H = _chain_view(self.N, value)          # the kernels read the couplings through this tensor's pointer
-        if self._tile_log2 is not None:
-            _set_chain_tile(self._H, self._tile_log2)
+    def _create(self, data):
+        raw = c_void_p()
+        check(_lib.load().dsea_op_create_chain(self.N, c_void_p(data.data_ptr()), byref(raw)), "dsea_op_create_chain")
+        return raw, data
 
     def set_tile_log2(self, tile_log2):
         """log2 of the rows of x a block stages in LDS (6..12; measurement aid, dsea_op_set_tuning)"""
-        _set_chain_tile(self._H, tile_log2)
-        self._tile_log2 = int(tile_log2)
+        self._set_tune_log2(tile_log2)
 
     @classmethod
     def tfim(cls, L, g, device=None):
@@ -271,20 +433,6 @@ class SpinChainOperator:
         c[2] = -1.0
         c[3] = -float(g)
         return cls(L, c, dev)
-
-    @property
-    def handle(self):
-        return self._H.handle
-
-    def H(self, v):
-        """H v, differentiable in v and in the couplings"""
-        return _ChainApply.apply(v, self._c, self, self._H)
-
-    __call__ = H
-
-    def Hadjoint_to_couplingsadjoint(self, v1, v2):
-        """adjoint hook: couplings-bar[t] = v1^T (dH/dp_t) v2, shape (5, L)"""
-        return _ChainForms.apply(v1, v2, self, self._H)
 
     def to_csr(self, layout="sell", col16="auto", values="auto"):
         """The same matrix as an explicit device CSR operand (2 L + 1 stored entries per row; at L = 2 the two bonds share a
@@ -308,53 +456,7 @@ class SpinChainOperator:
         for v, col in bond:
             cols.append(col)
             vals.append(v)
-        cols, vals = torch.stack(cols, dim=1), torch.stack(vals, dim=1)
-        order = torch.argsort(cols, dim=1)
-        cols, vals = torch.gather(cols, 1, order), torch.gather(vals, 1, order)
-        per = cols.shape[1]
-        rowptr = torch.arange(n + 1, dtype=torch.int64, device=self.device) * per
-        return CSROperator(rowptr, cols.reshape(-1), vals.reshape(-1).contiguous(), n, layout=layout, col16=col16, values=values)
-
-
-class _ChainApply(torch.autograd.Function):
-    """y = H[c] v.  Backward: H[c] gy (symmetric) and the forms(gy, v) -- both re-entrant."""
-
-    @staticmethod
-    def forward(ctx, v, c, op, view):
-        ctx.op, ctx.view = op, view
-        ctx.save_for_backward(v, c)
-        return engine.spmv(view, v.detach())
-
-    @staticmethod
-    def backward(ctx, gy):
-        v, c = ctx.saved_tensors
-        gv = _ChainApply.apply(gy, c, ctx.op, ctx.view) if ctx.needs_input_grad[0] else None
-        gc = _ChainForms.apply(gy, v, ctx.op, ctx.view).reshape(c.shape) if ctx.needs_input_grad[1] else None
-        return gv, gc, None, None
-
-
-class _ChainForms(torch.autograd.Function):
-    """out[t] = v1^T (dH/dp_t) v2, shape (5, L).  H is linear in the couplings, so with the incoming adjoint G as couplings the
-    backward is d/dv1 = H[G] v2 and d/dv2 = H[G] v1: the same mat-vec kernel."""
-
-    @staticmethod
-    def forward(ctx, v1, v2, op, view):
-        ctx.op, ctx.view = op, view
-        ctx.save_for_backward(v1, v2)
-        return _chain_forms(view, op.N, v1.detach(), v2.detach())
-
-    @staticmethod
-    def backward(ctx, G):
-        v1, v2 = ctx.saved_tensors
-        g1 = g2 = None
-        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
-            G = G.reshape(5, ctx.op.N)
-            adj = _chain_view(ctx.op.N, G, like=ctx.view)     # the chain Hamiltonian whose couplings are the adjoint
-            if ctx.needs_input_grad[0]:
-                g1 = _ChainApply.apply(v2, G, ctx.op, adj)
-            if ctx.needs_input_grad[1]:
-                g2 = _ChainApply.apply(v1, G, ctx.op, adj)
-        return g1, g2, None, None
+        return _csr_regular(torch.stack(cols, dim=1), torch.stack(vals, dim=1), n, layout, col16, values)
 
 
 # ------------------------------------------------------------------------------------------ XYZ spins on a bond list
@@ -396,38 +498,7 @@ def _check_bonds(L, bonds):
     return out
 
 
-def _lattice_view(L, bonds, couplings, like=None):
-    """(handle, n) of the bond-list Hamiltonian whose couplings are the (3 nb + 2 L,) tensor ``couplings``; ``like``: a view
-    whose tile tuning the new handle takes over."""
-    data = couplings.detach()
-    if data.dtype != F64 or not data.is_contiguous():
-        data = data.to(F64).contiguous()
-    flat = (c_int32 * (2 * len(bonds)))(*[s for bond in bonds for s in bond])
-    raw = c_void_p()
-    check(_lib.load().dsea_op_create_lattice(int(L), len(bonds), flat, c_void_p(data.data_ptr()), byref(raw)),
-          "dsea_op_create_lattice")
-    view = _NativeView(_Handle(raw, 1 << int(L), data))
-    view.tile_log2 = None
-    if like is not None and like.tile_log2 is not None:
-        _set_chain_tile(view, like.tile_log2)
-    return view
-
-
-def _lattice_forms(view, L, nb, v1, v2):
-    """all 3 nb + 2 L bilinear forms v1^T (dH/dp) v2 (dsea_op_lattice_forms: one pass, deterministic)"""
-    lib = _lib.load()
-    n = view.n
-    v1, v2 = engine.as_vector(v1, n), engine.as_vector(v2, n)
-    need = c_int64()
-    check(lib.dsea_op_lattice_forms_scratch_doubles(int(L), int(nb), byref(need)), "dsea_op_lattice_forms_scratch_doubles")
-    scratch = torch.empty(need.value, dtype=F64, device=v1.device)
-    out = torch.empty(3 * int(nb) + 2 * int(L), dtype=F64, device=v1.device)
-    check(lib.dsea_op_lattice_forms(view.handle, c_void_p(v1.data_ptr()), c_void_p(v2.data_ptr()), c_void_p(out.data_ptr()),
-                                    c_void_p(scratch.data_ptr()), engine._stream(v1.device)), "dsea_op_lattice_forms")
-    return out
-
-
-class SpinLatticeOperator:
+class SpinLatticeOperator(_CouplingsOperator):
     """H = sum_t [Jx_t X_a X_b + Jy_t Y_a Y_b + Jz_t Z_a Z_b] + sum_i [hx_i X_i + hz_i Z_i] on L sites, dimension 2^L,
     matrix-free, with bond t joining the sites ``bonds[t] = (a_t, b_t)`` of a caller-given list
     (docs/design/16-spin-lattice.md).  Site i is bit i of the row index; (a, b) and (b, a) are the same bond; a repeated bond
@@ -442,7 +513,8 @@ class SpinLatticeOperator:
     so second order works as for ``SpinChainOperator``.
     Row-partitioned slabs, a fused Lanczos tail and the persistent single-launch forms do not exist for this operator."""
 
-    _native_methods = ("H", "__call__")
+    _families = "Jx(nb), Jy(nb), Jz(nb), hx(L), hz(L)"
+    _forms_stem = "dsea_op_lattice"
 
     def __init__(self, L, bonds, couplings, device=None):
         self.N = int(L)
@@ -452,54 +524,28 @@ class SpinLatticeOperator:
         self.nb = len(self._bonds)
         self.nparam = 3 * self.nb + 2 * self.N
         self.dim = self.n = 1 << self.N
-        if device is None:
-            device = couplings.device if torch.is_tensor(couplings) else "cuda"
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError("SpinLatticeOperator is a device operator; use device='cuda'")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        self._c = None
-        self._H = None
-        self._tile_log2 = None
-        self.couplings = couplings
+        self.device = _cuda_device("SpinLatticeOperator", device, couplings)
+        self._forms_sizes = (self.N, self.nb)
+        self._bind(couplings)
+
+    def _create(self, data):
+        raw = c_void_p()
+        check(_lib.load().dsea_op_create_lattice(self.N, self.nb, _flat_bonds(self._bonds), c_void_p(data.data_ptr()),
+                                                 byref(raw)), "dsea_op_create_lattice")
+        return raw, data
 
     @property
     def bonds(self):
         """the bond list as a tuple of (a, b) pairs, in the order of the couplings (read-only)"""
         return self._bonds
 
-    @property
-    def couplings(self):
-        return self._c
-
-    @couplings.setter
-    def couplings(self, value):
-        if not torch.is_tensor(value):
-            value = torch.as_tensor(value, dtype=F64).to(self.device)
-        if value.device != self.device or value.dtype != F64:
-            raise ValueError("couplings must be a float64 tensor on %s" % self.device)
-        if tuple(value.shape) != (self.nparam,) or not value.is_contiguous():
-            raise ValueError("couplings must be a contiguous tensor of shape (%d,): Jx(nb), Jy(nb), Jz(nb), hx(L), hz(L)"
-                             % self.nparam)
-        self._c = value
-        self._H = _lattice_view(self.N, self._bonds, value)   # the kernels read the couplings through this tensor's pointer
-        if self._tile_log2 is not None:
-            _set_chain_tile(self._H, self._tile_log2)
-
     def set_tile_log2(self, tile_log2):
         """log2 of the rows of x a block stages in LDS (6..12; measurement aid, dsea_op_set_tuning)"""
-        _set_chain_tile(self._H, tile_log2)
-        self._tile_log2 = int(tile_log2)
+        self._set_tune_log2(tile_log2)
 
     def pack(self, Jx, Jy, Jz, hx, hz):
         """the five families (scalars, or one value per bond / per site) as one parameter tensor on the operator's device"""
-        sizes = (self.nb, self.nb, self.nb, self.N, self.N)
-        parts = []
-        for value, size in zip((Jx, Jy, Jz, hx, hz), sizes):
-            t = torch.as_tensor(value, dtype=F64).to(self.device)
-            parts.append(t.expand(size) if t.dim() == 0 else t.reshape(size))
-        return torch.cat(parts).contiguous()
+        return _pack(self.device, (Jx, Jy, Jz, hx, hz), (self.nb, self.nb, self.nb, self.N, self.N))
 
     def unpack(self, t):
         """views (Jx, Jy, Jz, hx, hz) of a parameter tensor"""
@@ -507,20 +553,6 @@ class SpinLatticeOperator:
         if tuple(t.shape) != (self.nparam,):
             raise ValueError("expected a tensor of shape (%d,)" % self.nparam)
         return t[:nb], t[nb:2 * nb], t[2 * nb:3 * nb], t[3 * nb:3 * nb + L], t[3 * nb + L:]
-
-    @property
-    def handle(self):
-        return self._H.handle
-
-    def H(self, v):
-        """H v, differentiable in v and in the couplings"""
-        return _LatticeApply.apply(v, self._c, self, self._H)
-
-    __call__ = H
-
-    def Hadjoint_to_couplingsadjoint(self, v1, v2):
-        """adjoint hook: couplings-bar[t] = v1^T (dH/dp_t) v2, shape (3 nb + 2 L,)"""
-        return _LatticeForms.apply(v1, v2, self, self._H)
 
     def to_csr(self, layout="sell", col16="auto", values="auto"):
         """The same matrix as an explicit device CSR operand: the diagonal, L field columns and one column per distinct bond
@@ -546,53 +578,7 @@ class SpinLatticeOperator:
         for m, v in by_mask.items():
             cols.append(idx ^ m)
             vals.append(v)
-        cols, vals = torch.stack(cols, dim=1), torch.stack(vals, dim=1)
-        order = torch.argsort(cols, dim=1)
-        cols, vals = torch.gather(cols, 1, order), torch.gather(vals, 1, order)
-        per = cols.shape[1]
-        rowptr = torch.arange(n + 1, dtype=torch.int64, device=self.device) * per
-        return CSROperator(rowptr, cols.reshape(-1), vals.reshape(-1).contiguous(), n, layout=layout, col16=col16, values=values)
-
-
-class _LatticeApply(torch.autograd.Function):
-    """y = H[c] v.  Backward: H[c] gy (symmetric) and the forms(gy, v) -- both re-entrant."""
-
-    @staticmethod
-    def forward(ctx, v, c, op, view):
-        ctx.op, ctx.view = op, view
-        ctx.save_for_backward(v, c)
-        return engine.spmv(view, v.detach())
-
-    @staticmethod
-    def backward(ctx, gy):
-        v, c = ctx.saved_tensors
-        gv = _LatticeApply.apply(gy, c, ctx.op, ctx.view) if ctx.needs_input_grad[0] else None
-        gc = _LatticeForms.apply(gy, v, ctx.op, ctx.view).reshape(c.shape) if ctx.needs_input_grad[1] else None
-        return gv, gc, None, None
-
-
-class _LatticeForms(torch.autograd.Function):
-    """out[t] = v1^T (dH/dp_t) v2, shape (3 nb + 2 L,).  H is linear in the couplings, so with the incoming adjoint G as
-    couplings the backward is d/dv1 = H[G] v2 and d/dv2 = H[G] v1: the same mat-vec kernel on the same bond list."""
-
-    @staticmethod
-    def forward(ctx, v1, v2, op, view):
-        ctx.op, ctx.view = op, view
-        ctx.save_for_backward(v1, v2)
-        return _lattice_forms(view, op.N, op.nb, v1.detach(), v2.detach())
-
-    @staticmethod
-    def backward(ctx, G):
-        v1, v2 = ctx.saved_tensors
-        g1 = g2 = None
-        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
-            G = G.reshape(ctx.op.nparam)
-            adj = _lattice_view(ctx.op.N, ctx.op.bonds, G, like=ctx.view)   # the Hamiltonian whose couplings are the adjoint
-            if ctx.needs_input_grad[0]:
-                g1 = _LatticeApply.apply(v2, G, ctx.op, adj)
-            if ctx.needs_input_grad[1]:
-                g2 = _LatticeApply.apply(v1, G, ctx.op, adj)
-        return g1, g2, None, None
+        return _csr_regular(torch.stack(cols, dim=1), torch.stack(vals, dim=1), n, layout, col16, values)
 
 
 # ------------------------------------------------------------------------------------------ XXZ spins in one S^z sector
@@ -632,171 +618,18 @@ def _check_sector(L, ndown):
     return L, ndown, n
 
 
-def _sector_view(op, couplings, like=None):
-    """(handle, n) of the sector Hamiltonian of ``op`` (its bonds and its tables) whose couplings are the (2 nb + L,) tensor
-    ``couplings``; ``like``: a view whose grid cap the new handle takes over."""
-    data = couplings.detach()
-    if data.dtype != F64 or not data.is_contiguous():
-        data = data.to(F64).contiguous()
-    bonds = op.bonds
-    flat = (c_int32 * (2 * len(bonds)))(*[s for bond in bonds for s in bond])
-    states, lo_rank, hi_base = op._tables
-    raw = c_void_p()
-    check(_lib.load().dsea_op_create_sector(op.N, op.ndown, len(bonds), flat, c_void_p(data.data_ptr()),
-                                            c_void_p(states.data_ptr()), c_void_p(lo_rank.data_ptr()),
-                                            c_void_p(hi_base.data_ptr()), byref(raw)), "dsea_op_create_sector")
-    view = _NativeView(_Handle(raw, op.n, (data, op._tables)))
-    view.grid_log2 = None
-    if like is not None and like.grid_log2 is not None:
-        _set_sector_grid(view, like.grid_log2)
-    return view
-
-
-def _set_sector_grid(view, grid_log2):
-    check(_lib.load().dsea_op_set_tuning(view.handle, _lib.TUNE_TFIM_TILE_LOG2, int(grid_log2)), "dsea_op_set_tuning")
-    view.grid_log2 = int(grid_log2)
-
-
-def _sector_forms(view, op, v1, v2):
-    """all 2 nb + L bilinear forms v1^T (dH/dp) v2 (dsea_op_sector_forms: one pass, deterministic)"""
-    lib = _lib.load()
-    v1, v2 = engine.as_vector(v1, view.n), engine.as_vector(v2, view.n)
-    need = c_int64()
-    check(lib.dsea_op_sector_forms_scratch_doubles(op.N, op.ndown, op.nb, byref(need)), "dsea_op_sector_forms_scratch_doubles")
-    scratch = torch.empty(need.value, dtype=F64, device=v1.device)
-    out = torch.empty(op.nparam, dtype=F64, device=v1.device)
-    check(lib.dsea_op_sector_forms(view.handle, c_void_p(v1.data_ptr()), c_void_p(v2.data_ptr()), c_void_p(out.data_ptr()),
-                                   c_void_p(scratch.data_ptr()), engine._stream(v1.device)), "dsea_op_sector_forms")
-    return out
-
-
-class SpinSectorOperator:
-    """H = sum_t [Jxy_t (X_a X_b + Y_a Y_b) + Jz_t Z_a Z_b] + sum_i hz_i Z_i on L sites, restricted to the states with exactly
-    ``ndown`` set bits (total S^z fixed), matrix-free (docs/design/18-spin-sector.md).  Sites, bits and ``bonds`` are those of
-    ``SpinLatticeOperator`` (this is its Hamiltonian with Jx = Jy = Jxy and hx = 0); 2 <= L <= 40, 1 <= ndown <= L - 1 and
-    n = C(L, ndown) <= 2^31 - 1.  Row r is the r-th such state in increasing integer order: ``states`` (int64, on the device),
-    ``sector_states(L, ndown)`` on the host.
-
-    ``couplings`` is ONE contiguous float64 device tensor of length 2 nb + L in the order [Jxy(nb), Jz(nb), hz(L)] -- the
-    parameter (it may require grad; ``pack`` / ``unpack`` convert).  The kernels read it through its device pointer on every
-    launch: in-place optimiser steps are seen, binding another tensor makes a new handle on the same tables.  ``H(v)`` is
-    differentiable in v and in ``couplings``; ``Hadjoint_to_couplingsadjoint(v1, v2)`` is the hook for
-    ``setDominantSparseSymeig`` / ``setLowestSparseSymeig``: all 2 nb + L forms in one pass.  Both are re-entrant (H is linear
-    in the couplings), so second order works.  The state table and the two rank tables are built once per operator by the
-    library's kernels and kept alive by it.  ``embed`` / ``restrict`` convert to and from the 2^L space (L <= 30)."""
-
-    _native_methods = ("H", "__call__")
-
-    def __init__(self, L, bonds, couplings, ndown, device=None):
-        self.N, self.ndown, n = _check_sector(L, ndown)
-        self._bonds = _check_bonds(self.N, bonds)
-        self.nb = len(self._bonds)
-        self.nparam = 2 * self.nb + self.N
-        self.dim = self.n = n
-        if device is None:
-            device = couplings.device if torch.is_tensor(couplings) else "cuda"
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError("SpinSectorOperator is a device operator; use device='cuda'")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        self.Llo = (self.N + 1) // 2
-        states = torch.empty(n, dtype=torch.int64, device=self.device)
-        lo_rank = torch.empty(1 << self.Llo, dtype=torch.int32, device=self.device)
-        hi_base = torch.empty(1 << (self.N - self.Llo), dtype=torch.int32, device=self.device)
-        with torch.cuda.device(self.device):
-            check(_lib.load().dsea_sector_build_tables(self.N, self.ndown, c_void_p(states.data_ptr()),
-                                                       c_void_p(lo_rank.data_ptr()), c_void_p(hi_base.data_ptr()),
-                                                       engine._stream(self.device)), "dsea_sector_build_tables")
-        self._tables = (states, lo_rank, hi_base)
-        self._c = None
-        self._H = None
-        self._grid_log2 = None
-        self.couplings = couplings
-
-    @property
-    def bonds(self):
-        """the bond list as a tuple of (a, b) pairs, in the order of the couplings (read-only)"""
-        return self._bonds
+class _SectorRows:
+    """What the two operators whose rows are the states of one S^z sector share: they carry ``N``, ``ndown``, ``Llo``, ``device``
+    and ``_tables = (states, lo_rank, hi_base)``."""
 
     @property
     def states(self):
         """states[r] = the basis state of row r (int64 device tensor, increasing)"""
         return self._tables[0]
 
-    @property
-    def couplings(self):
-        return self._c
-
-    @couplings.setter
-    def couplings(self, value):
-        if not torch.is_tensor(value):
-            value = torch.as_tensor(value, dtype=F64).to(self.device)
-        if value.device != self.device or value.dtype != F64:
-            raise ValueError("couplings must be a float64 tensor on %s" % self.device)
-        if tuple(value.shape) != (self.nparam,) or not value.is_contiguous():
-            raise ValueError("couplings must be a contiguous tensor of shape (%d,): Jxy(nb), Jz(nb), hz(L)" % self.nparam)
-        self._c = value
-        self._H = _sector_view(self, value)     # the kernels read the couplings through this tensor's pointer
-        if self._grid_log2 is not None:
-            _set_sector_grid(self._H, self._grid_log2)
-
-    def set_grid_log2(self, grid_log2):
-        """log2 of the most blocks a launch uses (6..12, default 12; measurement aid, dsea_op_set_tuning)"""
-        _set_sector_grid(self._H, grid_log2)
-        self._grid_log2 = int(grid_log2)
-
-    def pack(self, Jxy, Jz, hz):
-        """the three families (scalars, or one value per bond / per site) as one parameter tensor on the operator's device"""
-        parts = []
-        for value, size in zip((Jxy, Jz, hz), (self.nb, self.nb, self.N)):
-            t = torch.as_tensor(value, dtype=F64).to(self.device)
-            parts.append(t.expand(size) if t.dim() == 0 else t.reshape(size))
-        return torch.cat(parts).contiguous()
-
-    def unpack(self, t):
-        """views (Jxy, Jz, hz) of a parameter tensor"""
-        nb = self.nb
-        if tuple(t.shape) != (self.nparam,):
-            raise ValueError("expected a tensor of shape (%d,)" % self.nparam)
-        return t[:nb], t[nb:2 * nb], t[2 * nb:]
-
-    @property
-    def handle(self):
-        return self._H.handle
-
-    def H(self, v):
-        """H v, differentiable in v and in the couplings"""
-        return _SectorApply.apply(v, self._c, self, self._H)
-
-    __call__ = H
-
-    def apply_block(self, X):
-        """H X for a device tensor X of shape (n, R), any R >= 1: all columns in one pass over the rows per block of 8, 4, 2 or
-        1 columns (dsea_op_sector_block_apply, docs/design/27-finite-temperature.md); column j equals ``H(X[:, j])`` bit for bit.
-        Plain, not differentiable: X is detached."""
-        from .thermal import _as_block, block_pieces
-        X = _as_block(self, X, "apply_block")
-        lib = _lib.load()
-        out = []
-        for first, w in block_pieces(X.shape[1]):
-            Xp = X[:, first:first + w].to(F64).contiguous()
-            if Xp.data_ptr() % 16:
-                Xp = Xp.clone()
-            Yp = torch.empty_like(Xp)
-            check(lib.dsea_op_sector_block_apply(self.handle, w, c_void_p(Xp.data_ptr()), c_void_p(Yp.data_ptr()),
-                                                 engine._stream(Xp.device)), "dsea_op_sector_block_apply")
-            out.append(Yp)
-        return out[0] if len(out) == 1 else torch.cat(out, dim=1)
-
-    def Hadjoint_to_couplingsadjoint(self, v1, v2):
-        """adjoint hook: couplings-bar[t] = v1^T (dH/dp_t) v2, shape (2 nb + L,)"""
-        return _SectorForms.apply(v1, v2, self, self._H)
-
     def rank(self, s):
         """the row of every state in the int64 device tensor ``s`` (states of the sector only): the two-table lookup"""
-        _, lo_rank, hi_base = self._tables
-        return hi_base[s >> self.Llo].to(torch.int64) + lo_rank[s & ((1 << self.Llo) - 1)].to(torch.int64)
+        return _table_rank(self._tables, self.Llo, s)
 
     def embed(self, v):
         """the sector vector v as a vector of the full 2^L space (zero outside the sector); L <= 30"""
@@ -819,6 +652,71 @@ class SpinSectorOperator:
         """the ``SpinSectorLadder`` from this sector to the sector of ``dst`` (ndown + 1, ndown or ndown - 1; ``dst`` may be
         this operator), on the two operators' tables"""
         return SpinSectorLadder(self, dst)
+
+
+class SpinSectorOperator(_SectorRows, _CouplingsOperator):
+    """H = sum_t [Jxy_t (X_a X_b + Y_a Y_b) + Jz_t Z_a Z_b] + sum_i hz_i Z_i on L sites, restricted to the states with exactly
+    ``ndown`` set bits (total S^z fixed), matrix-free (docs/design/18-spin-sector.md).  Sites, bits and ``bonds`` are those of
+    ``SpinLatticeOperator`` (this is its Hamiltonian with Jx = Jy = Jxy and hx = 0); 2 <= L <= 40, 1 <= ndown <= L - 1 and
+    n = C(L, ndown) <= 2^31 - 1.  Row r is the r-th such state in increasing integer order: ``states`` (int64, on the device),
+    ``sector_states(L, ndown)`` on the host.
+
+    ``couplings`` is ONE contiguous float64 device tensor of length 2 nb + L in the order [Jxy(nb), Jz(nb), hz(L)] -- the
+    parameter (it may require grad; ``pack`` / ``unpack`` convert).  The kernels read it through its device pointer on every
+    launch: in-place optimiser steps are seen, binding another tensor makes a new handle on the same tables.  ``H(v)`` is
+    differentiable in v and in ``couplings``; ``Hadjoint_to_couplingsadjoint(v1, v2)`` is the hook for
+    ``setDominantSparseSymeig`` / ``setLowestSparseSymeig``: all 2 nb + L forms in one pass.  Both are re-entrant (H is linear
+    in the couplings), so second order works.  The state table and the two rank tables are built once per operator by the
+    library's kernels and kept alive by it.  ``embed`` / ``restrict`` convert to and from the 2^L space (L <= 30)."""
+
+    _families = "Jxy(nb), Jz(nb), hz(L)"
+    _forms_stem = "dsea_op_sector"
+
+    def __init__(self, L, bonds, couplings, ndown, device=None):
+        self.N, self.ndown, n = _check_sector(L, ndown)
+        self._bonds = _check_bonds(self.N, bonds)
+        self.nb = len(self._bonds)
+        self.nparam = 2 * self.nb + self.N
+        self.dim = self.n = n
+        self.device = _cuda_device("SpinSectorOperator", device, couplings)
+        self.Llo = (self.N + 1) // 2
+        self._tables = _build_sector_tables(self.N, self.ndown, n, self.device)
+        self._forms_sizes = (self.N, self.ndown, self.nb)
+        self._bind(couplings)
+
+    def _create(self, data):
+        states, lo_rank, hi_base = self._tables
+        raw = c_void_p()
+        check(_lib.load().dsea_op_create_sector(self.N, self.ndown, self.nb, _flat_bonds(self._bonds), c_void_p(data.data_ptr()),
+                                                c_void_p(states.data_ptr()), c_void_p(lo_rank.data_ptr()),
+                                                c_void_p(hi_base.data_ptr()), byref(raw)), "dsea_op_create_sector")
+        return raw, (data, self._tables)
+
+    @property
+    def bonds(self):
+        """the bond list as a tuple of (a, b) pairs, in the order of the couplings (read-only)"""
+        return self._bonds
+
+    def set_grid_log2(self, grid_log2):
+        """log2 of the most blocks a launch uses (6..12, default 12; measurement aid, dsea_op_set_tuning)"""
+        self._set_tune_log2(grid_log2)
+
+    def pack(self, Jxy, Jz, hz):
+        """the three families (scalars, or one value per bond / per site) as one parameter tensor on the operator's device"""
+        return _pack(self.device, (Jxy, Jz, hz), (self.nb, self.nb, self.N))
+
+    def unpack(self, t):
+        """views (Jxy, Jz, hz) of a parameter tensor"""
+        nb = self.nb
+        if tuple(t.shape) != (self.nparam,):
+            raise ValueError("expected a tensor of shape (%d,)" % self.nparam)
+        return t[:nb], t[nb:2 * nb], t[2 * nb:]
+
+    def apply_block(self, X):
+        """H X for a device tensor X of shape (n, R), any R >= 1: all columns in one pass over the rows per block of 8, 4, 2 or
+        1 columns (dsea_op_sector_block_apply, docs/design/27-finite-temperature.md); column j equals ``H(X[:, j])`` bit for bit.
+        Plain, not differentiable: X is detached."""
+        return _apply_block(self, X, "dsea_op_sector_block_apply")
 
     def pair_operator(self, couplings=None):
         """the ``SpinSectorPairOperator`` of this sector on the operator's tables; ``couplings=None``: zeros, the correlator
@@ -853,52 +751,7 @@ class SpinSectorOperator:
             r_all.append(flips)
             c_all.append(self.rank(s[flips] ^ m))
             v_all.append(v.expand(flips.numel()))
-        r_all, c_all, v_all = torch.cat(r_all), torch.cat(c_all), torch.cat(v_all)
-        order = torch.argsort(r_all * n + c_all)
-        rowptr = torch.zeros(n + 1, dtype=torch.int64, device=self.device)
-        rowptr[1:] = torch.cumsum(torch.bincount(r_all, minlength=n), 0)
-        return CSROperator(rowptr, c_all[order], v_all[order].contiguous(), n, layout=layout, col16=col16, values=values)
-
-
-class _SectorApply(torch.autograd.Function):
-    """y = H[c] v.  Backward: H[c] gy (symmetric) and the forms(gy, v) -- both re-entrant."""
-
-    @staticmethod
-    def forward(ctx, v, c, op, view):
-        ctx.op, ctx.view = op, view
-        ctx.save_for_backward(v, c)
-        return engine.spmv(view, v.detach())
-
-    @staticmethod
-    def backward(ctx, gy):
-        v, c = ctx.saved_tensors
-        gv = _SectorApply.apply(gy, c, ctx.op, ctx.view) if ctx.needs_input_grad[0] else None
-        gc = _SectorForms.apply(gy, v, ctx.op, ctx.view).reshape(c.shape) if ctx.needs_input_grad[1] else None
-        return gv, gc, None, None
-
-
-class _SectorForms(torch.autograd.Function):
-    """out[t] = v1^T (dH/dp_t) v2, shape (2 nb + L,).  H is linear in the couplings, so with the incoming adjoint G as
-    couplings the backward is d/dv1 = H[G] v2 and d/dv2 = H[G] v1: a second handle on the same tables."""
-
-    @staticmethod
-    def forward(ctx, v1, v2, op, view):
-        ctx.op, ctx.view = op, view
-        ctx.save_for_backward(v1, v2)
-        return _sector_forms(view, op, v1.detach(), v2.detach())
-
-    @staticmethod
-    def backward(ctx, G):
-        v1, v2 = ctx.saved_tensors
-        g1 = g2 = None
-        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
-            G = G.reshape(ctx.op.nparam)
-            adj = _sector_view(ctx.op, G, like=ctx.view)      # the Hamiltonian whose couplings are the adjoint
-            if ctx.needs_input_grad[0]:
-                g1 = _SectorApply.apply(v2, G, ctx.op, adj)
-            if ctx.needs_input_grad[1]:
-                g2 = _SectorApply.apply(v1, G, ctx.op, adj)
-        return g1, g2, None, None
+        return _csr_from_coo(r_all, c_all, v_all, n, layout, col16, values)
 
 
 # ------------------------------------------------------------------------------------------ all-pair XXZ couplings in one S^z sector
@@ -946,38 +799,7 @@ def ring_structure_factor(C):
     return (phase * C[None, :, :]).sum(dim=(1, 2)) / L
 
 
-def _pairsector_view(op, couplings, like=None):
-    """(handle, n) of the all-pair sector Hamiltonian on the tables of ``op`` whose couplings are the (2 P + L,) tensor
-    ``couplings``; ``like``: a view whose grid cap the new handle takes over."""
-    data = couplings.detach()
-    if data.dtype != F64 or not data.is_contiguous():
-        data = data.to(F64).contiguous()
-    states, lo_rank, hi_base = op._tables
-    raw = c_void_p()
-    check(_lib.load().dsea_op_create_pairsector(op.N, op.ndown, c_void_p(data.data_ptr()), c_void_p(states.data_ptr()),
-                                                c_void_p(lo_rank.data_ptr()), c_void_p(hi_base.data_ptr()), byref(raw)),
-          "dsea_op_create_pairsector")
-    view = _NativeView(_Handle(raw, op.n, (data, op._tables)))
-    view.grid_log2 = None
-    if like is not None and like.grid_log2 is not None:
-        _set_sector_grid(view, like.grid_log2)
-    return view
-
-
-def _pairsector_forms(view, op, v1, v2):
-    """all 2 P + L bilinear forms v1^T (dH/dp) v2 (dsea_op_pairsector_forms: deterministic)"""
-    lib = _lib.load()
-    v1, v2 = engine.as_vector(v1, view.n), engine.as_vector(v2, view.n)
-    need = c_int64()
-    check(lib.dsea_op_pairsector_forms_scratch_doubles(op.N, op.ndown, byref(need)), "dsea_op_pairsector_forms_scratch_doubles")
-    scratch = torch.empty(need.value, dtype=F64, device=v1.device)
-    out = torch.empty(op.nparam, dtype=F64, device=v1.device)
-    check(lib.dsea_op_pairsector_forms(view.handle, c_void_p(v1.data_ptr()), c_void_p(v2.data_ptr()), c_void_p(out.data_ptr()),
-                                       c_void_p(scratch.data_ptr()), engine._stream(v1.device)), "dsea_op_pairsector_forms")
-    return out
-
-
-class SpinSectorPairOperator:
+class SpinSectorPairOperator(_SectorRows, _CouplingsOperator):
     """H = sum_{i<j} [Jxy_ij (X_i X_j + Y_i Y_j) + Jz_ij Z_i Z_j] + sum_i hz_i Z_i on L sites with a coupling on EVERY pair of
     sites, restricted to the states with exactly ``ndown`` set bits, matrix-free (docs/design/22-pair-sector.md).  Rows, bits,
     ``states``, the two rank tables and the limits are those of ``SpinSectorOperator``: 2 <= L <= 40, 1 <= ndown <= L - 1,
@@ -994,39 +816,34 @@ class SpinSectorPairOperator:
     ``correlations(v1, v2)`` arranges the forms as the L x L matrices of v1^T (X_i X_j + Y_i Y_j) v2 and v1^T Z_i Z_j v2 and
     the vector v1^T Z_i v2."""
 
-    _native_methods = ("H", "__call__")
+    _families = "Jxy(P), Jz(P), hz(L)"
+    _forms_stem = "dsea_op_pairsector"
 
     def __init__(self, L, couplings, ndown, device=None, _tables=None):
         self.N, self.ndown, n = _check_sector(L, ndown)
         self.npair = pair_count(self.N)
         self.nparam = 2 * self.npair + self.N
         self.dim = self.n = n
-        if device is None:
-            device = couplings.device if torch.is_tensor(couplings) else "cuda"
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError("SpinSectorPairOperator is a device operator; use device='cuda'")
+        self.device = _cuda_device("SpinSectorPairOperator", device, couplings, index=False)
         if torch.is_tensor(couplings) and tuple(couplings.shape) != (self.nparam,):
             raise ValueError("couplings must have shape (%d,): Jxy(P), Jz(P), hz(L) with P = %d" % (self.nparam, self.npair))
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = _cuda_device("SpinSectorPairOperator", self.device)
         self.Llo = (self.N + 1) // 2
         if _tables is None:
-            states = torch.empty(n, dtype=torch.int64, device=self.device)
-            lo_rank = torch.empty(1 << self.Llo, dtype=torch.int32, device=self.device)
-            hi_base = torch.empty(1 << (self.N - self.Llo), dtype=torch.int32, device=self.device)
-            with torch.cuda.device(self.device):
-                check(_lib.load().dsea_sector_build_tables(self.N, self.ndown, c_void_p(states.data_ptr()),
-                                                           c_void_p(lo_rank.data_ptr()), c_void_p(hi_base.data_ptr()),
-                                                           engine._stream(self.device)), "dsea_sector_build_tables")
-            _tables = (states, lo_rank, hi_base)
+            _tables = _build_sector_tables(self.N, self.ndown, n, self.device)
         self._tables = tuple(_tables)
         self._pairs = tuple((i, j) for i in range(self.N) for j in range(i + 1, self.N))
         self._upper = None
-        self._c = None
-        self._H = None
-        self._grid_log2 = None
-        self.couplings = torch.zeros(self.nparam, dtype=F64, device=self.device) if couplings is None else couplings
+        self._forms_sizes = (self.N, self.ndown)
+        self._bind(torch.zeros(self.nparam, dtype=F64, device=self.device) if couplings is None else couplings)
+
+    def _create(self, data):
+        states, lo_rank, hi_base = self._tables
+        raw = c_void_p()
+        check(_lib.load().dsea_op_create_pairsector(self.N, self.ndown, c_void_p(data.data_ptr()), c_void_p(states.data_ptr()),
+                                                    c_void_p(lo_rank.data_ptr()), c_void_p(hi_base.data_ptr()), byref(raw)),
+              "dsea_op_create_pairsector")
+        return raw, (data, self._tables)
 
     @property
     def pairs(self):
@@ -1045,45 +862,21 @@ class SpinSectorPairOperator:
             self._upper = (iu, ju)
         return self._upper
 
-    @property
-    def states(self):
-        """states[r] = the basis state of row r (int64 device tensor, increasing)"""
-        return self._tables[0]
-
-    @property
-    def couplings(self):
-        return self._c
-
-    @couplings.setter
-    def couplings(self, value):
-        if not torch.is_tensor(value):
-            value = torch.as_tensor(value, dtype=F64).to(self.device)
-        if value.device != self.device or value.dtype != F64:
-            raise ValueError("couplings must be a float64 tensor on %s" % self.device)
-        if tuple(value.shape) != (self.nparam,) or not value.is_contiguous():
-            raise ValueError("couplings must be a contiguous tensor of shape (%d,): Jxy(P), Jz(P), hz(L)" % self.nparam)
-        self._c = value
-        self._H = _pairsector_view(self, value)     # the kernels read the couplings through this tensor's pointer
-        if self._grid_log2 is not None:
-            _set_sector_grid(self._H, self._grid_log2)
-
     def set_grid_log2(self, grid_log2):
         """log2 of the most blocks a launch uses (6..12, default 12; measurement aid, dsea_op_set_tuning)"""
-        _set_sector_grid(self._H, grid_log2)
-        self._grid_log2 = int(grid_log2)
+        self._set_tune_log2(grid_log2)
 
     def pack(self, Jxy, Jz, hz):
         """the three families as one parameter tensor on the operator's device.  Jxy and Jz: a scalar, one value per pair, or
         an L x L matrix of which the strict upper triangle is read; hz: a scalar or one value per site.  Differentiable."""
-        parts = []
-        for value, size in zip((Jxy, Jz, hz), (self.npair, self.npair, self.N)):
+        def per_pair(value):
             t = torch.as_tensor(value, dtype=F64).to(self.device)
-            if t.dim() == 2 and size == self.npair:
+            if t.dim() == 2:
                 if tuple(t.shape) != (self.N, self.N):
                     raise ValueError("a coupling matrix must have shape (%d, %d)" % (self.N, self.N))
                 t = t[self._upper_index()]
-            parts.append(t.expand(size) if t.dim() == 0 else t.reshape(size))
-        return torch.cat(parts).contiguous()
+            return t
+        return _pack(self.device, (per_pair(Jxy), per_pair(Jz), hz), (self.npair, self.npair, self.N))
 
     def unpack(self, t):
         """views (Jxy, Jz, hz) of a parameter tensor"""
@@ -1091,20 +884,6 @@ class SpinSectorPairOperator:
         if tuple(t.shape) != (self.nparam,):
             raise ValueError("expected a tensor of shape (%d,)" % self.nparam)
         return t[:P], t[P:2 * P], t[2 * P:]
-
-    @property
-    def handle(self):
-        return self._H.handle
-
-    def H(self, v):
-        """H v, differentiable in v and in the couplings"""
-        return _PairSectorApply.apply(v, self._c, self, self._H)
-
-    __call__ = H
-
-    def Hadjoint_to_couplingsadjoint(self, v1, v2):
-        """adjoint hook: couplings-bar[t] = v1^T (dH/dp_t) v2, shape (2 P + L,)"""
-        return _PairSectorForms.apply(v1, v2, self, self._H)
 
     def correlations(self, v1, v2=None):
         """(xy, zz, z): xy[i, j] = v1^T (X_i X_j + Y_i Y_j) v2 and zz[i, j] = v1^T Z_i Z_j v2 as symmetric L x L matrices (their
@@ -1121,33 +900,6 @@ class SpinSectorPairOperator:
             upper = torch.zeros((self.N, self.N), dtype=F64, device=f.device).index_put(index, part)
             out.append(upper + upper.t() + weight * eye)      # (x + 0 and 0 + x: the two triangles carry the same bits)
         return out[0], out[1], z
-
-    def ladder(self, dst):
-        """the ``SpinSectorLadder`` from this sector to the sector of ``dst`` (ndown + 1, ndown or ndown - 1; ``dst`` may be
-        this operator), on the two operators' tables"""
-        return SpinSectorLadder(self, dst)
-
-    def rank(self, s):
-        """the row of every state in the int64 device tensor ``s`` (states of the sector only): the two-table lookup"""
-        _, lo_rank, hi_base = self._tables
-        return hi_base[s >> self.Llo].to(torch.int64) + lo_rank[s & ((1 << self.Llo) - 1)].to(torch.int64)
-
-    def embed(self, v):
-        """the sector vector v as a vector of the full 2^L space (zero outside the sector); L <= 30"""
-        if self.N > 30:
-            raise ValueError("embed / restrict need L <= 30")
-        w = torch.zeros(1 << self.N, dtype=v.dtype, device=v.device)
-        return w.index_put((self.states.to(v.device),), v)
-
-    def restrict(self, w):
-        """the sector part of a vector of the full 2^L space; L <= 30"""
-        if self.N > 30:
-            raise ValueError("embed / restrict need L <= 30")
-        return w[self.states.to(w.device)]
-
-    def bipartition(self, sites):
-        """the ``Bipartition`` of this sector into the sites ``sites`` and the rest, on the operator's rank tables"""
-        return Bipartition(self.N, sites, ndown=self.ndown, device=self.device, _tables=self._tables[1:])
 
     def to_csr(self, layout="sell", col16="auto", values="auto"):
         """The sector matrix as an explicit device CSR operand: the diagonal, and for every pair one entry in the rows that
@@ -1167,53 +919,7 @@ class SpinSectorPairOperator:
             r_all.append(flips)
             c_all.append(self.rank(s[flips] ^ ((1 << a) | (1 << b))))
             off.append((2.0 * jxy[t]).expand(flips.numel()))
-        v_all = [diag] + off
-        r_all, c_all, v_all = torch.cat(r_all), torch.cat(c_all), torch.cat(v_all)
-        order = torch.argsort(r_all * n + c_all)
-        rowptr = torch.zeros(n + 1, dtype=torch.int64, device=self.device)
-        rowptr[1:] = torch.cumsum(torch.bincount(r_all, minlength=n), 0)
-        return CSROperator(rowptr, c_all[order], v_all[order].contiguous(), n, layout=layout, col16=col16, values=values)
-
-
-class _PairSectorApply(torch.autograd.Function):
-    """y = H[c] v.  Backward: H[c] gy (symmetric) and the forms(gy, v) -- both re-entrant."""
-
-    @staticmethod
-    def forward(ctx, v, c, op, view):
-        ctx.op, ctx.view = op, view
-        ctx.save_for_backward(v, c)
-        return engine.spmv(view, v.detach())
-
-    @staticmethod
-    def backward(ctx, gy):
-        v, c = ctx.saved_tensors
-        gv = _PairSectorApply.apply(gy, c, ctx.op, ctx.view) if ctx.needs_input_grad[0] else None
-        gc = _PairSectorForms.apply(gy, v, ctx.op, ctx.view).reshape(c.shape) if ctx.needs_input_grad[1] else None
-        return gv, gc, None, None
-
-
-class _PairSectorForms(torch.autograd.Function):
-    """out[t] = v1^T (dH/dp_t) v2, shape (2 P + L,).  H is linear in the couplings, so with the incoming adjoint G as
-    couplings the backward is d/dv1 = H[G] v2 and d/dv2 = H[G] v1: a second handle on the same tables."""
-
-    @staticmethod
-    def forward(ctx, v1, v2, op, view):
-        ctx.op, ctx.view = op, view
-        ctx.save_for_backward(v1, v2)
-        return _pairsector_forms(view, op, v1.detach(), v2.detach())
-
-    @staticmethod
-    def backward(ctx, G):
-        v1, v2 = ctx.saved_tensors
-        g1 = g2 = None
-        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
-            G = G.reshape(ctx.op.nparam).contiguous()
-            adj = _pairsector_view(ctx.op, G, like=ctx.view)      # the Hamiltonian whose couplings are the adjoint
-            if ctx.needs_input_grad[0]:
-                g1 = _PairSectorApply.apply(v2, G, ctx.op, adj)
-            if ctx.needs_input_grad[1]:
-                g2 = _PairSectorApply.apply(v1, G, ctx.op, adj)
-        return g1, g2, None, None
+        return _csr_from_coo(r_all, c_all, [diag] + off, n, layout, col16, values)
 
 
 # ------------------------------------------------------------------------------------------ ladder maps between two S^z sectors
@@ -1424,13 +1130,7 @@ class Bipartition:
         self.N, self.ndown, self.sites = L, (None if full else ndown), tuple(sites)
         self._nd = -1 if full else ndown
         self._sites = (c_int32 * LA)(*sites)
-        if device is None:
-            device = "cuda"
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError("Bipartition is a device object; use device='cuda'")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = _cuda_device("Bipartition", device, what="object")
         lib = _lib.load()
         n, nblk, out_len = c_int64(), c_int(), c_int64()
         table = (c_int64 * (5 * _lib.RDM_MAX_BLOCKS))()
@@ -1458,14 +1158,7 @@ class Bipartition:
                                                     engine._stream(self.device)), "dsea_rdm_build_index_full")
             else:
                 if _tables is None:
-                    Llo = (L + 1) // 2
-                    states = torch.empty(self.n, dtype=torch.int64, device=self.device)
-                    lo_rank = torch.empty(1 << Llo, dtype=torch.int32, device=self.device)
-                    hi_base = torch.empty(1 << (L - Llo), dtype=torch.int32, device=self.device)
-                    check(lib.dsea_sector_build_tables(L, ndown, c_void_p(states.data_ptr()), c_void_p(lo_rank.data_ptr()),
-                                                       c_void_p(hi_base.data_ptr()), engine._stream(self.device)),
-                          "dsea_sector_build_tables")
-                    _tables = (lo_rank, hi_base)
+                    _tables = _build_sector_tables(L, ndown, self.n, self.device)[1:]
                 lo_rank, hi_base = _tables
                 check(lib.dsea_rdm_build_index_sector(L, ndown, LA, self._sites, c_void_p(lo_rank.data_ptr()),
                                                       c_void_p(hi_base.data_ptr()), c_void_p(self.idx.data_ptr()),
@@ -1783,50 +1476,7 @@ def symmetry_sector_dim(L, ndown, generators):
     return count
 
 
-def _symsector_view(op, couplings, like=None):
-    """(handle, n) of the symmetry-sector Hamiltonian of ``op`` (its bonds, group and tables) whose couplings are the
-    (2 nb + L,) tensor ``couplings``; ``like``: a view whose grid cap the new handle takes over."""
-    data = couplings.detach()
-    if data.dtype != F64 or not data.is_contiguous():
-        data = data.to(F64).contiguous()
-    bonds = op.bonds
-    flat = (c_int32 * (2 * len(bonds)))(*[s for bond in bonds for s in bond])
-    chars = (c_int32 * op.ng)(*[c for _, c in op.group])
-    orbits = (c_int32 * op.nparam)(*op.orbits)
-    reps, bucket, perm_tab = op._tables
-    raw = c_void_p()
-    if any(op.flips):
-        flips = (c_int32 * op.ng)(*[int(f) for f in op.flips])
-        signs = (c_int32 * op.N)(*op.site_signs)
-        check(_lib.load().dsea_op_create_symsector_flip(op.N, op.ndown, len(bonds), flat, c_void_p(data.data_ptr()), op.ng, chars,
-                                                        flips, signs, orbits, op.n, c_void_p(reps.data_ptr()),
-                                                        c_void_p(bucket.data_ptr()), c_void_p(perm_tab.data_ptr()), byref(raw)),
-              "dsea_op_create_symsector_flip")
-    else:
-        check(_lib.load().dsea_op_create_symsector(op.N, op.ndown, len(bonds), flat, c_void_p(data.data_ptr()), op.ng, chars,
-                                                   orbits, op.n, c_void_p(reps.data_ptr()), c_void_p(bucket.data_ptr()),
-                                                   c_void_p(perm_tab.data_ptr()), byref(raw)), "dsea_op_create_symsector")
-    view = _NativeView(_Handle(raw, op.n, (data, op._tables)))
-    view.grid_log2 = None
-    if like is not None and like.grid_log2 is not None:
-        _set_sector_grid(view, like.grid_log2)
-    return view
-
-
-def _symsector_forms(view, op, v1, v2):
-    """all 2 nb + L orbit-averaged bilinear forms (dsea_op_symsector_forms: one pass, deterministic)"""
-    lib = _lib.load()
-    v1, v2 = engine.as_vector(v1, view.n), engine.as_vector(v2, view.n)
-    need = c_int64()
-    check(lib.dsea_op_symsector_forms_scratch_doubles(op.n, op.N, op.nb, byref(need)), "dsea_op_symsector_forms_scratch_doubles")
-    scratch = torch.empty(need.value, dtype=F64, device=v1.device)
-    out = torch.empty(op.nparam, dtype=F64, device=v1.device)
-    check(lib.dsea_op_symsector_forms(view.handle, c_void_p(v1.data_ptr()), c_void_p(v2.data_ptr()), c_void_p(out.data_ptr()),
-                                      c_void_p(scratch.data_ptr()), engine._stream(v1.device)), "dsea_op_symsector_forms")
-    return out
-
-
-class SpinSymmetrySectorOperator:
+class SpinSymmetrySectorOperator(_CouplingsOperator):
     """The Hamiltonian of ``SpinSectorOperator`` (same bits, bonds and parameter tensor [Jxy(nb), Jz(nb), hz(L)]) restricted
     further to one sector of a lattice-symmetry group G with a real one-dimensional character, matrix-free
     (docs/design/20-symmetry-sector.md).  ``generators`` is a list of (perm, char): perm[i] is the site that site i is sent to,
@@ -1839,14 +1489,17 @@ class SpinSymmetrySectorOperator:
     |r> = (|G| sigma_r)^(-1/2) sum_g chi(g) |g s_r>, for any couplings: they enter through their orbit means (``symmetrise``).
     ``H(v)`` is differentiable in v and in ``couplings``; ``Hadjoint_to_couplingsadjoint(v1, v2)`` returns all 2 nb + L entries in
     one pass; both are re-entrant (second order works).  The couplings are read through the tensor's pointer on every launch;
-    binding another tensor makes a new handle on the same tables.
+    binding another tensor makes a new handle on the same tables.  The hook returns couplings-bar = S raw with
+    raw[t] = v1^T A_t v2: H_sym is linear in the couplings and sees them through S, which is symmetric, so with an incoming
+    adjoint G as couplings the backward of the forms is d/dv1 = H_sym[G] v2 and d/dv2 = H_sym[G] v1.
 
     Spin inversion (docs/design/23-spin-inversion.md): a generator may also be (perm, char, flip); with ``flip`` the element acts
     as g(s) = perm(s) ^ (2^L - 1) (``spin_inversion``, or ``spin_flip=`` of the builders).  It needs ndown = L / 2 (ValueError
     otherwise).  ``flips`` holds the flip bit of every element of ``group``; hz then enters through the signed orbit mean with the
     signs ``site_signs``.  Without a flipped generator the operator is exactly the one above."""
 
-    _native_methods = ("H", "__call__")
+    _families = "Jxy(nb), Jz(nb), hz(L)"
+    _forms_stem = "dsea_op_symsector"
     SLAB_ROWS = 1 << 26
 
     def __init__(self, L, bonds, couplings, ndown, generators, device=None):
@@ -1861,13 +1514,7 @@ class SpinSymmetrySectorOperator:
         self._orbits = tuple(_orbit_ids(self.N, self._bonds, self._group))
         self._site_signs = tuple(_site_signs(self.N, self._group, self._flips))
         self._has_flip = any(self._flips)
-        if device is None:
-            device = couplings.device if torch.is_tensor(couplings) else "cuda"
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError("SpinSymmetrySectorOperator is a device operator; use device='cuda'")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = _cuda_device("SpinSymmetrySectorOperator", device, couplings)
         self.Llo = (self.N + 1) // 2
         self.nsl = (self.N + 7) // 8
         lib = _lib.load()
@@ -1909,10 +1556,28 @@ class SpinSymmetrySectorOperator:
         self._param_signs = torch.tensor([1.0] * (2 * self.nb) + [float(e) for e in self._site_signs], dtype=F64,
                                          device=self.device)
         self._sector_tables = None
-        self._c = None
-        self._H = None
-        self._grid_log2 = None
-        self.couplings = couplings
+        self._forms_sizes = (self.n, self.N, self.nb)
+        self._bind(couplings)
+
+    def _create(self, data):
+        lib = _lib.load()
+        flat = _flat_bonds(self._bonds)
+        chars = (c_int32 * self.ng)(*[c for _, c in self._group])
+        orbits = (c_int32 * self.nparam)(*self._orbits)
+        reps, bucket, perm_tab = self._tables
+        raw = c_void_p()
+        if self._has_flip:
+            flips = (c_int32 * self.ng)(*[int(f) for f in self._flips])
+            signs = (c_int32 * self.N)(*self._site_signs)
+            check(lib.dsea_op_create_symsector_flip(self.N, self.ndown, self.nb, flat, c_void_p(data.data_ptr()), self.ng, chars,
+                                                    flips, signs, orbits, self.n, c_void_p(reps.data_ptr()),
+                                                    c_void_p(bucket.data_ptr()), c_void_p(perm_tab.data_ptr()), byref(raw)),
+                  "dsea_op_create_symsector_flip")
+        else:
+            check(lib.dsea_op_create_symsector(self.N, self.ndown, self.nb, flat, c_void_p(data.data_ptr()), self.ng, chars,
+                                               orbits, self.n, c_void_p(reps.data_ptr()), c_void_p(bucket.data_ptr()),
+                                               c_void_p(perm_tab.data_ptr()), byref(raw)), "dsea_op_create_symsector")
+        return raw, (data, self._tables)
 
     @property
     def bonds(self):
@@ -1950,44 +1615,12 @@ class SpinSymmetrySectorOperator:
         """norms[r] = sigma_r, the size of the representative's stabiliser (int64 device tensor)"""
         return self._norms
 
-    @property
-    def couplings(self):
-        return self._c
-
-    @couplings.setter
-    def couplings(self, value):
-        if not torch.is_tensor(value):
-            value = torch.as_tensor(value, dtype=F64).to(self.device)
-        if value.device != self.device or value.dtype != F64:
-            raise ValueError("couplings must be a float64 tensor on %s" % self.device)
-        if tuple(value.shape) != (self.nparam,) or not value.is_contiguous():
-            raise ValueError("couplings must be a contiguous tensor of shape (%d,): Jxy(nb), Jz(nb), hz(L)" % self.nparam)
-        self._c = value
-        self._H = _symsector_view(self, value)     # the kernels read the couplings through this tensor's pointer
-        if self._grid_log2 is not None:
-            _set_sector_grid(self._H, self._grid_log2)
-
     def set_grid_log2(self, grid_log2):
         """log2 of the most blocks a launch uses (6..12, default 12; measurement aid, dsea_op_set_tuning)"""
-        _set_sector_grid(self._H, grid_log2)
-        self._grid_log2 = int(grid_log2)
+        self._set_tune_log2(grid_log2)
 
     pack = SpinSectorOperator.pack
     unpack = SpinSectorOperator.unpack
-
-    @property
-    def handle(self):
-        return self._H.handle
-
-    def H(self, v):
-        """H v, differentiable in v and in the couplings"""
-        return _SymSectorApply.apply(v, self._c, self, self._H)
-
-    __call__ = H
-
-    def Hadjoint_to_couplingsadjoint(self, v1, v2):
-        """adjoint hook: couplings-bar = S raw, raw[t] = v1^T A_t v2, shape (2 nb + L,)"""
-        return _SymSectorForms.apply(v1, v2, self, self._H)
 
     def symmetrise(self, p):
         """S p: every coupling replaced by the mean over its orbit, for hz under flipped elements the signed mean
@@ -2026,13 +1659,7 @@ class SpinSymmetrySectorOperator:
         if self.n_sector > 1 << 27:
             raise ValueError("expand needs n_sector <= 2^27")
         if self._sector_tables is None:
-            states = torch.empty(self.n_sector, dtype=torch.int64, device=self.device)
-            lo_rank = torch.empty(1 << self.Llo, dtype=torch.int32, device=self.device)
-            hi_base = torch.empty(1 << (self.N - self.Llo), dtype=torch.int32, device=self.device)
-            with torch.cuda.device(self.device):
-                check(_lib.load().dsea_sector_build_tables(self.N, self.ndown, c_void_p(states.data_ptr()),
-                                                           c_void_p(lo_rank.data_ptr()), c_void_p(hi_base.data_ptr()),
-                                                           engine._stream(self.device)), "dsea_sector_build_tables")
+            _, lo_rank, hi_base = _build_sector_tables(self.N, self.ndown, self.n_sector, self.device)
             self._sector_tables = (lo_rank.to(torch.int64), hi_base.to(torch.int64))
         lo_rank, hi_base = self._sector_tables
         coef = v / torch.sqrt(float(self.ng) * self._norms.to(v.dtype))
@@ -2075,48 +1702,6 @@ class SpinSymmetrySectorOperator:
         return CSROperator(rowptr, uniq - r_u * n, vals.contiguous(), n, layout=layout, col16=col16, values=values)
 
 
-class _SymSectorApply(torch.autograd.Function):
-    """y = H_sym[c] v.  Backward: H_sym[c] gy (symmetric) and the forms(gy, v) -- both re-entrant."""
-
-    @staticmethod
-    def forward(ctx, v, c, op, view):
-        ctx.op, ctx.view = op, view
-        ctx.save_for_backward(v, c)
-        return engine.spmv(view, v.detach())
-
-    @staticmethod
-    def backward(ctx, gy):
-        v, c = ctx.saved_tensors
-        gv = _SymSectorApply.apply(gy, c, ctx.op, ctx.view) if ctx.needs_input_grad[0] else None
-        gc = _SymSectorForms.apply(gy, v, ctx.op, ctx.view).reshape(c.shape) if ctx.needs_input_grad[1] else None
-        return gv, gc, None, None
-
-
-class _SymSectorForms(torch.autograd.Function):
-    """out = S raw(v1, v2), shape (2 nb + L,).  H_sym is linear in the couplings and sees them through S, which is symmetric: with
-    the incoming adjoint G as couplings the backward is d/dv1 = H_sym[G] v2 and d/dv2 = H_sym[G] v1 -- a second handle on the same
-    tables."""
-
-    @staticmethod
-    def forward(ctx, v1, v2, op, view):
-        ctx.op, ctx.view = op, view
-        ctx.save_for_backward(v1, v2)
-        return _symsector_forms(view, op, v1.detach(), v2.detach())
-
-    @staticmethod
-    def backward(ctx, G):
-        v1, v2 = ctx.saved_tensors
-        g1 = g2 = None
-        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
-            G = G.reshape(ctx.op.nparam)
-            adj = _symsector_view(ctx.op, G, like=ctx.view)      # the Hamiltonian whose couplings are the adjoint
-            if ctx.needs_input_grad[0]:
-                g1 = _SymSectorApply.apply(v2, G, ctx.op, adj)
-            if ctx.needs_input_grad[1]:
-                g2 = _SymSectorApply.apply(v1, G, ctx.op, adj)
-        return g1, g2, None, None
-
-
 # ------------------------------------------------------------------------------------------ Hubbard model at fixed (N_up, N_dn)
 def hubbard_dim(L, nup, ndn):
     """the dimension C(L, nup) C(L, ndn) of the Hubbard space of L sites with nup up and ndn down particles (pure Python)"""
@@ -2137,40 +1722,7 @@ def _check_hubbard(L, nup, ndn):
     return L, nup, ndn, n_up, n_dn
 
 
-def _hubbard_view(op, couplings, like=None):
-    """(handle, n) of the Hubbard Hamiltonian of ``op`` (its bonds and its tables) whose couplings are the (2 nb + 2 L,) tensor
-    ``couplings``; ``like``: a view whose grid cap the new handle takes over."""
-    data = couplings.detach()
-    if data.dtype != F64 or not data.is_contiguous():
-        data = data.to(F64).contiguous()
-    bonds = op.bonds
-    flat = (c_int32 * (2 * len(bonds)))(*[s for bond in bonds for s in bond])
-    tables = op._up + op._dn
-    raw = c_void_p()
-    check(_lib.load().dsea_op_create_hubbard(op.N, op.nup, op.ndn, len(bonds), flat, c_void_p(data.data_ptr()),
-                                             *[c_void_p(t.data_ptr()) for t in tables], byref(raw)), "dsea_op_create_hubbard")
-    view = _NativeView(_Handle(raw, op.n, (data, tables)))
-    view.grid_log2 = None
-    if like is not None and like.grid_log2 is not None:
-        _set_sector_grid(view, like.grid_log2)
-    return view
-
-
-def _hubbard_forms(view, op, v1, v2):
-    """all 2 nb + 2 L bilinear forms v1^T (dH/dp) v2 (dsea_op_hubbard_forms: one pass, deterministic)"""
-    lib = _lib.load()
-    v1, v2 = engine.as_vector(v1, view.n), engine.as_vector(v2, view.n)
-    need = c_int64()
-    check(lib.dsea_op_hubbard_forms_scratch_doubles(op.N, op.nup, op.ndn, op.nb, byref(need)),
-          "dsea_op_hubbard_forms_scratch_doubles")
-    scratch = torch.empty(need.value, dtype=F64, device=v1.device)
-    out = torch.empty(op.nparam, dtype=F64, device=v1.device)
-    check(lib.dsea_op_hubbard_forms(view.handle, c_void_p(v1.data_ptr()), c_void_p(v2.data_ptr()), c_void_p(out.data_ptr()),
-                                    c_void_p(scratch.data_ptr()), engine._stream(v1.device)), "dsea_op_hubbard_forms")
-    return out
-
-
-class HubbardOperator:
+class HubbardOperator(_CouplingsOperator):
     """H = sum_t [-t_t sum_s (c+_{a s} c_{b s} + h.c.) + V_t n_a n_b] + sum_i U_i n_{i up} n_{i dn} + sum_i eps_i n_i on L sites
     with exactly ``nup`` up and ``ndn`` down fermions, matrix-free (docs/design/19-hubbard.md).  ``bonds`` follows the rules of
     ``SpinLatticeOperator``; 2 <= L <= 40, 1 <= nup, ndn <= L - 1 and n = C(L, nup) C(L, ndn) <= 2^31 - 1.  Bit i of the word u
@@ -2187,7 +1739,8 @@ class HubbardOperator:
     in the couplings), so second order works.  The state and rank tables of each species are built once per operator by the
     library's sector-table kernels and kept alive by it; with nup == ndn one set serves both species."""
 
-    _native_methods = ("H", "__call__")
+    _families = "t(nb), V(nb), U(L), eps(L)"
+    _forms_stem = "dsea_op_hubbard"
 
     def __init__(self, L, bonds, couplings, nup, ndn, device=None):
         self.N, self.nup, self.ndn, self.n_up, self.n_dn = _check_hubbard(L, nup, ndn)
@@ -2195,31 +1748,20 @@ class HubbardOperator:
         self.nb = len(self._bonds)
         self.nparam = 2 * self.nb + 2 * self.N
         self.dim = self.n = self.n_up * self.n_dn
-        if device is None:
-            device = couplings.device if torch.is_tensor(couplings) else "cuda"
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError("HubbardOperator is a device operator; use device='cuda'")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = _cuda_device("HubbardOperator", device, couplings)
         self.Llo = (self.N + 1) // 2
-        self._up = self._build_tables(self.nup, self.n_up)
-        self._dn = self._up if self.ndn == self.nup else self._build_tables(self.ndn, self.n_dn)
-        self._c = None
-        self._H = None
-        self._grid_log2 = None
-        self.couplings = couplings
+        self._up = _build_sector_tables(self.N, self.nup, self.n_up, self.device)
+        self._dn = self._up if self.ndn == self.nup else _build_sector_tables(self.N, self.ndn, self.n_dn, self.device)
+        self._forms_sizes = (self.N, self.nup, self.ndn, self.nb)
+        self._bind(couplings)
 
-    def _build_tables(self, count, rows):
-        """(states, lo_rank, hi_base) of the L-bit words with ``count`` set bits: dsea_sector_build_tables"""
-        states = torch.empty(rows, dtype=torch.int64, device=self.device)
-        lo_rank = torch.empty(1 << self.Llo, dtype=torch.int32, device=self.device)
-        hi_base = torch.empty(1 << (self.N - self.Llo), dtype=torch.int32, device=self.device)
-        with torch.cuda.device(self.device):
-            check(_lib.load().dsea_sector_build_tables(self.N, count, c_void_p(states.data_ptr()), c_void_p(lo_rank.data_ptr()),
-                                                       c_void_p(hi_base.data_ptr()), engine._stream(self.device)),
-                  "dsea_sector_build_tables")
-        return (states, lo_rank, hi_base)
+    def _create(self, data):
+        tables = self._up + self._dn
+        raw = c_void_p()
+        check(_lib.load().dsea_op_create_hubbard(self.N, self.nup, self.ndn, self.nb, _flat_bonds(self._bonds),
+                                                 c_void_p(data.data_ptr()), *[c_void_p(t.data_ptr()) for t in tables], byref(raw)),
+              "dsea_op_create_hubbard")
+        return raw, (data, tables)
 
     @property
     def bonds(self):
@@ -2236,35 +1778,13 @@ class HubbardOperator:
         """dn_states[rd] = the down word of the rows rd, n_dn + rd, ... (int64 device tensor, increasing)"""
         return self._dn[0]
 
-    @property
-    def couplings(self):
-        return self._c
-
-    @couplings.setter
-    def couplings(self, value):
-        if not torch.is_tensor(value):
-            value = torch.as_tensor(value, dtype=F64).to(self.device)
-        if value.device != self.device or value.dtype != F64:
-            raise ValueError("couplings must be a float64 tensor on %s" % self.device)
-        if tuple(value.shape) != (self.nparam,) or not value.is_contiguous():
-            raise ValueError("couplings must be a contiguous tensor of shape (%d,): t(nb), V(nb), U(L), eps(L)" % self.nparam)
-        self._c = value
-        self._H = _hubbard_view(self, value)     # the kernels read the couplings through this tensor's pointer
-        if self._grid_log2 is not None:
-            _set_sector_grid(self._H, self._grid_log2)
-
     def set_grid_log2(self, grid_log2):
         """log2 of the most blocks a launch uses (6..12, default 12; measurement aid, dsea_op_set_tuning)"""
-        _set_sector_grid(self._H, grid_log2)
-        self._grid_log2 = int(grid_log2)
+        self._set_tune_log2(grid_log2)
 
     def pack(self, t, V, U, eps):
         """the four families (scalars, or one value per bond / per site) as one parameter tensor on the operator's device"""
-        parts = []
-        for value, size in zip((t, V, U, eps), (self.nb, self.nb, self.N, self.N)):
-            x = torch.as_tensor(value, dtype=F64).to(self.device)
-            parts.append(x.expand(size) if x.dim() == 0 else x.reshape(size))
-        return torch.cat(parts).contiguous()
+        return _pack(self.device, (t, V, U, eps), (self.nb, self.nb, self.N, self.N))
 
     def unpack(self, p):
         """views (t, V, U, eps) of a parameter tensor"""
@@ -2273,45 +1793,15 @@ class HubbardOperator:
             raise ValueError("expected a tensor of shape (%d,)" % self.nparam)
         return p[:nb], p[nb:2 * nb], p[2 * nb:2 * nb + L], p[2 * nb + L:]
 
-    @property
-    def handle(self):
-        return self._H.handle
-
-    def H(self, v):
-        """H v, differentiable in v and in the couplings"""
-        return _HubbardApply.apply(v, self._c, self, self._H)
-
-    __call__ = H
-
     def apply_block(self, X):
         """H X for a device tensor X of shape (n, R), any R >= 1: all columns in one pass over the rows per block of 8, 4, 2 or
         1 columns (dsea_op_hubbard_block_apply, docs/design/28-hubbard-finite-temperature.md); column j equals ``H(X[:, j])`` bit
         for bit.  Plain, not differentiable: X is detached."""
-        from .thermal import _as_block, block_pieces
-        X = _as_block(self, X, "apply_block")
-        lib = _lib.load()
-        out = []
-        for first, w in block_pieces(X.shape[1]):
-            Xp = X[:, first:first + w].to(F64).contiguous()
-            if Xp.data_ptr() % 16:
-                Xp = Xp.clone()
-            Yp = torch.empty_like(Xp)
-            check(lib.dsea_op_hubbard_block_apply(self.handle, w, c_void_p(Xp.data_ptr()), c_void_p(Yp.data_ptr()),
-                                                  engine._stream(Xp.device)), "dsea_op_hubbard_block_apply")
-            out.append(Yp)
-        return out[0] if len(out) == 1 else torch.cat(out, dim=1)
-
-    def Hadjoint_to_couplingsadjoint(self, v1, v2):
-        """adjoint hook: couplings-bar[p] = v1^T (dH/dp) v2, shape (2 nb + 2 L,)"""
-        return _HubbardForms.apply(v1, v2, self, self._H)
-
-    def _species_rank(self, tables, w):
-        _, lo_rank, hi_base = tables
-        return hi_base[w >> self.Llo].to(torch.int64) + lo_rank[w & ((1 << self.Llo) - 1)].to(torch.int64)
+        return _apply_block(self, X, "dsea_op_hubbard_block_apply")
 
     def rank(self, u, d):
         """the row of every pair of words in the int64 device tensors ``u`` (nup set bits) and ``d`` (ndn set bits)"""
-        return self._species_rank(self._up, u) * self.n_dn + self._species_rank(self._dn, d)
+        return _table_rank(self._up, self.Llo, u) * self.n_dn + _table_rank(self._dn, self.Llo, d)
 
     def ladder(self, dst, species=None):
         """the site-weighted c+ / c / n maps of one species from this sector into the sector of ``dst`` (``HubbardLadder``)"""
@@ -2343,7 +1833,7 @@ class HubbardOperator:
                 w = u if up else d
                 moved = rows[((w >> lo) ^ (w >> hi)) & 1 == 1]
                 wm = w[moved]
-                partner = self._species_rank(self._up if up else self._dn, wm ^ m)
+                partner = _table_rank(self._up if up else self._dn, self.Llo, wm ^ m)
                 # sgn = (-1)^popcount(w & between): the parity by folding the word onto its lowest bit
                 par = wm & between
                 for shift in (32, 16, 8, 4, 2, 1):
@@ -2351,52 +1841,7 @@ class HubbardOperator:
                 r_all.append(moved)
                 c_all.append(partner * n_dn + rd[moved] if up else ru[moved] * n_dn + partner)
                 v_all.append(amp * (1 - 2 * (par & 1)).to(F64))
-        r_all, c_all, v_all = torch.cat(r_all), torch.cat(c_all), torch.cat(v_all)
-        order = torch.argsort(r_all * n + c_all)
-        rowptr = torch.zeros(n + 1, dtype=torch.int64, device=self.device)
-        rowptr[1:] = torch.cumsum(torch.bincount(r_all, minlength=n), 0)
-        return CSROperator(rowptr, c_all[order], v_all[order].contiguous(), n, layout=layout, col16=col16, values=values)
-
-
-class _HubbardApply(torch.autograd.Function):
-    """y = H[c] v.  Backward: H[c] gy (symmetric) and the forms(gy, v) -- both re-entrant."""
-
-    @staticmethod
-    def forward(ctx, v, c, op, view):
-        ctx.op, ctx.view = op, view
-        ctx.save_for_backward(v, c)
-        return engine.spmv(view, v.detach())
-
-    @staticmethod
-    def backward(ctx, gy):
-        v, c = ctx.saved_tensors
-        gv = _HubbardApply.apply(gy, c, ctx.op, ctx.view) if ctx.needs_input_grad[0] else None
-        gc = _HubbardForms.apply(gy, v, ctx.op, ctx.view).reshape(c.shape) if ctx.needs_input_grad[1] else None
-        return gv, gc, None, None
-
-
-class _HubbardForms(torch.autograd.Function):
-    """out[p] = v1^T (dH/dp) v2, shape (2 nb + 2 L,).  H is linear in the couplings, so with the incoming adjoint G as
-    couplings the backward is d/dv1 = H[G] v2 and d/dv2 = H[G] v1: a second handle on the same tables."""
-
-    @staticmethod
-    def forward(ctx, v1, v2, op, view):
-        ctx.op, ctx.view = op, view
-        ctx.save_for_backward(v1, v2)
-        return _hubbard_forms(view, op, v1.detach(), v2.detach())
-
-    @staticmethod
-    def backward(ctx, G):
-        v1, v2 = ctx.saved_tensors
-        g1 = g2 = None
-        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
-            G = G.reshape(ctx.op.nparam)
-            adj = _hubbard_view(ctx.op, G, like=ctx.view)      # the Hamiltonian whose couplings are the adjoint
-            if ctx.needs_input_grad[0]:
-                g1 = _HubbardApply.apply(v2, G, ctx.op, adj)
-            if ctx.needs_input_grad[1]:
-                g2 = _HubbardApply.apply(v1, G, ctx.op, adj)
-        return g1, g2, None, None
+        return _csr_from_coo(r_all, c_all, v_all, n, layout, col16, values)
 
 
 # ------------------------------------------------------------------------------------------ c / c+ between two Hubbard sectors
