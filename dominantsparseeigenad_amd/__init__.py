@@ -14,7 +14,10 @@ empty; users import sub-modules by name):
     dominantsparseeigenad_amd.spectral  lanczos_measure, SpectralMeasure, dynamical_structure_factor,
                                         hubbard_spectral_function (re-exported here)
     dominantsparseeigenad_amd.thermal   block_lanczos_measures, sector_trace_measure, ThermalEnsemble, spin_thermodynamics,
-                                        GrandCanonicalEnsemble, hubbard_thermodynamics (finite temperature; re-exported here)
+                                        GrandCanonicalEnsemble, hubbard_thermodynamics, thermal_correlations (finite
+                                        temperature; re-exported here)
+    dominantsparseeigenad_amd.chebyshev chebyshev_coefficients, exp_order, spectral_bounds, chebyshev_apply, expm_block,
+                                        time_evolve (f(H) X without a basis; re-exported here)
 
 The top-level ``DominantSparseEigenAD`` package in this repository re-exports the same modules
 under the reference's import names.
@@ -30,8 +33,13 @@ def __getattr__(name):
         mod = importlib.import_module(__name__ + ".spectral")
         return mod if name == "spectral" else getattr(mod, name)
     if name in ("thermal", "block_lanczos_measures", "sector_trace_measure", "ThermalEnsemble", "spin_thermodynamics",
-                "GrandCanonicalEnsemble", "hubbard_thermodynamics"):
+                "GrandCanonicalEnsemble", "hubbard_thermodynamics", "thermal_correlations"):
         import importlib
         mod = importlib.import_module(__name__ + ".thermal")
         return mod if name == "thermal" else getattr(mod, name)
+    if name in ("chebyshev", "chebyshev_coefficients", "exp_order", "spectral_bounds", "chebyshev_apply", "expm_block",
+                "time_evolve"):
+        import importlib
+        mod = importlib.import_module(__name__ + ".chebyshev")
+        return mod if name == "chebyshev" else getattr(mod, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -5,6 +5,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <cmath>
 #include <new>
 
 #include "dsea_internal.h"
@@ -2114,6 +2115,22 @@ int dsea_op_sector_block_lanczos(dsea_op_t op, int R, int k, double* Q, double* 
           DSEA_ERR_ARG);
   REQUIRE(aligned16(Q) && aligned16(W), DSEA_ERR_ALIGN);
   if (launch_sector_block_lanczos(op->d, R, k, Q, W, norm2, alphas, betas, steps, scratch, static_cast<hipStream_t>(stream)) != 0)
+    return DSEA_ERR_UNSUPPORTED;
+  return check_launch();
+}
+
+int dsea_op_sector_block_chebyshev(dsea_op_t op, int R, int A, int M, double centre, double halfwidth, const double* coeffs,
+                                   const double* X, double* U, double* V, double* ACC, void* stream) {
+  REQUIRE(op && op->d.kind == OP_SECTOR && block_width_ok(R) && (A == 1 || A == 2) && M >= 2 && coeffs && X && U && V && ACC &&
+              std::isfinite(centre) && std::isfinite(halfwidth) && halfwidth > 0.0,
+          DSEA_ERR_ARG);
+  const double* blocks[5] = {X, U, V, ACC, ACC + (A - 1) * op->d.n * R};     // (the first 3 + A are compared)
+  for (int i = 0; i < 3 + A; ++i)
+    for (int j = i + 1; j < 3 + A; ++j) REQUIRE(blocks[i] != blocks[j], DSEA_ERR_ARG);
+  // (the second accumulator at ACC + n R needs no check of its own: n R * 8 is a multiple of 16 for R >= 2, and at R = 1 every
+  // access is 8 bytes wide)
+  REQUIRE(aligned16(X) && aligned16(U) && aligned16(V) && aligned16(ACC), DSEA_ERR_ALIGN);
+  if (launch_sector_block_chebyshev(op->d, R, A, M, centre, halfwidth, coeffs, X, U, V, ACC, static_cast<hipStream_t>(stream)) < 0)
     return DSEA_ERR_UNSUPPORTED;
   return check_launch();
 }

@@ -579,6 +579,11 @@ int64_t sector_block_lanczos_scratch_doubles(int64_t n, int R);
 int launch_sector_block_apply(const OpDesc& op, int R, const double* X, double* Y, hipStream_t st);
 int launch_sector_block_lanczos(const OpDesc& op, int R, int k, double* Q, double* W, double* norm2, double* alphas, double* betas,
                                 int32_t* steps, double* scratch, hipStream_t st);
+// launch_sector_block_chebyshev (docs/design/31-chebyshev-propagator.md): ACC[a] = sum_{m < M} coeffs[a * M + m] T_m((H - centre)
+// / halfwidth) X, a in [0, A), ACC [A, n, R], in M - 1 launches of k_cheb_sector_block<R, A>; coeffs is a HOST array, U and V are
+// work blocks, X is not written, nothing is read back.  The blocks launched, or -1 for a descriptor out of range.
+int launch_sector_block_chebyshev(const OpDesc& op, int R, int A, int M, double centre, double halfwidth, const double* coeffs,
+                                  const double* X, double* U, double* V, double* ACC, hipStream_t st);
 // The driver of that recurrence for any operator (defined in dsea_sector_block.hip, beside the recurrence kernels it launches):
 // the start and k steps on nblk blocks of 256 rows, the mat-vec of a step being the caller's step(q, w, state, first, PA), which
 // launches W = H q - w diag(state[0 .. R)) over w (first != 0: W = H q, w is not read) with the partials of q_j . W_j in

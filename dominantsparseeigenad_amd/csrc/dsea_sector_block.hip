@@ -213,6 +213,96 @@ __global__ __launch_bounds__(256) void k_spmv_sector_block(SectorBlockParams p, 
   if constexpr (LZ) sblock_partials<R>(acc, sm, P);
 }
 
+// the per-accumulator arguments of one Chebyshev order, by value
+template <int A>
+struct ChebAccs {
+  double* acc[A];
+  double c0[A], c1[A];
+};
+
+// One order of the Chebyshev recurrence of f(H) X (docs/design/31-chebyshev-propagator.md): with w the row of H x exactly as
+// k_spmv_sector_block<R, false> forms it (the same loop, the same operation order, the same bits),
+//   t = g (w - centre x)                                  g = 1 / halfwidth on the first order, 2 / halfwidth afterwards
+//   first:  acc_a = c0_a x + c1_a t                       (old and acc are not read)
+//   else:   t = t - old,  acc_a = acc_a + c1_a t
+//   out = t
+// every product and sum rounded on its own.  x is T_m, old T_{m-1}, out T_{m+1}; the tail touches the thread's own row only,
+// so old == out is allowed (neither is __restrict__); x and the accumulators are distinct from every other block.  old and acc
+// are read after the last chunk's gathers are consumed.  No atomics, no reductions.
+template <int R, int A>
+__global__ __launch_bounds__(256) void k_cheb_sector_block(SectorBlockParams p, const double* __restrict__ x, const double* old,
+                                                           double* out, ChebAccs<A> ca, double centre, double g, int first) {
+  constexpr int CH = SblockChunk<R>::value;
+  __shared__ double cp[DSEA_SBLOCK_MAX_PARAMS];
+  __shared__ uint16_t tb[DSEA_LATTICE_MAX_BONDS];
+  const int L = p.L, nb = p.nb, Llo = p.Llo;
+  const int64_t n = p.n;
+  for (int c = threadIdx.x; c < 2 * nb + L; c += 256) cp[c] = p.c[c];
+  for (int c = threadIdx.x; c < nb; c += 256) tb[c] = p.tb[c];
+  __syncthreads();
+  const double* __restrict__ jxy = cp;
+  const double* __restrict__ jzs = cp + nb;
+  const double* __restrict__ hzs = cp + 2 * nb;
+  for (int64_t row0 = (int64_t)blockIdx.x * 256; row0 < n; row0 += (int64_t)gridDim.x * 256) {
+    const int64_t r = row0 + threadIdx.x;
+    const bool have = r < n;                       // (a thread past the last row reads row n - 1 and writes nothing)
+    const int64_t rr = have ? r : n - 1;
+    const uint64_t s = p.states[rr];
+    double xr[R];
+    sblock_load<R>(xr, x, rr);
+    uint32_t rk[CH], hi[CH], lo[CH];
+    sblock_ranks<CH>(hi, lo, s, have, 0, nb, Llo, tb, p.lo_rank, p.hi_base);
+    double diag = 0.0, sum[R];
+#pragma unroll
+    for (int j = 0; j < R; ++j) sum[j] = 0.0;
+    for (int i = 0; i < L; ++i) diag += sblock_signed(hzs[i], (s >> i) & 1ull);
+    for (int k0 = 0; k0 < nb; k0 += CH) {
+      double xv[CH][R];
+#pragma unroll
+      for (int e = 0; e < CH; ++e) rk[e] = hi[e] + lo[e];
+      sblock_gather<R, CH>(xv, rk, x);
+      sblock_ranks<CH>(hi, lo, s, have, k0 + CH, nb, Llo, tb, p.lo_rank, p.hi_base);
+#pragma unroll
+      for (int e = 0; e < CH; ++e) {
+        if (k0 + e < nb) {
+          diag += sblock_signed(jzs[k0 + e], sblock_differ(s, tb[k0 + e]));
+          const double c2 = 2.0 * jxy[k0 + e];
+#pragma unroll
+          for (int j = 0; j < R; ++j) sum[j] = fma(c2, xv[e][j], sum[j]);
+        }
+      }
+    }
+    if (have) {
+      double t[R];
+#pragma unroll
+      for (int j = 0; j < R; ++j) {
+        const double w = fma(diag, xr[j], sum[j]);
+        t[j] = __dmul_rn(g, __dsub_rn(w, __dmul_rn(centre, xr[j])));
+      }
+      if (!first) {
+        double ov[R];
+        sblock_load<R>(ov, old, r);
+#pragma unroll
+        for (int j = 0; j < R; ++j) t[j] = __dsub_rn(t[j], ov[j]);
+      }
+#pragma unroll
+      for (int a = 0; a < A; ++a) {
+        double av[R];
+        if (first) {
+#pragma unroll
+          for (int j = 0; j < R; ++j) av[j] = __dadd_rn(__dmul_rn(ca.c0[a], xr[j]), __dmul_rn(ca.c1[a], t[j]));
+        } else {
+          sblock_load<R>(av, ca.acc[a], r);
+#pragma unroll
+          for (int j = 0; j < R; ++j) av[j] = __dadd_rn(av[j], __dmul_rn(ca.c1[a], t[j]));
+        }
+        sblock_store<R>(ca.acc[a], r, av);
+      }
+      sblock_store<R>(out, r, t);
+    }
+  }
+}
+
 // per-block partials of |q_j|^2 of the start block
 template <int R>
 __global__ __launch_bounds__(256) void k_sblock_norm(const double* __restrict__ q, int64_t n, double* __restrict__ P) {
@@ -361,6 +451,35 @@ int launch_sector_block_apply(const OpDesc& op, int R, const double* X, double* 
   const int nblk = sector_block_blocks(op);
   dispatch_block_width(R, [&](auto r) {
     klaunch(nullptr, k_spmv_sector_block<decltype(r)::value, false>, nblk, 256, 0, st, p, X, Y, nullptr, 1, nullptr);
+  });
+  return nblk;
+}
+
+// ACC[a] = sum_{m < M} coeffs[a * M + m] T_m((H - centre) / halfwidth) X in M - 1 launches of k_cheb_sector_block: order 1 is
+// `first` with x = X and out = U; order 2 reads x = U, old = X and writes V; from order 3 on old == out, U and V in turn.  The
+// two coefficients of an order go into its launch by value from the host array.  Nothing is read back, no synchronise.
+int launch_sector_block_chebyshev(const OpDesc& op, int R, int A, int M, double centre, double halfwidth, const double* coeffs,
+                                  const double* X, double* U, double* V, double* ACC, hipStream_t st) {
+  SectorBlockParams p;
+  if (!sector_block_params(op, &p)) return -1;
+  const int nblk = sector_block_blocks(op);
+  dispatch_block_width(R, [&](auto r) {
+    dispatch_int<1, 2>(A, [&](auto na) {
+      constexpr int RR = decltype(r)::value, AA = decltype(na)::value;
+      ChebAccs<AA> ca;
+      for (int a = 0; a < AA; ++a) {
+        ca.acc[a] = ACC + (int64_t)a * op.n * RR;
+        ca.c0[a] = coeffs[(int64_t)a * M];
+      }
+      double* const t[2] = {U, V};                 // T_m lives in t[(m - 1) & 1]
+      for (int m = 1; m < M; ++m) {
+        for (int a = 0; a < AA; ++a) ca.c1[a] = coeffs[(int64_t)a * M + m];
+        const double* x = m == 1 ? X : t[m & 1];
+        const double* old = m == 2 ? X : t[(m - 1) & 1];
+        klaunch(nullptr, k_cheb_sector_block<RR, AA>, nblk, 256, 0, st, p, x, old, t[(m - 1) & 1], ca, centre,
+                (m == 1 ? 1.0 : 2.0) / halfwidth, m == 1 ? 1 : 0);
+      }
+    });
   });
   return nblk;
 }

@@ -15,6 +15,8 @@ through the three-term recurrence at once as one [n, R] block, on the block mat-
     spin_thermodynamics(L, bonds, couplings, ...)   the ensemble over all magnetisation sectors of a bond-list XXZ model
     GrandCanonicalEnsemble(entries)         ln Xi, <H>, <N>, kappa, chi_s, C and S of a list of (measure, nup, ndn) over (beta, mu)
     hubbard_thermodynamics(L, bonds, couplings, ...)   that ensemble over all (nup, ndn) sectors of a Hubbard model
+    thermal_correlations(L, bonds, couplings, betas, ...)   <X_i X_j + Y_i Y_j>, <Z_i Z_j>, <Z_i>, E and ln Z at T > 0 from thermal
+                                                       pure quantum states e^{-beta H / 2} |r> (docs/design/31-chebyshev-propagator.md)
 
 Plain host float64 numbers: nothing here is differentiable.
 """
@@ -269,6 +271,125 @@ def spin_thermodynamics(L, bonds, couplings, R=8, k=100, seed=0, dense_below=256
         entries.append((sector_trace_measure(op, R=R, k=k, seed=seed, dense_below=dense_below), m))
         del op
     return ThermalEnsemble(entries)
+
+
+class ThermalCorrelations:
+    """What ``thermal_correlations`` returns, host float64 tensors over the B inverse temperatures ``betas``: ``logZ`` [B],
+    ``energy`` [B], ``xy`` [B, L, L] = <X_i X_j + Y_i Y_j>, ``zz`` [B, L, L] = <Z_i Z_j> (diagonals 2 and 1) and ``z`` [B, L] =
+    <Z_i>."""
+
+    def __init__(self, betas, logZ, energy, xy, zz, z):
+        self.betas, self.logZ, self.energy, self.xy, self.zz, self.z = betas, logZ, energy, xy, zz, z
+
+
+def _dense_sector_correlations(op, betas):
+    """(log weight [B], E [B], xy, zz, z) of a sector from its full spectrum: H from ``apply_block`` on identity columns, host
+    ``eigh``, and ``correlations(v, v)`` of every eigenvector"""
+    n = int(op.n)
+    H = torch.empty((n, n), dtype=F64, device=op.device)
+    for first in range(0, n, 8):
+        w = min(8, n - first)
+        X = torch.zeros((n, w), dtype=F64, device=op.device)
+        X[first:first + w] = torch.eye(w, dtype=F64, device=op.device)
+        H[:, first:first + w] = op.apply_block(X)
+    theta, V = torch.linalg.eigh(H.cpu())
+    pair = op.pair_operator()
+    Vd = V.to(op.device)
+    parts = [pair.correlations(Vd[:, j].contiguous()) for j in range(n)]
+    xy, zz, z = (torch.stack([q[i] for q in parts]).cpu() for i in range(3))
+    logw = -betas[:, None] * theta[None, :]
+    logsum = torch.logsumexp(logw, dim=1)
+    prob = torch.exp(logw - logsum[:, None])
+    return logsum, prob @ theta, torch.einsum("bj,jkl->bkl", prob, xy), torch.einsum("bj,jkl->bkl", prob, zz), prob @ z
+
+
+def _tpq_sector_correlations(op, betas, R, seed, tol):
+    """the same five from R thermal pure quantum states: the columns r_j = normal_vector(n, seed + j), normalised, are stepped
+    from one beta to the next by ``expm_block`` over half the difference and renormalised, the logarithms of their norms kept
+    on the host; at every beta column j weighs exp(2 log norm_j) and the sector weighs (n / R) times their sum"""
+    from .chebyshev import expm_block, spectral_bounds
+    from .synthetic import normal_vector
+    n = int(op.n)
+    Phi = torch.stack([torch.from_numpy(normal_vector(n, int(seed) + j)) for j in range(R)], dim=1).to(op.device)
+    Phi = Phi / torch.linalg.vector_norm(Phi, dim=0)
+    bounds = spectral_bounds(op, seed=seed)
+    pair = op.pair_operator()
+    lognorm = torch.zeros(R, dtype=F64)
+    out = [[] for _ in range(5)]
+    before = 0.0
+    for beta in betas.tolist():
+        tau = 0.5 * (beta - before)
+        before = beta
+        Y, shift = expm_block(op, Phi, tau, bounds, tol)
+        norms = torch.linalg.vector_norm(Y, dim=0)
+        Phi = Y / norms
+        lognorm = lognorm + torch.log(norms.cpu()) - tau * shift
+        energy = (Phi * op.apply_block(Phi)).sum(dim=0).cpu()
+        parts = [pair.correlations(Phi[:, j].contiguous()) for j in range(R)]
+        top = 2.0 * lognorm.max()
+        w = torch.exp(2.0 * lognorm - top)
+        total = w.sum()
+        out[0].append(math.log(n / R) + top + torch.log(total))
+        out[1].append((w * energy).sum() / total)
+        for i in range(3):
+            q = torch.stack([part[i] for part in parts]).cpu()
+            out[2 + i].append((w.reshape((R,) + (1,) * (q.dim() - 1)) * q).sum(dim=0) / total)
+    return tuple(torch.stack(o) for o in out)
+
+
+def thermal_correlations(L, bonds, couplings, betas, R=8, seed=0, dense_below=256, sectors=None, tol=1e-15, device=None):
+    """Thermal averages that do not commute with H, for the model and the parameter order of ``spin_thermodynamics``, at the
+    ascending inverse temperatures ``betas`` >= 0: a ``ThermalCorrelations`` with ``logZ``, ``energy``, ``xy``, ``zz`` and ``z``.
+
+    A sector with n > ``dense_below`` rows is sampled by R canonical thermal pure quantum states |beta, r> = e^{-beta H / 2} |r>
+    on the start vectors and with the sector weight n / R of ``sector_trace_measure``: |e^{-beta H / 2} r|^2 estimates what its
+    <r| e^{-beta H} |r> estimates.  Each state is stepped from the previous beta by ``chebyshev.expm_block`` (order chosen by
+    ``tol``) and renormalised; at every beta it costs one ``apply_block`` for <H> and one ``correlations`` per column.  A
+    smaller sector is exact: its full spectrum, and ``correlations(v, v)`` of every eigenvector (at most ``dense_below`` forms
+    calls per sector, made once for all betas).  ndown = 0 and ndown = L are one state each: xy = 0 off the diagonal, zz = 1,
+    z = +1 or -1, the energy from host arithmetic.  The sectors are combined by a log-sum-exp of their log weights; one
+    sector's tables are released before the next is built.  The error of a sampled sector is the sampling error of R
+    vectors; it is not estimated."""
+    from .operators import SpinSectorOperator, _check_bonds
+    L = int(L)
+    bonds = _check_bonds(L, bonds)
+    nb = len(bonds)
+    c = torch.as_tensor(couplings, dtype=F64).detach()
+    if tuple(c.shape) != (2 * nb + L,):
+        raise ValueError("couplings must have shape (%d,): Jxy(nb), Jz(nb), hz(L)" % (2 * nb + L))
+    betas = torch.as_tensor(betas, dtype=F64).detach().cpu().reshape(-1)
+    if betas.numel() < 1 or not bool(torch.isfinite(betas).all()) or bool((betas < 0).any()) or bool((betas[1:] < betas[:-1]).any()):
+        raise ValueError("betas must be finite, >= 0 and ascending")
+    R = int(R)
+    if R < 1:
+        raise ValueError("thermal_correlations needs R >= 1")
+    sectors = list(range(L + 1)) if sectors is None else [int(s) for s in sectors]
+    if not sectors or any(not 0 <= s <= L for s in sectors) or len(set(sectors)) != len(sectors):
+        raise ValueError("sectors must be distinct values of ndown in 0 .. %d" % L)
+    host = c.cpu()
+    jz_sum, hz_sum = float(host[nb:2 * nb].sum()), float(host[2 * nb:].sum())
+    if device is None:
+        device = c.device if c.is_cuda else "cuda"
+    B = betas.numel()
+    parts = []
+    for ndown in sectors:
+        if ndown in (0, L):
+            sign = 1.0 if ndown == 0 else -1.0
+            one = torch.ones((B, L, L), dtype=F64)
+            parts.append((-betas * (jz_sum + sign * hz_sum), torch.full((B,), jz_sum + sign * hz_sum, dtype=F64),
+                          2.0 * torch.eye(L, dtype=F64).expand(B, L, L), one, sign * torch.ones((B, L), dtype=F64)))
+            continue
+        op = SpinSectorOperator(L, bonds, c.to(device), ndown, device)
+        if op.n <= int(dense_below):
+            parts.append(_dense_sector_correlations(op, betas))
+        else:
+            parts.append(_tpq_sector_correlations(op, betas, R, seed, tol))
+        del op
+    logw = torch.stack([p[0] for p in parts])                              # [sectors, B]
+    logZ = torch.logsumexp(logw, dim=0)
+    prob = torch.exp(logw - logZ)
+    mix = lambda i: sum(prob[s].reshape((B,) + (1,) * (parts[s][i].dim() - 1)) * parts[s][i] for s in range(len(parts)))  # noqa: E731
+    return ThermalCorrelations(betas, logZ, mix(1), mix(2), mix(3), mix(4))
 
 
 class GrandCanonicalEnsemble:

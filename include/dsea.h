@@ -1030,6 +1030,24 @@ int dsea_op_hubbard_block_lanczos(dsea_op_t op, int R, int k, double *Q /* [n,R]
                                   double *alphas /* [k,R] */, double *betas /* [k,R]: betas[i,j] = beta_{i+1} */,
                                   int32_t *steps /* [R]: k, or the break step */, double *scratch, void *stream);
 
+/* ------------------------------------------------------------------ Chebyshev block propagator (docs/design/31-chebyshev-propagator.md)
+ * ACC[a] = f_a(H) X for the operator of dsea_op_create_sector and a block X, without a stored basis: f_a(E) ~=
+ * sum_{m < M} coeffs[a * M + m] T_m((E - centre) / halfwidth), a in [0, A), with coeffs[a * M + 0] ALREADY HALVED and the
+ * spectrum of H inside [centre - halfwidth, centre + halfwidth] (outside it the polynomials grow without bound).  Blocks as
+ * above: fp64 [n, R] row-major, 16-byte aligned (DSEA_ERR_ALIGN otherwise), R in {1, 2, 4, 8}.  coeffs [A, M] is a HOST array:
+ * two numbers per accumulator go into each launch by value.  X is never written; U and V are work blocks (on return they hold
+ * the last two T_m X); ACC is [A, n, R], one block per accumulator, A in {1, 2}.  M - 1 launches, one fused mat-vec and tail
+ * each: T_1 X = (H X - centre X) / halfwidth, T_{m+1} X = (2 / halfwidth)(H T_m X - centre T_m X) - T_{m-1} X, every product and
+ * sum rounded on its own (no contraction), so the result equals dsea_op_sector_block_apply followed by separate elementwise
+ * operations bit for bit.  No reductions, no atomics: identical calls return identical bits.  Nothing is read back, the call
+ * does not synchronise, the library allocates nothing; every check is host arithmetic before any device work.  DSEA_ERR_ARG:
+ * any other operator kind, R outside {1, 2, 4, 8}, A outside {1, 2}, M < 2, a null pointer, centre or halfwidth not finite,
+ * halfwidth <= 0, any two of X, U, V, ACC, ACC + n R equal. */
+int dsea_op_sector_block_chebyshev(dsea_op_t op, int R, int A, int M, double centre, double halfwidth,
+                                   const double *coeffs /* host [A,M], c_0 halved */, const double *X /* [n,R] */,
+                                   double *U /* [n,R] work */, double *V /* [n,R] work */, double *ACC /* [A,n,R] out */,
+                                   void *stream);
+
 #ifdef __cplusplus
 }
 #endif
