@@ -2104,7 +2104,7 @@ int dsea_op_sector_block_apply(dsea_op_t op, int R, const double* X, double* Y, 
 int dsea_op_sector_block_lanczos_scratch_doubles(int L, int ndown, int R, int64_t* out) {
   int64_t n, n_lo, n_hi;
   REQUIRE(out && sector_sizes(L, ndown, &n, &n_lo, &n_hi) && block_width_ok(R), DSEA_ERR_ARG);
-  *out = sector_block_lanczos_scratch_doubles(n, R);
+  *out = block_lanczos_scratch_doubles(n, R);
   return DSEA_OK;
 }
 
@@ -2145,7 +2145,7 @@ int dsea_op_hubbard_block_apply(dsea_op_t op, int R, const double* X, double* Y,
 int dsea_op_hubbard_block_lanczos_scratch_doubles(int L, int nup, int ndn, int R, int64_t* out) {
   int64_t n, n_up, n_dn;
   REQUIRE(out && hubbard_sizes(L, nup, ndn, &n, &n_up, &n_dn) && block_width_ok(R), DSEA_ERR_ARG);
-  *out = sector_block_lanczos_scratch_doubles(n, R);   // (the layout is the recurrence driver's, whatever the operator)
+  *out = block_lanczos_scratch_doubles(n, R);
   return DSEA_OK;
 }
 

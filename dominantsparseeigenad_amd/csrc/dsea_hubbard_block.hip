@@ -1,22 +1,20 @@
 // dsea_hubbard_block.hip -- the Hubbard Hamiltonian of dsea_hubbard.hip applied to a BLOCK of R vectors at once, plain and with
-// the tail of the basis-free block Lanczos step fused in (docs/design/28-hubbard-finite-temperature.md):
-// k_spmv_hubbard_block<R, LZ> and its launchers.  The recurrence kernels and their driver are those of dsea_sector_block.hip.
+// the tail of the basis-free block Lanczos step fused in (docs/design/28-hubbard-finite-temperature.md): the kernel
+// k_spmv_hubbard_block<R, LZ> -- the family's row walk with the tail block_spmv_tail of dsea_block.h -- and its launchers.  The
+// recurrence kernels and their driver are those of dsea_block_lanczos.hip.
 //
-// A block is an fp64 array [n, R], row-major (element (r, j) at r * R + j), 16-byte aligned, R in {1, 2, 4, 8}.  One row per
-// thread: the division r / n_dn, the two state words, the move tests, the two parities, the two table reads of every hop that
-// moves a particle and the partner rows are paid once per row and hop slot for all R columns, and every gather is R contiguous
-// doubles (R / 2 16-byte loads; one 8-byte load at R = 1).  The per-row arithmetic of a column is that of the single-vector
-// mat-vec of dsea_hubbard.hip without a shift, in the same order -- the diagonal over the sites (U, then the fma with eps) and
-// then over the bonds (fma(V_t, n_a n_b, diag)); sum = fma(+-t_t, x_up partner, sum), fma(+-t_t, x_dn partner, sum) per bond in
-// list order, a hop that moves nothing included with the value 0; then fma(diag, x_r, sum) -- so column j of Y = H X equals the
-// single-vector result bit for bit.
-// Nothing here is shared with dsea_hubbard.hip or dsea_sector_block.hip: the file has its own helpers.
+// One row per thread: the division r / n_dn, the two state words, the move tests, the two parities, the two table reads of every
+// hop that moves a particle and the partner rows are paid once per row and hop slot for all R columns, and every gather is R
+// contiguous doubles (R / 2 16-byte loads; one 8-byte load at R = 1).  The per-row arithmetic of a column is that of the
+// single-vector mat-vec of dsea_hubbard.hip without a shift, in the same order -- the diagonal over the sites (U, then the fma
+// with eps) and then over the bonds (fma(V_t, n_a n_b, diag)); sum = fma(+-t_t, x_up partner, sum), fma(+-t_t, x_dn partner, sum)
+// per bond in list order, a hop that moves nothing included with the value 0; then fma(diag, x_r, sum) in the tail -- so column j
+// of Y = H X equals the single-vector result bit for bit.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "dsea_internal.h"
-#include "dsea_device.h"
+#include "dsea_block.h"
 
 namespace dsea {
 
@@ -45,13 +43,7 @@ struct HubbardBlockParams {
   uint16_t tb[DSEA_LATTICE_MAX_BONDS];   // a | b << 8, the caller's order
 };
 
-// v * (1 - 2 bit), exact: the bit goes into the sign
-__device__ __forceinline__ double hblock_signed(double v, uint64_t bit) {
-  return __longlong_as_double(__double_as_longlong(v) ^ (long long)(bit << 63));
-}
 __device__ __forceinline__ uint64_t hblock_bit(uint64_t w, uint32_t site) { return (w >> site) & 1ull; }
-__device__ __forceinline__ uint64_t hblock_moves(uint64_t w, uint32_t e) { return ((w >> (e & 255u)) ^ (w >> (e >> 8))) & 1ull; }
-__device__ __forceinline__ uint64_t hblock_mask(uint32_t e) { return (1ull << (e & 255u)) | (1ull << (e >> 8)); }
 // the bits strictly between the two sites of the bond
 __device__ __forceinline__ uint64_t hblock_between(uint32_t e) {
   const uint32_t a = e & 255u, b = e >> 8;
@@ -64,32 +56,6 @@ __device__ __forceinline__ uint64_t hblock_parity(uint64_t w, uint64_t between) 
 __device__ __forceinline__ double hblock_nn(uint64_t u, uint64_t d, uint32_t e) {
   const uint32_t a = e & 255u, b = e >> 8;
   return (double)((hblock_bit(u, a) + hblock_bit(d, a)) * (hblock_bit(u, b) + hblock_bit(d, b)));
-}
-
-// one row of a block: R / 2 16-byte loads or stores (one 8-byte access at R = 1)
-template <int R>
-__device__ __forceinline__ void hblock_load(double (&v)[R], const double* __restrict__ p, int64_t row) {
-  if constexpr (R == 1) {
-    v[0] = p[row];
-  } else {
-    const double2* __restrict__ q = reinterpret_cast<const double2*>(p + row * R);
-#pragma unroll
-    for (int h = 0; h < R / 2; ++h) {
-      const double2 t = q[h];
-      v[2 * h] = t.x;
-      v[2 * h + 1] = t.y;
-    }
-  }
-}
-template <int R>
-__device__ __forceinline__ void hblock_store(double* __restrict__ p, int64_t row, const double (&v)[R]) {
-  if constexpr (R == 1) {
-    p[row] = v[0];
-  } else {
-    double2* __restrict__ q = reinterpret_cast<double2*>(p + row * R);
-#pragma unroll
-    for (int h = 0; h < R / 2; ++h) q[h] = make_double2(v[2 * h], v[2 * h + 1]);
-  }
 }
 
 // the table reads of bonds k0 .. k0 + CH - 1 for the row with words (u, d): slot 2 e is the up hop of bond k0 + e, slot 2 e + 1
@@ -110,14 +76,14 @@ __device__ __forceinline__ uint32_t hblock_lookups(uint32_t (&hi)[2 * CH], uint3
   for (int e = 0; e < CH; ++e) {
     const bool in = have && k0 + e < p.nb;
     const uint32_t w = k0 + e < p.nb ? tb[k0 + e] : 0u;
-    const uint64_t m = hblock_mask(w);
+    const uint64_t m = block_mask(w);
     const uint64_t u2 = u ^ m, d2 = d ^ m;
-    if (in && hblock_moves(u, w) != 0) {
+    if (in && block_differ(u, w) != 0) {
       hi[2 * e] = up_hi[u2 >> Llo];
       lo[2 * e] = up_lo[u2 & lomask];
       on |= 1u << (2 * e);
     }
-    if (in && hblock_moves(d, w) != 0) {
+    if (in && block_differ(d, w) != 0) {
       hi[2 * e + 1] = dn_hi[d2 >> Llo];
       lo[2 * e + 1] = dn_lo[d2 & lomask];
       on |= 2u << (2 * e);
@@ -143,41 +109,25 @@ __device__ __forceinline__ void hblock_gather(double (&xv)[HOPS][R], const uint3
   for (int e = 0; e < HOPS; ++e) {
 #pragma unroll
     for (int j = 0; j < R; ++j) xv[e][j] = 0.0;
-    if (rw[e] != DSEA_HBLOCK_NO_ROW) hblock_load<R>(xv[e], v, (int64_t)rw[e]);
-  }
-}
-
-// per-block partials of R per-thread sums: wave sums, then the four waves in fixed order; P[j * gridDim.x + block]
-template <int R>
-__device__ __forceinline__ void hblock_partials(const double (&acc)[R], double (*sm)[4], double* __restrict__ P) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int j = 0; j < R; ++j) {
-    const double t = wave_sum(acc[j]);
-    if (lane == 0) sm[j][wv] = t;
-  }
-  __syncthreads();
-  if (threadIdx.x < R) {
-    const double* s4 = sm[threadIdx.x];
-    P[(int64_t)threadIdx.x * gridDim.x + blockIdx.x] = ((s4[0] + s4[1]) + s4[2]) + s4[3];
+    if (rw[e] != DSEA_HBLOCK_NO_ROW) block_load<R>(xv[e], v, (int64_t)rw[e]);
   }
 }
 }  // namespace
 
-// Y = H X for the R columns of a block.  One row per thread: the row of X and the row of Y move coalesced, dn_states[rd] too;
-// up_states[ru] is one address for all lanes that share ru.  The table reads of chunk c + 1 are issued before the gathers of
-// chunk c are consumed.  A block walks the row ranges blockIdx.x, + gridDim.x, ... of 256 rows.
-// LZ (the Lanczos step): y holds Q_{i-1} on entry and receives W = H x - y diag(beta), beta = st[0 .. R) (first: W = H x, y is
-// not read); P receives the per-block partials of x_j . W_j.
+// Y = H X for the R columns of a block; LZ: the Lanczos step W = H x - y diag(st[0 .. R)) with the partials of x_j . W_j in P.
+// The family's row walk, written here because this is its one kernel, then the tail block_spmv_tail: the couplings, the bond
+// table and the bonds' between-masks are staged in LDS; one row per thread, the row of X and the row of Y move coalesced,
+// dn_states[rd] too; up_states[ru] is one address for all lanes that share ru.  The table reads of chunk c + 1 are issued before
+// the gathers of chunk c are consumed.  A block walks the row ranges blockIdx.x, + gridDim.x, ... of 256 rows.
 template <int R, bool LZ>
 __global__ __launch_bounds__(256) void k_spmv_hubbard_block(HubbardBlockParams p, const double* __restrict__ x, double* __restrict__ y,
                                                             const double* __restrict__ st, int first, double* __restrict__ P) {
-  constexpr int CH = HblockChunk<R>::value;
-  constexpr int HOPS = 2 * CH;
   __shared__ double cp[DSEA_HBLOCK_MAX_PARAMS];
   __shared__ uint64_t bm[DSEA_LATTICE_MAX_BONDS];
   __shared__ uint16_t tb[DSEA_LATTICE_MAX_BONDS];
   __shared__ double sm[R][4];
+  constexpr int CH = HblockChunk<R>::value;
+  constexpr int HOPS = 2 * CH;
   const int L = p.L, nb = p.nb;
   const int64_t n = p.n;
   for (int c = threadIdx.x; c < 2 * nb + 2 * L; c += 256) cp[c] = p.c[c];
@@ -205,7 +155,7 @@ __global__ __launch_bounds__(256) void k_spmv_hubbard_block(HubbardBlockParams p
     const uint32_t ru = rr / p.n_dn, rd = rr - ru * p.n_dn;
     const uint64_t u = p.up_states[ru], d = p.dn_states[rd];
     double xr[R];
-    hblock_load<R>(xr, x, (int64_t)rr);
+    block_load<R>(xr, x, (int64_t)rr);
     uint32_t hi[HOPS], lo[HOPS];
     uint32_t on = hblock_lookups<CH>(hi, lo, u, d, have, 0, p, tb);
     double diag = 0.0, sum[R];
@@ -230,8 +180,8 @@ __global__ __launch_bounds__(256) void k_spmv_hubbard_block(HubbardBlockParams p
           const double tt = ts[k0 + e];
           diag = fma(Vs[k0 + e], hblock_nn(u, d, w), diag);
           // -t sgn = t (-1)^(parity + 1): the sign goes into the sign bit of the coupling
-          const double tu = hblock_signed(tt, hblock_parity(u, between) ^ 1ull);
-          const double td = hblock_signed(tt, hblock_parity(d, between) ^ 1ull);
+          const double tu = block_signed(tt, hblock_parity(u, between) ^ 1ull);
+          const double td = block_signed(tt, hblock_parity(d, between) ^ 1ull);
 #pragma unroll
           for (int j = 0; j < R; ++j) {
             sum[j] = fma(tu, xv[2 * e][j], sum[j]);
@@ -240,32 +190,9 @@ __global__ __launch_bounds__(256) void k_spmv_hubbard_block(HubbardBlockParams p
         }
       }
     }
-    if (have) {
-      double v[R];
-#pragma unroll
-      for (int j = 0; j < R; ++j) v[j] = fma(diag, xr[j], sum[j]);
-      if constexpr (LZ) {
-        if (!first) {
-          double old[R];
-          hblock_load<R>(old, y, r);
-#pragma unroll
-          for (int j = 0; j < R; ++j) v[j] = __dsub_rn(v[j], __dmul_rn(beta[j], old[j]));
-        }
-#pragma unroll
-        for (int j = 0; j < R; ++j) acc[j] = fma(xr[j], v[j], acc[j]);
-      }
-      hblock_store<R>(y, r, v);
-    }
+    if (have) block_spmv_tail<R, LZ>(y, first, beta, acc, r, xr, diag, sum);
   }
-  if constexpr (LZ) hblock_partials<R>(acc, sm, P);
-}
-
-// one block per 256 rows up to the cap 2^tune_tile_log2 (6 .. 12, 12 at creation: 4096); beyond it blocks walk row ranges
-static inline int hubbard_block_blocks(const OpDesc& op) {
-  int64_t nblk = (op.n + 255) / 256;
-  const int64_t cap = (int64_t)1 << op.tune_tile_log2;
-  if (nblk > cap) nblk = cap;
-  return (int)nblk;
+  if constexpr (LZ) block_partials<R>(acc, sm, P);
 }
 
 // the kernel arguments; false when the descriptor is out of range
@@ -289,20 +216,15 @@ static bool hubbard_block_params(const OpDesc& op, HubbardBlockParams* p) {
   p->dn_states = d.dn_states;
   p->dn_lo = d.dn_lo;
   p->dn_hi = d.dn_hi;
-  for (int t = 0; t < DSEA_LATTICE_MAX_BONDS; ++t)
-    p->tb[t] = t < d.nb ? (uint16_t)((uint32_t)d.a[t] | ((uint32_t)d.b[t] << 8)) : (uint16_t)0;
+  block_pack_bonds(p->tb, d.a, d.b, d.nb);
   return true;
 }
-
-// the one place of this file that turns the run-time R into the template argument
-template <class F>
-static inline void dispatch_hubbard_block_width(int R, F&& f) { dispatch_int<1, 2, 4, 8>(R, f); }
 
 int launch_hubbard_block_apply(const OpDesc& op, int R, const double* X, double* Y, hipStream_t st) {
   HubbardBlockParams p;
   if (!hubbard_block_params(op, &p)) return -1;
-  const int nblk = hubbard_block_blocks(op);
-  dispatch_hubbard_block_width(R, [&](auto r) {
+  const int nblk = block_blocks(op);
+  dispatch_block_width(R, [&](auto r) {
     klaunch(nullptr, k_spmv_hubbard_block<decltype(r)::value, false>, nblk, 256, 0, st, p, X, Y, nullptr, 1, nullptr);
   });
   return nblk;
@@ -313,10 +235,10 @@ int launch_hubbard_block_lanczos(const OpDesc& op, int R, int k, double* Q, doub
                                  int32_t* steps, double* scratch, hipStream_t st) {
   HubbardBlockParams p;
   if (!hubbard_block_params(op, &p)) return -1;
-  const int nblk = hubbard_block_blocks(op);
+  const int nblk = block_blocks(op);
   return block_lanczos_drive(op.n, nblk, R, k, Q, W, norm2, alphas, betas, steps, scratch, st,
                              [&](const double* q, double* w, const double* state, int first, double* PA) {
-                               dispatch_hubbard_block_width(R, [&](auto r) {
+                               dispatch_block_width(R, [&](auto r) {
                                  klaunch(nullptr, k_spmv_hubbard_block<decltype(r)::value, true>, nblk, 256, 0, st, p, q, w, state,
                                          first, PA);
                                });

@@ -572,10 +572,8 @@ int launch_hubbard_ladder_forms(int L, int nup_src, int ndn_src, int species, in
                                 double* out, double* scratch, int grid_log2, hipStream_t st);
 // dsea_sector_block.hip (the bond-list sector Hamiltonian on a block of R vectors, docs/design/27-finite-temperature.md): a block is
 // fp64 [n, R] row-major, R in {1, 2, 4, 8}.  launch_sector_block_apply: Y = H X (column j bit for bit the single-vector mat-vec).
-// launch_sector_block_lanczos: the start and k steps of the basis-free block recurrence with the per-column break record, three
-// launches per step, nothing read back; scratch of sector_block_lanczos_scratch_doubles(n, R) doubles (enough for every grid
-// cap).  The launchers return -1 when the descriptor is out of range; the callers check R.
-int64_t sector_block_lanczos_scratch_doubles(int64_t n, int R);
+// launch_sector_block_lanczos: block_lanczos_drive (below) with the file's Lanczos-step kernel as the mat-vec.  The launchers
+// return -1 when the descriptor is out of range; the callers check R.
 int launch_sector_block_apply(const OpDesc& op, int R, const double* X, double* Y, hipStream_t st);
 int launch_sector_block_lanczos(const OpDesc& op, int R, int k, double* Q, double* W, double* norm2, double* alphas, double* betas,
                                 int32_t* steps, double* scratch, hipStream_t st);
@@ -584,19 +582,21 @@ int launch_sector_block_lanczos(const OpDesc& op, int R, int k, double* Q, doubl
 // work blocks, X is not written, nothing is read back.  The blocks launched, or -1 for a descriptor out of range.
 int launch_sector_block_chebyshev(const OpDesc& op, int R, int A, int M, double centre, double halfwidth, const double* coeffs,
                                   const double* X, double* U, double* V, double* ACC, hipStream_t st);
-// The driver of that recurrence for any operator (defined in dsea_sector_block.hip, beside the recurrence kernels it launches):
-// the start and k steps on nblk blocks of 256 rows, the mat-vec of a step being the caller's step(q, w, state, first, PA), which
-// launches W = H q - w diag(state[0 .. R)) over w (first != 0: W = H q, w is not read) with the partials of q_j . W_j in
-// PA[j * nblk + block].  Scratch as sector_block_lanczos_scratch_doubles(n, R).  Returns 0.
-typedef std::function<void(const double* q, double* w, const double* state, int first, double* PA)> BlockLanczosStep;
-int block_lanczos_drive(int64_t n, int nblk, int R, int k, double* Q, double* W, double* norm2, double* alphas, double* betas,
-                        int32_t* steps, double* scratch, hipStream_t st, const BlockLanczosStep& step);
 // dsea_hubbard_block.hip (the Hubbard Hamiltonian on a block of R vectors, docs/design/28-hubbard-finite-temperature.md): the twins
 // of launch_sector_block_apply and launch_sector_block_lanczos for an OP_HUBBARD descriptor; column j of Y = H X is bit for bit
 // the single-vector mat-vec without a shift.  -1 when the descriptor is out of range; the callers check R.
 int launch_hubbard_block_apply(const OpDesc& op, int R, const double* X, double* Y, hipStream_t st);
 int launch_hubbard_block_lanczos(const OpDesc& op, int R, int k, double* Q, double* W, double* norm2, double* alphas, double* betas,
                                  int32_t* steps, double* scratch, hipStream_t st);
+// dsea_block_lanczos.hip (the basis-free block Lanczos recurrence for any operator; the device parts the block kernels share are
+// in dsea_block.h, docs/design/32-block-kernel-parts.md): the start and k steps with the per-column break record on nblk blocks
+// of 256 rows, three launches per step, nothing read back.  The mat-vec of a step is the caller's step(q, w, state, first, PA),
+// which launches W = H q - w diag(state[0 .. R)) over w (first != 0: W = H q, w is not read) with the partials of q_j . W_j in
+// PA[j * nblk + block].  Scratch of block_lanczos_scratch_doubles(n, R) doubles (enough for every grid cap).  Returns 0.
+int64_t block_lanczos_scratch_doubles(int64_t n, int R);
+typedef std::function<void(const double* q, double* w, const double* state, int first, double* PA)> BlockLanczosStep;
+int block_lanczos_drive(int64_t n, int nblk, int R, int k, double* Q, double* W, double* norm2, double* alphas, double* betas,
+                        int32_t* steps, double* scratch, hipStream_t st, const BlockLanczosStep& step);
 // dsea_cg_persist_tfim_big.hip
 bool cg_persist_tfim_big_applicable(const OpDesc& op);
 size_t cg_persist_tfim_big_comm_bytes(int64_t n);
