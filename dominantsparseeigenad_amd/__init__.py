@@ -12,12 +12,14 @@ empty; users import sub-modules by name):
                                         SpinSectorLadder (sigma^-, sigma^+ and Z maps between magnetisation sectors)
                                         HubbardLadder (c+, c and n maps between Hubbard sectors), one_body_density_matrix
     dominantsparseeigenad_amd.spectral  lanczos_measure, SpectralMeasure, dynamical_structure_factor,
-                                        hubbard_spectral_function (re-exported here)
+                                        hubbard_spectral_function, kpm_measure, kpm_structure_factor (re-exported here)
     dominantsparseeigenad_amd.thermal   block_lanczos_measures, sector_trace_measure, ThermalEnsemble, spin_thermodynamics,
-                                        GrandCanonicalEnsemble, hubbard_thermodynamics, thermal_correlations (finite
-                                        temperature; re-exported here)
+                                        GrandCanonicalEnsemble, hubbard_thermodynamics, thermal_correlations,
+                                        sector_density_of_states, spin_density_of_states (finite temperature; re-exported here)
     dominantsparseeigenad_amd.chebyshev chebyshev_coefficients, exp_order, spectral_bounds, chebyshev_apply, expm_block,
-                                        time_evolve (f(H) X without a basis; re-exported here)
+                                        time_evolve (f(H) X without a basis), chebyshev_moments, jackson_kernel,
+                                        lorentz_kernel, ChebyshevMeasure (moments and kernel polynomial densities; re-exported
+                                        here)
 
 The top-level ``DominantSparseEigenAD`` package in this repository re-exports the same modules
 under the reference's import names.
@@ -28,17 +30,18 @@ __version__ = "0.1.0"
 def __getattr__(name):
     # the spectral functions under the package's own name, resolved on first use (the module imports torch and the engine)
     if name in ("spectral", "lanczos_measure", "SpectralMeasure", "dynamical_structure_factor",
-                "hubbard_spectral_function"):
+                "hubbard_spectral_function", "kpm_measure", "kpm_structure_factor"):
         import importlib
         mod = importlib.import_module(__name__ + ".spectral")
         return mod if name == "spectral" else getattr(mod, name)
     if name in ("thermal", "block_lanczos_measures", "sector_trace_measure", "ThermalEnsemble", "spin_thermodynamics",
-                "GrandCanonicalEnsemble", "hubbard_thermodynamics", "thermal_correlations"):
+                "GrandCanonicalEnsemble", "hubbard_thermodynamics", "thermal_correlations", "sector_density_of_states",
+                "spin_density_of_states"):
         import importlib
         mod = importlib.import_module(__name__ + ".thermal")
         return mod if name == "thermal" else getattr(mod, name)
     if name in ("chebyshev", "chebyshev_coefficients", "exp_order", "spectral_bounds", "chebyshev_apply", "expm_block",
-                "time_evolve"):
+                "time_evolve", "chebyshev_moments", "jackson_kernel", "lorentz_kernel", "ChebyshevMeasure"):
         import importlib
         mod = importlib.import_module(__name__ + ".chebyshev")
         return mod if name == "chebyshev" else getattr(mod, name)

@@ -14,12 +14,20 @@ On a ``SpinSectorOperator`` every order is ONE launch of k_cheb_sector_block: th
     expm_block(op, X, tau)                  (Y, shift) with e^{-tau H} X = e^{-tau shift} Y
     time_evolve(op, psi, t)                 e^{-i H t} psi
 
+and what the propagated block projects onto (docs/design/33-chebyshev-moments.md): the moments mu_m = <l| T_m(s) |x>, on a
+``SpinSectorOperator`` one launch of k_cheb_sector_moments per order with the two dot products inside, two moments per order
+when l = x.  They do not depend on f: one run serves every function and the kernel polynomial method's densities.
+
+    chebyshev_moments(op, X, M, bounds)     mu [M, R], optionally against a left block
+    jackson_kernel(M), lorentz_kernel(M)    the damping factors g_m
+    ChebyshevMeasure(moments, bounds)       density(E), trace(f), logtrace_exp(beta), shifted(E0), +
+
 Plain host float64 numbers and detached blocks: nothing here is differentiable.
 """
 from __future__ import annotations
 
 import math
-from ctypes import c_double, c_void_p
+from ctypes import byref, c_double, c_int64, c_void_p
 
 import numpy as np
 import torch
@@ -173,6 +181,12 @@ def chebyshev_apply(op, X, coeffs, bounds, fused=None):
     return out[0] if single else out
 
 
+def _aligned_piece(X, first, w):
+    """columns first .. first + w of X as a contiguous block on a 16-byte boundary"""
+    piece = X[:, first:first + w].contiguous()
+    return piece.clone() if piece.data_ptr() % 16 else piece
+
+
 def _apply_fused(op, X, c, centre, h):
     lib = _lib.load()
     A, M = c.shape
@@ -181,9 +195,7 @@ def _apply_fused(op, X, c, centre, h):
     out = torch.empty((A, n, R), dtype=F64, device=X.device)
     ptr = lambda t: c_void_p(t.data_ptr())  # noqa: E731
     for first, w in block_pieces(R):
-        Xp = X[:, first:first + w].contiguous()
-        if Xp.data_ptr() % 16:
-            Xp = Xp.clone()
+        Xp = _aligned_piece(X, first, w)
         U, V = torch.empty_like(Xp), torch.empty_like(Xp)
         acc = torch.empty((A, n, w), dtype=F64, device=X.device)
         check(lib.dsea_op_sector_block_chebyshev(op.handle, w, A, M, centre, h, host, ptr(Xp), ptr(U), ptr(V), ptr(acc),
@@ -207,6 +219,195 @@ def _apply_unfused(op, X, c, centre, h):
             acc = [acc[a] + c[a][m] * t for a in range(A)]
         old, x = x, t
     return torch.stack(acc)
+
+
+def chebyshev_moments(op, X, M, bounds, left=None, fused=None):
+    """mu [M, R] (host float64) with mu[m, j] = <l_j| T_m((H - centre) / h) |x_j> for a device block X (n, R), any R >= 1, M >= 2
+    and ``bounds`` = (a, b) = (centre - h, centre + h), which must hold the spectrum of H; l = X unless a second block ``left``
+    (n, R) is given (docs/design/33-chebyshev-moments.md).  Without ``left`` the product rule T_a T_b = (T_{a+b} + T_{|a-b|}) / 2
+    gives two moments per order, mu_{2m-2} = 2 <T_{m-1} x|T_{m-1} x> - mu_0 and mu_{2m-1} = 2 <T_{m-1} x|T_m x> - mu_1: ceil(M / 2)
+    mat-vecs; with ``left`` M - 1.
+
+    ``fused=True``: dsea_op_sector_block_moments, one launch per order with the dot products inside and one small launch that
+    closes them, ``SpinSectorOperator`` only (``ValueError`` otherwise), the columns in pieces of 8, 4, 2 and 1.
+    ``fused=False``: ``op.apply_block``, torch elementwise operations in the order of the kernel's tail and column sums, for any
+    operator with ``apply_block`` (a ``HubbardOperator`` among them).  ``None``: fused where the entry exists.  The two paths run
+    the same recurrence bit for bit but sum the dot products in different orders: their moments agree to rounding, NOT bit for
+    bit.  X and ``left`` are detached and not written."""
+    from .operators import SpinSectorOperator
+    M = int(M)
+    if M < 2:
+        raise ValueError("chebyshev_moments needs M >= 2, got %d" % M)
+    centre, h = _check_bounds(bounds)
+    can_fuse = isinstance(op, SpinSectorOperator)
+    if fused is None:
+        fused = can_fuse
+    if fused and not can_fuse:
+        raise ValueError("the fused moments kernel exists for SpinSectorOperator only, got %s" % type(op).__name__)
+    if not callable(getattr(op, "apply_block", None)):
+        raise ValueError("chebyshev_moments needs an operator with apply_block, got %s" % type(op).__name__)
+    X = _as_block(op, X, "chebyshev_moments").to(F64)
+    if left is not None:
+        left = _as_block(op, left, "chebyshev_moments").to(F64)
+        if left.shape != X.shape:
+            raise ValueError("the left block must have the shape %r of X, got %r" % (tuple(X.shape), tuple(left.shape)))
+    return (_moments_fused if fused else _moments_unfused)(op, X, left, M, centre, h)
+
+
+def _moments_fused(op, X, left, M, centre, h):
+    lib = _lib.load()
+    dev = X.device
+    ptr = lambda t: c_void_p(t.data_ptr())  # noqa: E731
+    out = []
+    for first, w in block_pieces(X.shape[1]):
+        Xp = _aligned_piece(X, first, w)
+        Yp = None if left is None else _aligned_piece(left, first, w)
+        U, V = torch.empty_like(Xp), torch.empty_like(Xp)
+        mu = torch.empty((M, w), dtype=F64, device=dev)
+        need = c_int64()
+        check(lib.dsea_op_sector_block_moments_scratch_doubles(op.N, op.ndown, w, byref(need)),
+              "dsea_op_sector_block_moments_scratch_doubles")
+        scratch = torch.empty(need.value, dtype=F64, device=dev)
+        check(lib.dsea_op_sector_block_moments(op.handle, w, M, centre, h, ptr(Xp), None if Yp is None else ptr(Yp), ptr(U), ptr(V),
+                                               ptr(mu), ptr(scratch), engine._stream(dev)), "dsea_op_sector_block_moments")
+        out.append(mu.cpu())
+    return torch.cat(out, dim=1)
+
+
+def _moments_unfused(op, X, left, M, centre, h):
+    """the orders of k_cheb_sector_moments on ``op.apply_block``: the tail as separate elementwise operations, each rounded on
+    its own, the dot products as column sums, and the doubling of k_cheb_moments_finish"""
+    mu = torch.empty((M, X.shape[1]), dtype=F64, device=X.device)
+    x, old = X, None
+    for m in range(1, (M if left is not None else (M + 1) // 2 + 1)):
+        t = ((1.0 if m == 1 else 2.0) / h) * (op.apply_block(x) - centre * x)
+        if m > 1:
+            t = t - old
+        l = x if left is None else left
+        a, b = (l * x).sum(0), (l * t).sum(0)
+        if m == 1:
+            mu[0], mu[1] = a, b
+        elif left is not None:
+            mu[m] = b
+        else:
+            if 2 * m - 2 < M:
+                mu[2 * m - 2] = 2.0 * a - mu[0]
+            if 2 * m - 1 < M:
+                mu[2 * m - 1] = 2.0 * b - mu[1]
+        old, x = x, t
+    return mu.cpu()
+
+
+def jackson_kernel(M):
+    """g [M] (float64): the Jackson damping factors g_m = [(M - m + 1) cos(pi m / (M + 1)) + sin(pi m / (M + 1)) cot(pi / (M + 1))]
+    / (M + 1) of the kernel polynomial method: g_0 = 1, decreasing, and the damped density of a positive measure is positive
+    with the resolution pi h / M"""
+    M = int(M)
+    if M < 1:
+        raise ValueError("jackson_kernel needs M >= 1, got %d" % M)
+    pi = 4 * np.arctan(LD(1))
+    m = np.arange(M, dtype=LD)
+    q = pi / LD(M + 1)
+    return (((LD(M + 1) - m) * np.cos(m * q) + np.sin(m * q) / np.tan(q)) / LD(M + 1)).astype(np.float64)
+
+
+def lorentz_kernel(M, lam=4.0):
+    """g [M] (float64): the Lorentz damping factors g_m = sinh(lam (1 - m / M)) / sinh(lam), which turn a pole into a Lorentzian
+    of width lam h / M (the kernel for Green's functions)"""
+    M, lam = int(M), float(lam)
+    if M < 1 or not (lam > 0 and math.isfinite(lam)):
+        raise ValueError("lorentz_kernel needs M >= 1 and a finite lam > 0, got %d and %r" % (M, lam))
+    m = np.arange(M, dtype=LD)
+    return (np.sinh(LD(lam) * (LD(1) - m / LD(M))) / np.sinh(LD(lam))).astype(np.float64)
+
+
+_KERNELS = {"jackson": jackson_kernel, "lorentz": lorentz_kernel}
+
+
+class ChebyshevMeasure:
+    """A measure on the interval ``bounds`` = (a, b) given by its M Chebyshev moments mu_m = int T_m((E - centre) / h) d mu(E):
+    <x| . |x> of one vector (``spectral.kpm_measure``), or a trace (``thermal.sector_density_of_states``).  ``moments`` is a host
+    float64 tensor [M].  The sum of two measures on the same interval with the same M adds their moments.  Plain numbers:
+    nothing here is differentiable."""
+
+    def __init__(self, moments, bounds):
+        self.moments = torch.as_tensor(moments, dtype=F64).detach().cpu().reshape(-1).clone()
+        if self.moments.numel() < 1 or not bool(torch.isfinite(self.moments).all()):
+            raise ValueError("a ChebyshevMeasure needs at least one moment, all finite")
+        self.centre, self.halfwidth = _check_bounds(bounds)
+        self.bounds = (float(bounds[0]), float(bounds[1]))
+
+    def __len__(self):
+        return self.moments.numel()
+
+    def _damping(self, kernel):
+        M = len(self)
+        if kernel is None:
+            return np.ones(M)
+        if isinstance(kernel, str):
+            if kernel not in _KERNELS:
+                raise ValueError("kernel must be one of %s, None or an array of %d factors, got %r"
+                                 % (", ".join(repr(k) for k in sorted(_KERNELS)), M, kernel))
+            return _KERNELS[kernel](M)
+        g = np.array(kernel, dtype=np.float64)
+        if g.shape != (M,) or not np.isfinite(g).all():
+            raise ValueError("an array of damping factors must be finite and of shape (%d,), got %r" % (M, g.shape))
+        return g
+
+    def density(self, E, kernel="jackson"):
+        """[g_0 mu_0 + 2 sum_{m >= 1} g_m mu_m T_m(s)] / (pi h sqrt(1 - s^2)) at the energies ``E`` (any shape) strictly inside
+        the bounds, 0 outside; a host float64 tensor of the shape of E.  ``kernel``: "jackson", "lorentz", None (no damping) or
+        an array of M factors.  cos(m arccos s) is formed a few orders at a time: host memory is O(len E)."""
+        c = self._damping(kernel) * self.moments.numpy()
+        c[1:] *= 2.0
+        E = np.asarray(torch.as_tensor(E, dtype=F64).detach().cpu().numpy())
+        s = (E.reshape(-1) - self.centre) / self.halfwidth
+        inside = np.abs(s) < 1.0
+        theta = np.arccos(s[inside])
+        acc = np.zeros(theta.shape)
+        for first in range(0, len(c), COEFFICIENT_ROWS):
+            m = np.arange(first, min(len(c), first + COEFFICIENT_ROWS), dtype=np.float64)
+            acc += c[first:first + m.size] @ np.cos(m[:, None] * theta[None, :])
+        out = np.zeros(s.shape)
+        out[inside] = acc / (math.pi * self.halfwidth * np.sqrt(1.0 - s[inside] ** 2))
+        return torch.from_numpy(out.reshape(E.shape))
+
+    def _expansion(self, g):
+        """sum_m c_m mu_m with the coefficients of g(s) on [-1, 1] (c_0 halved as ``chebyshev_coefficients`` returns it)"""
+        return float(np.dot(chebyshev_coefficients(g, len(self)), self.moments.numpy()))
+
+    def trace(self, f):
+        """sum_m c_m mu_m with the M Chebyshev coefficients of f on the bounds: the undamped estimate of int f d mu, that is of
+        <x| f(H) |x> or tr f(H).  ``f`` takes and returns a ``numpy.longdouble`` array of energies."""
+        centre, h = LD(self.centre), LD(self.halfwidth)
+        return self._expansion(lambda s: f(centre + h * s))
+
+    def logtrace_exp(self, beta):
+        """ln int e^{-beta E} d mu(E) for beta >= 0 as -beta a + ln sum_m c_m mu_m with the coefficients of e^{-beta h (s + 1)},
+        which are at most 1 (the shift of ``expm_block``); M should reach ``exp_order(beta h)``"""
+        beta = float(beta)
+        if not (beta >= 0 and math.isfinite(beta)):
+            raise ValueError("logtrace_exp needs a finite beta >= 0, got %r" % (beta,))
+        x = LD(beta * self.halfwidth)
+        total = self._expansion(lambda s: np.exp(-x * (s + LD(1))))
+        if not total > 0:
+            raise ValueError("the expansion of e^{-beta H} sums to %r: too few moments for beta h = %g" % (total, float(x)))
+        return math.log(total) - beta * self.bounds[0]
+
+    def shifted(self, E0):
+        """the same moments on the bounds moved by -E0: the measure as a function of E - E0"""
+        return ChebyshevMeasure(self.moments, (self.bounds[0] - float(E0), self.bounds[1] - float(E0)))
+
+    def __add__(self, other):
+        if not isinstance(other, ChebyshevMeasure):
+            return NotImplemented
+        if other.bounds != self.bounds or len(other) != len(self):
+            raise ValueError("only measures with the same bounds and the same number of moments add")
+        return ChebyshevMeasure(self.moments + other.moments, self.bounds)
+
+    def __repr__(self):
+        return "ChebyshevMeasure(%d moments on [%.6g, %.6g], mu_0 = %.6g)" % (len(self), self.bounds[0], self.bounds[1],
+                                                                              float(self.moments[0]))
 
 
 def expm_block(op, X, tau, bounds=None, tol=1e-15):

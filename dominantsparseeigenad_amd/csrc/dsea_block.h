@@ -1,7 +1,7 @@
 // dsea_block.h -- what a block kernel needs whatever the operator (docs/design/32-block-kernel-parts.md): the row access and
 // the partials of a block, the helpers of the a | b << 8 bond table, the tail of the plain and the Lanczos-step mat-vec, and the
-// host rules of the launchers (grid, width dispatch, bond table).  Used by dsea_sector_block.hip, dsea_hubbard_block.hip and
-// dsea_block_lanczos.hip.
+// host rules of the launchers (grid, width dispatch, bond table).  Used by dsea_sector_block.hip, dsea_hubbard_block.hip,
+// dsea_block_lanczos.hip and dsea_block_moments.hip.
 //
 // A block is an fp64 array [n, R], row-major (element (r, j) at r * R + j), 16-byte aligned, R in {1, 2, 4, 8}.  A family's
 // mat-vec kernel forms, one row per thread, diag and sum[j] of the row of H x and hands them to block_spmv_tail after the last

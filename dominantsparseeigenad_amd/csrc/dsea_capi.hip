@@ -2135,6 +2135,27 @@ int dsea_op_sector_block_chebyshev(dsea_op_t op, int R, int A, int M, double cen
   return check_launch();
 }
 
+int dsea_op_sector_block_moments_scratch_doubles(int L, int ndown, int R, int64_t* out) {
+  int64_t n, n_lo, n_hi;
+  REQUIRE(out && sector_sizes(L, ndown, &n, &n_lo, &n_hi) && block_width_ok(R), DSEA_ERR_ARG);
+  *out = block_moments_scratch_doubles(n, R);
+  return DSEA_OK;
+}
+
+int dsea_op_sector_block_moments(dsea_op_t op, int R, int M, double centre, double halfwidth, const double* X, const double* Y,
+                                 double* U, double* V, double* MU, double* scratch, void* stream) {
+  REQUIRE(op && op->d.kind == OP_SECTOR && block_width_ok(R) && M >= 2 && X && U && V && MU && scratch && std::isfinite(centre) &&
+              std::isfinite(halfwidth) && halfwidth > 0.0,
+          DSEA_ERR_ARG);
+  const double* blocks[4] = {X, U, V, Y};                                      // (a null Y, self mode, equals none of the others)
+  for (int i = 0; i < 4; ++i)
+    for (int j = i + 1; j < 4; ++j) REQUIRE(blocks[i] != blocks[j], DSEA_ERR_ARG);
+  REQUIRE(aligned16(X) && aligned16(Y) && aligned16(U) && aligned16(V), DSEA_ERR_ALIGN);
+  if (launch_sector_block_moments(op->d, R, M, centre, halfwidth, X, Y, U, V, MU, scratch, static_cast<hipStream_t>(stream)) != 0)
+    return DSEA_ERR_UNSUPPORTED;
+  return check_launch();
+}
+
 int dsea_op_hubbard_block_apply(dsea_op_t op, int R, const double* X, double* Y, void* stream) {
   REQUIRE(op && op->d.kind == OP_HUBBARD && block_width_ok(R) && X && Y && X != Y, DSEA_ERR_ARG);
   REQUIRE(aligned16(X) && aligned16(Y), DSEA_ERR_ALIGN);

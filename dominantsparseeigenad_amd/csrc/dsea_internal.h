@@ -582,6 +582,22 @@ int launch_sector_block_lanczos(const OpDesc& op, int R, int k, double* Q, doubl
 // work blocks, X is not written, nothing is read back.  The blocks launched, or -1 for a descriptor out of range.
 int launch_sector_block_chebyshev(const OpDesc& op, int R, int A, int M, double centre, double halfwidth, const double* coeffs,
                                   const double* X, double* U, double* V, double* ACC, hipStream_t st);
+// launch_sector_block_moments (docs/design/33-chebyshev-moments.md): MU[m, j] = l_j . T_m((H - centre) / halfwidth) x_j, m < M,
+// l = X for a null Y (self mode, ceil(M / 2) orders) or Y (left mode, M - 1 orders): block_moments_drive (below) with the file's
+// k_cheb_sector_moments<R, LEFT> as the step.  Returns 0, or -1 for a descriptor out of range.
+int launch_sector_block_moments(const OpDesc& op, int R, int M, double centre, double halfwidth, const double* X, const double* Y,
+                                double* U, double* V, double* MU, double* scratch, hipStream_t st);
+// dsea_block_moments.hip (the finish kernel and the launch schedule of the Chebyshev moments for any operator): K = ceil(M / 2)
+// orders (left: M - 1) on nblk blocks of 256 rows, each the caller's step(x, old, out, first, P) -- one order of the recurrence,
+// out = g (H x - centre x) [- old], with the per-block partials of a_j = l_j . x_j and b_j = l_j . out_j in P[(which R + j) nblk
+// + block] -- and one launch of k_cheb_moments_finish<R>.  Order 1 is first with x = X, out = U; order 2 x = U, old = X, out = V;
+// then old == out, U and V in turn.  ON RETURN T_K X is in U for odd K and in V for even K, and T_{K-1} X in the other work block
+// (in X for K = 1), so that a caller can continue the run.  Scratch of block_moments_scratch_doubles(n, R) = 2 R min(4096,
+// ceil(n / 256)) doubles (enough for every grid cap).  Nothing is read back, no synchronise, no allocation.  Returns 0.
+int64_t block_moments_scratch_doubles(int64_t n, int R);
+typedef std::function<void(const double* x, const double* old, double* out, int first, double* P)> BlockMomentsStep;
+int block_moments_drive(int64_t n, int nblk, int R, int M, bool left, const double* X, double* U, double* V, double* MU,
+                        double* scratch, hipStream_t st, const BlockMomentsStep& step);
 // dsea_hubbard_block.hip (the Hubbard Hamiltonian on a block of R vectors, docs/design/28-hubbard-finite-temperature.md): the twins
 // of launch_sector_block_apply and launch_sector_block_lanczos for an OP_HUBBARD descriptor; column j of Y = H X is bit for bit
 // the single-vector mat-vec without a shift.  -1 when the descriptor is out of range; the callers check R.

@@ -3,6 +3,8 @@
 // their launchers, on the block parts of dsea_block.h.  The block Lanczos recurrence that runs around the LZ kernel is in
 // dsea_block_lanczos.hip.  The two kernels hold the same row walk, statement for statement: written once, as a function called
 // by both or as a walker that takes the tail, the R = 8 kernels ran 0.5 to 1.4 % slower (docs/design/32-block-kernel-parts.md).
+// k_cheb_sector_moments<R, LEFT> (docs/design/33-chebyshev-moments.md) is a third holder of that walk: the Chebyshev order with
+// the two dot products of the moments; its finish kernel and launch schedule are in dsea_block_moments.hip.
 //
 // One row per thread: the row's state word and the two table reads of a flipped bond are paid once for all R columns, and every
 // gather is R contiguous doubles (R / 2 16-byte loads; one 8-byte load at R = 1).  The per-row arithmetic of a column is that of
@@ -224,6 +226,101 @@ __global__ __launch_bounds__(256) void k_cheb_sector_block(SectorBlockParams p, 
   }
 }
 
+// One order of the Chebyshev recurrence WITH the two reductions of the moments (docs/design/33-chebyshev-moments.md).  The row
+// walk is that of k_cheb_sector_block<R, 1>, statement for statement (32-block-kernel-parts.md: sharing it changed the
+// existing symbols), and the recurrence part of the tail is its tail without the accumulator block:
+//   t = g (w - centre x),  !first: t = t - old,  out = t
+//   LEFT = false:  a_j += x_j x_j,  b_j += x_j t_j          LEFT = true:  a_j += y_j x_j,  b_j += y_j t_j
+// by fma into the thread's accumulators; y is the row of the left block, read after the last chunk's gathers are consumed like
+// old.  A thread without a row adds nothing.  After the row loop the block's partials go to P[(which R + j) gridDim.x + block],
+// which = 0 for a, 1 for b: no atomics.  old == out is allowed; x and y are distinct from every written block.
+template <int R, bool LEFT>
+__global__ __launch_bounds__(256) void k_cheb_sector_moments(SectorBlockParams p, const double* __restrict__ x, const double* old,
+                                                             double* out, const double* __restrict__ y, double centre, double g,
+                                                             int first, double* __restrict__ P) {
+  constexpr int CH = SblockChunk<R>::value;
+  __shared__ double cp[DSEA_SBLOCK_MAX_PARAMS];
+  __shared__ uint16_t tb[DSEA_LATTICE_MAX_BONDS];
+  __shared__ double sma[R][4];
+  __shared__ double smb[R][4];
+  const int L = p.L, nb = p.nb, Llo = p.Llo;
+  const int64_t n = p.n;
+  for (int c = threadIdx.x; c < 2 * nb + L; c += 256) cp[c] = p.c[c];
+  for (int c = threadIdx.x; c < nb; c += 256) tb[c] = p.tb[c];
+  __syncthreads();
+  const double* __restrict__ jxy = cp;
+  const double* __restrict__ jzs = cp + nb;
+  const double* __restrict__ hzs = cp + 2 * nb;
+  double acca[R], accb[R];
+#pragma unroll
+  for (int j = 0; j < R; ++j) {
+    acca[j] = 0.0;
+    accb[j] = 0.0;
+  }
+  for (int64_t row0 = (int64_t)blockIdx.x * 256; row0 < n; row0 += (int64_t)gridDim.x * 256) {
+    const int64_t r = row0 + threadIdx.x;
+    const bool have = r < n;                       // (a thread past the last row reads row n - 1 and writes nothing)
+    const int64_t rr = have ? r : n - 1;
+    const uint64_t s = p.states[rr];
+    double xr[R];
+    block_load<R>(xr, x, rr);
+    uint32_t rk[CH], hi[CH], lo[CH];
+    sblock_ranks<CH>(hi, lo, s, have, 0, nb, Llo, tb, p.lo_rank, p.hi_base);
+    double diag = 0.0, sum[R];
+#pragma unroll
+    for (int j = 0; j < R; ++j) sum[j] = 0.0;
+    for (int i = 0; i < L; ++i) diag += block_signed(hzs[i], (s >> i) & 1ull);
+    for (int k0 = 0; k0 < nb; k0 += CH) {
+      double xv[CH][R];
+#pragma unroll
+      for (int e = 0; e < CH; ++e) rk[e] = hi[e] + lo[e];
+      sblock_gather<R, CH>(xv, rk, x);
+      sblock_ranks<CH>(hi, lo, s, have, k0 + CH, nb, Llo, tb, p.lo_rank, p.hi_base);
+#pragma unroll
+      for (int e = 0; e < CH; ++e) {
+        if (k0 + e < nb) {
+          diag += block_signed(jzs[k0 + e], block_differ(s, tb[k0 + e]));
+          const double c2 = 2.0 * jxy[k0 + e];
+#pragma unroll
+          for (int j = 0; j < R; ++j) sum[j] = fma(c2, xv[e][j], sum[j]);
+        }
+      }
+    }
+    if (have) {
+      double t[R];
+#pragma unroll
+      for (int j = 0; j < R; ++j) {
+        const double w = fma(diag, xr[j], sum[j]);
+        t[j] = __dmul_rn(g, __dsub_rn(w, __dmul_rn(centre, xr[j])));
+      }
+      if (!first) {
+        double ov[R];
+        block_load<R>(ov, old, r);
+#pragma unroll
+        for (int j = 0; j < R; ++j) t[j] = __dsub_rn(t[j], ov[j]);
+      }
+      block_store<R>(out, r, t);
+      if constexpr (LEFT) {
+        double yv[R];
+        block_load<R>(yv, y, r);
+#pragma unroll
+        for (int j = 0; j < R; ++j) {
+          acca[j] = fma(yv[j], xr[j], acca[j]);
+          accb[j] = fma(yv[j], t[j], accb[j]);
+        }
+      } else {
+#pragma unroll
+        for (int j = 0; j < R; ++j) {
+          acca[j] = fma(xr[j], xr[j], acca[j]);
+          accb[j] = fma(xr[j], t[j], accb[j]);
+        }
+      }
+    }
+  }
+  block_partials<R>(acca, sma, P);
+  block_partials<R>(accb, smb, P + (int64_t)R * gridDim.x);
+}
+
 // the kernel arguments; false when the descriptor is out of range
 static bool sector_block_params(const OpDesc& op, SectorBlockParams* p) {
   const SectorDesc& d = op.sector;
@@ -279,6 +376,23 @@ int launch_sector_block_chebyshev(const OpDesc& op, int R, int A, int M, double 
     });
   });
   return nblk;
+}
+
+// the schedule of block_moments_drive with this file's moments kernel as the step; Y null: self mode
+int launch_sector_block_moments(const OpDesc& op, int R, int M, double centre, double halfwidth, const double* X, const double* Y,
+                                double* U, double* V, double* MU, double* scratch, hipStream_t st) {
+  SectorBlockParams p;
+  if (!sector_block_params(op, &p)) return -1;
+  const int nblk = block_blocks(op);
+  return block_moments_drive(op.n, nblk, R, M, Y != nullptr, X, U, V, MU, scratch, st,
+                             [&](const double* x, const double* old, double* out, int first, double* P) {
+                               dispatch_block_width(R, [&](auto r) {
+                                 dispatch_bool(Y != nullptr, [&](auto left) {
+                                   klaunch(nullptr, k_cheb_sector_moments<decltype(r)::value, decltype(left)::value>, nblk, 256, 0,
+                                           st, p, x, old, out, Y, centre, (first ? 1.0 : 2.0) / halfwidth, first, P);
+                                 });
+                               });
+                             });
 }
 
 // the recurrence of block_lanczos_drive with this file's mat-vec as the step

@@ -11,6 +11,8 @@ k x k eigenproblem is solved on the host.
     SpectralMeasure                                               poles and weights: greens(z), __call__(omega, eta), moment(m)
     dynamical_structure_factor(op0, psi0, E0, weights, channel)   S^{zz}, S^{-}, S^{+} of a sector state through SpinSectorLadder
     hubbard_spectral_function(op0, psi0, E0, weights, channel)    c, c+, charge and spin channels of a Hubbard state (HubbardLadder)
+    kpm_measure(op, phi, M), kpm_structure_factor(...)            the same by Chebyshev moments: a ``chebyshev.ChebyshevMeasure``
+                                                                  of uniform, chosen resolution (docs/design/33-chebyshev-moments.md)
 
 A ``SpectralMeasure`` holds host float64 tensors and is NOT differentiable: derivatives of poles and weights are out of scope.
 Static quantities built on the ladder itself (|sigma^-_q psi0|^2, matrix elements) are differentiable through
@@ -124,6 +126,31 @@ def _weight_parts(weights):
     return [t.to(F64)]
 
 
+def _spin_step(channel):
+    step = {"zz": 0, "-": 1, "+": -1}.get(channel)
+    if step is None:
+        raise ValueError("channel must be 'zz', '-' or '+', got %r" % (channel,))
+    return step
+
+
+def _spin_ladder(op0, step, channel, target):
+    """(target, ladder) of a spin channel: ``target`` None builds the Hamiltonian of the destination sector from ``op0``"""
+    from .operators import SpinSectorLadder, SpinSectorOperator, SpinSectorPairOperator
+    if target is None:
+        if step == 0:
+            target = op0
+        else:
+            couplings = op0.couplings.detach()
+            if hasattr(op0, "bonds"):
+                target = SpinSectorOperator(op0.N, op0.bonds, couplings, op0.ndown + step, op0.device)
+            else:
+                target = SpinSectorPairOperator(op0.N, couplings, op0.ndown + step, op0.device)
+    lad = SpinSectorLadder(op0, target)
+    if lad.step != step:
+        raise ValueError("channel %r needs a target at ndown = %d, got %d" % (channel, op0.ndown + step, target.ndown))
+    return target, lad
+
+
 def dynamical_structure_factor(op0, psi0, E0, weights, channel, k=200, target=None, basis_free=False):
     """The spectral measure of O psi0 as a function of the excitation energy E - E0, for the eigenstate (psi0, E0) of the sector
     operator ``op0`` (``SpinSectorOperator`` or ``SpinSectorPairOperator``) and the site-weighted operator
@@ -139,24 +166,11 @@ def dynamical_structure_factor(op0, psi0, E0, weights, channel, k=200, target=No
     tables.  ``k`` Lanczos steps per real vector.  ``basis_free=True`` (bond-list ``SpinSectorOperator`` only): the real and the
     imaginary part run as one block of 1 or 2 columns through ``thermal.block_lanczos_measures`` -- no stored basis, no
     re-orthogonalisation, memory independent of k (docs/design/27-finite-temperature.md).  Plain numbers: not differentiable."""
-    from .operators import SpinSectorLadder, SpinSectorOperator, SpinSectorPairOperator
-    step = {"zz": 0, "-": 1, "+": -1}.get(channel)
-    if step is None:
-        raise ValueError("channel must be 'zz', '-' or '+', got %r" % (channel,))
+    from .operators import SpinSectorOperator
+    step = _spin_step(channel)
     if basis_free and not (isinstance(op0, SpinSectorOperator) and (target is None or isinstance(target, SpinSectorOperator))):
         raise ValueError("basis_free=True works on the bond-list SpinSectorOperator only")
-    if target is None:
-        if step == 0:
-            target = op0
-        else:
-            couplings = op0.couplings.detach()
-            if hasattr(op0, "bonds"):
-                target = SpinSectorOperator(op0.N, op0.bonds, couplings, op0.ndown + step, op0.device)
-            else:
-                target = SpinSectorPairOperator(op0.N, couplings, op0.ndown + step, op0.device)
-    lad = SpinSectorLadder(op0, target)
-    if lad.step != step:
-        raise ValueError("channel %r needs a target at ndown = %d, got %d" % (channel, op0.ndown + step, target.ndown))
+    target, lad = _spin_ladder(op0, step, channel, target)
     psi0 = psi0.detach()
     if basis_free:
         from .thermal import block_lanczos_measures
@@ -175,24 +189,9 @@ _HUBBARD_CHANNELS = {"c_up": ("up", -1), "c_dn": ("dn", -1), "cdag_up": ("up", 1
                      "sz": (None, 0)}
 
 
-def hubbard_spectral_function(op0, psi0, E0, weights, channel, k=200, target=None, basis_free=False):
-    """The spectral measure of O psi0 as a function of the excitation energy E - E0, for the eigenstate (psi0, E0) of the
-    ``HubbardOperator`` ``op0`` and the site-weighted operator (docs/design/25-hubbard-ladder.md)
-
-        channel "c_up", "c_dn":        O = sum_i w_i c_{i s}        (photoemission; lands in the sector with one s particle less)
-        channel "cdag_up", "cdag_dn":  O = sum_i w_i c+_{i s}       (inverse photoemission; one s particle more)
-        channel "n":                   O = sum_i w_i (n_{i up} + n_{i dn})     (charge; stays in the sector, ``target`` = op0)
-        channel "sz":                  O = sum_i w_i (n_{i up} - n_{i dn})     (2 S^z; stays in the sector)
-
-    ``weights``: a real vector [L], a ``(re, im)`` pair (``ring_momentum_weights``) or a complex tensor.  For complex weights
-    the result is the sum of the measures of the real and of the imaginary part: H is real symmetric, so the cross terms of
-    <a + ib| f(H) |a + ib> cancel.  ``target`` is the Hamiltonian of the destination sector; ``None`` builds it from the bonds
-    and couplings of ``op0`` at the new particle numbers, on new tables.  ``k`` Lanczos steps per real vector.  A removal
-    measure comes out in E_n - E0 >= 0 like every other; ``reflected()`` places it at omega = E0 - E_n, so that
-    ``cdag + c.reflected()`` is the one-particle spectral function A(omega).  ``basis_free=True``: the real and the imaginary
-    part run as one block of 1 or 2 columns through ``thermal.block_lanczos_measures`` -- no stored basis, no
-    re-orthogonalisation, memory independent of k (docs/design/28-hubbard-finite-temperature.md).  Plain numbers: not
-    differentiable."""
+def _hubbard_excitation(op0, psi0, channel, target):
+    """(target, excited) of a Hubbard channel: ``excited(w)`` is sum_i w_i O_i psi0 in the sector of ``target``; ``target`` None
+    builds the Hamiltonian of the destination sector from ``op0``"""
     from .operators import HubbardLadder, HubbardOperator
     if channel not in _HUBBARD_CHANNELS:
         raise ValueError("channel must be one of %s, got %r" % (", ".join(repr(c) for c in _HUBBARD_CHANNELS), channel))
@@ -217,6 +216,28 @@ def hubbard_spectral_function(op0, psi0, E0, weights, channel, k=200, target=Non
         phi = ladders[0](w, psi0)
         return phi + sign * ladders[1](w, psi0) if step == 0 else phi
 
+    return target, excited
+
+
+def hubbard_spectral_function(op0, psi0, E0, weights, channel, k=200, target=None, basis_free=False):
+    """The spectral measure of O psi0 as a function of the excitation energy E - E0, for the eigenstate (psi0, E0) of the
+    ``HubbardOperator`` ``op0`` and the site-weighted operator (docs/design/25-hubbard-ladder.md)
+
+        channel "c_up", "c_dn":        O = sum_i w_i c_{i s}        (photoemission; lands in the sector with one s particle less)
+        channel "cdag_up", "cdag_dn":  O = sum_i w_i c+_{i s}       (inverse photoemission; one s particle more)
+        channel "n":                   O = sum_i w_i (n_{i up} + n_{i dn})     (charge; stays in the sector, ``target`` = op0)
+        channel "sz":                  O = sum_i w_i (n_{i up} - n_{i dn})     (2 S^z; stays in the sector)
+
+    ``weights``: a real vector [L], a ``(re, im)`` pair (``ring_momentum_weights``) or a complex tensor.  For complex weights
+    the result is the sum of the measures of the real and of the imaginary part: H is real symmetric, so the cross terms of
+    <a + ib| f(H) |a + ib> cancel.  ``target`` is the Hamiltonian of the destination sector; ``None`` builds it from the bonds
+    and couplings of ``op0`` at the new particle numbers, on new tables.  ``k`` Lanczos steps per real vector.  A removal
+    measure comes out in E_n - E0 >= 0 like every other; ``reflected()`` places it at omega = E0 - E_n, so that
+    ``cdag + c.reflected()`` is the one-particle spectral function A(omega).  ``basis_free=True``: the real and the imaginary
+    part run as one block of 1 or 2 columns through ``thermal.block_lanczos_measures`` -- no stored basis, no
+    re-orthogonalisation, memory independent of k (docs/design/28-hubbard-finite-temperature.md).  Plain numbers: not
+    differentiable."""
+    target, excited = _hubbard_excitation(op0, psi0, channel, target)
     if basis_free:
         from .thermal import block_lanczos_measures
         Phi = torch.stack([excited(w).detach() for w in _weight_parts(weights)], dim=1)
@@ -228,3 +249,38 @@ def hubbard_spectral_function(op0, psi0, E0, weights, channel, k=200, target=Non
         part = lanczos_measure(target, excited(w), k)
         total = part if total is None else total + part
     return total.shifted(float(E0))
+
+
+def kpm_measure(op, phi, M, bounds=None):
+    """The ``chebyshev.ChebyshevMeasure`` of the vector ``phi`` under ``op``: its M moments mu_m = <phi| T_m((H - centre) / h)
+    |phi> from ceil(M / 2) mat-vecs without a basis (``chebyshev.chebyshev_moments``; docs/design/33-chebyshev-moments.md), the
+    counterpart of ``lanczos_measure`` with a resolution pi h / M that is the same all over ``bounds`` = (a, b).  ``bounds`` must
+    hold the spectrum; None takes ``chebyshev.spectral_bounds(op)``.  Not differentiable: phi is detached."""
+    from .chebyshev import ChebyshevMeasure, chebyshev_moments, spectral_bounds
+    if not torch.is_tensor(phi) or phi.dim() != 1 or phi.numel() != int(op.n):
+        raise ValueError("expected a vector of %d elements, got %r"
+                         % (int(op.n), tuple(phi.shape) if torch.is_tensor(phi) else type(phi).__name__))
+    if bounds is None:
+        bounds = spectral_bounds(op)
+    return ChebyshevMeasure(chebyshev_moments(op, phi.detach().reshape(-1, 1), M, bounds)[:, 0], bounds)
+
+
+def kpm_structure_factor(op0, psi0, E0, weights, channel, M=256, target=None, bounds=None):
+    """``dynamical_structure_factor`` by the kernel polynomial method: the ``chebyshev.ChebyshevMeasure`` of O psi0 as a function
+    of omega = E - E0, from one ladder application and ONE moments run in the destination sector (the real and the imaginary
+    part of complex weights are the two columns of one block, and their moments add).  ``op0`` a ``SpinSectorOperator`` with
+    the channels "zz", "-", "+" (the fused kernel), or a ``HubbardOperator`` with the channel names of
+    ``hubbard_spectral_function`` (``apply_block`` and torch).  ``bounds`` of the TARGET's spectrum; None takes
+    ``chebyshev.spectral_bounds(target)``.  Plain numbers: not differentiable."""
+    from .chebyshev import ChebyshevMeasure, chebyshev_moments, spectral_bounds
+    from .operators import HubbardOperator
+    if isinstance(op0, HubbardOperator):
+        target, excited = _hubbard_excitation(op0, psi0, channel, target)
+    else:
+        target, lad = _spin_ladder(op0, _spin_step(channel), channel, target)
+        psi0 = psi0.detach()
+        excited = lambda c: lad(c, psi0)  # noqa: E731
+    Phi = torch.stack([excited(w).detach() for w in _weight_parts(weights)], dim=1)
+    if bounds is None:
+        bounds = spectral_bounds(target)
+    return ChebyshevMeasure(chebyshev_moments(target, Phi, M, bounds).sum(dim=1), bounds).shifted(float(E0))

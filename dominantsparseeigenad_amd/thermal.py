@@ -13,6 +13,8 @@ through the three-term recurrence at once as one [n, R] block, on the block mat-
     sector_trace_measure(op, R, k, seed)    a measure with sum_j w_j f(theta_j) ~= tr f(H_sector); exact for small sectors
     ThermalEnsemble(entries)                ln Z, E, C, S and chi of a list of (measure, m) over a tensor of inverse temperatures
     spin_thermodynamics(L, bonds, couplings, ...)   the ensemble over all magnetisation sectors of a bond-list XXZ model
+    sector_density_of_states(op, M, bounds, ...)    the Chebyshev moments of tr T_m(H_sector): a ``chebyshev.ChebyshevMeasure``
+    spin_density_of_states(L, bonds, couplings, M)  those of all sectors on one interval (docs/design/33-chebyshev-moments.md)
     GrandCanonicalEnsemble(entries)         ln Xi, <H>, <N>, kappa, chi_s, C and S of a list of (measure, nup, ndn) over (beta, mu)
     hubbard_thermodynamics(L, bonds, couplings, ...)   that ensemble over all (nup, ndn) sectors of a Hubbard model
     thermal_correlations(L, bonds, couplings, betas, ...)   <X_i X_j + Y_i Y_j>, <Z_i Z_j>, <Z_i>, E and ln Z at T > 0 from thermal
@@ -139,6 +141,18 @@ def block_lanczos_measures(op, Phi, k):
     return out
 
 
+def _dense_sector_matrix(op):
+    """H of the sector as a host matrix: ``op.apply_block`` on the identity columns, eight at a time"""
+    n = int(op.n)
+    H = torch.empty((n, n), dtype=F64, device=op.device)
+    for first in range(0, n, 8):
+        w = min(8, n - first)
+        X = torch.zeros((n, w), dtype=F64, device=op.device)
+        X[first:first + w] = torch.eye(w, dtype=F64, device=op.device)
+        H[:, first:first + w] = op.apply_block(X)
+    return H.cpu()
+
+
 def sector_trace_measure(op, R=8, k=100, seed=0, dense_below=256):
     """A ``SpectralMeasure`` with sum_j w_j f(theta_j) ~= tr f(H) over the sector of ``op``, a ``SpinSectorOperator`` or a
     ``HubbardOperator``.
@@ -154,13 +168,7 @@ def sector_trace_measure(op, R=8, k=100, seed=0, dense_below=256):
     if R < 1 or k < 1:
         raise ValueError("sector_trace_measure needs R >= 1 and k >= 1")
     if n <= int(dense_below):
-        H = torch.empty((n, n), dtype=F64, device=op.device)
-        for first in range(0, n, 8):
-            w = min(8, n - first)
-            X = torch.zeros((n, w), dtype=F64, device=op.device)
-            X[first:first + w] = torch.eye(w, dtype=F64, device=op.device)
-            H[:, first:first + w] = op.apply_block(X)
-        poles = torch.linalg.eigvalsh(H.cpu())
+        poles = torch.linalg.eigvalsh(_dense_sector_matrix(op))
         return SpectralMeasure(poles, torch.ones(n, dtype=F64), float(n), n)
     from .synthetic import normal_vector
     Phi = torch.stack([torch.from_numpy(normal_vector(n, int(seed) + j)) for j in range(R)], dim=1).to(op.device)
@@ -240,13 +248,10 @@ class ThermalEnsemble:
         return float((self.weights * self.poles ** int(p)).sum())
 
 
-def spin_thermodynamics(L, bonds, couplings, R=8, k=100, seed=0, dense_below=256, sectors=None, device=None):
-    """The ``ThermalEnsemble`` of H = sum_t [Jxy_t (X_a X_b + Y_a Y_b) + Jz_t Z_a Z_b] + sum_i hz_i Z_i (the Hamiltonian and the
-    parameter order [Jxy(nb), Jz(nb), hz(L)] of ``SpinSectorOperator``) over the sectors ndown = 0 .. L, or over the list
-    ``sectors``.  Every sector contributes ``sector_trace_measure(op, R, k, seed, dense_below)`` at m = L / 2 - ndown; the two
-    one-state sectors ndown = 0 and ndown = L, which the operator refuses, contribute their energy sum_t Jz_t +- sum_i hz_i from
-    host arithmetic.  One sector's tables are released before the next sector is built."""
-    from .operators import SpinSectorOperator, _check_bonds
+def _spin_model(L, bonds, couplings, sectors, device):
+    """(L, bonds, couplings, sectors, sum Jz, sum hz, device) of a bond-list XXZ model, checked: the parameter order is
+    [Jxy(nb), Jz(nb), hz(L)], ``sectors`` None means ndown = 0 .. L"""
+    from .operators import _check_bonds
     L = int(L)
     bonds = _check_bonds(L, bonds)
     nb = len(bonds)
@@ -260,6 +265,17 @@ def spin_thermodynamics(L, bonds, couplings, R=8, k=100, seed=0, dense_below=256
     jz_sum, hz_sum = float(host[nb:2 * nb].sum()), float(host[2 * nb:].sum())
     if device is None:
         device = c.device if c.is_cuda else "cuda"
+    return L, bonds, c, sectors, jz_sum, hz_sum, device
+
+
+def spin_thermodynamics(L, bonds, couplings, R=8, k=100, seed=0, dense_below=256, sectors=None, device=None):
+    """The ``ThermalEnsemble`` of H = sum_t [Jxy_t (X_a X_b + Y_a Y_b) + Jz_t Z_a Z_b] + sum_i hz_i Z_i (the Hamiltonian and the
+    parameter order [Jxy(nb), Jz(nb), hz(L)] of ``SpinSectorOperator``) over the sectors ndown = 0 .. L, or over the list
+    ``sectors``.  Every sector contributes ``sector_trace_measure(op, R, k, seed, dense_below)`` at m = L / 2 - ndown; the two
+    one-state sectors ndown = 0 and ndown = L, which the operator refuses, contribute their energy sum_t Jz_t +- sum_i hz_i from
+    host arithmetic.  One sector's tables are released before the next sector is built."""
+    from .operators import SpinSectorOperator
+    L, bonds, c, sectors, jz_sum, hz_sum, device = _spin_model(L, bonds, couplings, sectors, device)
     entries = []
     for ndown in sectors:
         m = 0.5 * L - ndown
@@ -271,6 +287,71 @@ def spin_thermodynamics(L, bonds, couplings, R=8, k=100, seed=0, dense_below=256
         entries.append((sector_trace_measure(op, R=R, k=k, seed=seed, dense_below=dense_below), m))
         del op
     return ThermalEnsemble(entries)
+
+
+def _trace_moments(poles, M, centre, h):
+    """mu [M] = sum_i T_m((theta_i - centre) / h) = sum_i cos(m arccos s_i) of a host tensor of eigenvalues inside the bounds"""
+    s = (poles.to(F64) - centre) / h
+    if bool((s.abs() > 1.0).any()):
+        raise ValueError("the bounds (%r, %r) do not hold the spectrum [%r, %r]"
+                         % (centre - h, centre + h, float(poles.min()), float(poles.max())))
+    return torch.cos(torch.arange(M, dtype=F64)[:, None] * torch.acos(s)[None, :]).sum(dim=1)
+
+
+def sector_density_of_states(op, M, bounds, R=8, seed=0, dense_below=256):
+    """A ``chebyshev.ChebyshevMeasure`` with the moments mu_m ~= tr T_m((H - centre) / h) over the sector of ``op``: its density
+    is the density of states of the sector, its ``trace(f)`` is tr f(H) (docs/design/33-chebyshev-moments.md).  ``bounds`` must
+    hold the spectrum.
+
+    n <= ``dense_below``: EXACT -- mu_m = sum_i T_m(s_i) over the eigenvalues (host ``eigvalsh``) of the matrix formed by
+    ``op.apply_block`` on the identity columns.  Otherwise the start vectors and the weight n / R of ``sector_trace_measure``:
+    mu_m = (n / R) sum_j <r_j| T_m |r_j> / <r_j|r_j> over r_j = ``synthetic.normal_vector(n, seed + j)``, all R columns in the
+    runs of ``chebyshev.chebyshev_moments`` (ceil(M / 2) mat-vecs) -- a stochastic estimate whose error is the sampling error of
+    R vectors."""
+    from .chebyshev import ChebyshevMeasure, _check_bounds, chebyshev_moments
+    op = _sector_operator(op, "sector_density_of_states")
+    n, M, R = int(op.n), int(M), int(R)
+    if R < 1 or M < 2:
+        raise ValueError("sector_density_of_states needs R >= 1 and M >= 2")
+    centre, h = _check_bounds(bounds)
+    if n <= int(dense_below):
+        return ChebyshevMeasure(_trace_moments(torch.linalg.eigvalsh(_dense_sector_matrix(op)), M, centre, h), bounds)
+    from .synthetic import normal_vector
+    Phi = torch.stack([torch.from_numpy(normal_vector(n, int(seed) + j)) for j in range(R)], dim=1).to(op.device)
+    mu = chebyshev_moments(op, Phi, M, bounds)
+    return ChebyshevMeasure((n / R) * (mu / mu[0]).sum(dim=1), bounds)
+
+
+def spin_density_of_states(L, bonds, couplings, M, R=8, seed=0, dense_below=256, sectors=None, bounds=None, device=None):
+    """The ``chebyshev.ChebyshevMeasure`` of the whole spectrum of the model of ``spin_thermodynamics`` (all magnetisation
+    sectors, or the list ``sectors``): mu_m ~= tr T_m over the 2^L states, so that mu_0 = 2^L, ``density(E) / 2^L`` is the
+    normalised density of states and ``logtrace_exp(beta)`` is ln Z.  All sectors are expanded on ONE interval, so their moments
+    add: ``bounds``, or by default the rigorous (-B, B) with B = sum_t (2 |Jxy_t| + |Jz_t|) + sum_i |hz_i| >= ||H||.  Every sector
+    contributes ``sector_density_of_states(op, M, bounds, R, seed, dense_below)``; ndown = 0 and ndown = L are one state each,
+    T_m of their energy sum_t Jz_t +- sum_i hz_i from host arithmetic."""
+    from .chebyshev import ChebyshevMeasure, _check_bounds
+    from .operators import SpinSectorOperator
+    L, bonds, c, sectors, jz_sum, hz_sum, device = _spin_model(L, bonds, couplings, sectors, device)
+    M = int(M)
+    if M < 2:
+        raise ValueError("spin_density_of_states needs M >= 2, got %d" % M)
+    if bounds is None:
+        nb = len(bonds)
+        host = c.cpu().abs()
+        B = float(2.0 * host[:nb].sum() + host[nb:].sum())
+        bounds = (-B, B)
+    centre, h = _check_bounds(bounds)
+    total = None
+    for ndown in sectors:
+        if ndown in (0, L):
+            energy = jz_sum + (hz_sum if ndown == 0 else -hz_sum)
+            part = ChebyshevMeasure(_trace_moments(torch.tensor([energy], dtype=F64), M, centre, h), bounds)
+        else:
+            op = SpinSectorOperator(L, bonds, c.to(device), ndown, device)
+            part = sector_density_of_states(op, M, bounds, R=R, seed=seed, dense_below=dense_below)
+            del op
+        total = part if total is None else total + part
+    return total
 
 
 class ThermalCorrelations:
@@ -286,13 +367,7 @@ def _dense_sector_correlations(op, betas):
     """(log weight [B], E [B], xy, zz, z) of a sector from its full spectrum: H from ``apply_block`` on identity columns, host
     ``eigh``, and ``correlations(v, v)`` of every eigenvector"""
     n = int(op.n)
-    H = torch.empty((n, n), dtype=F64, device=op.device)
-    for first in range(0, n, 8):
-        w = min(8, n - first)
-        X = torch.zeros((n, w), dtype=F64, device=op.device)
-        X[first:first + w] = torch.eye(w, dtype=F64, device=op.device)
-        H[:, first:first + w] = op.apply_block(X)
-    theta, V = torch.linalg.eigh(H.cpu())
+    theta, V = torch.linalg.eigh(_dense_sector_matrix(op))
     pair = op.pair_operator()
     Vd = V.to(op.device)
     parts = [pair.correlations(Vd[:, j].contiguous()) for j in range(n)]

@@ -1048,6 +1048,28 @@ int dsea_op_sector_block_chebyshev(dsea_op_t op, int R, int A, int M, double cen
                                    double *U /* [n,R] work */, double *V /* [n,R] work */, double *ACC /* [A,n,R] out */,
                                    void *stream);
 
+/* ------------------------------------------------------------------ Chebyshev block moments (docs/design/33-chebyshev-moments.md)
+ * MU[m, j] = l_j . T_m((H - centre) / halfwidth) x_j, m in [0, M), for the operator of dsea_op_create_sector, the columns x_j of a
+ * block X and l = X (Y null: self mode) or the columns of a second block Y (left mode), without a stored basis; the spectrum of
+ * H must lie inside [centre - halfwidth, centre + halfwidth].  Blocks as above: fp64 [n, R] row-major, 16-byte aligned
+ * (DSEA_ERR_ALIGN otherwise), R in {1, 2, 4, 8}.  MU is a DEVICE array [M, R] row-major.  X and Y are never written; U and V are
+ * work blocks.  Every order is one launch of the fused mat-vec, recurrence tail and two dot products per column, followed by one
+ * one-block launch that sums the per-block partials in index order.  Self mode takes K = ceil(M / 2) orders: order m gives
+ * mu_{2m-2} = 2 <T_{m-1} x | T_{m-1} x> - mu_0 and mu_{2m-1} = 2 <T_{m-1} x | T_m x> - mu_1 (the product rule T_a T_b =
+ * (T_{a+b} + T_{|a-b|}) / 2; the doubling is exact and the subtraction rounds once).  Left mode takes K = M - 1 orders: order m
+ * gives mu_m = y . T_m x.  ON RETURN T_K X is in U for odd K and in V for even K, and T_{K-1} X is in the other work block (for
+ * K = 1 it is X itself and V is untouched); they equal the work blocks of dsea_op_sector_block_chebyshev after K orders bit for
+ * bit.  No atomics: identical calls return identical bits.  Nothing is read back, the call does not synchronise, the library
+ * allocates nothing; every check is host arithmetic before any device work.  scratch: caller-owned,
+ * dsea_op_sector_block_moments_scratch_doubles(L, ndown, R) = 2 R min(4096, ceil(n / 256)) doubles (enough for every grid cap).
+ * DSEA_ERR_ARG: any other operator kind, R outside {1, 2, 4, 8}, M < 2, a null X, U, V, MU or scratch, centre or halfwidth not
+ * finite, halfwidth <= 0, any two of X, Y, U, V equal; in the scratch query (L, ndown) outside the limits of
+ * dsea_sector_table_sizes or a null out. */
+int dsea_op_sector_block_moments_scratch_doubles(int L, int ndown, int R, int64_t *out);
+int dsea_op_sector_block_moments(dsea_op_t op, int R, int M, double centre, double halfwidth, const double *X /* [n,R] */,
+                                 const double *Y /* [n,R] left block, or NULL: self mode */, double *U /* [n,R] work */,
+                                 double *V /* [n,R] work */, double *MU /* device [M,R] out */, double *scratch, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
