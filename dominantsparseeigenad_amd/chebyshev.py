@@ -5,7 +5,8 @@ With the spectrum of H inside [a, b], centre = (a + b) / 2, h = (b - a) / 2 and 
     f(H) X ~= sum_{m < M} c_m T_m(s) X,     T_0 X = X,  T_1 X = s X,  T_{m+1} X = 2 s T_m X - T_{m-1} X
 
 a three-term recurrence with no reductions, whose memory (X, two work blocks, one block per function) does not depend on M.
-On a ``SpinSectorOperator`` every order is ONE launch of k_cheb_sector_block: the block mat-vec with the recurrence tail inside.
+On a ``SpinSectorOperator`` every order is ONE launch of k_cheb_sector_block, on a ``HubbardOperator`` of k_cheb_hubbard_block
+(docs/design/34-hubbard-chebyshev.md): the block mat-vec with the recurrence tail inside.
 
     chebyshev_coefficients(f, M)            c_0 / 2, c_1, ..., c_{M-1} of f on [-1, 1]
     exp_order(x, tol)                       the order that e^{-x (s + 1)} needs
@@ -15,8 +16,8 @@ On a ``SpinSectorOperator`` every order is ONE launch of k_cheb_sector_block: th
     time_evolve(op, psi, t)                 e^{-i H t} psi
 
 and what the propagated block projects onto (docs/design/33-chebyshev-moments.md): the moments mu_m = <l| T_m(s) |x>, on a
-``SpinSectorOperator`` one launch of k_cheb_sector_moments per order with the two dot products inside, two moments per order
-when l = x.  They do not depend on f: one run serves every function and the kernel polynomial method's densities.
+``SpinSectorOperator`` or a ``HubbardOperator`` one launch of k_cheb_sector_moments or k_cheb_hubbard_moments per order with the
+two dot products inside, two moments per order when l = x.  They do not depend on f: one run serves every function and the kernel polynomial method's densities.
 
     chebyshev_moments(op, X, M, bounds)     mu [M, R], optionally against a left block
     jackson_kernel(M), lorentz_kernel(M)    the damping factors g_m
@@ -103,8 +104,13 @@ def exp_order(x, tol=1e-15):
 
 
 def coupling_bound(op):
-    """B = sum_t (2 |Jxy_t| + |Jz_t|) + sum_i |hz_i| >= ||H||_2 of a ``SpinSectorOperator``; None for another operator"""
-    from .operators import SpinSectorOperator
+    """B >= ||H||_2 from the couplings alone: sum_t (2 |Jxy_t| + |Jz_t|) + sum_i |hz_i| of a ``SpinSectorOperator``,
+    sum_t (2 |t_t| + 4 |V_t|) + sum_i (|U_i| + 2 |eps_i|) of a ``HubbardOperator`` (a hop has norm 1 per species, n_a n_b <= 4,
+    n_up n_dn <= 1, n_i <= 2); None for another operator"""
+    from .operators import HubbardOperator, SpinSectorOperator
+    if isinstance(op, HubbardOperator):
+        t, V, U, eps = op.unpack(op.couplings.detach())
+        return float(2.0 * t.abs().sum() + 4.0 * V.abs().sum() + U.abs().sum() + 2.0 * eps.abs().sum())
     if not isinstance(op, SpinSectorOperator):
         return None
     jxy, jz, hz = op.unpack(op.couplings.detach())
@@ -160,18 +166,20 @@ def chebyshev_apply(op, X, coeffs, bounds, fused=None):
     (centre - h, centre + h), which must hold the spectrum of H.  ``coeffs`` (M,) returns (n, R); (A, M) returns (A, n, R):
     all A functions share the M - 1 mat-vecs.  c_0 is taken as given (``chebyshev_coefficients`` halves it).
 
-    ``fused=True``: dsea_op_sector_block_chebyshev, one launch per order, ``SpinSectorOperator`` and A in {1, 2} only
-    (``ValueError`` otherwise), the columns in pieces of 8, 4, 2 and 1.  ``fused=False``: ``op.apply_block`` and torch
-    elementwise operations in exactly the order of the kernel's tail, for any operator with ``apply_block``; the two paths
-    return the same bits.  ``None``: fused where the entry exists.  X is detached and not written."""
-    from .operators import SpinSectorOperator
+    ``fused=True`` names the spin-sector entry: dsea_op_sector_block_chebyshev, one launch per order, ``SpinSectorOperator`` and
+    A in {1, 2} only (``ValueError`` otherwise, for a ``HubbardOperator`` too), the columns in pieces of 8, 4, 2 and 1.
+    ``fused=False``: ``op.apply_block`` and torch elementwise operations in exactly the order of the kernel's tail, for any
+    operator with ``apply_block``; the two paths return the same bits.  ``None``: fused where an entry exists -- the spin-sector
+    one, or for a ``HubbardOperator`` with A in {1, 2} dsea_op_hubbard_block_chebyshev, the same schedule on
+    k_cheb_hubbard_block; ``None`` is how a Hubbard operator reaches its kernel.  X is detached and not written."""
+    from .operators import HubbardOperator, SpinSectorOperator
     c, single = _check_coeffs(coeffs)
     centre, h = _check_bounds(bounds)
     A, M = c.shape
     can_fuse = isinstance(op, SpinSectorOperator) and A in FUSED_ACCUMULATORS
     if fused is None:
-        fused = can_fuse
-    if fused and not can_fuse:
+        fused = can_fuse or (isinstance(op, HubbardOperator) and A in FUSED_ACCUMULATORS)
+    elif fused and not can_fuse:
         raise ValueError("the fused Chebyshev kernel exists for SpinSectorOperator and 1 or 2 coefficient rows only, got %s and %d"
                          % (type(op).__name__, A))
     if not callable(getattr(op, "apply_block", None)):
@@ -187,8 +195,22 @@ def _aligned_piece(X, first, w):
     return piece.clone() if piece.data_ptr() % 16 else piece
 
 
+def _fused_entries(op, lib):
+    """(propagator, its name, scratch query of the moments with the sector's sizes bound, moments, their name): the fused ABI
+    entries of the operator's kind"""
+    from .operators import HubbardOperator
+    if isinstance(op, HubbardOperator):
+        return (lib.dsea_op_hubbard_block_chebyshev, "dsea_op_hubbard_block_chebyshev",
+                lambda w, out: lib.dsea_op_hubbard_block_moments_scratch_doubles(op.N, op.nup, op.ndn, w, out),
+                lib.dsea_op_hubbard_block_moments, "dsea_op_hubbard_block_moments")
+    return (lib.dsea_op_sector_block_chebyshev, "dsea_op_sector_block_chebyshev",
+            lambda w, out: lib.dsea_op_sector_block_moments_scratch_doubles(op.N, op.ndown, w, out),
+            lib.dsea_op_sector_block_moments, "dsea_op_sector_block_moments")
+
+
 def _apply_fused(op, X, c, centre, h):
     lib = _lib.load()
+    run, name = _fused_entries(op, lib)[:2]
     A, M = c.shape
     n, R = X.shape
     host = (c_double * (A * M))(*c.reshape(-1).tolist())
@@ -198,8 +220,7 @@ def _apply_fused(op, X, c, centre, h):
         Xp = _aligned_piece(X, first, w)
         U, V = torch.empty_like(Xp), torch.empty_like(Xp)
         acc = torch.empty((A, n, w), dtype=F64, device=X.device)
-        check(lib.dsea_op_sector_block_chebyshev(op.handle, w, A, M, centre, h, host, ptr(Xp), ptr(U), ptr(V), ptr(acc),
-                                                 engine._stream(X.device)), "dsea_op_sector_block_chebyshev")
+        check(run(op.handle, w, A, M, centre, h, host, ptr(Xp), ptr(U), ptr(V), ptr(acc), engine._stream(X.device)), name)
         out[:, :, first:first + w] = acc
     return out
 
@@ -228,21 +249,23 @@ def chebyshev_moments(op, X, M, bounds, left=None, fused=None):
     gives two moments per order, mu_{2m-2} = 2 <T_{m-1} x|T_{m-1} x> - mu_0 and mu_{2m-1} = 2 <T_{m-1} x|T_m x> - mu_1: ceil(M / 2)
     mat-vecs; with ``left`` M - 1.
 
-    ``fused=True``: dsea_op_sector_block_moments, one launch per order with the dot products inside and one small launch that
-    closes them, ``SpinSectorOperator`` only (``ValueError`` otherwise), the columns in pieces of 8, 4, 2 and 1.
-    ``fused=False``: ``op.apply_block``, torch elementwise operations in the order of the kernel's tail and column sums, for any
-    operator with ``apply_block`` (a ``HubbardOperator`` among them).  ``None``: fused where the entry exists.  The two paths run
-    the same recurrence bit for bit but sum the dot products in different orders: their moments agree to rounding, NOT bit for
-    bit.  X and ``left`` are detached and not written."""
-    from .operators import SpinSectorOperator
+    ``fused=True`` names the spin-sector entry: dsea_op_sector_block_moments, one launch per order with the dot products inside
+    and one small launch that closes them, ``SpinSectorOperator`` only (``ValueError`` otherwise, for a ``HubbardOperator``
+    too), the columns in pieces of 8, 4, 2 and 1.  ``fused=False``: ``op.apply_block``, torch elementwise operations in the order
+    of the kernel's tail and column sums, for any operator with ``apply_block``.  ``None``: fused where an entry exists -- the
+    spin-sector one, or for a ``HubbardOperator`` dsea_op_hubbard_block_moments, the same schedule on k_cheb_hubbard_moments;
+    ``None`` is how a Hubbard operator reaches its kernel.  The two paths run the same recurrence bit for bit but sum the dot
+    products in different orders: their moments agree to rounding, NOT bit for bit.  X and ``left`` are detached and not
+    written."""
+    from .operators import HubbardOperator, SpinSectorOperator
     M = int(M)
     if M < 2:
         raise ValueError("chebyshev_moments needs M >= 2, got %d" % M)
     centre, h = _check_bounds(bounds)
     can_fuse = isinstance(op, SpinSectorOperator)
     if fused is None:
-        fused = can_fuse
-    if fused and not can_fuse:
+        fused = can_fuse or isinstance(op, HubbardOperator)
+    elif fused and not can_fuse:
         raise ValueError("the fused moments kernel exists for SpinSectorOperator only, got %s" % type(op).__name__)
     if not callable(getattr(op, "apply_block", None)):
         raise ValueError("chebyshev_moments needs an operator with apply_block, got %s" % type(op).__name__)
@@ -258,6 +281,7 @@ def _moments_fused(op, X, left, M, centre, h):
     lib = _lib.load()
     dev = X.device
     ptr = lambda t: c_void_p(t.data_ptr())  # noqa: E731
+    _, _, query, run, name = _fused_entries(op, lib)
     out = []
     for first, w in block_pieces(X.shape[1]):
         Xp = _aligned_piece(X, first, w)
@@ -265,11 +289,10 @@ def _moments_fused(op, X, left, M, centre, h):
         U, V = torch.empty_like(Xp), torch.empty_like(Xp)
         mu = torch.empty((M, w), dtype=F64, device=dev)
         need = c_int64()
-        check(lib.dsea_op_sector_block_moments_scratch_doubles(op.N, op.ndown, w, byref(need)),
-              "dsea_op_sector_block_moments_scratch_doubles")
+        check(query(w, byref(need)), name + "_scratch_doubles")
         scratch = torch.empty(need.value, dtype=F64, device=dev)
-        check(lib.dsea_op_sector_block_moments(op.handle, w, M, centre, h, ptr(Xp), None if Yp is None else ptr(Yp), ptr(U), ptr(V),
-                                               ptr(mu), ptr(scratch), engine._stream(dev)), "dsea_op_sector_block_moments")
+        check(run(op.handle, w, M, centre, h, ptr(Xp), None if Yp is None else ptr(Yp), ptr(U), ptr(V), ptr(mu), ptr(scratch),
+                  engine._stream(dev)), name)
         out.append(mu.cpu())
     return torch.cat(out, dim=1)
 

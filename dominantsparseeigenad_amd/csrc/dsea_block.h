@@ -1,6 +1,6 @@
 // dsea_block.h -- what a block kernel needs whatever the operator (docs/design/32-block-kernel-parts.md): the row access and
-// the partials of a block, the helpers of the a | b << 8 bond table, the tail of the plain and the Lanczos-step mat-vec, and the
-// host rules of the launchers (grid, width dispatch, bond table).  Used by dsea_sector_block.hip, dsea_hubbard_block.hip,
+// the partials of a block, the helpers of the a | b << 8 bond table, the tail of the plain and the Lanczos-step mat-vec, the
+// accumulator arguments of the Chebyshev kernels, and the host rules of the launchers (grid, width dispatch, bond table).  Used by dsea_sector_block.hip, dsea_hubbard_block.hip,
 // dsea_block_lanczos.hip and dsea_block_moments.hip.
 //
 // A block is an fp64 array [n, R], row-major (element (r, j) at r * R + j), 16-byte aligned, R in {1, 2, 4, 8}.  A family's
@@ -91,6 +91,13 @@ __device__ __forceinline__ void block_spmv_tail(double* __restrict__ y, int firs
   }
   block_store<R>(y, r, v);
 }
+
+// the per-accumulator arguments of one Chebyshev order, by value
+template <int A>
+struct ChebAccs {
+  double* acc[A];
+  double c0[A], c1[A];
+};
 
 // one block per 256 rows up to the cap 2^tune_tile_log2 (6 .. 12, 12 at creation: 4096); beyond it blocks walk row ranges
 inline int block_blocks(const OpDesc& op) {

@@ -2181,6 +2181,42 @@ int dsea_op_hubbard_block_lanczos(dsea_op_t op, int R, int k, double* Q, double*
   return check_launch();
 }
 
+int dsea_op_hubbard_block_chebyshev(dsea_op_t op, int R, int A, int M, double centre, double halfwidth, const double* coeffs,
+                                    const double* X, double* U, double* V, double* ACC, void* stream) {
+  REQUIRE(op && op->d.kind == OP_HUBBARD && block_width_ok(R) && (A == 1 || A == 2) && M >= 2 && coeffs && X && U && V && ACC &&
+              std::isfinite(centre) && std::isfinite(halfwidth) && halfwidth > 0.0,
+          DSEA_ERR_ARG);
+  const double* blocks[5] = {X, U, V, ACC, ACC + (A - 1) * op->d.n * R};     // (the first 3 + A are compared)
+  for (int i = 0; i < 3 + A; ++i)
+    for (int j = i + 1; j < 3 + A; ++j) REQUIRE(blocks[i] != blocks[j], DSEA_ERR_ARG);
+  // (the second accumulator at ACC + n R needs no check of its own, as in dsea_op_sector_block_chebyshev)
+  REQUIRE(aligned16(X) && aligned16(U) && aligned16(V) && aligned16(ACC), DSEA_ERR_ALIGN);
+  if (launch_hubbard_block_chebyshev(op->d, R, A, M, centre, halfwidth, coeffs, X, U, V, ACC, static_cast<hipStream_t>(stream)) < 0)
+    return DSEA_ERR_UNSUPPORTED;
+  return check_launch();
+}
+
+int dsea_op_hubbard_block_moments_scratch_doubles(int L, int nup, int ndn, int R, int64_t* out) {
+  int64_t n, n_up, n_dn;
+  REQUIRE(out && hubbard_sizes(L, nup, ndn, &n, &n_up, &n_dn) && block_width_ok(R), DSEA_ERR_ARG);
+  *out = block_moments_scratch_doubles(n, R);
+  return DSEA_OK;
+}
+
+int dsea_op_hubbard_block_moments(dsea_op_t op, int R, int M, double centre, double halfwidth, const double* X, const double* Y,
+                                  double* U, double* V, double* MU, double* scratch, void* stream) {
+  REQUIRE(op && op->d.kind == OP_HUBBARD && block_width_ok(R) && M >= 2 && X && U && V && MU && scratch && std::isfinite(centre) &&
+              std::isfinite(halfwidth) && halfwidth > 0.0,
+          DSEA_ERR_ARG);
+  const double* blocks[4] = {X, U, V, Y};                                      // (a null Y, self mode, equals none of the others)
+  for (int i = 0; i < 4; ++i)
+    for (int j = i + 1; j < 4; ++j) REQUIRE(blocks[i] != blocks[j], DSEA_ERR_ARG);
+  REQUIRE(aligned16(X) && aligned16(Y) && aligned16(U) && aligned16(V), DSEA_ERR_ALIGN);
+  if (launch_hubbard_block_moments(op->d, R, M, centre, halfwidth, X, Y, U, V, MU, scratch, static_cast<hipStream_t>(stream)) != 0)
+    return DSEA_ERR_UNSUPPORTED;
+  return check_launch();
+}
+
 int dsea_hubbard_ladder_apply(int L, int nup_src, int ndn_src, int species, int step, const double* weights_dev,
                               const int64_t* states_dst, const int32_t* lo_rank_src, const int32_t* hi_base_src, const double* x,
                               double* y, int grid_log2, void* stream) {

@@ -1,7 +1,10 @@
 // dsea_hubbard_block.hip -- the Hubbard Hamiltonian of dsea_hubbard.hip applied to a BLOCK of R vectors at once, plain and with
 // the tail of the basis-free block Lanczos step fused in (docs/design/28-hubbard-finite-temperature.md): the kernel
 // k_spmv_hubbard_block<R, LZ> -- the family's row walk with the tail block_spmv_tail of dsea_block.h -- and its launchers.  The
-// recurrence kernels and their driver are those of dsea_block_lanczos.hip.
+// recurrence kernels and their driver are those of dsea_block_lanczos.hip.  k_cheb_hubbard_block<R, A> and
+// k_cheb_hubbard_moments<R, LEFT> (docs/design/34-hubbard-chebyshev.md) hold the same row walk, statement for statement, with the
+// Chebyshev tails of dsea_sector_block.hip; the finish kernel and the launch schedule of the moments are in
+// dsea_block_moments.hip.
 //
 // One row per thread: the division r / n_dn, the two state words, the move tests, the two parities, the two table reads of every
 // hop that moves a particle and the partner rows are paid once per row and hop slot for all R columns, and every gather is R
@@ -195,6 +198,226 @@ __global__ __launch_bounds__(256) void k_spmv_hubbard_block(HubbardBlockParams p
   if constexpr (LZ) block_partials<R>(acc, sm, P);
 }
 
+// One order of the Chebyshev recurrence of f(H) X (docs/design/34-hubbard-chebyshev.md), the Hubbard twin of
+// k_cheb_sector_block<R, A>.  The row walk is that of k_spmv_hubbard_block<R, false>, statement for statement (a copy, not a
+// shared function: 32-block-kernel-parts.md measured what sharing did to the existing symbols), so w = fma(diag, x_r, sum) has
+// the bits of the block mat-vec.  The tail is that of the sector kernel:
+//   t = g (w - centre x)                                  g = 1 / halfwidth on the first order, 2 / halfwidth afterwards
+//   first:  acc_a = c0_a x + c1_a t                       (old and acc are not read)
+//   else:   t = t - old,  acc_a = acc_a + c1_a t
+//   out = t
+// every product and sum rounded on its own.  The tail touches the thread's own row only, so old == out is allowed (neither is
+// __restrict__); x and the accumulators are distinct from every other block.  old and acc are read after the last chunk's
+// gathers are consumed.  No atomics, no reductions.
+template <int R, int A>
+__global__ __launch_bounds__(256) void k_cheb_hubbard_block(HubbardBlockParams p, const double* __restrict__ x, const double* old,
+                                                            double* out, ChebAccs<A> ca, double centre, double g, int first) {
+  __shared__ double cp[DSEA_HBLOCK_MAX_PARAMS];
+  __shared__ uint64_t bm[DSEA_LATTICE_MAX_BONDS];
+  __shared__ uint16_t tb[DSEA_LATTICE_MAX_BONDS];
+  constexpr int CH = HblockChunk<R>::value;
+  constexpr int HOPS = 2 * CH;
+  const int L = p.L, nb = p.nb;
+  const int64_t n = p.n;
+  for (int c = threadIdx.x; c < 2 * nb + 2 * L; c += 256) cp[c] = p.c[c];
+  for (int c = threadIdx.x; c < nb; c += 256) {
+    const uint16_t e = p.tb[c];
+    tb[c] = e;
+    bm[c] = hblock_between(e);
+  }
+  __syncthreads();
+  const double* __restrict__ ts = cp;
+  const double* __restrict__ Vs = cp + nb;
+  const double* __restrict__ Us = cp + 2 * nb;
+  const double* __restrict__ es = cp + 2 * nb + L;
+  for (int64_t row0 = (int64_t)blockIdx.x * 256; row0 < n; row0 += (int64_t)gridDim.x * 256) {
+    const int64_t r = row0 + threadIdx.x;
+    const bool have = r < n;                       // (a thread past the last row reads row n - 1 and writes nothing)
+    const uint32_t rr = (uint32_t)(have ? r : n - 1);
+    const uint32_t ru = rr / p.n_dn, rd = rr - ru * p.n_dn;
+    const uint64_t u = p.up_states[ru], d = p.dn_states[rd];
+    double xr[R];
+    block_load<R>(xr, x, (int64_t)rr);
+    uint32_t hi[HOPS], lo[HOPS];
+    uint32_t on = hblock_lookups<CH>(hi, lo, u, d, have, 0, p, tb);
+    double diag = 0.0, sum[R];
+#pragma unroll
+    for (int j = 0; j < R; ++j) sum[j] = 0.0;
+    const uint64_t both = u & d;
+    for (int i = 0; i < L; ++i) {
+      diag += hblock_bit(both, i) ? Us[i] : 0.0;
+      diag = fma(es[i], (double)(hblock_bit(u, i) + hblock_bit(d, i)), diag);
+    }
+    for (int k0 = 0; k0 < nb; k0 += CH) {
+      uint32_t rw[HOPS];
+      double xv[HOPS][R];
+      hblock_rows<CH>(rw, on, hi, lo, ru, rd, p.n_dn);
+      hblock_gather<R, HOPS>(xv, rw, x);
+      on = hblock_lookups<CH>(hi, lo, u, d, have, k0 + CH, p, tb);
+#pragma unroll
+      for (int e = 0; e < CH; ++e) {
+        if (k0 + e < nb) {
+          const uint32_t w = tb[k0 + e];
+          const uint64_t between = bm[k0 + e];
+          const double tt = ts[k0 + e];
+          diag = fma(Vs[k0 + e], hblock_nn(u, d, w), diag);
+          // -t sgn = t (-1)^(parity + 1): the sign goes into the sign bit of the coupling
+          const double tu = block_signed(tt, hblock_parity(u, between) ^ 1ull);
+          const double td = block_signed(tt, hblock_parity(d, between) ^ 1ull);
+#pragma unroll
+          for (int j = 0; j < R; ++j) {
+            sum[j] = fma(tu, xv[2 * e][j], sum[j]);
+            sum[j] = fma(td, xv[2 * e + 1][j], sum[j]);
+          }
+        }
+      }
+    }
+    if (have) {
+      double t[R];
+#pragma unroll
+      for (int j = 0; j < R; ++j) {
+        const double w = fma(diag, xr[j], sum[j]);
+        t[j] = __dmul_rn(g, __dsub_rn(w, __dmul_rn(centre, xr[j])));
+      }
+      if (!first) {
+        double ov[R];
+        block_load<R>(ov, old, r);
+#pragma unroll
+        for (int j = 0; j < R; ++j) t[j] = __dsub_rn(t[j], ov[j]);
+      }
+#pragma unroll
+      for (int a = 0; a < A; ++a) {
+        double av[R];
+        if (first) {
+#pragma unroll
+          for (int j = 0; j < R; ++j) av[j] = __dadd_rn(__dmul_rn(ca.c0[a], xr[j]), __dmul_rn(ca.c1[a], t[j]));
+        } else {
+          block_load<R>(av, ca.acc[a], r);
+#pragma unroll
+          for (int j = 0; j < R; ++j) av[j] = __dadd_rn(av[j], __dmul_rn(ca.c1[a], t[j]));
+        }
+        block_store<R>(ca.acc[a], r, av);
+      }
+      block_store<R>(out, r, t);
+    }
+  }
+}
+
+// One order of the Chebyshev recurrence WITH the two reductions of the moments, the Hubbard twin of k_cheb_sector_moments<R,
+// LEFT>: the same row walk once more, the recurrence part of the tail above without the accumulator block,
+//   t = g (w - centre x),  !first: t = t - old,  out = t
+//   LEFT = false:  a_j += x_j x_j,  b_j += x_j t_j          LEFT = true:  a_j += y_j x_j,  b_j += y_j t_j
+// by fma into the thread's accumulators; y is the row of the left block, read after the last chunk's gathers are consumed like
+// old.  A thread without a row adds nothing.  After the row loop the block's partials go to P[(which R + j) gridDim.x + block],
+// which = 0 for a, 1 for b, through one LDS array each (33-chebyshev-moments.md: one array for both would race): no atomics.
+// old == out is allowed; x and y are distinct from every written block.
+template <int R, bool LEFT>
+__global__ __launch_bounds__(256) void k_cheb_hubbard_moments(HubbardBlockParams p, const double* __restrict__ x, const double* old,
+                                                              double* out, const double* __restrict__ y, double centre, double g,
+                                                              int first, double* __restrict__ P) {
+  __shared__ double cp[DSEA_HBLOCK_MAX_PARAMS];
+  __shared__ uint64_t bm[DSEA_LATTICE_MAX_BONDS];
+  __shared__ uint16_t tb[DSEA_LATTICE_MAX_BONDS];
+  __shared__ double sma[R][4];
+  __shared__ double smb[R][4];
+  constexpr int CH = HblockChunk<R>::value;
+  constexpr int HOPS = 2 * CH;
+  const int L = p.L, nb = p.nb;
+  const int64_t n = p.n;
+  for (int c = threadIdx.x; c < 2 * nb + 2 * L; c += 256) cp[c] = p.c[c];
+  for (int c = threadIdx.x; c < nb; c += 256) {
+    const uint16_t e = p.tb[c];
+    tb[c] = e;
+    bm[c] = hblock_between(e);
+  }
+  __syncthreads();
+  const double* __restrict__ ts = cp;
+  const double* __restrict__ Vs = cp + nb;
+  const double* __restrict__ Us = cp + 2 * nb;
+  const double* __restrict__ es = cp + 2 * nb + L;
+  double acca[R], accb[R];
+#pragma unroll
+  for (int j = 0; j < R; ++j) {
+    acca[j] = 0.0;
+    accb[j] = 0.0;
+  }
+  for (int64_t row0 = (int64_t)blockIdx.x * 256; row0 < n; row0 += (int64_t)gridDim.x * 256) {
+    const int64_t r = row0 + threadIdx.x;
+    const bool have = r < n;                       // (a thread past the last row reads row n - 1 and writes nothing)
+    const uint32_t rr = (uint32_t)(have ? r : n - 1);
+    const uint32_t ru = rr / p.n_dn, rd = rr - ru * p.n_dn;
+    const uint64_t u = p.up_states[ru], d = p.dn_states[rd];
+    double xr[R];
+    block_load<R>(xr, x, (int64_t)rr);
+    uint32_t hi[HOPS], lo[HOPS];
+    uint32_t on = hblock_lookups<CH>(hi, lo, u, d, have, 0, p, tb);
+    double diag = 0.0, sum[R];
+#pragma unroll
+    for (int j = 0; j < R; ++j) sum[j] = 0.0;
+    const uint64_t both = u & d;
+    for (int i = 0; i < L; ++i) {
+      diag += hblock_bit(both, i) ? Us[i] : 0.0;
+      diag = fma(es[i], (double)(hblock_bit(u, i) + hblock_bit(d, i)), diag);
+    }
+    for (int k0 = 0; k0 < nb; k0 += CH) {
+      uint32_t rw[HOPS];
+      double xv[HOPS][R];
+      hblock_rows<CH>(rw, on, hi, lo, ru, rd, p.n_dn);
+      hblock_gather<R, HOPS>(xv, rw, x);
+      on = hblock_lookups<CH>(hi, lo, u, d, have, k0 + CH, p, tb);
+#pragma unroll
+      for (int e = 0; e < CH; ++e) {
+        if (k0 + e < nb) {
+          const uint32_t w = tb[k0 + e];
+          const uint64_t between = bm[k0 + e];
+          const double tt = ts[k0 + e];
+          diag = fma(Vs[k0 + e], hblock_nn(u, d, w), diag);
+          // -t sgn = t (-1)^(parity + 1): the sign goes into the sign bit of the coupling
+          const double tu = block_signed(tt, hblock_parity(u, between) ^ 1ull);
+          const double td = block_signed(tt, hblock_parity(d, between) ^ 1ull);
+#pragma unroll
+          for (int j = 0; j < R; ++j) {
+            sum[j] = fma(tu, xv[2 * e][j], sum[j]);
+            sum[j] = fma(td, xv[2 * e + 1][j], sum[j]);
+          }
+        }
+      }
+    }
+    if (have) {
+      double t[R];
+#pragma unroll
+      for (int j = 0; j < R; ++j) {
+        const double w = fma(diag, xr[j], sum[j]);
+        t[j] = __dmul_rn(g, __dsub_rn(w, __dmul_rn(centre, xr[j])));
+      }
+      if (!first) {
+        double ov[R];
+        block_load<R>(ov, old, r);
+#pragma unroll
+        for (int j = 0; j < R; ++j) t[j] = __dsub_rn(t[j], ov[j]);
+      }
+      block_store<R>(out, r, t);
+      if constexpr (LEFT) {
+        double yv[R];
+        block_load<R>(yv, y, r);
+#pragma unroll
+        for (int j = 0; j < R; ++j) {
+          acca[j] = fma(yv[j], xr[j], acca[j]);
+          accb[j] = fma(yv[j], t[j], accb[j]);
+        }
+      } else {
+#pragma unroll
+        for (int j = 0; j < R; ++j) {
+          acca[j] = fma(xr[j], xr[j], acca[j]);
+          accb[j] = fma(xr[j], t[j], accb[j]);
+        }
+      }
+    }
+  }
+  block_partials<R>(acca, sma, P);
+  block_partials<R>(accb, smb, P + (int64_t)R * gridDim.x);
+}
+
 // the kernel arguments; false when the descriptor is out of range
 static bool hubbard_block_params(const OpDesc& op, HubbardBlockParams* p) {
   const HubbardDesc& d = op.hubbard;
@@ -228,6 +451,53 @@ int launch_hubbard_block_apply(const OpDesc& op, int R, const double* X, double*
     klaunch(nullptr, k_spmv_hubbard_block<decltype(r)::value, false>, nblk, 256, 0, st, p, X, Y, nullptr, 1, nullptr);
   });
   return nblk;
+}
+
+// ACC[a] = sum_{m < M} coeffs[a * M + m] T_m((H - centre) / halfwidth) X in M - 1 launches of k_cheb_hubbard_block, on the
+// schedule of launch_sector_block_chebyshev: order 1 is `first` with x = X and out = U; order 2 reads x = U, old = X and writes
+// V; from order 3 on old == out, U and V in turn.  The two coefficients of an order go into its launch by value from the host
+// array.  Nothing is read back, no synchronise.
+int launch_hubbard_block_chebyshev(const OpDesc& op, int R, int A, int M, double centre, double halfwidth, const double* coeffs,
+                                   const double* X, double* U, double* V, double* ACC, hipStream_t st) {
+  HubbardBlockParams p;
+  if (!hubbard_block_params(op, &p)) return -1;
+  const int nblk = block_blocks(op);
+  dispatch_block_width(R, [&](auto r) {
+    dispatch_int<1, 2>(A, [&](auto na) {
+      constexpr int RR = decltype(r)::value, AA = decltype(na)::value;
+      ChebAccs<AA> ca;
+      for (int a = 0; a < AA; ++a) {
+        ca.acc[a] = ACC + (int64_t)a * op.n * RR;
+        ca.c0[a] = coeffs[(int64_t)a * M];
+      }
+      double* const t[2] = {U, V};                 // T_m lives in t[(m - 1) & 1]
+      for (int m = 1; m < M; ++m) {
+        for (int a = 0; a < AA; ++a) ca.c1[a] = coeffs[(int64_t)a * M + m];
+        const double* x = m == 1 ? X : t[m & 1];
+        const double* old = m == 2 ? X : t[(m - 1) & 1];
+        klaunch(nullptr, k_cheb_hubbard_block<RR, AA>, nblk, 256, 0, st, p, x, old, t[(m - 1) & 1], ca, centre,
+                (m == 1 ? 1.0 : 2.0) / halfwidth, m == 1 ? 1 : 0);
+      }
+    });
+  });
+  return nblk;
+}
+
+// the schedule of block_moments_drive with this file's moments kernel as the step; Y null: self mode
+int launch_hubbard_block_moments(const OpDesc& op, int R, int M, double centre, double halfwidth, const double* X, const double* Y,
+                                 double* U, double* V, double* MU, double* scratch, hipStream_t st) {
+  HubbardBlockParams p;
+  if (!hubbard_block_params(op, &p)) return -1;
+  const int nblk = block_blocks(op);
+  return block_moments_drive(op.n, nblk, R, M, Y != nullptr, X, U, V, MU, scratch, st,
+                             [&](const double* x, const double* old, double* out, int first, double* P) {
+                               dispatch_block_width(R, [&](auto r) {
+                                 dispatch_bool(Y != nullptr, [&](auto left) {
+                                   klaunch(nullptr, k_cheb_hubbard_moments<decltype(r)::value, decltype(left)::value>, nblk, 256, 0,
+                                           st, p, x, old, out, Y, centre, (first ? 1.0 : 2.0) / halfwidth, first, P);
+                                 });
+                               });
+                             });
 }
 
 // the recurrence of block_lanczos_drive with this file's mat-vec as the step

@@ -604,6 +604,13 @@ int block_moments_drive(int64_t n, int nblk, int R, int M, bool left, const doub
 int launch_hubbard_block_apply(const OpDesc& op, int R, const double* X, double* Y, hipStream_t st);
 int launch_hubbard_block_lanczos(const OpDesc& op, int R, int k, double* Q, double* W, double* norm2, double* alphas, double* betas,
                                  int32_t* steps, double* scratch, hipStream_t st);
+// launch_hubbard_block_chebyshev, launch_hubbard_block_moments (docs/design/34-hubbard-chebyshev.md): the twins of
+// launch_sector_block_chebyshev and launch_sector_block_moments for an OP_HUBBARD descriptor, on k_cheb_hubbard_block<R, A> and
+// k_cheb_hubbard_moments<R, LEFT>, with the same arguments, schedules and return values.
+int launch_hubbard_block_chebyshev(const OpDesc& op, int R, int A, int M, double centre, double halfwidth, const double* coeffs,
+                                   const double* X, double* U, double* V, double* ACC, hipStream_t st);
+int launch_hubbard_block_moments(const OpDesc& op, int R, int M, double centre, double halfwidth, const double* X, const double* Y,
+                                 double* U, double* V, double* MU, double* scratch, hipStream_t st);
 // dsea_block_lanczos.hip (the basis-free block Lanczos recurrence for any operator; the device parts the block kernels share are
 // in dsea_block.h, docs/design/32-block-kernel-parts.md): the start and k steps with the per-column break record on nblk blocks
 // of 256 rows, three launches per step, nothing read back.  The mat-vec of a step is the caller's step(q, w, state, first, PA),

@@ -136,13 +136,6 @@ __global__ __launch_bounds__(256) void k_spmv_sector_block(SectorBlockParams p, 
   if constexpr (LZ) block_partials<R>(acc, sm, P);
 }
 
-// the per-accumulator arguments of one Chebyshev order, by value
-template <int A>
-struct ChebAccs {
-  double* acc[A];
-  double c0[A], c1[A];
-};
-
 // One order of the Chebyshev recurrence of f(H) X (docs/design/31-chebyshev-propagator.md): with w the row of H x exactly as
 // k_spmv_sector_block<R, false> forms it (the same loop, the same operation order, the same bits),
 //   t = g (w - centre x)                                  g = 1 / halfwidth on the first order, 2 / halfwidth afterwards

@@ -269,8 +269,8 @@ def kpm_structure_factor(op0, psi0, E0, weights, channel, M=256, target=None, bo
     """``dynamical_structure_factor`` by the kernel polynomial method: the ``chebyshev.ChebyshevMeasure`` of O psi0 as a function
     of omega = E - E0, from one ladder application and ONE moments run in the destination sector (the real and the imaginary
     part of complex weights are the two columns of one block, and their moments add).  ``op0`` a ``SpinSectorOperator`` with
-    the channels "zz", "-", "+" (the fused kernel), or a ``HubbardOperator`` with the channel names of
-    ``hubbard_spectral_function`` (``apply_block`` and torch).  ``bounds`` of the TARGET's spectrum; None takes
+    the channels "zz", "-", "+", or a ``HubbardOperator`` with the channel names of ``hubbard_spectral_function``; either way
+    the moments run on the operator's fused kernel.  ``bounds`` of the TARGET's spectrum; None takes
     ``chebyshev.spectral_bounds(target)``.  Plain numbers: not differentiable."""
     from .chebyshev import ChebyshevMeasure, chebyshev_moments, spectral_bounds
     from .operators import HubbardOperator

@@ -17,6 +17,8 @@ through the three-term recurrence at once as one [n, R] block, on the block mat-
     spin_density_of_states(L, bonds, couplings, M)  those of all sectors on one interval (docs/design/33-chebyshev-moments.md)
     GrandCanonicalEnsemble(entries)         ln Xi, <H>, <N>, kappa, chi_s, C and S of a list of (measure, nup, ndn) over (beta, mu)
     hubbard_thermodynamics(L, bonds, couplings, ...)   that ensemble over all (nup, ndn) sectors of a Hubbard model
+    hubbard_density_of_states(L, bonds, couplings, M)  the Chebyshev moments of tr T_m over all (nup, ndn) sectors on one interval
+                                                       (docs/design/34-hubbard-chebyshev.md)
     thermal_correlations(L, bonds, couplings, betas, ...)   <X_i X_j + Y_i Y_j>, <Z_i Z_j>, <Z_i>, E and ln Z at T > 0 from thermal
                                                        pure quantum states e^{-beta H / 2} |r> (docs/design/31-chebyshev-propagator.md)
 
@@ -592,21 +594,13 @@ def one_species_matrix(L, bonds, couplings, count, other_full):
     return H
 
 
-def hubbard_thermodynamics(L, bonds, couplings, R=8, k=100, seed=0, dense_below=256, sectors=None, spin_symmetric=True,
-                           edge_dense_max=4096, device=None):
-    """The ``GrandCanonicalEnsemble`` of the Hubbard model of ``HubbardOperator`` (its Hamiltonian and its parameter order
-    [t(nb), V(nb), U(L), eps(L)]) over all sectors (nup, ndn) in {0 .. L}^2, or over the list ``sectors`` of distinct pairs.
-
-    A bulk sector, 1 <= nup, ndn <= L - 1, contributes ``sector_trace_measure(op, R, k, seed, dense_below)`` of its
-    ``HubbardOperator``; one sector's operator and tables are released before the next is built.  An edge sector -- a species
-    empty or full, which the operator refuses -- is always exact: the other species sees ``one_species_matrix``, whose
-    eigenvalues (host ``eigvalsh``) enter with weight 1; a one-species dimension above ``edge_dense_max`` raises ``ValueError``;
-    both species frozen is one state from host arithmetic.  ``spin_symmetric=True``: H has no spin-dependent term, so the
-    sectors (a, b) and (b, a) share a spectrum; only nup >= ndn is computed and the measure is entered for both."""
-    from .operators import HubbardOperator, _check_bonds
+def _hubbard_model(what, L, bonds, couplings, sectors, edge_dense_max, device):
+    """The argument checks that ``hubbard_thermodynamics`` and ``hubbard_density_of_states`` share (``ValueError`` in the name of
+    ``what``, before any sector is computed): (L, bonds, couplings, sectors, device) as ``_hubbard_sector_sweep`` takes them"""
+    from .operators import _check_bonds
     L = int(L)
     if not 2 <= L <= _lib.SECTOR_MAX_L:
-        raise ValueError("hubbard_thermodynamics needs 2 <= L <= %d, got %d" % (_lib.SECTOR_MAX_L, L))
+        raise ValueError("%s needs 2 <= L <= %d, got %d" % (what, _lib.SECTOR_MAX_L, L))
     bonds = _check_bonds(L, bonds)
     nb = len(bonds)
     c = torch.as_tensor(couplings, dtype=F64).detach()
@@ -624,26 +618,33 @@ def hubbard_thermodynamics(L, bonds, couplings, R=8, k=100, seed=0, dense_below=
             if n > int(edge_dense_max):
                 raise ValueError("the edge sector (nup, ndn) = (%d, %d) has a one-species dimension of %d, above edge_dense_max = %d"
                                  % (nup, ndn, n, int(edge_dense_max)))
-    host = c.cpu()
     if device is None:
         device = c.device if c.is_cuda else "cuda"
+    return L, bonds, c, sectors, device
+
+
+def _hubbard_sector_sweep(L, bonds, c, sectors, device, spin_symmetric, exact, bulk):
+    """The sector bookkeeping that ``hubbard_thermodynamics`` and ``hubbard_density_of_states`` share, on the checked arguments
+    of ``_hubbard_model``: [(value, nup, ndn)] over the sectors in the caller's order.  An edge sector -- a species empty or
+    full -- gives ``exact(poles)`` with the host float64 eigenvalues of ``one_species_matrix`` (both species frozen: the one
+    energy); a bulk sector gives ``bulk(op)`` of its ``HubbardOperator``, which is released before the next is built.
+    ``spin_symmetric``: (a, b) and (b, a) share the value computed for nup >= ndn."""
+    from .operators import HubbardOperator
+    host = c.cpu()
     on_device = None
 
-    def measure(nup, ndn):
+    def value(nup, ndn):
         nonlocal on_device
         frozen = [s for s in (nup, ndn) if s in (0, L)]
         if len(frozen) == 2:
-            energy = one_species_matrix(L, bonds, host, nup, ndn == L)
-            return SpectralMeasure(energy.reshape(1), torch.ones(1, dtype=F64), 1.0, 1)
+            return exact(one_species_matrix(L, bonds, host, nup, ndn == L).reshape(1))
         if frozen:
             count, other = (ndn, nup) if nup in (0, L) else (nup, ndn)
-            n = math.comb(L, count)
-            poles = torch.linalg.eigvalsh(one_species_matrix(L, bonds, host, count, other == L))
-            return SpectralMeasure(poles, torch.ones(n, dtype=F64), float(n), n)
+            return exact(torch.linalg.eigvalsh(one_species_matrix(L, bonds, host, count, other == L)))
         if on_device is None:
             on_device = c.to(device)
         op = HubbardOperator(L, bonds, on_device, nup, ndn, device)
-        out = sector_trace_measure(op, R=R, k=k, seed=seed, dense_below=dense_below)
+        out = bulk(op)
         del op
         return out
 
@@ -651,6 +652,56 @@ def hubbard_thermodynamics(L, bonds, couplings, R=8, k=100, seed=0, dense_below=
     for nup, ndn in sectors:
         key = (max(nup, ndn), min(nup, ndn)) if spin_symmetric else (nup, ndn)
         if key not in done:
-            done[key] = measure(*key)
+            done[key] = value(*key)
         entries.append((done[key], nup, ndn))
-    return GrandCanonicalEnsemble(entries)
+    return entries
+
+
+def hubbard_thermodynamics(L, bonds, couplings, R=8, k=100, seed=0, dense_below=256, sectors=None, spin_symmetric=True,
+                           edge_dense_max=4096, device=None):
+    """The ``GrandCanonicalEnsemble`` of the Hubbard model of ``HubbardOperator`` (its Hamiltonian and its parameter order
+    [t(nb), V(nb), U(L), eps(L)]) over all sectors (nup, ndn) in {0 .. L}^2, or over the list ``sectors`` of distinct pairs.
+
+    A bulk sector, 1 <= nup, ndn <= L - 1, contributes ``sector_trace_measure(op, R, k, seed, dense_below)`` of its
+    ``HubbardOperator``; one sector's operator and tables are released before the next is built.  An edge sector -- a species
+    empty or full, which the operator refuses -- is always exact: the other species sees ``one_species_matrix``, whose
+    eigenvalues (host ``eigvalsh``) enter with weight 1; a one-species dimension above ``edge_dense_max`` raises ``ValueError``;
+    both species frozen is one state from host arithmetic.  ``spin_symmetric=True``: H has no spin-dependent term, so the
+    sectors (a, b) and (b, a) share a spectrum; only nup >= ndn is computed and the measure is entered for both."""
+    model = _hubbard_model("hubbard_thermodynamics", L, bonds, couplings, sectors, edge_dense_max, device)
+    return GrandCanonicalEnsemble(_hubbard_sector_sweep(
+        *model, spin_symmetric,
+        lambda poles: SpectralMeasure(poles, torch.ones(poles.numel(), dtype=F64), float(poles.numel()), poles.numel()),
+        lambda op: sector_trace_measure(op, R=R, k=k, seed=seed, dense_below=dense_below)))
+
+
+def hubbard_density_of_states(L, bonds, couplings, M, R=8, seed=0, dense_below=256, sectors=None, spin_symmetric=True,
+                              edge_dense_max=4096, bounds=None, device=None):
+    """The ``chebyshev.ChebyshevMeasure`` of the spectrum of the model of ``hubbard_thermodynamics`` over all sectors (nup, ndn)
+    in {0 .. L}^2, or over the list ``sectors``: mu_m ~= tr T_m over the listed sectors, so that over all of them mu_0 = 4^L,
+    ``density(E) / 4^L`` is the normalised density of states and ``logtrace_exp(beta)`` is ln Z at zero chemical potential
+    (docs/design/34-hubbard-chebyshev.md).  All sectors are expanded on ONE interval, so their moments add: ``bounds``, or by
+    default the rigorous (-B, B) with B = sum_t (2 |t_t| + 4 |V_t|) + sum_i (|U_i| + 2 |eps_i|) >= ||H|| in every sector.  A bulk
+    sector contributes ``sector_density_of_states(op, M, bounds, R, seed, dense_below)`` of its ``HubbardOperator``, on the fused
+    Hubbard moments kernel; an edge sector is exact, sum_i T_m of the eigenvalues of ``one_species_matrix`` or of the one frozen
+    state.  The sectors, their refusals (``ValueError`` before any sector is computed) and ``spin_symmetric`` are those of
+    ``hubbard_thermodynamics``."""
+    from .chebyshev import ChebyshevMeasure, _check_bounds
+    M = int(M)
+    if M < 2 or int(R) < 1:
+        raise ValueError("hubbard_density_of_states needs M >= 2 and R >= 1, got %d and %d" % (M, int(R)))
+    model = _hubbard_model("hubbard_density_of_states", L, bonds, couplings, sectors, edge_dense_max, device)
+    if bounds is None:
+        L, nb = model[0], len(model[1])
+        host = model[2].cpu().abs()
+        B = float(2.0 * host[:nb].sum() + 4.0 * host[nb:2 * nb].sum() + host[2 * nb:2 * nb + L].sum() + 2.0 * host[2 * nb + L:].sum())
+        bounds = (-B, B)
+    centre, h = _check_bounds(bounds)
+    entries = _hubbard_sector_sweep(
+        *model, spin_symmetric,
+        lambda poles: ChebyshevMeasure(_trace_moments(poles, M, centre, h), bounds),
+        lambda op: sector_density_of_states(op, M, bounds, R=R, seed=seed, dense_below=dense_below))
+    total = entries[0][0]
+    for part, _, _ in entries[1:]:
+        total = total + part
+    return total

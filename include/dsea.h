@@ -1070,6 +1070,35 @@ int dsea_op_sector_block_moments(dsea_op_t op, int R, int M, double centre, doub
                                  const double *Y /* [n,R] left block, or NULL: self mode */, double *U /* [n,R] work */,
                                  double *V /* [n,R] work */, double *MU /* device [M,R] out */, double *scratch, void *stream);
 
+/* ------------------------------------------------------------------ Hubbard Chebyshev propagator and moments (docs/design/34-hubbard-chebyshev.md)
+ * The twins of dsea_op_sector_block_chebyshev and of the two moments entries above for the operator of dsea_op_create_hubbard:
+ * the same quantities, blocks (fp64 [n, R] row-major, 16-byte aligned, DSEA_ERR_ALIGN otherwise, R in {1, 2, 4, 8}), host coeffs
+ * [A, M] with coeffs[a * M + 0] ALREADY HALVED, device MU [M, R], launch schedules and rounding: every order is one launch of
+ * the Hubbard block mat-vec with the recurrence tail inside (the moments: with the two dot products per column inside, then one
+ * one-block launch that sums the per-block partials in index order), every product and sum of the recurrence rounded on its
+ * own, so that ACC, U and V equal dsea_op_hubbard_block_apply followed by separate elementwise operations bit for bit.  The
+ * spectrum of H must lie inside [centre - halfwidth, centre + halfwidth].  X and Y are never written; U and V are work blocks.
+ * dsea_op_hubbard_block_chebyshev: ACC[a] = sum_{m < M} coeffs[a * M + m] T_m((H - centre) / halfwidth) X, a in [0, A), A in
+ * {1, 2}, ACC [A, n, R], in M - 1 launches; on return U and V hold the last two T_m X.  No reductions, no atomics.
+ * dsea_op_hubbard_block_moments: MU[m, j] = l_j . T_m((H - centre) / halfwidth) x_j, m in [0, M), l = X (Y null: self mode,
+ * K = ceil(M / 2) orders, two moments per order by the product rule) or the columns of Y (left mode, K = M - 1 orders).  ON
+ * RETURN T_K X is in U for odd K and in V for even K, and T_{K-1} X is in the other work block (for K = 1 it is X itself and V is
+ * untouched); they equal the work blocks of dsea_op_hubbard_block_chebyshev after K orders bit for bit.  No atomics: identical
+ * calls return identical bits.  scratch: caller-owned, dsea_op_hubbard_block_moments_scratch_doubles(L, nup, ndn, R) =
+ * 2 R min(4096, ceil(n / 256)) doubles (enough for every grid cap).
+ * Nothing is read back, the calls do not synchronise, the library allocates nothing; every check is host arithmetic before any
+ * device work.  DSEA_ERR_ARG: any other operator kind, R outside {1, 2, 4, 8}, A outside {1, 2}, M < 2, a null coeffs, X, U, V,
+ * ACC, MU or scratch, centre or halfwidth not finite, halfwidth <= 0, any two of X, U, V, ACC, ACC + n R equal (propagator), any
+ * two of X, Y, U, V equal (moments); in the scratch query (L, nup, ndn) outside the limits of dsea_hubbard_sizes or a null out. */
+int dsea_op_hubbard_block_chebyshev(dsea_op_t op, int R, int A, int M, double centre, double halfwidth,
+                                    const double *coeffs /* host [A,M], c_0 halved */, const double *X /* [n,R] */,
+                                    double *U /* [n,R] work */, double *V /* [n,R] work */, double *ACC /* [A,n,R] out */,
+                                    void *stream);
+int dsea_op_hubbard_block_moments_scratch_doubles(int L, int nup, int ndn, int R, int64_t *out);
+int dsea_op_hubbard_block_moments(dsea_op_t op, int R, int M, double centre, double halfwidth, const double *X /* [n,R] */,
+                                  const double *Y /* [n,R] left block, or NULL: self mode */, double *U /* [n,R] work */,
+                                  double *V /* [n,R] work */, double *MU /* device [M,R] out */, double *scratch, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
