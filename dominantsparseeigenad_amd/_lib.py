@@ -113,6 +113,11 @@ _SIGNATURES = {
     "dsea_sector_ladder_forms_scratch_doubles": (c_int, [c_int, c_int, c_int, POINTER(c_int64)]),
     "dsea_sector_ladder_forms": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                          c_void_p, c_int, c_void_p]),
+    "dsea_sector_ladder_block_apply": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                               c_void_p, c_int, c_void_p]),
+    "dsea_sector_ladder_block_dots_scratch_doubles": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_int64)]),
+    "dsea_sector_ladder_block_dots": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                              c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "dsea_hubbard_ladder_apply": (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_int, c_void_p]),
     "dsea_hubbard_ladder_forms_scratch_doubles": (c_int, [c_int, c_int, c_int, c_int, c_int, POINTER(c_int64)]),

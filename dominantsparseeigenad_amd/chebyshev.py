@@ -27,6 +27,7 @@ Plain host float64 numbers and detached blocks: nothing here is differentiable.
 """
 from __future__ import annotations
 
+import functools
 import math
 from ctypes import byref, c_double, c_int64, c_void_p
 
@@ -456,6 +457,23 @@ def expm_block(op, X, tau, bounds=None, tol=1e-15):
     return chebyshev_apply(op, X, coeffs, bounds), a
 
 
+@functools.lru_cache(maxsize=16)
+def _evolution_rows(t, centre, h, tol):
+    """[2, M]: the coefficient rows of cos and sin of H t = h t s + centre t.  Kept for the last few (t, interval) pairs: a time
+    grid asks for the same rows at every step (``thermal.thermal_dynamics``).  Never written to."""
+    w, phase = LD(h * t), LD(centre * t)
+    fc = lambda s: np.cos(w * s + phase)  # noqa: E731
+    fs = lambda s: np.sin(w * s + phase)  # noqa: E731
+    guess = _order_guess(abs(h * t))
+    found = [_truncated_expansion(f, guess, tol) for f in (fc, fs)]
+    M = max(m for m, _ in found)
+    rows = np.zeros((2, M))                     # (the shorter row is padded: its coefficients beyond its own order are below tol)
+    for a, (m, c) in enumerate(found):
+        rows[a, :m] = c
+    rows.setflags(write=False)
+    return rows
+
+
 def time_evolve(op, psi, t, bounds=None, tol=1e-15):
     """e^{-i H t} psi (complex128) for a real or complex device tensor psi of shape (n,) or (n, R) and a real time t.  H is
     real, so the real and the imaginary parts are columns of ONE real block that goes through ONE ``chebyshev_apply`` with
@@ -478,16 +496,7 @@ def time_evolve(op, psi, t, bounds=None, tol=1e-15):
     R = block.shape[1]
     if block.is_complex():
         block = torch.cat([block.real, block.imag], dim=1)
-    w, phase = LD(h * t), LD(centre * t)
-    fc = lambda s: np.cos(w * s + phase)  # noqa: E731
-    fs = lambda s: np.sin(w * s + phase)  # noqa: E731
-    guess = _order_guess(abs(h * t))
-    found = [_truncated_expansion(f, guess, tol) for f in (fc, fs)]
-    M = max(m for m, _ in found)
-    rows = np.zeros((2, M))                     # (the shorter row is padded: its coefficients beyond its own order are below tol)
-    for a, (m, c) in enumerate(found):
-        rows[a, :m] = c
-    C, S = chebyshev_apply(op, block, rows, bounds)
+    C, S = chebyshev_apply(op, block, _evolution_rows(t, centre, h, float(tol)), bounds)
     if block.shape[1] == R:
         out = torch.complex(C, -S)
     else:

@@ -553,6 +553,16 @@ int launch_sector_ladder(int L, int ndown_src, int step, const double* c, const 
 int launch_sector_ladder_forms(int L, int ndown_src, int step, const uint64_t* states_dst, const uint32_t* lo_rank_src,
                                const uint32_t* hi_base_src, const double* v1, const double* v2, double* out, double* scratch,
                                int grid_log2, hipStream_t st);
+// The block forms (docs/design/35-finite-temperature-dynamics.md): Y = S(c) X for a block fp64 [n, R] row-major, R in {1, 2, 4, 8}
+// (column j bit for bit launch_sector_ladder on column j), and out[j] = sum_r' Lft[r', j] (S(c) X)[r', j] through per-block partials
+// in the caller's scratch (ladder_block_dots_scratch_doubles doubles).  The same -1 as above; the caller has checked R.
+int64_t ladder_block_dots_scratch_doubles(int64_t n_dst, int R);
+int launch_sector_ladder_block(int L, int ndown_src, int step, int R, const double* c, const uint64_t* states_dst,
+                               const uint32_t* lo_rank_src, const uint32_t* hi_base_src, const double* X, double* Y, int grid_log2,
+                               hipStream_t st);
+int launch_sector_ladder_block_dots(int L, int ndown_src, int step, int R, const double* c, const uint64_t* states_dst,
+                                    const uint32_t* lo_rank_src, const uint32_t* hi_base_src, const double* Lft, const double* X,
+                                    double* out, double* scratch, int grid_log2, hipStream_t st);
 // dsea_hubbard_ladder.hip (linear maps between two particle-number sectors of the Hubbard space,
 // docs/design/25-hubbard-ladder.md): sum_i c_i c+_{i s} (step +1), sum_i c_i n_{i s} (step 0) and sum_i c_i c_{i s} (step -1) of the
 // species s (0 up, 1 dn) from (L, nup_src, ndn_src) to the sector with that species' count changed by step, as gathers over

@@ -1,5 +1,7 @@
 // dsea_ladder.hip -- linear maps between two magnetisation sectors of the same L sites (docs/design/24-dynamics.md): the ladder
-// k_sector_ladder<STEP>, its site forms k_sector_ladder_forms<STEP> (+ k_sector_ladder_forms_reduce), and their launchers.
+// k_sector_ladder<STEP>, its site forms k_sector_ladder_forms<STEP> (+ k_sector_ladder_forms_reduce), the block forms
+// k_sector_ladder_block<STEP, R> and k_sector_ladder_block_dots<STEP, R> (docs/design/35-finite-temperature-dynamics.md), and
+// their launchers.
 //
 // Site i is bit i of a state, a set bit is a down spin, z_i(s) = 1 - 2 bit_i(s).  For site weights c (fp64 [L], read through
 // their device pointer on every launch) the map takes the source sector (L, ndown_src) to the destination sector
@@ -14,13 +16,15 @@
 // at or above Llo one hi_base read and one gather.  The row's own hi_base_src entry enters a sum only when a low site
 // contributes, and then it belongs to a valid source state; the row's own lo_rank_src entry is the rank of the low word among
 // the words of its popcount and is always valid.
-// Nothing here is shared with dsea_sector.hip: the file has its own helpers.
+// Nothing here is shared with dsea_sector.hip: the file has its own helpers.  The block forms take the row access and the
+// partials of a block from dsea_block.h.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "dsea_internal.h"
 #include "dsea_device.h"
+#include "dsea_block.h"
 
 namespace dsea {
 
@@ -172,6 +176,135 @@ __global__ __launch_bounds__(256) void k_sector_ladder_forms_reduce(const double
   if (threadIdx.x == 0) out[blockIdx.x] = tot;
 }
 
+// ---- the block forms (docs/design/35-finite-temperature-dynamics.md): the map and its column dots on blocks fp64 [n, R]
+// row-major, R in {1, 2, 4, 8} (dsea_block.h).  The row walk is that of k_sector_ladder; what changes is that a contributing
+// site costs one table read and one block_load<R> of the source row for all R columns.  The helpers are written apart from
+// the single-vector ones above (whose chunk is a macro), so that those keep their instructions.
+namespace {
+// sites in flight per thread: R * chunk doubles of gathered rows are live beside sum[R] (and acc[R] in the dots)
+template <int R>
+constexpr int ladder_block_chunk() {
+  return R <= 2 ? 8 : (R == 4 ? 4 : 2);
+}
+
+// ladder_ranks with the chunk as a template argument
+template <int STEP, int CH>
+__device__ __forceinline__ void ladder_block_ranks(uint32_t (&rk)[CH], uint64_t s, bool have, int k0, int end, int base, uint32_t word,
+                                                   uint32_t other, const uint32_t* __restrict__ table) {
+#pragma unroll
+  for (int e = 0; e < CH; ++e) {
+    const int i = k0 + e;
+    const bool on = have && i < end && ladder_qualifies<STEP>(s, i);
+    rk[e] = DSEA_LADDER_NO_RANK;
+    if (on) rk[e] = other + table[word ^ (1u << (i - base))];
+  }
+}
+
+// one group of sites [base, end) of one row: sum[j] = fma(cw[i], X[rank_i, j], sum[j]) for every site of the group in order
+// (X[rank_i, :] = 0 for a site that does not contribute: the single-vector kernel adds the same zero product).  The table
+// reads of chunk c + 1 are issued before the gathers of chunk c are consumed.
+template <int STEP, int R>
+__device__ __forceinline__ void ladder_block_group(uint64_t s, bool have, int base, int end, uint32_t word, uint32_t other,
+                                                   const uint32_t* __restrict__ table, const double* __restrict__ X,
+                                                   const double (&cw)[DSEA_SECTOR_MAX_L], double (&sum)[R]) {
+  constexpr int CH = ladder_block_chunk<R>();
+  uint32_t rkA[CH], rkB[CH];
+  ladder_block_ranks<STEP, CH>(rkA, s, have, base, end, base, word, other, table);
+  for (int k0 = base; k0 < end; k0 += CH) {
+    double xv[CH][R];
+#pragma unroll
+    for (int e = 0; e < CH; ++e) {
+#pragma unroll
+      for (int j = 0; j < R; ++j) xv[e][j] = 0.0;
+      if (rkA[e] != DSEA_LADDER_NO_RANK) block_load<R>(xv[e], X, (int64_t)rkA[e]);
+    }
+    ladder_block_ranks<STEP, CH>(rkB, s, have, k0 + CH, end, base, word, other, table);
+#pragma unroll
+    for (int e = 0; e < CH; ++e) {
+      if (k0 + e < end) {                          // (the same for every lane)
+        const double w = cw[k0 + e];
+#pragma unroll
+        for (int j = 0; j < R; ++j) sum[j] = fma(w, xv[e][j], sum[j]);
+      }
+      rkA[e] = rkB[e];
+    }
+  }
+}
+
+// sum[j] = (S(c) X)[r, j] of the row r (row n - 1 for a thread without a row): column j in the operations and the order of
+// k_sector_ladder on column j
+template <int STEP, int R>
+__device__ __forceinline__ void ladder_block_row(const LadderParams& p, const double (&cw)[DSEA_SECTOR_MAX_L], uint64_t lomask,
+                                                 int64_t r, bool have, const double* __restrict__ X, double (&sum)[R]) {
+  const int64_t rr = have ? r : p.n - 1;
+  const uint64_t st = p.states[rr];
+  if constexpr (STEP == 0) {
+    double xr[R];
+    block_load<R>(xr, X, rr);
+    double diag = 0.0;
+    for (int i = 0; i < p.L; ++i) diag += ladder_signed(cw[i], (st >> i) & 1ull);
+#pragma unroll
+    for (int j = 0; j < R; ++j) sum[j] = diag * xr[j];
+  } else {
+#pragma unroll
+    for (int j = 0; j < R; ++j) sum[j] = 0.0;
+    const uint32_t sl = (uint32_t)(st & lomask), sh = (uint32_t)(st >> p.Llo);
+    const uint32_t own_hi = p.hi_base[sh], own_lo = p.lo_rank[sl];
+    ladder_block_group<STEP, R>(st, have, 0, p.Llo, sl, own_hi, p.lo_rank, X, cw, sum);
+    ladder_block_group<STEP, R>(st, have, p.Llo, p.L, sh, own_lo, p.hi_base, X, cw, sum);
+  }
+}
+}  // namespace
+
+// Y = S(c) X.  The grid, the 256-row ranges and the thread past the last row as in k_sector_ladder; column j of Y equals
+// k_sector_ladder on column j of X bit for bit.
+template <int STEP, int R>
+__global__ __launch_bounds__(256) void k_sector_ladder_block(LadderParams p, const double* __restrict__ X, double* __restrict__ Y) {
+  __shared__ double cw[DSEA_SECTOR_MAX_L];
+  const int64_t n = p.n;
+  for (int c = threadIdx.x; c < p.L; c += 256) cw[c] = p.c[c];
+  __syncthreads();
+  const uint64_t lomask = (1ull << p.Llo) - 1;
+  for (int64_t row0 = (int64_t)blockIdx.x * 256; row0 < n; row0 += (int64_t)gridDim.x * 256) {
+    const int64_t r = row0 + threadIdx.x;
+    const bool have = r < n;
+    double sum[R];
+    ladder_block_row<STEP, R>(p, cw, lomask, r, have, X, sum);
+    if (have) block_store<R>(Y, r, sum);
+  }
+}
+
+// The column dots d[j] = sum_r' Lft[r', j] (S(c) X)[r', j] without the product block: the same rows and the same sum[j], the
+// row of Lft read after the last chunk's gathers are consumed, one accumulator per column and thread over the rows it walks
+// (a thread without a row adds nothing), then block_partials into scratch[j * gridDim.x + block].
+// k_sector_ladder_forms_reduce with R blocks closes them.  No atomics.
+template <int STEP, int R>
+__global__ __launch_bounds__(256) void k_sector_ladder_block_dots(LadderParams p, const double* __restrict__ Lft,
+                                                                  const double* __restrict__ X, double* __restrict__ scratch) {
+  __shared__ double cw[DSEA_SECTOR_MAX_L];
+  __shared__ double sm[R][4];
+  const int64_t n = p.n;
+  for (int c = threadIdx.x; c < p.L; c += 256) cw[c] = p.c[c];
+  __syncthreads();
+  const uint64_t lomask = (1ull << p.Llo) - 1;
+  double acc[R];
+#pragma unroll
+  for (int j = 0; j < R; ++j) acc[j] = 0.0;
+  for (int64_t row0 = (int64_t)blockIdx.x * 256; row0 < n; row0 += (int64_t)gridDim.x * 256) {
+    const int64_t r = row0 + threadIdx.x;
+    const bool have = r < n;
+    double sum[R];
+    ladder_block_row<STEP, R>(p, cw, lomask, r, have, X, sum);
+    if (have) {
+      double l[R];
+      block_load<R>(l, Lft, r);
+#pragma unroll
+      for (int j = 0; j < R; ++j) acc[j] = fma(l[j], sum[j], acc[j]);
+    }
+  }
+  block_partials<R>(acc, sm, scratch);
+}
+
 // the rows of the destination; false when either sector is outside the limits of sector_sizes or step outside -1 .. 1 (host
 // arithmetic only)
 bool ladder_sizes(int L, int ndown_src, int step, int64_t* n_src, int64_t* n_dst) {
@@ -234,6 +367,50 @@ int launch_sector_ladder_forms(int L, int ndown_src, int step, const uint64_t* s
   else if (step < 0) hipLaunchKernelGGL((k_sector_ladder_forms<-1>), grid, dim3(256), 0, st, p, v1, v2, scratch);
   else hipLaunchKernelGGL((k_sector_ladder_forms<0>), grid, dim3(256), 0, st, p, v1, v2, scratch);
   hipLaunchKernelGGL(k_sector_ladder_forms_reduce, dim3((unsigned)L), dim3(256), 0, st, scratch, nblk, out);
+  return 0;
+}
+
+// partials that launch_sector_ladder_block_dots may write at any grid cap
+int64_t ladder_block_dots_scratch_doubles(int64_t n_dst, int R) {
+  int64_t nblk = (n_dst + 255) / 256;
+  if (nblk > DSEA_MAX_TFIM_BLOCKS) nblk = DSEA_MAX_TFIM_BLOCKS;
+  return (int64_t)R * nblk;
+}
+
+// the one place that turns the run-time step of a block launch into the template argument (0 for anything but +-1)
+template <class F>
+static inline void dispatch_ladder_step(int step, F&& f) {
+  dispatch_int<1, -1, 0>(step, f);
+}
+
+int launch_sector_ladder_block(int L, int ndown_src, int step, int R, const double* c, const uint64_t* states_dst,
+                               const uint32_t* lo_rank_src, const uint32_t* hi_base_src, const double* X, double* Y, int grid_log2,
+                               hipStream_t st) {
+  LadderParams p;
+  if (!c || !ladder_params(L, ndown_src, step, grid_log2, c, states_dst, lo_rank_src, hi_base_src, &p)) return -1;
+  const dim3 grid((unsigned)ladder_blocks(p.n, grid_log2));
+  dispatch_ladder_step(step, [&](auto s) {
+    dispatch_block_width(R, [&](auto w) {
+      hipLaunchKernelGGL((k_sector_ladder_block<decltype(s)::value, decltype(w)::value>), grid, dim3(256), 0, st, p, X, Y);
+    });
+  });
+  return 0;
+}
+
+int launch_sector_ladder_block_dots(int L, int ndown_src, int step, int R, const double* c, const uint64_t* states_dst,
+                                    const uint32_t* lo_rank_src, const uint32_t* hi_base_src, const double* Lft, const double* X,
+                                    double* out, double* scratch, int grid_log2, hipStream_t st) {
+  LadderParams p;
+  if (!c || !ladder_params(L, ndown_src, step, grid_log2, c, states_dst, lo_rank_src, hi_base_src, &p)) return -1;
+  const int nblk = ladder_blocks(p.n, grid_log2);
+  const dim3 grid((unsigned)nblk);
+  dispatch_ladder_step(step, [&](auto s) {
+    dispatch_block_width(R, [&](auto w) {
+      hipLaunchKernelGGL((k_sector_ladder_block_dots<decltype(s)::value, decltype(w)::value>), grid, dim3(256), 0, st, p, Lft, X,
+                         scratch);
+    });
+  });
+  hipLaunchKernelGGL(k_sector_ladder_forms_reduce, dim3((unsigned)R), dim3(256), 0, st, scratch, nblk, out);
   return 0;
 }
 

@@ -21,6 +21,10 @@ through the three-term recurrence at once as one [n, R] block, on the block mat-
                                                        (docs/design/34-hubbard-chebyshev.md)
     thermal_correlations(L, bonds, couplings, betas, ...)   <X_i X_j + Y_i Y_j>, <Z_i Z_j>, <Z_i>, E and ln Z at T > 0 from thermal
                                                        pure quantum states e^{-beta H / 2} |r> (docs/design/31-chebyshev-propagator.md)
+    thermal_dynamics(L, bonds, couplings, weights, channel, betas, dt, steps, ...)   C(t) = <A^T(t) A> at T > 0 for A = sum_i c_i Z_i,
+                                                       sigma^-_i or sigma^+_i, and its spectrum S(q, omega; T): those states stepped
+                                                       in real time, the block ladder map in between
+                                                       (docs/design/35-finite-temperature-dynamics.md)
 
 Plain host float64 numbers: nothing here is differentiable.
 """
@@ -380,19 +384,20 @@ def _dense_sector_correlations(op, betas):
     return logsum, prob @ theta, torch.einsum("bj,jkl->bkl", prob, xy), torch.einsum("bj,jkl->bkl", prob, zz), prob @ z
 
 
-def _tpq_sector_correlations(op, betas, R, seed, tol):
-    """the same five from R thermal pure quantum states: the columns r_j = normal_vector(n, seed + j), normalised, are stepped
-    from one beta to the next by ``expm_block`` over half the difference and renormalised, the logarithms of their norms kept
-    on the host; at every beta column j weighs exp(2 log norm_j) and the sector weighs (n / R) times their sum"""
+def _tpq_states(op, betas, R, seed, tol, bounds=None):
+    """The R canonical thermal pure quantum states of the sector of ``op`` at every beta in turn, as a generator of
+    (Phi [n, R] normalised columns on the device, log norms [R] on the host, top, w [R], log weight of the sector): the columns
+    r_j = normal_vector(n, seed + j), normalised, are stepped from one beta to the next by ``expm_block`` over half the difference
+    and renormalised, the logarithms of their norms kept on the host; column j weighs w_j = exp(2 log norm_j - top) with
+    top = 2 max_j log norm_j, and the sector weighs (n / R) e^top sum_j w_j.  ``bounds`` None: ``spectral_bounds(op, seed=seed)``."""
     from .chebyshev import expm_block, spectral_bounds
     from .synthetic import normal_vector
     n = int(op.n)
     Phi = torch.stack([torch.from_numpy(normal_vector(n, int(seed) + j)) for j in range(R)], dim=1).to(op.device)
     Phi = Phi / torch.linalg.vector_norm(Phi, dim=0)
-    bounds = spectral_bounds(op, seed=seed)
-    pair = op.pair_operator()
+    if bounds is None:
+        bounds = spectral_bounds(op, seed=seed)
     lognorm = torch.zeros(R, dtype=F64)
-    out = [[] for _ in range(5)]
     before = 0.0
     for beta in betas.tolist():
         tau = 0.5 * (beta - before)
@@ -401,12 +406,21 @@ def _tpq_sector_correlations(op, betas, R, seed, tol):
         norms = torch.linalg.vector_norm(Y, dim=0)
         Phi = Y / norms
         lognorm = lognorm + torch.log(norms.cpu()) - tau * shift
-        energy = (Phi * op.apply_block(Phi)).sum(dim=0).cpu()
-        parts = [pair.correlations(Phi[:, j].contiguous()) for j in range(R)]
         top = 2.0 * lognorm.max()
         w = torch.exp(2.0 * lognorm - top)
+        yield Phi, lognorm, top, w, math.log(n / R) + top + torch.log(w.sum())
+
+
+def _tpq_sector_correlations(op, betas, R, seed, tol):
+    """the same five from the R thermal pure quantum states of ``_tpq_states``: at every beta column j weighs exp(2 log norm_j)
+    and the sector weighs (n / R) times their sum"""
+    pair = op.pair_operator()
+    out = [[] for _ in range(5)]
+    for Phi, _, _, w, logweight in _tpq_states(op, betas, R, seed, tol):
+        energy = (Phi * op.apply_block(Phi)).sum(dim=0).cpu()
+        parts = [pair.correlations(Phi[:, j].contiguous()) for j in range(R)]
         total = w.sum()
-        out[0].append(math.log(n / R) + top + torch.log(total))
+        out[0].append(logweight)
         out[1].append((w * energy).sum() / total)
         for i in range(3):
             q = torch.stack([part[i] for part in parts]).cpu()
@@ -467,6 +481,182 @@ def thermal_correlations(L, bonds, couplings, betas, R=8, seed=0, dense_below=25
     prob = torch.exp(logw - logZ)
     mix = lambda i: sum(prob[s].reshape((B,) + (1,) * (parts[s][i].dim() - 1)) * parts[s][i] for s in range(len(parts)))  # noqa: E731
     return ThermalCorrelations(betas, logZ, mix(1), mix(2), mix(3), mix(4))
+
+
+class ThermalDynamics:
+    """What ``thermal_dynamics`` returns, host tensors: ``betas`` [B], ``times`` [K + 1] with t_k = k dt, ``logZ`` [B] and
+    ``correlation`` [B, K + 1] (complex128), C(t_k) = tr[e^{-beta H} A^T(t_k) A] / Z at every beta."""
+
+    def __init__(self, betas, times, logZ, correlation):
+        self.betas, self.times, self.logZ, self.correlation = betas, times, logZ, correlation
+
+    def static(self):
+        """C(0).real [B]: the equal-time correlation <A^T A>"""
+        return self.correlation[:, 0].real.clone()
+
+    def spectrum(self, omega, eta):
+        """S(omega) [B, len omega] = (1 / pi) Re sum_k w_k e^{i omega t_k} C(t_k) e^{-(eta t_k)^2 / 2} with the trapezoid weights
+        w_k = dt (dt / 2 at both ends): (1 / 2 pi) int dt e^{i omega t} C(t) e^{-(eta t)^2 / 2} over all times, folded onto t >= 0
+        with C(-t) = C(t)^* (which holds in the exact trace), so that a pole of C at the excitation energy eps becomes a
+        Gaussian of width ``eta`` at omega = eps.  THE CALLER picks dt and K: eta t_K >= 8, so that the window has decayed where
+        the record ends, and pi / dt well above the band width, so that the trapezoid sum does not alias."""
+        eta = float(eta)
+        if not (eta > 0 and math.isfinite(eta)):
+            raise ValueError("spectrum needs a finite eta > 0, got %r" % (eta,))
+        K = self.times.numel() - 1
+        if K < 1:
+            raise ValueError("spectrum needs at least one time step")
+        omega = torch.as_tensor(omega, dtype=F64).detach().cpu().reshape(-1)
+        t = self.times
+        w = torch.full((K + 1,), float(t[1] - t[0]), dtype=F64)
+        w[0] = w[-1] = 0.5 * float(t[1] - t[0])
+        window = w * torch.exp(-0.5 * (eta * t) ** 2)
+        phase = torch.exp(torch.complex(torch.zeros(omega.numel(), K + 1, dtype=F64), omega[:, None] * t[None, :]))
+        return (torch.einsum("wk,bk->bw", phase * window, self.correlation).real / math.pi).contiguous()
+
+
+def _dense_ladder_matrix(L, ndown_src, step, c):
+    """the n_dst x n_src host matrix of sum_i c_i O_i from the sector (L, ndown_src) to (L, ndown_src + step), from
+    ``sector_states`` (edge sectors included): sigma^- arrives at a set bit, sigma^+ at a clear one, Z is diagonal"""
+    from .operators import sector_states
+    src, dst = sector_states(L, ndown_src), sector_states(L, ndown_src + step)
+    A = torch.zeros((len(dst), len(src)), dtype=F64)
+    c = c.tolist()
+    if step == 0:
+        for r, s in enumerate(dst):
+            A[r, r] = sum(c[i] * (1 - 2 * ((s >> i) & 1)) for i in range(L))
+        return A
+    rank = {s: r for r, s in enumerate(src)}
+    want = 1 if step > 0 else 0
+    for r, s in enumerate(dst):
+        for i in range(L):
+            if (s >> i) & 1 == want:
+                A[r, rank[s ^ (1 << i)]] = c[i]
+    return A
+
+
+def _dense_pair_dynamics(spec_src, spec_dst, maps, betas, times):
+    """(log weight [B], C [B, K + 1]) of a sector pair from the full spectra (theta, V) of its two sides and the host matrices
+    ``maps`` of the real parts of A: C(t) = sum_{n, m} p_n sum_parts |<m|A|n>|^2 e^{-i (E_m - E_n) t}, p_n = e^{-beta E_n} / Z_src.
+    ``spec_dst`` None: the destination does not exist, C = 0."""
+    theta, V = spec_src
+    logw = -betas[:, None] * theta[None, :]
+    logsum = torch.logsumexp(logw, dim=1)
+    if spec_dst is None:
+        return logsum, torch.zeros((betas.numel(), times.numel()), dtype=torch.complex128)
+    prob = torch.exp(logw - logsum[:, None])
+    theta2, V2 = spec_dst
+    W = sum((V2.t() @ A @ V) ** 2 for A in maps)                                  # [m, n]
+    unit = lambda e: torch.exp(torch.complex(torch.zeros(times.numel(), e.numel(), dtype=F64), times[:, None] * e[None, :]))  # noqa: E731
+    G = unit(-theta2) @ W.to(torch.complex128)                                    # [k, n] = sum_m e^{-i E_m t_k} W[m, n]
+    return logsum, torch.einsum("bn,kn->bk", prob.to(torch.complex128), unit(theta) * G)
+
+
+def _tpq_pair_dynamics(src, dst, lad, parts, betas, dt, steps, R, seed, tol):
+    """the same pair from the thermal pure quantum states of ``_tpq_states`` on the source: per beta and per real part c of the
+    weights, b_0 = Phi and a_0 = S(c) Phi (``apply_block``) are stepped by ``time_evolve`` over dt on the source and on the
+    destination, and at every step two ``block_dots`` calls on the (re | im) blocks give
+    C_j(t_k) = <S(c) b_k,j | a_k,j> = [d(a_re, b_re) + d(a_im, b_im)] + i [d(a_im, b_re) - d(a_re, b_im)]"""
+    from .chebyshev import spectral_bounds, time_evolve
+    bounds_src = spectral_bounds(src, seed=seed)
+    bounds_dst = bounds_src if dst is src else spectral_bounds(dst, seed=seed)
+    parts = [c.to(lad.device) for c in parts]
+    logweights, rows = [], []
+    for Phi, _, _, w, logweight in _tpq_states(src, betas, R, seed, tol, bounds_src):
+        Cj = torch.zeros((steps + 1, R), dtype=torch.complex128)
+        for c in parts:
+            b = torch.complex(Phi, torch.zeros_like(Phi))
+            a0 = lad.apply_block(c, Phi)
+            a = torch.complex(a0, torch.zeros_like(a0))
+            for k in range(steps + 1):
+                if k:
+                    b = time_evolve(src, b, dt, bounds_src, tol)
+                    a = time_evolve(dst, a, dt, bounds_dst, tol)
+                bb = torch.cat([b.real, b.imag], dim=1)
+                d1 = lad.block_dots(c, torch.cat([a.real, a.imag], dim=1), bb).cpu()
+                d2 = lad.block_dots(c, torch.cat([a.imag, a.real], dim=1), bb).cpu()
+                Cj[k] += torch.complex(d1[:R] + d1[R:], d2[:R] - d2[R:])
+        logweights.append(logweight)
+        rows.append((Cj * w).sum(dim=1) / w.sum())
+    return torch.stack(logweights), torch.stack(rows)
+
+
+def thermal_dynamics(L, bonds, couplings, weights, channel, betas, dt, steps, R=8, seed=0, dense_below=256, sectors=None,
+                     tol=1e-15, device=None):
+    """The finite-temperature correlation function of A = sum_i c_i O_i for the model and the parameter order of
+    ``spin_thermodynamics`` (docs/design/35-finite-temperature-dynamics.md): a ``ThermalDynamics`` with
+
+        C(t_k) = (1 / Z) sum_sectors tr_src[ e^{-beta H} e^{i H t_k} A^T e^{-i H' t_k} A ],    t_k = k dt,  k = 0 .. steps
+
+    at the ascending inverse temperatures ``betas`` >= 0.  ``channel`` "zz", "-" or "+": O = Z, sigma^- or sigma^+ (the channels
+    of ``spectral.dynamical_structure_factor``), which take the source sector ndown to ndown, ndown + 1 or ndown - 1 with the
+    Hamiltonian H'.  ``weights``: a real vector [L], a ``(re, im)`` pair (``ring_momentum_weights``) or a complex tensor; for
+    complex weights the result is the sum of the correlation functions of the real and of the imaginary part -- all matrices are
+    real, so the cross terms cancel in the exact trace, and dropping them removes an estimator of zero.  ``sectors`` lists the
+    SOURCE sectors (default 0 .. L): Z is the sum over them, and a source whose destination does not exist contributes to Z only.
+
+    A sector pair with more than ``dense_below`` rows on either side is sampled by the R thermal pure quantum states of
+    ``thermal_correlations`` on the source (same start vectors ``normal_vector(n, seed + j)``, same stepping in beta, same
+    weights): a_0 = A |beta, j> by ``SpinSectorLadder.apply_block``, both sides stepped by ``chebyshev.time_evolve`` over dt on one
+    ``spectral_bounds`` interval per sector, and C_j(t_k) = <A b_k,j | a_k,j> by two ``block_dots`` calls per step.  A smaller
+    pair, and every pair with an edge sector (ndown = 0 or L) on one side, is exact on the host: the full spectra of both sides
+    and the matrix of A from ``operators.sector_states``.  One pair of operators is alive at a time.  The error of a sampled
+    pair is the sampling error of R vectors; it is not estimated.  Plain numbers: not differentiable."""
+    from .operators import SpinSectorLadder, SpinSectorOperator
+    from .spectral import _spin_step, _weight_parts
+    step = _spin_step(channel)
+    L, bonds, c, sectors, jz_sum, hz_sum, device = _spin_model(L, bonds, couplings, sectors, device)
+    parts = [p.detach().cpu() for p in _weight_parts(weights)]
+    if any(tuple(p.shape) != (L,) or not bool(torch.isfinite(p).all()) for p in parts):
+        raise ValueError("weights must be %d finite site weights: a real vector, a (re, im) pair or a complex tensor" % L)
+    betas = torch.as_tensor(betas, dtype=F64).detach().cpu().reshape(-1)
+    if betas.numel() < 1 or not bool(torch.isfinite(betas).all()) or bool((betas < 0).any()) or bool((betas[1:] < betas[:-1]).any()):
+        raise ValueError("betas must be finite, >= 0 and ascending")
+    dt, steps, R = float(dt), int(steps), int(R)
+    if not (dt > 0 and math.isfinite(dt)):
+        raise ValueError("thermal_dynamics needs a finite dt > 0, got %r" % (dt,))
+    if steps < 0:
+        raise ValueError("thermal_dynamics needs steps >= 0, got %d" % steps)
+    if R < 1:
+        raise ValueError("thermal_dynamics needs R >= 1")
+    times = dt * torch.arange(steps + 1, dtype=F64)
+    on_device = [None]
+
+    def operator(ndown):
+        if on_device[0] is None:
+            on_device[0] = c.to(device)
+        return SpinSectorOperator(L, bonds, on_device[0], ndown, device)
+
+    def spectrum(ndown, op):
+        """(theta, V) of a side of a dense pair: the closed energy of an edge sector, host ``eigh`` otherwise"""
+        if ndown in (0, L):
+            return torch.tensor([jz_sum + (hz_sum if ndown == 0 else -hz_sum)], dtype=F64), torch.ones((1, 1), dtype=F64)
+        return torch.linalg.eigh(_dense_sector_matrix(op))
+
+    out = []
+    for ndown in sectors:
+        other = ndown + step
+        if not 0 <= other <= L:
+            out.append(_dense_pair_dynamics(spectrum(ndown, None), None, (), betas, times))
+            continue
+        edge = ndown in (0, L) or other in (0, L)
+        src = None if ndown in (0, L) else operator(ndown)
+        dst = src if step == 0 else (None if other in (0, L) else operator(other))
+        if edge or max(math.comb(L, ndown), math.comb(L, other)) <= int(dense_below):
+            spec_src = spectrum(ndown, src)
+            spec_dst = spec_src if step == 0 else spectrum(other, dst)
+            maps = [_dense_ladder_matrix(L, ndown, step, p) for p in parts]
+            out.append(_dense_pair_dynamics(spec_src, spec_dst, maps, betas, times))
+        else:
+            lad = SpinSectorLadder(src, dst)
+            out.append(_tpq_pair_dynamics(src, dst, lad, parts, betas, dt, steps, R, seed, tol))
+            del lad
+        del src, dst
+    logw = torch.stack([p[0] for p in out])                                 # [sectors, B]
+    logZ = torch.logsumexp(logw, dim=0)
+    prob = torch.exp(logw - logZ)
+    correlation = sum(prob[s][:, None] * out[s][1] for s in range(len(out)))
+    return ThermalDynamics(betas, times, logZ, correlation)
 
 
 class GrandCanonicalEnsemble:
