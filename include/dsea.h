@@ -1005,7 +1005,7 @@ int dsea_hubbard_ladder_forms(int L, int nup_src, int ndn_src, int species, int 
  * zeroed, its entries alphas[i >= s, j] and betas[i >= s - 1, j] are 0, and the other columns go on; steps[j] = k otherwise.
  * Every reduction runs in fixed order (no floating-point atomics): identical calls return identical bits.  scratch:
  * caller-owned, dsea_op_sector_block_lanczos_scratch_doubles(L, ndown, R) = 64 + 2 R min(4096, ceil(n / 256)) doubles (enough
- * for every grid cap). */
+ * for every grid cap).  After k steps Q_k lies in W for odd k and in Q for even k, Q_{k-1} in the other array. */
 int dsea_op_sector_block_apply(dsea_op_t op, int R, const double *X, double *Y, void *stream);
 int dsea_op_sector_block_lanczos_scratch_doubles(int L, int ndown, int R, int64_t *out);
 int dsea_op_sector_block_lanczos(dsea_op_t op, int R, int k, double *Q /* [n,R] in: start block, any norms; overwritten */,

@@ -56,7 +56,7 @@ def block_lanczos(L, ndown, bonds, p, Phi, k, dtype=np.float64):
     beta = np.sqrt(norm2)
     alive = beta > 0
     steps[~alive] = 0
-    scale = np.zeros(R, dtype=dtype)
+    scale = np.where(alive, beta, dtype(0.0))          # (beta_0 = |phi| counts among the earlier betas, as in k_sblock_finish)
     safe = np.where(alive, beta, dtype(1.0))
     Q = np.where(alive, Phi / safe, dtype(0.0))
     prev = np.zeros_like(Q)
