@@ -2299,4 +2299,58 @@ int dsea_hubbard_ladder_forms(int L, int nup_src, int ndn_src, int species, int 
   return check_launch();
 }
 
+// what the two block Hubbard ladder entries refuse with DSEA_ERR_ARG besides their own blocks: everything
+// dsea_hubbard_ladder_apply refuses, and a width outside {1, 2, 4, 8}
+static inline bool hubbard_ladder_block_args_ok(int L, int nup_src, int ndn_src, int species, int step, int R, int grid_log2,
+                                                const void* weights_dev, const void* states_dst, const void* lo_rank_src,
+                                                const void* hi_base_src) {
+  int64_t n_src, n_dst, n_dn_src, n_dn_dst;
+  return hubbard_ladder_sizes(L, nup_src, ndn_src, species, step, &n_src, &n_dst, &n_dn_src, &n_dn_dst) &&
+         (grid_log2 == 0 || (grid_log2 >= 6 && grid_log2 <= 12)) && block_width_ok(R) && weights_dev && states_dst && lo_rank_src &&
+         hi_base_src;
+}
+
+int dsea_hubbard_ladder_block_apply(int L, int nup_src, int ndn_src, int species, int step, int R, const double* weights_dev,
+                                    const int64_t* states_dst, const int32_t* lo_rank_src, const int32_t* hi_base_src,
+                                    const double* X, double* Y, int grid_log2, void* stream) {
+  REQUIRE(hubbard_ladder_block_args_ok(L, nup_src, ndn_src, species, step, R, grid_log2, weights_dev, states_dst, lo_rank_src,
+                                       hi_base_src) &&
+              X && Y && (step == 0 || X != Y),
+          DSEA_ERR_ARG);
+  REQUIRE(aligned16(X) && aligned16(Y), DSEA_ERR_ALIGN);
+  if (launch_hubbard_ladder_block(L, nup_src, ndn_src, species, step, R, weights_dev,
+                                  reinterpret_cast<const uint64_t*>(states_dst), reinterpret_cast<const uint32_t*>(lo_rank_src),
+                                  reinterpret_cast<const uint32_t*>(hi_base_src), X, Y, grid_log2,
+                                  static_cast<hipStream_t>(stream)) != 0)
+    return DSEA_ERR_ARG;
+  return check_launch();
+}
+
+int dsea_hubbard_ladder_block_dots_scratch_doubles(int L, int nup_src, int ndn_src, int species, int step, int R, int64_t* out) {
+  int64_t n_src, n_dst, n_dn_src, n_dn_dst;
+  REQUIRE(out && hubbard_ladder_sizes(L, nup_src, ndn_src, species, step, &n_src, &n_dst, &n_dn_src, &n_dn_dst) &&
+              block_width_ok(R),
+          DSEA_ERR_ARG);
+  *out = hubbard_ladder_block_dots_scratch_doubles(n_dst, R);
+  return DSEA_OK;
+}
+
+int dsea_hubbard_ladder_block_dots(int L, int nup_src, int ndn_src, int species, int step, int R, const double* weights_dev,
+                                   const int64_t* states_dst, const int32_t* lo_rank_src, const int32_t* hi_base_src,
+                                   const double* Lft, const double* X, double* out_dev, double* scratch, int grid_log2,
+                                   void* stream) {
+  REQUIRE(hubbard_ladder_block_args_ok(L, nup_src, ndn_src, species, step, R, grid_log2, weights_dev, states_dst, lo_rank_src,
+                                       hi_base_src) &&
+              Lft && X && out_dev && scratch,
+          DSEA_ERR_ARG);
+  REQUIRE(aligned16(Lft) && aligned16(X), DSEA_ERR_ALIGN);
+  if (launch_hubbard_ladder_block_dots(L, nup_src, ndn_src, species, step, R, weights_dev,
+                                       reinterpret_cast<const uint64_t*>(states_dst),
+                                       reinterpret_cast<const uint32_t*>(lo_rank_src),
+                                       reinterpret_cast<const uint32_t*>(hi_base_src), Lft, X, out_dev, scratch, grid_log2,
+                                       static_cast<hipStream_t>(stream)) != 0)
+    return DSEA_ERR_ARG;
+  return check_launch();
+}
+
 }  // extern "C"

@@ -1,6 +1,7 @@
 // dsea_hubbard_ladder.hip -- linear maps between two particle-number sectors of the Hubbard space of the same L sites
 // (docs/design/25-hubbard-ladder.md): the ladder k_hubbard_ladder<SPECIES, STEP>, its site forms
-// k_hubbard_ladder_forms<SPECIES, STEP> (+ k_hubbard_ladder_forms_reduce), and their launchers.
+// k_hubbard_ladder_forms<SPECIES, STEP> (+ k_hubbard_ladder_forms_reduce), the block forms k_hubbard_ladder_block<SPECIES, STEP, R>
+// and k_hubbard_ladder_block_dots<SPECIES, STEP, R> (docs/design/37-hubbard-finite-temperature-dynamics.md), and their launchers.
 //
 // Conventions of docs/design/19-hubbard.md: bit i of the word u is the occupation of (i, up), bit i of d that of (i, dn);
 // |u, d> = (prod_{i in u, ascending} c+_{i up}) (prod_{j in d, ascending} c+_{j dn}) |0>; row r = ru * n_dn + rd.  With
@@ -25,6 +26,7 @@
 
 #include "dsea_internal.h"
 #include "dsea_device.h"
+#include "dsea_block.h"
 
 namespace dsea {
 
@@ -223,6 +225,147 @@ __global__ __launch_bounds__(256) void k_hubbard_ladder_forms_reduce(const doubl
   if (threadIdx.x == 0) out[blockIdx.x] = tot;
 }
 
+// ---- the block forms (docs/design/37-hubbard-finite-temperature-dynamics.md): the map and its column dots on blocks fp64
+// [n, R] row-major, R in {1, 2, 4, 8} (dsea_block.h).  The row walk is that of k_hubbard_ladder; what changes is that a
+// contributing site costs one table read and one block_load<R> of the source row for all R columns.  The helpers are written
+// apart from the single-vector ones above (whose chunk is a macro), so that those keep their instructions.
+namespace {
+// sites in flight per thread: R * chunk doubles of gathered rows are live beside sum[R] (and acc[R] in the dots)
+template <int R>
+constexpr int hladder_block_chunk() {
+  return R <= 2 ? 8 : (R == 4 ? 4 : 2);
+}
+
+// the partner rows of sites k0 .. k0 + CH - 1 of one group: hladder_lookups and hladder_rows with the chunk as a template
+// argument, DSEA_HLADDER_NO_ROW (and no table read) for a site that does not contribute or lies past the group's end
+template <int SPECIES, int STEP, int CH>
+__device__ __forceinline__ void hladder_block_rows(uint32_t (&rw)[CH], uint64_t w, bool have, int k0, int end, int base,
+                                                   uint32_t word, uint32_t other, uint32_t mul, uint32_t add,
+                                                   const uint32_t* __restrict__ table) {
+#pragma unroll
+  for (int e = 0; e < CH; ++e) {
+    const int i = k0 + e;
+    const bool on = have && i < end && hladder_qualifies<STEP>(w, i);   // (i < 40: the shifts are defined)
+    rw[e] = DSEA_HLADDER_NO_ROW;
+    if (on) {
+      const uint32_t rank = other + table[word ^ (1u << (i - base))];
+      rw[e] = SPECIES == 0 ? rank * mul + add : rank + add;
+    }
+  }
+}
+
+// one group of sites [base, end) of one row: sum[j] = fma(+-cw[i], X[partner_i, j], sum[j]) for every site of the group in
+// ascending order (X[partner_i, :] = 0 for a site that does not contribute: the single-vector kernel adds the same zero
+// product).  The table reads of chunk c + 1 are issued before the gathers of chunk c are consumed.
+template <int SPECIES, int STEP, int R>
+__device__ __forceinline__ void hladder_block_group(uint64_t w, bool have, int base, int end, uint32_t word, uint32_t other,
+                                                    uint32_t mul, uint32_t add, const uint32_t* __restrict__ table,
+                                                    const double* __restrict__ X, const double (&cw)[DSEA_SECTOR_MAX_L],
+                                                    uint32_t& par, double (&sum)[R]) {
+  constexpr int CH = hladder_block_chunk<R>();
+  uint32_t rwA[CH], rwB[CH];
+  hladder_block_rows<SPECIES, STEP, CH>(rwA, w, have, base, end, base, word, other, mul, add, table);
+  for (int k0 = base; k0 < end; k0 += CH) {
+    double xv[CH][R];
+#pragma unroll
+    for (int e = 0; e < CH; ++e) {
+#pragma unroll
+      for (int j = 0; j < R; ++j) xv[e][j] = 0.0;
+      if (rwA[e] != DSEA_HLADDER_NO_ROW) block_load<R>(xv[e], X, (int64_t)rwA[e]);
+    }
+    hladder_block_rows<SPECIES, STEP, CH>(rwB, w, have, k0 + CH, end, base, word, other, mul, add, table);
+#pragma unroll
+    for (int e = 0; e < CH; ++e) {
+      if (k0 + e < end) {                          // (the same for every lane)
+        const double c = hladder_signed(cw[k0 + e], par);
+#pragma unroll
+        for (int j = 0; j < R; ++j) sum[j] = fma(c, xv[e][j], sum[j]);
+        par ^= hladder_bit(w, k0 + e);
+      }
+      rwA[e] = rwB[e];
+    }
+  }
+}
+
+// sum[j] = (S(c) X)[r, j] of the row r (row n - 1 for a thread without a row): column j in the operations and the order of
+// k_hubbard_ladder on column j
+template <int SPECIES, int STEP, int R>
+__device__ __forceinline__ void hladder_block_row(const HubbardLadderParams& p, const double (&cw)[DSEA_SECTOR_MAX_L],
+                                                  uint64_t lomask, int64_t r, bool have, const double* __restrict__ X,
+                                                  double (&sum)[R]) {
+  const uint32_t rr = (uint32_t)(have ? r : p.n - 1);
+  const HubbardLadderRow q = hladder_row(rr, p.n_dn_dst);
+  const uint64_t w = p.states[SPECIES == 0 ? q.ru : q.rd];
+  if constexpr (STEP == 0) {
+    double xr[R];
+    block_load<R>(xr, X, (int64_t)rr);
+    double diag = 0.0;
+    for (int i = 0; i < p.L; ++i) diag += hladder_bit(w, i) ? cw[i] : 0.0;
+#pragma unroll
+    for (int j = 0; j < R; ++j) sum[j] = diag * xr[j];
+  } else {
+#pragma unroll
+    for (int j = 0; j < R; ++j) sum[j] = 0.0;
+    const uint32_t wl = (uint32_t)(w & lomask), wh = (uint32_t)(w >> p.Llo);
+    const uint32_t own_hi = p.hi_base[wh], own_lo = p.lo_rank[wl];
+    const uint32_t mul = p.n_dn_src, add = SPECIES == 0 ? q.rd : q.ru * p.n_dn_src;
+    uint32_t par = p.g;                            // the parity of the particles below the site, times the sector sign
+    hladder_block_group<SPECIES, STEP, R>(w, have, 0, p.Llo, wl, own_hi, mul, add, p.lo_rank, X, cw, par, sum);
+    hladder_block_group<SPECIES, STEP, R>(w, have, p.Llo, p.L, wh, own_lo, mul, add, p.hi_base, X, cw, par, sum);
+  }
+}
+}  // namespace
+
+// Y = S(c) X.  The grid, the 256-row ranges and the thread past the last row as in k_hubbard_ladder; column j of Y equals
+// k_hubbard_ladder on column j of X bit for bit.  At STEP = 0 a thread reads its row of X before it writes that row of Y.
+template <int SPECIES, int STEP, int R>
+__global__ __launch_bounds__(256) void k_hubbard_ladder_block(HubbardLadderParams p, const double* __restrict__ X,
+                                                              double* __restrict__ Y) {
+  __shared__ double cw[DSEA_SECTOR_MAX_L];
+  const int64_t n = p.n;
+  for (int c = threadIdx.x; c < p.L; c += 256) cw[c] = p.c[c];
+  __syncthreads();
+  const uint64_t lomask = (1ull << p.Llo) - 1;
+  for (int64_t row0 = (int64_t)blockIdx.x * 256; row0 < n; row0 += (int64_t)gridDim.x * 256) {
+    const int64_t r = row0 + threadIdx.x;
+    const bool have = r < n;
+    double sum[R];
+    hladder_block_row<SPECIES, STEP, R>(p, cw, lomask, r, have, X, sum);
+    if (have) block_store<R>(Y, r, sum);
+  }
+}
+
+// The column dots d[j] = sum_r' Lft[r', j] (S(c) X)[r', j] without the product block: the same rows and the same sum[j], the
+// row of Lft read after the last chunk's gathers are consumed, one accumulator per column and thread over the rows it walks
+// (a thread without a row adds nothing), then block_partials into scratch[j * gridDim.x + block].
+// k_hubbard_ladder_forms_reduce with R blocks closes them.  No atomics.
+template <int SPECIES, int STEP, int R>
+__global__ __launch_bounds__(256) void k_hubbard_ladder_block_dots(HubbardLadderParams p, const double* __restrict__ Lft,
+                                                                   const double* __restrict__ X, double* __restrict__ scratch) {
+  __shared__ double cw[DSEA_SECTOR_MAX_L];
+  __shared__ double sm[R][4];
+  const int64_t n = p.n;
+  for (int c = threadIdx.x; c < p.L; c += 256) cw[c] = p.c[c];
+  __syncthreads();
+  const uint64_t lomask = (1ull << p.Llo) - 1;
+  double acc[R];
+#pragma unroll
+  for (int j = 0; j < R; ++j) acc[j] = 0.0;
+  for (int64_t row0 = (int64_t)blockIdx.x * 256; row0 < n; row0 += (int64_t)gridDim.x * 256) {
+    const int64_t r = row0 + threadIdx.x;
+    const bool have = r < n;
+    double sum[R];
+    hladder_block_row<SPECIES, STEP, R>(p, cw, lomask, r, have, X, sum);
+    if (have) {
+      double l[R];
+      block_load<R>(l, Lft, r);
+#pragma unroll
+      for (int j = 0; j < R; ++j) acc[j] = fma(l[j], sum[j], acc[j]);
+    }
+  }
+  block_partials<R>(acc, sm, scratch);
+}
+
 // the rows and the down strides of the two sectors; false when species is outside {0, 1}, step outside -1 .. 1, or either
 // sector outside the limits of hubbard_sizes (host arithmetic only)
 bool hubbard_ladder_sizes(int L, int nup_src, int ndn_src, int species, int step, int64_t* n_src, int64_t* n_dst,
@@ -310,6 +453,48 @@ int launch_hubbard_ladder_forms(int L, int nup_src, int ndn_src, int species, in
                        scratch);
   });
   hipLaunchKernelGGL(k_hubbard_ladder_forms_reduce, dim3((unsigned)L), dim3(256), 0, st, scratch, nblk, out);
+  return 0;
+}
+
+// partials that launch_hubbard_ladder_block_dots may write at any grid cap
+int64_t hubbard_ladder_block_dots_scratch_doubles(int64_t n_dst, int R) {
+  int64_t nblk = (n_dst + 255) / 256;
+  if (nblk > DSEA_MAX_TFIM_BLOCKS) nblk = DSEA_MAX_TFIM_BLOCKS;
+  return (int64_t)R * nblk;
+}
+
+int launch_hubbard_ladder_block(int L, int nup_src, int ndn_src, int species, int step, int R, const double* c,
+                                const uint64_t* states_dst, const uint32_t* lo_rank_src, const uint32_t* hi_base_src,
+                                const double* X, double* Y, int grid_log2, hipStream_t st) {
+  HubbardLadderParams p;
+  if (!c || !hubbard_ladder_params(L, nup_src, ndn_src, species, step, grid_log2, c, states_dst, lo_rank_src, hi_base_src, &p))
+    return -1;
+  const dim3 grid((unsigned)hubbard_ladder_blocks(p.n, grid_log2));
+  hubbard_ladder_dispatch(species, step, [&](auto sp, auto stp) {
+    dispatch_block_width(R, [&](auto w) {
+      hipLaunchKernelGGL((k_hubbard_ladder_block<decltype(sp)::value, decltype(stp)::value, decltype(w)::value>), grid, dim3(256),
+                         0, st, p, X, Y);
+    });
+  });
+  return 0;
+}
+
+int launch_hubbard_ladder_block_dots(int L, int nup_src, int ndn_src, int species, int step, int R, const double* c,
+                                     const uint64_t* states_dst, const uint32_t* lo_rank_src, const uint32_t* hi_base_src,
+                                     const double* Lft, const double* X, double* out, double* scratch, int grid_log2,
+                                     hipStream_t st) {
+  HubbardLadderParams p;
+  if (!c || !hubbard_ladder_params(L, nup_src, ndn_src, species, step, grid_log2, c, states_dst, lo_rank_src, hi_base_src, &p))
+    return -1;
+  const int nblk = hubbard_ladder_blocks(p.n, grid_log2);
+  const dim3 grid((unsigned)nblk);
+  hubbard_ladder_dispatch(species, step, [&](auto sp, auto stp) {
+    dispatch_block_width(R, [&](auto w) {
+      hipLaunchKernelGGL((k_hubbard_ladder_block_dots<decltype(sp)::value, decltype(stp)::value, decltype(w)::value>), grid,
+                         dim3(256), 0, st, p, Lft, X, scratch);
+    });
+  });
+  hipLaunchKernelGGL(k_hubbard_ladder_forms_reduce, dim3((unsigned)R), dim3(256), 0, st, scratch, nblk, out);
   return 0;
 }
 

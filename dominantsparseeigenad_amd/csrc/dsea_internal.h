@@ -580,6 +580,18 @@ int launch_hubbard_ladder(int L, int nup_src, int ndn_src, int species, int step
 int launch_hubbard_ladder_forms(int L, int nup_src, int ndn_src, int species, int step, const uint64_t* states_dst,
                                 const uint32_t* lo_rank_src, const uint32_t* hi_base_src, const double* v1, const double* v2,
                                 double* out, double* scratch, int grid_log2, hipStream_t st);
+// The block forms (docs/design/37-hubbard-finite-temperature-dynamics.md): Y = S(c) X for a block fp64 [n, R] row-major, R in
+// {1, 2, 4, 8} (column j bit for bit launch_hubbard_ladder on column j), and out[j] = sum_r' Lft[r', j] (S(c) X)[r', j] through
+// per-block partials in the caller's scratch (hubbard_ladder_block_dots_scratch_doubles doubles).  The same -1 as above; the
+// caller has checked R.
+int64_t hubbard_ladder_block_dots_scratch_doubles(int64_t n_dst, int R);
+int launch_hubbard_ladder_block(int L, int nup_src, int ndn_src, int species, int step, int R, const double* c,
+                                const uint64_t* states_dst, const uint32_t* lo_rank_src, const uint32_t* hi_base_src,
+                                const double* X, double* Y, int grid_log2, hipStream_t st);
+int launch_hubbard_ladder_block_dots(int L, int nup_src, int ndn_src, int species, int step, int R, const double* c,
+                                     const uint64_t* states_dst, const uint32_t* lo_rank_src, const uint32_t* hi_base_src,
+                                     const double* Lft, const double* X, double* out, double* scratch, int grid_log2,
+                                     hipStream_t st);
 // dsea_sector_block.hip (the bond-list sector Hamiltonian on a block of R vectors, docs/design/27-finite-temperature.md): a block is
 // fp64 [n, R] row-major, R in {1, 2, 4, 8}.  launch_sector_block_apply: Y = H X (column j bit for bit the single-vector mat-vec).
 // launch_sector_block_lanczos: block_lanczos_drive (below) with the file's Lanczos-step kernel as the mat-vec.  The launchers

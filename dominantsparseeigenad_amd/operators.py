@@ -962,6 +962,16 @@ class _SectorLadderBase:
             raise ValueError("%s must live on %s, got %s" % (what, self.device, v.device))
         return v
 
+    def _block(self, X, n, what):
+        if not torch.is_tensor(X) or X.dim() != 2 or X.shape[0] != n or X.shape[1] < 1:
+            raise ValueError("%s must be a tensor of shape (%d, R) with R >= 1, got %r"
+                             % (what, n, tuple(X.shape) if torch.is_tensor(X) else type(X).__name__))
+        if X.device != self.device:
+            raise ValueError("%s must live on %s, got %s" % (what, self.device, X.device))
+        if X.is_complex():
+            raise ValueError("%s must be real: the real and the imaginary part are columns of one real block" % what)
+        return X.detach().to(F64)
+
     def __call__(self, c, x):
         """the vector sum_i c_i O_i x of the destination sector, differentiable in c and in x"""
         return _LadderApply.apply(self._weights(c), self._vector(x, self.n_src, "x"), self)
@@ -1054,16 +1064,6 @@ class SpinSectorLadder(_SectorLadderBase):
                                                c_void_p(scratch.data_ptr()), self._grid[0], engine._stream(self.device)),
                   "dsea_sector_ladder_forms")
         return out
-
-    def _block(self, X, n, what):
-        if not torch.is_tensor(X) or X.dim() != 2 or X.shape[0] != n or X.shape[1] < 1:
-            raise ValueError("%s must be a tensor of shape (%d, R) with R >= 1, got %r"
-                             % (what, n, tuple(X.shape) if torch.is_tensor(X) else type(X).__name__))
-        if X.device != self.device:
-            raise ValueError("%s must live on %s, got %s" % (what, self.device, X.device))
-        if X.is_complex():
-            raise ValueError("%s must be real: the real and the imaginary part are columns of one real block" % what)
-        return X.detach().to(F64)
 
     def apply_block(self, c, X):
         """sum_i c_i O_i X for a device tensor X of shape (n_src, R), any R >= 1: (n_dst, R), in blocks of 8, 4, 2 and 1 columns
@@ -2011,6 +2011,64 @@ class HubbardLadder(_SectorLadderBase):
                                                 c_void_p(hi_base.data_ptr()), c_void_p(v1.data_ptr()), c_void_p(v2.data_ptr()),
                                                 c_void_p(out.data_ptr()), c_void_p(scratch.data_ptr()), self._grid[0],
                                                 engine._stream(self.device)), "dsea_hubbard_ladder_forms")
+        return out
+
+    def apply_block(self, w, X):
+        """sum_i w_i O_i X for a device tensor X of shape (n_src, R), any R >= 1: (n_dst, R), in blocks of 8, 4, 2 and 1 columns
+        (dsea_hubbard_ladder_block_apply, docs/design/37-hubbard-finite-temperature-dynamics.md).  Column j equals
+        ``lad(w, X[:, j])`` bit for bit; a row's division, state word and table reads are made once for all columns of a block.
+        Detached, not differentiable."""
+        from .chebyshev import _aligned_piece
+        from .thermal import block_pieces
+        w = self._weights(w)
+        X = self._block(X, self.n_src, "X")
+        w = engine.as_vector(w.detach(), self.L)
+        states, lo_rank, hi_base = self._tables
+        run = _lib.load().dsea_hubbard_ladder_block_apply
+        out = []
+        with torch.cuda.device(self.device):
+            for first, width in block_pieces(X.shape[1]):
+                Xp = _aligned_piece(X, first, width)
+                Yp = torch.empty((self.n_dst, width), dtype=F64, device=self.device)
+                check(run(*self._sector_args(), width, c_void_p(w.data_ptr()), c_void_p(states.data_ptr()),
+                          c_void_p(lo_rank.data_ptr()), c_void_p(hi_base.data_ptr()), c_void_p(Xp.data_ptr()),
+                          c_void_p(Yp.data_ptr()), self._grid[0], engine._stream(self.device)),
+                      "dsea_hubbard_ladder_block_apply")
+                out.append(Yp)
+        return out[0] if len(out) == 1 else torch.cat(out, dim=1)
+
+    def block_dots(self, w, Lft, X):
+        """d[j] = sum_r Lft[r, j] (sum_i w_i O_i X)[r, j] as a device tensor [R], for Lft (n_dst, R) and X (n_src, R), any R >= 1:
+        the column dots of ``Lft`` with ``apply_block(w, X)`` without the product block (dsea_hubbard_ladder_block_dots, in
+        blocks of 8, 4, 2 and 1 columns; fixed-order sums, identical calls return identical bits).  Detached, not
+        differentiable."""
+        from .chebyshev import _aligned_piece
+        from .thermal import block_pieces
+        w = self._weights(w)
+        X = self._block(X, self.n_src, "X")
+        Lft = self._block(Lft, self.n_dst, "Lft")
+        if Lft.shape[1] != X.shape[1]:
+            raise ValueError("Lft and X must have the same number of columns, got %d and %d" % (Lft.shape[1], X.shape[1]))
+        w = engine.as_vector(w.detach(), self.L)
+        lib = _lib.load()
+        states, lo_rank, hi_base = self._tables
+        out = torch.empty(X.shape[1], dtype=F64, device=self.device)
+        with torch.cuda.device(self.device):
+            for first, width in block_pieces(X.shape[1]):
+                need = c_int64()
+                check(lib.dsea_hubbard_ladder_block_dots_scratch_doubles(*self._sector_args(), width, byref(need)),
+                      "dsea_hubbard_ladder_block_dots_scratch_doubles")
+                scratch = torch.empty(need.value, dtype=F64, device=self.device)
+                Xp, Lp = _aligned_piece(X, first, width), _aligned_piece(Lft, first, width)
+                piece = torch.empty(width, dtype=F64, device=self.device)
+                check(lib.dsea_hubbard_ladder_block_dots(*self._sector_args(), width, c_void_p(w.data_ptr()),
+                                                         c_void_p(states.data_ptr()), c_void_p(lo_rank.data_ptr()),
+                                                         c_void_p(hi_base.data_ptr()), c_void_p(Lp.data_ptr()),
+                                                         c_void_p(Xp.data_ptr()), c_void_p(piece.data_ptr()),
+                                                         c_void_p(scratch.data_ptr()), self._grid[0],
+                                                         engine._stream(self.device)),
+                      "dsea_hubbard_ladder_block_dots")
+                out[first:first + width] = piece
         return out
 
 

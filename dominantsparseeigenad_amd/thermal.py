@@ -25,6 +25,9 @@ through the three-term recurrence at once as one [n, R] block, on the block mat-
                                                        sigma^-_i or sigma^+_i, and its spectrum S(q, omega; T): those states stepped
                                                        in real time, the block ladder map in between
                                                        (docs/design/35-finite-temperature-dynamics.md)
+    hubbard_thermal_dynamics(L, bonds, couplings, weights, channel, betas, mus, dt, steps, ...)   the same for the Hubbard model
+                                                       and A = sum_i w_i c_{i s}, c+_{i s}, n_i or 2 S^z_i at every (beta, mu): the
+                                                       one-particle A(k, omega; T) (docs/design/37-hubbard-finite-temperature-dynamics.md)
 
 Plain host float64 numbers: nothing here is differentiable.
 """
@@ -500,19 +503,25 @@ class ThermalDynamics:
         with C(-t) = C(t)^* (which holds in the exact trace), so that a pole of C at the excitation energy eps becomes a
         Gaussian of width ``eta`` at omega = eps.  THE CALLER picks dt and K: eta t_K >= 8, so that the window has decayed where
         the record ends, and pi / dt well above the band width, so that the trapezoid sum does not alias."""
-        eta = float(eta)
-        if not (eta > 0 and math.isfinite(eta)):
-            raise ValueError("spectrum needs a finite eta > 0, got %r" % (eta,))
-        K = self.times.numel() - 1
-        if K < 1:
-            raise ValueError("spectrum needs at least one time step")
-        omega = torch.as_tensor(omega, dtype=F64).detach().cpu().reshape(-1)
-        t = self.times
-        w = torch.full((K + 1,), float(t[1] - t[0]), dtype=F64)
-        w[0] = w[-1] = 0.5 * float(t[1] - t[0])
-        window = w * torch.exp(-0.5 * (eta * t) ** 2)
-        phase = torch.exp(torch.complex(torch.zeros(omega.numel(), K + 1, dtype=F64), omega[:, None] * t[None, :]))
-        return (torch.einsum("wk,bk->bw", phase * window, self.correlation).real / math.pi).contiguous()
+        return _windowed_spectrum(self.times, self.correlation, omega, eta)
+
+
+def _windowed_spectrum(times, correlation, omega, eta):
+    """the Gaussian-windowed transform of ``ThermalDynamics.spectrum`` for a record ``correlation`` [rows, K + 1] at ``times``:
+    [rows, len omega]"""
+    eta = float(eta)
+    if not (eta > 0 and math.isfinite(eta)):
+        raise ValueError("spectrum needs a finite eta > 0, got %r" % (eta,))
+    K = times.numel() - 1
+    if K < 1:
+        raise ValueError("spectrum needs at least one time step")
+    omega = torch.as_tensor(omega, dtype=F64).detach().cpu().reshape(-1)
+    t = times
+    w = torch.full((K + 1,), float(t[1] - t[0]), dtype=F64)
+    w[0] = w[-1] = 0.5 * float(t[1] - t[0])
+    window = w * torch.exp(-0.5 * (eta * t) ** 2)
+    phase = torch.exp(torch.complex(torch.zeros(omega.numel(), K + 1, dtype=F64), omega[:, None] * t[None, :]))
+    return (torch.einsum("wk,bk->bw", phase * window, correlation).real / math.pi).contiguous()
 
 
 def _dense_ladder_matrix(L, ndown_src, step, c):
@@ -552,33 +561,40 @@ def _dense_pair_dynamics(spec_src, spec_dst, maps, betas, times):
     return logsum, torch.einsum("bn,kn->bk", prob.to(torch.complex128), unit(theta) * G)
 
 
-def _tpq_pair_dynamics(src, dst, lad, parts, betas, dt, steps, R, seed, tol):
-    """the same pair from the thermal pure quantum states of ``_tpq_states`` on the source: per beta and per real part c of the
-    weights, b_0 = Phi and a_0 = S(c) Phi (``apply_block``) are stepped by ``time_evolve`` over dt on the source and on the
-    destination, and at every step two ``block_dots`` calls on the (re | im) blocks give
-    C_j(t_k) = <S(c) b_k,j | a_k,j> = [d(a_re, b_re) + d(a_im, b_im)] + i [d(a_im, b_re) - d(a_re, b_im)]"""
+def _tpq_block_dynamics(src, dst, apply, dots, parts, betas, dt, steps, R, seed, tol):
+    """(log weights [B], C [B, K + 1]) of a sector pair from the thermal pure quantum states of ``_tpq_states`` on ``src``, for a
+    map given as ``apply(c, X)`` (the block A X on the device) and ``dots(c, Lft, X)`` (the host column dots of Lft with A X):
+    per beta and per real part c of the weights, b_0 = Phi and a_0 = A Phi are stepped by ``time_evolve`` over dt on the source
+    and on the destination, and at every step two ``dots`` calls on the (re | im) blocks give
+    C_j(t_k) = <A b_k,j | a_k,j> = [d(a_re, b_re) + d(a_im, b_im)] + i [d(a_im, b_re) - d(a_re, b_im)]"""
     from .chebyshev import spectral_bounds, time_evolve
     bounds_src = spectral_bounds(src, seed=seed)
     bounds_dst = bounds_src if dst is src else spectral_bounds(dst, seed=seed)
-    parts = [c.to(lad.device) for c in parts]
     logweights, rows = [], []
     for Phi, _, _, w, logweight in _tpq_states(src, betas, R, seed, tol, bounds_src):
         Cj = torch.zeros((steps + 1, R), dtype=torch.complex128)
         for c in parts:
             b = torch.complex(Phi, torch.zeros_like(Phi))
-            a0 = lad.apply_block(c, Phi)
+            a0 = apply(c, Phi)
             a = torch.complex(a0, torch.zeros_like(a0))
             for k in range(steps + 1):
                 if k:
                     b = time_evolve(src, b, dt, bounds_src, tol)
                     a = time_evolve(dst, a, dt, bounds_dst, tol)
                 bb = torch.cat([b.real, b.imag], dim=1)
-                d1 = lad.block_dots(c, torch.cat([a.real, a.imag], dim=1), bb).cpu()
-                d2 = lad.block_dots(c, torch.cat([a.imag, a.real], dim=1), bb).cpu()
+                d1 = dots(c, torch.cat([a.real, a.imag], dim=1), bb)
+                d2 = dots(c, torch.cat([a.imag, a.real], dim=1), bb)
                 Cj[k] += torch.complex(d1[:R] + d1[R:], d2[:R] - d2[R:])
         logweights.append(logweight)
         rows.append((Cj * w).sum(dim=1) / w.sum())
     return torch.stack(logweights), torch.stack(rows)
+
+
+def _tpq_pair_dynamics(src, dst, lad, parts, betas, dt, steps, R, seed, tol):
+    """``_tpq_block_dynamics`` for one ladder: ``lad.apply_block`` and ``lad.block_dots``"""
+    parts = [c.to(lad.device) for c in parts]
+    return _tpq_block_dynamics(src, dst, lad.apply_block, lambda c, Lft, X: lad.block_dots(c, Lft, X).cpu(), parts, betas, dt,
+                               steps, R, seed, tol)
 
 
 def thermal_dynamics(L, bonds, couplings, weights, channel, betas, dt, steps, R=8, seed=0, dense_below=256, sectors=None,
@@ -895,3 +911,186 @@ def hubbard_density_of_states(L, bonds, couplings, M, R=8, seed=0, dense_below=2
     for part, _, _ in entries[1:]:
         total = total + part
     return total
+
+
+class HubbardThermalDynamics:
+    """What ``hubbard_thermal_dynamics`` returns, host tensors: ``betas`` [B], ``mus`` [M], ``times`` [K + 1] with t_k = k dt,
+    ``logXi`` [B, M] and ``correlation`` [B, M, K + 1] (complex128), C(t_k; beta, mu) = tr[e^{-beta (H - mu N)} A^T(t_k) A] / Xi."""
+
+    def __init__(self, betas, mus, times, logXi, correlation):
+        self.betas, self.mus, self.times, self.logXi, self.correlation = betas, mus, times, logXi, correlation
+
+    def static(self):
+        """C(0).real [B, M]: the equal-time correlation <A^T A>"""
+        return self.correlation[:, :, 0].real.clone()
+
+    def spectrum(self, omega, eta, reflected=False):
+        """[B, M, len omega]: the Gaussian-windowed transform of ``ThermalDynamics.spectrum`` at every (beta, mu), with the same
+        duties of the caller towards dt and K.  ``reflected=True`` evaluates it at -omega, which places a removal channel at
+        omega = E_n - E_m <= 0 of the added-particle axis: ``cdag.spectrum(omega, eta) + c.spectrum(omega, eta, reflected=True)``
+        is the one-particle A(omega), as ``SpectralMeasure.reflected`` gives it at T = 0."""
+        omega = torch.as_tensor(omega, dtype=F64).detach().cpu().reshape(-1)
+        B, M, K1 = self.correlation.shape
+        flat = _windowed_spectrum(self.times, self.correlation.reshape(B * M, K1), -omega if reflected else omega, eta)
+        return flat.reshape(B, M, -1)
+
+
+def _dense_hubbard_ladder_matrix(L, nup_src, ndn_src, species, step, w):
+    """the n_dst x n_src host matrix of sum_i w_i c+_{i s} (step +1), c_{i s} (step -1) or n_{i s} (step 0) of the species
+    ``species`` ("up" or "dn") from the sector (nup_src, ndn_src), rows r = ru * n_dn + rd on ``sector_states`` of both species
+    (edge sectors included): the running parity of the moving species' word below the site, and the sector sign (-1)^nup_src
+    of a down operator with step +-1 (it stands right of all up operators)"""
+    from .operators import sector_states
+    count = nup_src if species == "up" else ndn_src
+    src, dst = sector_states(L, count), sector_states(L, count + step)
+    A = torch.zeros((len(dst), len(src)), dtype=F64)
+    w = w.tolist()
+    if step == 0:
+        for r, word in enumerate(dst):
+            A[r, r] = sum(w[i] * ((word >> i) & 1) for i in range(L))
+    else:
+        rank = {word: r for r, word in enumerate(src)}
+        want = 1 if step > 0 else 0
+        for r, word in enumerate(dst):
+            for i in range(L):
+                if (word >> i) & 1 == want:
+                    A[r, rank[word ^ (1 << i)]] = w[i] * (1 - 2 * (bin(word & ((1 << i) - 1)).count("1") & 1))
+    if species == "up":
+        return torch.kron(A, torch.eye(math.comb(L, ndn_src), dtype=F64))
+    g = -1.0 if step != 0 and nup_src & 1 else 1.0
+    return torch.kron(torch.eye(math.comb(L, nup_src), dtype=F64), g * A)
+
+
+def hubbard_thermal_dynamics(L, bonds, couplings, weights, channel, betas, mus, dt, steps, R=8, seed=0, dense_below=256,
+                             sectors=None, edge_dense_max=4096, tol=1e-15, device=None):
+    """The finite-temperature correlation function of A = sum_i w_i O_i for the Hubbard model and the parameter order
+    [t(nb), V(nb), U(L), eps(L)] of ``hubbard_thermodynamics`` (docs/design/37-hubbard-finite-temperature-dynamics.md): a
+    ``HubbardThermalDynamics`` with
+
+        C(t_k; beta, mu) = (1 / Xi) sum_src e^{beta mu N_src} tr_src[ e^{-beta H} e^{i H t_k} A^T e^{-i H' t_k} A ],
+        Xi = sum_src e^{beta mu N_src} tr e^{-beta H},    t_k = k dt,  k = 0 .. steps
+
+    at the ascending inverse temperatures ``betas`` >= 0 and the chemical potentials ``mus``.  ``channel`` is one of
+    ``spectral.hubbard_spectral_function``: "c_up", "c_dn", "cdag_up", "cdag_dn" (one particle of that species less or more, the
+    Hamiltonian H' of the destination), "n" and "sz" (O_i = n_{i up} +- n_{i dn}, H' = H).  ``weights``: a real vector [L], a
+    ``(re, im)`` pair (``ring_momentum_weights``) or a complex tensor; for complex weights the result is the sum of the
+    correlation functions of the real and of the imaginary part (all matrices are real, so the cross terms cancel in the exact
+    trace).  ``sectors`` lists the SOURCE pairs (nup, ndn), default all (L + 1)^2.  A sector's trace does not depend on mu: every
+    mu comes from one sweep over the sectors, combined by a log-sum-exp of log weight + beta mu N_src.
+
+    A source whose destination does not exist (the count would leave 0 .. L) contributes to Xi only.  A pair whose two sides
+    are bulk (1 <= nup, ndn <= L - 1) with more than ``dense_below`` rows on either side is sampled by the R thermal pure
+    quantum states of ``thermal_correlations`` on the source (start vectors ``normal_vector(n, seed + j)``): a_0 = A |beta, j> by
+    ``HubbardLadder.apply_block``, both sides stepped by ``chebyshev.time_evolve`` over dt on one ``spectral_bounds`` interval per
+    sector, C_j(t_k) = <A b_k,j | a_k,j> by ``block_dots`` on the (re | im) blocks; "n" and "sz" apply the step-0 ladders of both
+    species and add them with the sign +-1.  A smaller pair, and every pair with an edge side (a species empty or full, which
+    ``HubbardOperator`` refuses), is exact on the host: the spectrum of a bulk side from ``apply_block`` on identity columns,
+    that of an edge side from ``one_species_matrix`` or the one frozen energy, the matrix of A from ``operators.sector_states``
+    with the fermion signs.  AN EDGE SIDE IS NOT ONE STATE: the other side of such a pair has up to L C(L, k) rows, and a pair
+    with an edge side and more than ``edge_dense_max`` rows on either side raises ``ValueError`` before any sector is computed.
+    One pair of operators is alive at a time; (a, b) and (b, a) are computed separately.  The error of a sampled pair is the
+    sampling error of R vectors; it is not estimated.  Plain numbers: not differentiable."""
+    from .operators import HubbardLadder, HubbardOperator
+    from .spectral import _HUBBARD_CHANNELS, _weight_parts
+    what = "hubbard_thermal_dynamics"
+    if channel not in _HUBBARD_CHANNELS:
+        raise ValueError("channel must be one of %s, got %r" % (", ".join(repr(c) for c in _HUBBARD_CHANNELS), channel))
+    species, step = _HUBBARD_CHANNELS[channel]
+    sign = -1.0 if channel == "sz" else 1.0
+    L, bonds, c, sectors, device = _hubbard_model(what, L, bonds, couplings, sectors, edge_dense_max, device)
+    parts = [p.detach().cpu() for p in _weight_parts(weights)]
+    if any(tuple(p.shape) != (L,) or not bool(torch.isfinite(p).all()) for p in parts):
+        raise ValueError("weights must be %d finite site weights: a real vector, a (re, im) pair or a complex tensor" % L)
+    betas = torch.as_tensor(betas, dtype=F64).detach().cpu().reshape(-1)
+    if betas.numel() < 1 or not bool(torch.isfinite(betas).all()) or bool((betas < 0).any()) or bool((betas[1:] < betas[:-1]).any()):
+        raise ValueError("betas must be finite, >= 0 and ascending")
+    mus = torch.as_tensor(mus, dtype=F64).detach().cpu().reshape(-1)
+    if mus.numel() < 1 or not bool(torch.isfinite(mus).all()):
+        raise ValueError("mus must be at least one finite chemical potential")
+    dt, steps, R = float(dt), int(steps), int(R)
+    if not (dt > 0 and math.isfinite(dt)):
+        raise ValueError("%s needs a finite dt > 0, got %r" % (what, dt))
+    if steps < 0:
+        raise ValueError("%s needs steps >= 0, got %d" % (what, steps))
+    if R < 1:
+        raise ValueError("%s needs R >= 1" % what)
+    times = dt * torch.arange(steps + 1, dtype=F64)
+    host = c.cpu()
+    rows = lambda pair: math.comb(L, pair[0]) * math.comb(L, pair[1])           # noqa: E731
+    is_edge = lambda pair: pair[0] in (0, L) or pair[1] in (0, L)              # noqa: E731
+
+    def destination(nup, ndn):
+        other = (nup + step, ndn) if species == "up" else (nup, ndn + step) if species == "dn" else (nup, ndn)
+        return other if 0 <= other[0] <= L and 0 <= other[1] <= L else None
+
+    routes = []
+    for pair in sectors:                                         # (refused before any sector is computed)
+        other = destination(*pair)
+        if other is None:
+            routes.append("none")
+        elif is_edge(pair) or is_edge(other):
+            if max(rows(pair), rows(other)) > int(edge_dense_max):
+                raise ValueError("the pair (nup, ndn) = (%d, %d) -> (%d, %d) has an edge side and is exact on the host, but a "
+                                 "side of %d rows, above edge_dense_max = %d"
+                                 % (pair + other + (max(rows(pair), rows(other)), int(edge_dense_max))))
+            routes.append("dense")
+        else:
+            routes.append("dense" if max(rows(pair), rows(other)) <= int(dense_below) else "sampled")
+    on_device = [None]
+
+    def operator(pair):
+        if on_device[0] is None:
+            on_device[0] = c.to(device)
+        return HubbardOperator(L, bonds, on_device[0], pair[0], pair[1], device)
+
+    def spectrum(pair, op):
+        """(theta, V) of a side of a dense pair, rows r = ru * n_dn + rd: ``one_species_matrix`` of an edge side (the one energy
+        when both species are frozen), host ``eigh`` of the operator's matrix otherwise"""
+        nup, ndn = pair
+        if nup in (0, L) and ndn in (0, L):
+            return one_species_matrix(L, bonds, host, nup, ndn == L).reshape(1), torch.ones((1, 1), dtype=F64)
+        if is_edge(pair):
+            count, frozen = (ndn, nup) if nup in (0, L) else (nup, ndn)
+            return torch.linalg.eigh(one_species_matrix(L, bonds, host, count, frozen == L))
+        return torch.linalg.eigh(_dense_sector_matrix(op))
+
+    def matrix(pair, w):
+        if step != 0:
+            return _dense_hubbard_ladder_matrix(L, pair[0], pair[1], species, step, w)
+        return (_dense_hubbard_ladder_matrix(L, pair[0], pair[1], "up", 0, w)
+                + sign * _dense_hubbard_ladder_matrix(L, pair[0], pair[1], "dn", 0, w))
+
+    out = []
+    for pair, route in zip(sectors, routes):
+        other = destination(*pair)
+        if route == "none":
+            out.append(_dense_pair_dynamics(spectrum(pair, None), None, (), betas, times))
+            continue
+        src = None if is_edge(pair) else operator(pair)
+        dst = src if step == 0 else (None if is_edge(other) else operator(other))
+        if route == "dense":
+            spec_src = spectrum(pair, src)
+            spec_dst = spec_src if step == 0 else spectrum(other, dst)
+            out.append(_dense_pair_dynamics(spec_src, spec_dst, [matrix(pair, p) for p in parts], betas, times))
+        else:
+            if step != 0:
+                lads, signs = [HubbardLadder(src, dst, species)], [1.0]
+            else:
+                lads, signs = [HubbardLadder(src, dst, "up"), HubbardLadder(src, dst, "dn")], [1.0, sign]
+            if len(lads) == 1:
+                apply = lads[0].apply_block
+                dots = lambda w, Lft, X: lads[0].block_dots(w, Lft, X).cpu()                              # noqa: E731
+            else:
+                apply = lambda w, X: lads[0].apply_block(w, X) + signs[1] * lads[1].apply_block(w, X)      # noqa: E731
+                dots = lambda w, Lft, X: (lads[0].block_dots(w, Lft, X)                                    # noqa: E731
+                                          + signs[1] * lads[1].block_dots(w, Lft, X)).cpu()
+            out.append(_tpq_block_dynamics(src, dst, apply, dots, [p.to(device) for p in parts], betas, dt, steps, R, seed, tol))
+            del lads, apply, dots
+        del src, dst
+    logw = torch.stack([p[0] for p in out])                                 # [sources, B]
+    N = torch.tensor([float(a + b) for a, b in sectors], dtype=F64)
+    logw = logw[:, :, None] + betas[None, :, None] * mus[None, None, :] * N[:, None, None]      # [sources, B, M]
+    logXi = torch.logsumexp(logw, dim=0)
+    prob = torch.exp(logw - logXi)
+    correlation = sum(prob[s][:, :, None] * out[s][1][:, None, :] for s in range(len(out)))
+    return HubbardThermalDynamics(betas, mus, times, logXi, correlation)

@@ -1123,6 +1123,31 @@ int dsea_sector_ladder_block_dots(int L, int ndown_src, int step, int R, const d
                                   const double *X /* [n_src,R] */, double *out_dev /* [R] */, double *scratch, int grid_log2,
                                   void *stream);
 
+/* ------------------------------------------------------------------ block Hubbard ladder maps (docs/design/37-hubbard-finite-temperature-dynamics.md)
+ * The maps of dsea_hubbard_ladder_apply applied to R vectors at once, and their column dots.  The sectors, the species, the step,
+ * weights_dev (fp64 [L] on the device, READ THROUGH THE POINTER ON EVERY LAUNCH), the three tables and grid_log2 are those of
+ * dsea_hubbard_ladder_apply.  A block is fp64 [n, R] row-major (element (r, j) at r * R + j), 16-byte aligned (DSEA_ERR_ALIGN
+ * otherwise; the argument checks come first), R in {1, 2, 4, 8}: X and the result of the map are [n_src, R] and [n_dst, R].  A
+ * row's division, state word and table reads are made once for all R columns.
+ * dsea_hubbard_ladder_block_apply: Y = S(c) X; column j of Y equals dsea_hubbard_ladder_apply on column j of X bit for bit.
+ * dsea_hubbard_ladder_block_dots: out_dev[j] = sum_r' Lft[r', j] (S(c) X)[r', j], Lft [n_dst, R], out_dev fp64 [R] on the device;
+ * the product block is never stored.  Wave and block sums in fixed order into per-block partials in `scratch`, then one block
+ * per column: no floating-point atomics, repeated calls return identical bits, and column j of a call equals the call with
+ * R = 1 on that column.  `scratch`: caller-owned, dsea_hubbard_ladder_block_dots_scratch_doubles = R * min(4096,
+ * ceil(n_dst / 256)) doubles (enough for every grid cap).
+ * Nothing is allocated, read back or synchronised.  Refused by host arithmetic before any device work (DSEA_ERR_ARG):
+ * everything dsea_hubbard_ladder_apply refuses; R outside {1, 2, 4, 8}; X == Y when step != 0 (at step 0 a thread reads its row
+ * before it writes it); a null X, Y, Lft, out_dev, scratch or (in the query) out. */
+int dsea_hubbard_ladder_block_apply(int L, int nup_src, int ndn_src, int species /* 0 up, 1 dn */, int step, int R,
+                                    const double *weights_dev, const int64_t *states_dst, const int32_t *lo_rank_src,
+                                    const int32_t *hi_base_src, const double *X /* [n_src,R] */, double *Y /* [n_dst,R] */,
+                                    int grid_log2 /* 0 = default */, void *stream);
+int dsea_hubbard_ladder_block_dots_scratch_doubles(int L, int nup_src, int ndn_src, int species, int step, int R, int64_t *out);
+int dsea_hubbard_ladder_block_dots(int L, int nup_src, int ndn_src, int species, int step, int R, const double *weights_dev,
+                                   const int64_t *states_dst, const int32_t *lo_rank_src, const int32_t *hi_base_src,
+                                   const double *Lft /* [n_dst,R] */, const double *X /* [n_src,R] */, double *out_dev /* [R] */,
+                                   double *scratch, int grid_log2, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
