@@ -2057,12 +2057,20 @@ int dsea_rdm_pull(int L, int ndown, int LA, const int32_t* sites_host, const int
   return check_launch();
 }
 
+// what the four launching entries of the sector ladder refuse with DSEA_ERR_ARG besides their own operands: a pair of sectors
+// that ladder_sizes refuses, a grid cap that ladder_grid_ok refuses, a null table.  The entries that read the weights add
+// them, the block entries a width outside {1, 2, 4, 8}.
+static inline bool ladder_args_ok(int L, int ndown_src, int step, int grid_log2, const void* states_dst, const void* lo_rank_src,
+                                  const void* hi_base_src) {
+  int64_t n_src, n_dst;
+  return ladder_sizes(L, ndown_src, step, &n_src, &n_dst) && ladder_grid_ok(grid_log2) && states_dst && lo_rank_src && hi_base_src;
+}
+
 int dsea_sector_ladder_apply(int L, int ndown_src, int step, const double* weights_dev, const int64_t* states_dst,
                              const int32_t* lo_rank_src, const int32_t* hi_base_src, const double* x, double* y, int grid_log2,
                              void* stream) {
-  int64_t n_src, n_dst;
-  REQUIRE(ladder_sizes(L, ndown_src, step, &n_src, &n_dst) && (grid_log2 == 0 || (grid_log2 >= 6 && grid_log2 <= 12)) &&
-              weights_dev && states_dst && lo_rank_src && hi_base_src && x && y && (step == 0 || x != y),
+  REQUIRE(ladder_args_ok(L, ndown_src, step, grid_log2, states_dst, lo_rank_src, hi_base_src) && weights_dev && x && y &&
+              (step == 0 || x != y),
           DSEA_ERR_ARG);
   if (launch_sector_ladder(L, ndown_src, step, weights_dev, reinterpret_cast<const uint64_t*>(states_dst),
                            reinterpret_cast<const uint32_t*>(lo_rank_src), reinterpret_cast<const uint32_t*>(hi_base_src), x, y,
@@ -2074,16 +2082,14 @@ int dsea_sector_ladder_apply(int L, int ndown_src, int step, const double* weigh
 int dsea_sector_ladder_forms_scratch_doubles(int L, int ndown_src, int step, int64_t* out) {
   int64_t n_src, n_dst;
   REQUIRE(out && ladder_sizes(L, ndown_src, step, &n_src, &n_dst), DSEA_ERR_ARG);
-  *out = ladder_forms_scratch_doubles(n_dst, L);
+  *out = ladder_partials(n_dst, L);
   return DSEA_OK;
 }
 
 int dsea_sector_ladder_forms(int L, int ndown_src, int step, const int64_t* states_dst, const int32_t* lo_rank_src,
                              const int32_t* hi_base_src, const double* v1, const double* v2, double* out, double* scratch,
                              int grid_log2, void* stream) {
-  int64_t n_src, n_dst;
-  REQUIRE(ladder_sizes(L, ndown_src, step, &n_src, &n_dst) && (grid_log2 == 0 || (grid_log2 >= 6 && grid_log2 <= 12)) &&
-              states_dst && lo_rank_src && hi_base_src && v1 && v2 && out && scratch,
+  REQUIRE(ladder_args_ok(L, ndown_src, step, grid_log2, states_dst, lo_rank_src, hi_base_src) && v1 && v2 && out && scratch,
           DSEA_ERR_ARG);
   if (launch_sector_ladder_forms(L, ndown_src, step, reinterpret_cast<const uint64_t*>(states_dst),
                                  reinterpret_cast<const uint32_t*>(lo_rank_src), reinterpret_cast<const uint32_t*>(hi_base_src),
@@ -2094,20 +2100,11 @@ int dsea_sector_ladder_forms(int L, int ndown_src, int step, const int64_t* stat
 
 static inline bool block_width_ok(int R) { return R == 1 || R == 2 || R == 4 || R == 8; }
 
-// what the two block ladder entries refuse with DSEA_ERR_ARG besides their own blocks: everything dsea_sector_ladder_apply
-// refuses, and a width outside {1, 2, 4, 8}
-static inline bool ladder_block_args_ok(int L, int ndown_src, int step, int R, int grid_log2, const void* weights_dev,
-                                        const void* states_dst, const void* lo_rank_src, const void* hi_base_src) {
-  int64_t n_src, n_dst;
-  return ladder_sizes(L, ndown_src, step, &n_src, &n_dst) && (grid_log2 == 0 || (grid_log2 >= 6 && grid_log2 <= 12)) &&
-         block_width_ok(R) && weights_dev && states_dst && lo_rank_src && hi_base_src;
-}
-
 int dsea_sector_ladder_block_apply(int L, int ndown_src, int step, int R, const double* weights_dev, const int64_t* states_dst,
                                    const int32_t* lo_rank_src, const int32_t* hi_base_src, const double* X, double* Y,
                                    int grid_log2, void* stream) {
-  REQUIRE(ladder_block_args_ok(L, ndown_src, step, R, grid_log2, weights_dev, states_dst, lo_rank_src, hi_base_src) && X && Y &&
-              (step == 0 || X != Y),
+  REQUIRE(ladder_args_ok(L, ndown_src, step, grid_log2, states_dst, lo_rank_src, hi_base_src) && block_width_ok(R) &&
+              weights_dev && X && Y && (step == 0 || X != Y),
           DSEA_ERR_ARG);
   REQUIRE(aligned16(X) && aligned16(Y), DSEA_ERR_ALIGN);
   if (launch_sector_ladder_block(L, ndown_src, step, R, weights_dev, reinterpret_cast<const uint64_t*>(states_dst),
@@ -2120,15 +2117,15 @@ int dsea_sector_ladder_block_apply(int L, int ndown_src, int step, int R, const 
 int dsea_sector_ladder_block_dots_scratch_doubles(int L, int ndown_src, int step, int R, int64_t* out) {
   int64_t n_src, n_dst;
   REQUIRE(out && ladder_sizes(L, ndown_src, step, &n_src, &n_dst) && block_width_ok(R), DSEA_ERR_ARG);
-  *out = ladder_block_dots_scratch_doubles(n_dst, R);
+  *out = ladder_partials(n_dst, R);
   return DSEA_OK;
 }
 
 int dsea_sector_ladder_block_dots(int L, int ndown_src, int step, int R, const double* weights_dev, const int64_t* states_dst,
                                   const int32_t* lo_rank_src, const int32_t* hi_base_src, const double* Lft, const double* X,
                                   double* out_dev, double* scratch, int grid_log2, void* stream) {
-  REQUIRE(ladder_block_args_ok(L, ndown_src, step, R, grid_log2, weights_dev, states_dst, lo_rank_src, hi_base_src) && Lft && X &&
-              out_dev && scratch,
+  REQUIRE(ladder_args_ok(L, ndown_src, step, grid_log2, states_dst, lo_rank_src, hi_base_src) && block_width_ok(R) &&
+              weights_dev && Lft && X && out_dev && scratch,
           DSEA_ERR_ARG);
   REQUIRE(aligned16(Lft) && aligned16(X), DSEA_ERR_ALIGN);
   if (launch_sector_ladder_block_dots(L, ndown_src, step, R, weights_dev, reinterpret_cast<const uint64_t*>(states_dst),
@@ -2262,13 +2259,21 @@ int dsea_op_hubbard_block_moments(dsea_op_t op, int R, int M, double centre, dou
   return check_launch();
 }
 
+// what the four launching entries of the Hubbard ladder refuse with DSEA_ERR_ARG besides their own operands: a species, a
+// step or a pair of sectors that hubbard_ladder_sizes refuses, a grid cap that ladder_grid_ok refuses, a null table.  The
+// entries that read the weights add them, the block entries a width outside {1, 2, 4, 8}.
+static inline bool hubbard_ladder_args_ok(int L, int nup_src, int ndn_src, int species, int step, int grid_log2,
+                                          const void* states_dst, const void* lo_rank_src, const void* hi_base_src) {
+  int64_t n_src, n_dst, n_dn_src, n_dn_dst;
+  return hubbard_ladder_sizes(L, nup_src, ndn_src, species, step, &n_src, &n_dst, &n_dn_src, &n_dn_dst) &&
+         ladder_grid_ok(grid_log2) && states_dst && lo_rank_src && hi_base_src;
+}
+
 int dsea_hubbard_ladder_apply(int L, int nup_src, int ndn_src, int species, int step, const double* weights_dev,
                               const int64_t* states_dst, const int32_t* lo_rank_src, const int32_t* hi_base_src, const double* x,
                               double* y, int grid_log2, void* stream) {
-  int64_t n_src, n_dst, n_dn_src, n_dn_dst;
-  REQUIRE(hubbard_ladder_sizes(L, nup_src, ndn_src, species, step, &n_src, &n_dst, &n_dn_src, &n_dn_dst) &&
-              (grid_log2 == 0 || (grid_log2 >= 6 && grid_log2 <= 12)) && weights_dev && states_dst && lo_rank_src &&
-              hi_base_src && x && y && (step == 0 || x != y),
+  REQUIRE(hubbard_ladder_args_ok(L, nup_src, ndn_src, species, step, grid_log2, states_dst, lo_rank_src, hi_base_src) &&
+              weights_dev && x && y && (step == 0 || x != y),
           DSEA_ERR_ARG);
   if (launch_hubbard_ladder(L, nup_src, ndn_src, species, step, weights_dev, reinterpret_cast<const uint64_t*>(states_dst),
                             reinterpret_cast<const uint32_t*>(lo_rank_src), reinterpret_cast<const uint32_t*>(hi_base_src), x, y,
@@ -2280,17 +2285,15 @@ int dsea_hubbard_ladder_apply(int L, int nup_src, int ndn_src, int species, int 
 int dsea_hubbard_ladder_forms_scratch_doubles(int L, int nup_src, int ndn_src, int species, int step, int64_t* out) {
   int64_t n_src, n_dst, n_dn_src, n_dn_dst;
   REQUIRE(out && hubbard_ladder_sizes(L, nup_src, ndn_src, species, step, &n_src, &n_dst, &n_dn_src, &n_dn_dst), DSEA_ERR_ARG);
-  *out = hubbard_ladder_forms_scratch_doubles(n_dst, L);
+  *out = ladder_partials(n_dst, L);
   return DSEA_OK;
 }
 
 int dsea_hubbard_ladder_forms(int L, int nup_src, int ndn_src, int species, int step, const int64_t* states_dst,
                               const int32_t* lo_rank_src, const int32_t* hi_base_src, const double* v1, const double* v2,
                               double* out, double* scratch, int grid_log2, void* stream) {
-  int64_t n_src, n_dst, n_dn_src, n_dn_dst;
-  REQUIRE(hubbard_ladder_sizes(L, nup_src, ndn_src, species, step, &n_src, &n_dst, &n_dn_src, &n_dn_dst) &&
-              (grid_log2 == 0 || (grid_log2 >= 6 && grid_log2 <= 12)) && states_dst && lo_rank_src && hi_base_src && v1 && v2 &&
-              out && scratch,
+  REQUIRE(hubbard_ladder_args_ok(L, nup_src, ndn_src, species, step, grid_log2, states_dst, lo_rank_src, hi_base_src) && v1 &&
+              v2 && out && scratch,
           DSEA_ERR_ARG);
   if (launch_hubbard_ladder_forms(L, nup_src, ndn_src, species, step, reinterpret_cast<const uint64_t*>(states_dst),
                                   reinterpret_cast<const uint32_t*>(lo_rank_src), reinterpret_cast<const uint32_t*>(hi_base_src),
@@ -2299,23 +2302,11 @@ int dsea_hubbard_ladder_forms(int L, int nup_src, int ndn_src, int species, int 
   return check_launch();
 }
 
-// what the two block Hubbard ladder entries refuse with DSEA_ERR_ARG besides their own blocks: everything
-// dsea_hubbard_ladder_apply refuses, and a width outside {1, 2, 4, 8}
-static inline bool hubbard_ladder_block_args_ok(int L, int nup_src, int ndn_src, int species, int step, int R, int grid_log2,
-                                                const void* weights_dev, const void* states_dst, const void* lo_rank_src,
-                                                const void* hi_base_src) {
-  int64_t n_src, n_dst, n_dn_src, n_dn_dst;
-  return hubbard_ladder_sizes(L, nup_src, ndn_src, species, step, &n_src, &n_dst, &n_dn_src, &n_dn_dst) &&
-         (grid_log2 == 0 || (grid_log2 >= 6 && grid_log2 <= 12)) && block_width_ok(R) && weights_dev && states_dst && lo_rank_src &&
-         hi_base_src;
-}
-
 int dsea_hubbard_ladder_block_apply(int L, int nup_src, int ndn_src, int species, int step, int R, const double* weights_dev,
                                     const int64_t* states_dst, const int32_t* lo_rank_src, const int32_t* hi_base_src,
                                     const double* X, double* Y, int grid_log2, void* stream) {
-  REQUIRE(hubbard_ladder_block_args_ok(L, nup_src, ndn_src, species, step, R, grid_log2, weights_dev, states_dst, lo_rank_src,
-                                       hi_base_src) &&
-              X && Y && (step == 0 || X != Y),
+  REQUIRE(hubbard_ladder_args_ok(L, nup_src, ndn_src, species, step, grid_log2, states_dst, lo_rank_src, hi_base_src) &&
+              block_width_ok(R) && weights_dev && X && Y && (step == 0 || X != Y),
           DSEA_ERR_ARG);
   REQUIRE(aligned16(X) && aligned16(Y), DSEA_ERR_ALIGN);
   if (launch_hubbard_ladder_block(L, nup_src, ndn_src, species, step, R, weights_dev,
@@ -2331,7 +2322,7 @@ int dsea_hubbard_ladder_block_dots_scratch_doubles(int L, int nup_src, int ndn_s
   REQUIRE(out && hubbard_ladder_sizes(L, nup_src, ndn_src, species, step, &n_src, &n_dst, &n_dn_src, &n_dn_dst) &&
               block_width_ok(R),
           DSEA_ERR_ARG);
-  *out = hubbard_ladder_block_dots_scratch_doubles(n_dst, R);
+  *out = ladder_partials(n_dst, R);
   return DSEA_OK;
 }
 
@@ -2339,9 +2330,8 @@ int dsea_hubbard_ladder_block_dots(int L, int nup_src, int ndn_src, int species,
                                    const int64_t* states_dst, const int32_t* lo_rank_src, const int32_t* hi_base_src,
                                    const double* Lft, const double* X, double* out_dev, double* scratch, int grid_log2,
                                    void* stream) {
-  REQUIRE(hubbard_ladder_block_args_ok(L, nup_src, ndn_src, species, step, R, grid_log2, weights_dev, states_dst, lo_rank_src,
-                                       hi_base_src) &&
-              Lft && X && out_dev && scratch,
+  REQUIRE(hubbard_ladder_args_ok(L, nup_src, ndn_src, species, step, grid_log2, states_dst, lo_rank_src, hi_base_src) &&
+              block_width_ok(R) && weights_dev && Lft && X && out_dev && scratch,
           DSEA_ERR_ARG);
   REQUIRE(aligned16(Lft) && aligned16(X), DSEA_ERR_ALIGN);
   if (launch_hubbard_ladder_block_dots(L, nup_src, ndn_src, species, step, R, weights_dev,

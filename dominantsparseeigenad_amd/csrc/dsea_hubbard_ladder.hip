@@ -19,7 +19,9 @@
 // row loads its own hi_base_src[w >> Llo] and lo_rank_src[w & lomask] once; a site below Llo then costs one lo_rank read and
 // one gather, a site at or above Llo one hi_base read and one gather.  The sites are walked in ascending order, so
 // par(w & below_i) is a running parity: it goes into the sign bit of the weight (exact), and g is its starting value.
-// Nothing here is shared with dsea_hubbard.hip or dsea_ladder.hip: the file has its own helpers.
+// The device helpers are the file's own: nothing is shared with dsea_hubbard.hip, and the site walk differs from that of
+// dsea_ladder.hip by the running parity and the row arithmetic.  The block forms take the row access and the partials of a
+// block from dsea_block.h; the grid rules are those of both ladder files, in dsea_internal.h (docs/design/38-ladder-parts.md).
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -45,10 +47,6 @@ struct HubbardLadderParams {
   const uint32_t* hi_base;
 };
 
-// v * (-1)^bit, exact: the bit goes into the sign
-__device__ __forceinline__ double hladder_signed(double v, uint32_t bit) {
-  return __longlong_as_double(__double_as_longlong(v) ^ (long long)((uint64_t)bit << 63));
-}
 __device__ __forceinline__ uint32_t hladder_bit(uint64_t w, int i) { return (uint32_t)((w >> i) & 1ull); }
 // does site i contribute to the row whose moving word is w?  c+ arrives at an occupied site, c at an empty one
 template <int STEP>
@@ -159,7 +157,7 @@ __global__ __launch_bounds__(256) void k_hubbard_ladder(HubbardLadderParams p, c
       const uint32_t mul = p.n_dn_src, add = SPECIES == 0 ? q.rd : q.ru * p.n_dn_src;
       uint32_t par = p.g;                          // the parity of the particles below the site, times the sector sign
       auto use = [&](int i, double xv) {
-        sum = fma(hladder_signed(cw[i], par), xv, sum);
+        sum = fma(block_signed(cw[i], par), xv, sum);
         par ^= hladder_bit(w, i);
       };
       hladder_group<SPECIES, STEP>(w, have, 0, Llo, wl, own_hi, mul, add, p.lo_rank, x, use);
@@ -205,7 +203,7 @@ __global__ __launch_bounds__(256) void k_hubbard_ladder_forms(HubbardLadderParam
       const uint32_t mul = p.n_dn_src, add = SPECIES == 0 ? q.rd : q.ru * p.n_dn_src;
       uint32_t par = p.g;
       auto use = [&](int i, double xv) {
-        add_form(i, a * hladder_signed(xv, par));
+        add_form(i, a * block_signed(xv, par));
         par ^= hladder_bit(w, i);
       };
       hladder_group<SPECIES, STEP>(w, have, 0, Llo, wl, own_hi, mul, add, p.lo_rank, v2, use);
@@ -227,8 +225,10 @@ __global__ __launch_bounds__(256) void k_hubbard_ladder_forms_reduce(const doubl
 
 // ---- the block forms (docs/design/37-hubbard-finite-temperature-dynamics.md): the map and its column dots on blocks fp64
 // [n, R] row-major, R in {1, 2, 4, 8} (dsea_block.h).  The row walk is that of k_hubbard_ladder; what changes is that a
-// contributing site costs one table read and one block_load<R> of the source row for all R columns.  The helpers are written
-// apart from the single-vector ones above (whose chunk is a macro), so that those keep their instructions.
+// contributing site costs one table read and one block_load<R> of the source row for all R columns.  The block walk
+// (hladder_block_rows: the partner row formed inside the predicated table read) and the single-vector walk (hladder_lookups +
+// hladder_rows: the selects outside the loads, one wait per chunk) are two schedules, not two spellings of one
+// (docs/design/38-ladder-parts.md).
 namespace {
 // sites in flight per thread: R * chunk doubles of gathered rows are live beside sum[R] (and acc[R] in the dots)
 template <int R>
@@ -277,7 +277,7 @@ __device__ __forceinline__ void hladder_block_group(uint64_t w, bool have, int b
 #pragma unroll
     for (int e = 0; e < CH; ++e) {
       if (k0 + e < end) {                          // (the same for every lane)
-        const double c = hladder_signed(cw[k0 + e], par);
+        const double c = block_signed(cw[k0 + e], par);
 #pragma unroll
         for (int j = 0; j < R; ++j) sum[j] = fma(c, xv[e][j], sum[j]);
         par ^= hladder_bit(w, k0 + e);
@@ -376,28 +376,13 @@ bool hubbard_ladder_sizes(int L, int nup_src, int ndn_src, int species, int step
   return hubbard_sizes(L, nup_src, ndn_src, n_src, &n_up, n_dn_src) && hubbard_sizes(L, nup_dst, ndn_dst, n_dst, &n_up, n_dn_dst);
 }
 
-// one block per 256 rows up to the cap 2^grid_log2 (6 .. 12; 0 = 12); beyond it blocks walk row ranges
-static inline int hubbard_ladder_blocks(int64_t n, int grid_log2) {
-  int64_t nblk = (n + 255) / 256;
-  const int64_t cap = (int64_t)1 << (grid_log2 == 0 ? 12 : grid_log2);
-  if (nblk > cap) nblk = cap;
-  return (int)nblk;
-}
-
-// partials per form that launch_hubbard_ladder_forms may write at any grid cap: the largest cap gives the most blocks
-int64_t hubbard_ladder_forms_scratch_doubles(int64_t n_dst, int L) {
-  int64_t nblk = (n_dst + 255) / 256;
-  if (nblk > DSEA_MAX_TFIM_BLOCKS) nblk = DSEA_MAX_TFIM_BLOCKS;
-  return (int64_t)L * nblk;
-}
-
 // the kernel arguments (c: the weights, null for the forms); false when an argument is out of range
 static bool hubbard_ladder_params(int L, int nup_src, int ndn_src, int species, int step, int grid_log2, const double* c,
                                   const uint64_t* states_dst, const uint32_t* lo_rank_src, const uint32_t* hi_base_src,
                                   HubbardLadderParams* p) {
   int64_t n_src, n_dst, n_dn_src, n_dn_dst;
   if (!hubbard_ladder_sizes(L, nup_src, ndn_src, species, step, &n_src, &n_dst, &n_dn_src, &n_dn_dst)) return false;
-  if (grid_log2 != 0 && (grid_log2 < 6 || grid_log2 > 12)) return false;
+  if (!ladder_grid_ok(grid_log2)) return false;
   if (!states_dst || !lo_rank_src || !hi_base_src) return false;
   p->L = L;
   p->Llo = (L + 1) / 2;
@@ -412,19 +397,11 @@ static bool hubbard_ladder_params(int L, int nup_src, int ndn_src, int species, 
   return true;
 }
 
-// the instantiation of (species, step): f(std::integral_constant<int, SPECIES>, std::integral_constant<int, STEP>)
+// the one place that turns the run-time (species, step) of a launch into template arguments: f(int_c<SPECIES>, int_c<STEP>),
+// species 1 for anything but 0 and step 0 for anything but +-1 (hubbard_ladder_params has refused those)
 template <class F>
 static inline void hubbard_ladder_dispatch(int species, int step, F&& f) {
-  using std::integral_constant;
-  if (species == 0) {
-    if (step > 0) f(integral_constant<int, 0>{}, integral_constant<int, 1>{});
-    else if (step < 0) f(integral_constant<int, 0>{}, integral_constant<int, -1>{});
-    else f(integral_constant<int, 0>{}, integral_constant<int, 0>{});
-  } else {
-    if (step > 0) f(integral_constant<int, 1>{}, integral_constant<int, 1>{});
-    else if (step < 0) f(integral_constant<int, 1>{}, integral_constant<int, -1>{});
-    else f(integral_constant<int, 1>{}, integral_constant<int, 0>{});
-  }
+  dispatch_int<0, 1>(species, [&](auto sp) { dispatch_int<1, -1, 0>(step, [&](auto stp) { f(sp, stp); }); });
 }
 
 int launch_hubbard_ladder(int L, int nup_src, int ndn_src, int species, int step, const double* c, const uint64_t* states_dst,
@@ -433,7 +410,7 @@ int launch_hubbard_ladder(int L, int nup_src, int ndn_src, int species, int step
   HubbardLadderParams p;
   if (!c || !hubbard_ladder_params(L, nup_src, ndn_src, species, step, grid_log2, c, states_dst, lo_rank_src, hi_base_src, &p))
     return -1;
-  const dim3 grid((unsigned)hubbard_ladder_blocks(p.n, grid_log2));
+  const dim3 grid((unsigned)ladder_blocks(p.n, grid_log2));
   hubbard_ladder_dispatch(species, step, [&](auto sp, auto stp) {
     hipLaunchKernelGGL((k_hubbard_ladder<decltype(sp)::value, decltype(stp)::value>), grid, dim3(256), 0, st, p, x, y);
   });
@@ -446,7 +423,7 @@ int launch_hubbard_ladder_forms(int L, int nup_src, int ndn_src, int species, in
   HubbardLadderParams p;
   if (!hubbard_ladder_params(L, nup_src, ndn_src, species, step, grid_log2, nullptr, states_dst, lo_rank_src, hi_base_src, &p))
     return -1;
-  const int nblk = hubbard_ladder_blocks(p.n, grid_log2);
+  const int nblk = ladder_blocks(p.n, grid_log2);
   const dim3 grid((unsigned)nblk);
   hubbard_ladder_dispatch(species, step, [&](auto sp, auto stp) {
     hipLaunchKernelGGL((k_hubbard_ladder_forms<decltype(sp)::value, decltype(stp)::value>), grid, dim3(256), 0, st, p, v1, v2,
@@ -456,20 +433,13 @@ int launch_hubbard_ladder_forms(int L, int nup_src, int ndn_src, int species, in
   return 0;
 }
 
-// partials that launch_hubbard_ladder_block_dots may write at any grid cap
-int64_t hubbard_ladder_block_dots_scratch_doubles(int64_t n_dst, int R) {
-  int64_t nblk = (n_dst + 255) / 256;
-  if (nblk > DSEA_MAX_TFIM_BLOCKS) nblk = DSEA_MAX_TFIM_BLOCKS;
-  return (int64_t)R * nblk;
-}
-
 int launch_hubbard_ladder_block(int L, int nup_src, int ndn_src, int species, int step, int R, const double* c,
                                 const uint64_t* states_dst, const uint32_t* lo_rank_src, const uint32_t* hi_base_src,
                                 const double* X, double* Y, int grid_log2, hipStream_t st) {
   HubbardLadderParams p;
   if (!c || !hubbard_ladder_params(L, nup_src, ndn_src, species, step, grid_log2, c, states_dst, lo_rank_src, hi_base_src, &p))
     return -1;
-  const dim3 grid((unsigned)hubbard_ladder_blocks(p.n, grid_log2));
+  const dim3 grid((unsigned)ladder_blocks(p.n, grid_log2));
   hubbard_ladder_dispatch(species, step, [&](auto sp, auto stp) {
     dispatch_block_width(R, [&](auto w) {
       hipLaunchKernelGGL((k_hubbard_ladder_block<decltype(sp)::value, decltype(stp)::value, decltype(w)::value>), grid, dim3(256),
@@ -486,7 +456,7 @@ int launch_hubbard_ladder_block_dots(int L, int nup_src, int ndn_src, int specie
   HubbardLadderParams p;
   if (!c || !hubbard_ladder_params(L, nup_src, ndn_src, species, step, grid_log2, c, states_dst, lo_rank_src, hi_base_src, &p))
     return -1;
-  const int nblk = hubbard_ladder_blocks(p.n, grid_log2);
+  const int nblk = ladder_blocks(p.n, grid_log2);
   const dim3 grid((unsigned)nblk);
   hubbard_ladder_dispatch(species, step, [&](auto sp, auto stp) {
     dispatch_block_width(R, [&](auto w) {

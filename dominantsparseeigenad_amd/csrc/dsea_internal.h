@@ -540,14 +540,31 @@ int launch_rdm_cross(const RdmGeom& g, const int32_t* idx, const double* x, cons
                      int tile, hipStream_t st);
 int launch_rdm_pull(const RdmGeom& g, const int32_t* idx, const double* G, const double* y, double* out, int transpose,
                     hipStream_t st);
+// The two ladder files, dsea_ladder.hip and dsea_hubbard_ladder.hip (docs/design/38-ladder-parts.md), share their host rules,
+// stated here once; their launchers and their C entries ask these and nothing else.
+// the grid cap of a ladder launch is 2^grid_log2 blocks: 6 .. 12, or 0 for the default 12
+inline bool ladder_grid_ok(int grid_log2) { return grid_log2 == 0 || (grid_log2 >= 6 && grid_log2 <= 12); }
+// one block per 256 rows up to that cap; beyond it blocks walk row ranges
+inline int ladder_blocks(int64_t n, int grid_log2) {
+  int64_t nblk = (n + 255) / 256;
+  const int64_t cap = (int64_t)1 << (grid_log2 == 0 ? 12 : grid_log2);
+  if (nblk > cap) nblk = cap;
+  return (int)nblk;
+}
+// the scratch doubles of a two-stage sum of `terms` values (the L site forms, the R column dots) over the destination rows:
+// one partial per term and block at any grid cap -- the largest cap gives the most blocks
+inline int64_t ladder_partials(int64_t n_dst, int terms) {
+  int64_t nblk = (n_dst + 255) / 256;
+  if (nblk > DSEA_MAX_TFIM_BLOCKS) nblk = DSEA_MAX_TFIM_BLOCKS;
+  return nblk * terms;
+}
 // dsea_ladder.hip (linear maps between two magnetisation sectors, docs/design/24-dynamics.md): sigma^-(c) (step +1), Z(c)
 // (step 0) and sigma^+(c) (step -1) from the sector (L, ndown_src) to (L, ndown_src + step) as gathers over the destination
 // rows, on the state table of the destination and the two rank tables of the source; the L site forms v1^T (dS/dc_i) v2 into
-// out through per-block partials in the caller's scratch (ladder_forms_scratch_doubles doubles).  ladder_sizes is false, and
-// the launchers return -1, for a step outside -1 .. 1, a sector outside the limits of sector_sizes, a grid_log2 other than 0
-// (= 12) or 6 .. 12, or a null table.
+// out through per-block partials in the caller's scratch (ladder_partials(n_dst, L) doubles).  ladder_sizes is false, and
+// the launchers return -1, for a step outside -1 .. 1, a sector outside the limits of sector_sizes, a grid_log2 that
+// ladder_grid_ok refuses, or a null table.
 bool ladder_sizes(int L, int ndown_src, int step, int64_t* n_src, int64_t* n_dst);
-int64_t ladder_forms_scratch_doubles(int64_t n_dst, int L);
 int launch_sector_ladder(int L, int ndown_src, int step, const double* c, const uint64_t* states_dst, const uint32_t* lo_rank_src,
                          const uint32_t* hi_base_src, const double* x, double* y, int grid_log2, hipStream_t st);
 int launch_sector_ladder_forms(int L, int ndown_src, int step, const uint64_t* states_dst, const uint32_t* lo_rank_src,
@@ -555,8 +572,7 @@ int launch_sector_ladder_forms(int L, int ndown_src, int step, const uint64_t* s
                                int grid_log2, hipStream_t st);
 // The block forms (docs/design/35-finite-temperature-dynamics.md): Y = S(c) X for a block fp64 [n, R] row-major, R in {1, 2, 4, 8}
 // (column j bit for bit launch_sector_ladder on column j), and out[j] = sum_r' Lft[r', j] (S(c) X)[r', j] through per-block partials
-// in the caller's scratch (ladder_block_dots_scratch_doubles doubles).  The same -1 as above; the caller has checked R.
-int64_t ladder_block_dots_scratch_doubles(int64_t n_dst, int R);
+// in the caller's scratch (ladder_partials(n_dst, R) doubles).  The same -1 as above; the caller has checked R.
 int launch_sector_ladder_block(int L, int ndown_src, int step, int R, const double* c, const uint64_t* states_dst,
                                const uint32_t* lo_rank_src, const uint32_t* hi_base_src, const double* X, double* Y, int grid_log2,
                                hipStream_t st);
@@ -568,12 +584,11 @@ int launch_sector_ladder_block_dots(int L, int ndown_src, int step, int R, const
 // species s (0 up, 1 dn) from (L, nup_src, ndn_src) to the sector with that species' count changed by step, as gathers over
 // the destination rows, on the state table of the moving species at its destination count and its two rank tables at its source
 // count; the L site forms v1^T (dS/dc_i) v2 into out through per-block partials in the caller's scratch
-// (hubbard_ladder_forms_scratch_doubles doubles).  hubbard_ladder_sizes is false, and the launchers return -1, for a species
-// outside {0, 1}, a step outside -1 .. 1, a sector outside the limits of hubbard_sizes, a grid_log2 other than 0 (= 12) or
-// 6 .. 12, or a null table.
+// (ladder_partials(n_dst, L) doubles).  hubbard_ladder_sizes is false, and the launchers return -1, for a species outside
+// {0, 1}, a step outside -1 .. 1, a sector outside the limits of hubbard_sizes, a grid_log2 that ladder_grid_ok refuses, or a
+// null table.
 bool hubbard_ladder_sizes(int L, int nup_src, int ndn_src, int species, int step, int64_t* n_src, int64_t* n_dst,
                           int64_t* n_dn_src, int64_t* n_dn_dst);
-int64_t hubbard_ladder_forms_scratch_doubles(int64_t n_dst, int L);
 int launch_hubbard_ladder(int L, int nup_src, int ndn_src, int species, int step, const double* c, const uint64_t* states_dst,
                           const uint32_t* lo_rank_src, const uint32_t* hi_base_src, const double* x, double* y, int grid_log2,
                           hipStream_t st);
@@ -582,9 +597,8 @@ int launch_hubbard_ladder_forms(int L, int nup_src, int ndn_src, int species, in
                                 double* out, double* scratch, int grid_log2, hipStream_t st);
 // The block forms (docs/design/37-hubbard-finite-temperature-dynamics.md): Y = S(c) X for a block fp64 [n, R] row-major, R in
 // {1, 2, 4, 8} (column j bit for bit launch_hubbard_ladder on column j), and out[j] = sum_r' Lft[r', j] (S(c) X)[r', j] through
-// per-block partials in the caller's scratch (hubbard_ladder_block_dots_scratch_doubles doubles).  The same -1 as above; the
-// caller has checked R.
-int64_t hubbard_ladder_block_dots_scratch_doubles(int64_t n_dst, int R);
+// per-block partials in the caller's scratch (ladder_partials(n_dst, R) doubles).  The same -1 as above; the caller has
+// checked R.
 int launch_hubbard_ladder_block(int L, int nup_src, int ndn_src, int species, int step, int R, const double* c,
                                 const uint64_t* states_dst, const uint32_t* lo_rank_src, const uint32_t* hi_base_src,
                                 const double* X, double* Y, int grid_log2, hipStream_t st);

@@ -16,8 +16,9 @@
 // at or above Llo one hi_base read and one gather.  The row's own hi_base_src entry enters a sum only when a low site
 // contributes, and then it belongs to a valid source state; the row's own lo_rank_src entry is the rank of the low word among
 // the words of its popcount and is always valid.
-// Nothing here is shared with dsea_sector.hip: the file has its own helpers.  The block forms take the row access and the
-// partials of a block from dsea_block.h.
+// The site walk is written once, on a row of R columns (docs/design/38-ladder-parts.md): the single-vector kernels are its
+// R = 1 case.  The row access, the sign and the partials of a block come from dsea_block.h, the grid rules from
+// dsea_internal.h; nothing is shared with dsea_sector.hip.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -29,7 +30,6 @@
 namespace dsea {
 
 namespace {
-#define DSEA_LADDER_CHUNK 8             /* sites whose table lookups and gathers a thread keeps in flight together */
 #define DSEA_LADDER_NO_RANK 0xFFFFFFFFu /* "this site does not contribute to this row" (a rank is below 2^31) */
 
 struct LadderParams {
@@ -41,57 +41,94 @@ struct LadderParams {
   const uint32_t* hi_base;    // of the source
 };
 
-// v * (1 - 2 bit), exact: the bit goes into the sign
-__device__ __forceinline__ double ladder_signed(double v, uint64_t bit) {
-  return __longlong_as_double(__double_as_longlong(v) ^ (long long)(bit << 63));
-}
 // does site i contribute to the row with state s?  sigma^- arrives at a set bit, sigma^+ at a clear one
 template <int STEP>
 __device__ __forceinline__ bool ladder_qualifies(uint64_t s, int i) {
   return ((s >> i) & 1ull) == (STEP > 0 ? 1ull : 0ull);
 }
 
-// the source ranks of sites k0 .. k0 + CHUNK - 1 of one group (the low sites 0 .. Llo - 1 or the high sites Llo .. L - 1) for the row with
-// state s: one table read per contributing site, all requested before any is used; DSEA_LADDER_NO_RANK for a site that does
-// not contribute (and past the group's end).  `word` is the row's word of the group (s >> Llo or s & lomask), `base` the
+// sites whose table lookups and gathers a thread keeps in flight together: R * chunk doubles of gathered rows are live beside
+// sum[R] (and acc[R] in the dots)
+template <int R>
+constexpr int ladder_chunk() {
+  return R <= 2 ? 8 : (R == 4 ? 4 : 2);
+}
+
+// the source ranks of sites k0 .. k0 + CH - 1 of one group (the low sites 0 .. Llo - 1 or the high sites Llo .. L - 1) for the row
+// with state s: one table read per contributing site, all requested before any is used; DSEA_LADDER_NO_RANK for a site that
+// does not contribute (and past the group's end).  `word` is the row's word of the group (s >> Llo or s & lomask), `base` the
 // first site of the group, `other` the row's own entry of the other table.
-template <int STEP>
-__device__ __forceinline__ void ladder_ranks(uint32_t (&rk)[DSEA_LADDER_CHUNK], uint64_t s, bool have, int k0, int end, int base,
-                                             uint32_t word, uint32_t other, const uint32_t* __restrict__ table) {
+template <int STEP, int CH>
+__device__ __forceinline__ void ladder_ranks(uint32_t (&rk)[CH], uint64_t s, bool have, int k0, int end, int base, uint32_t word,
+                                             uint32_t other, const uint32_t* __restrict__ table) {
 #pragma unroll
-  for (int e = 0; e < DSEA_LADDER_CHUNK; ++e) {
+  for (int e = 0; e < CH; ++e) {
     const int i = k0 + e;
     const bool on = have && i < end && ladder_qualifies<STEP>(s, i);   // (i < 48: the shift is defined)
     rk[e] = DSEA_LADDER_NO_RANK;
     if (on) rk[e] = other + table[word ^ (1u << (i - base))];
   }
 }
-// the gathers of one chunk: v[rank], 0 where the site does not contribute
-__device__ __forceinline__ void ladder_gather(double (&xv)[DSEA_LADDER_CHUNK], const uint32_t (&rk)[DSEA_LADDER_CHUNK],
-                                              const double* __restrict__ v) {
-#pragma unroll
-  for (int e = 0; e < DSEA_LADDER_CHUNK; ++e) {
-    xv[e] = 0.0;
-    if (rk[e] != DSEA_LADDER_NO_RANK) xv[e] = v[rk[e]];
-  }
-}
 
-// one group of sites [base, end) of one row: use(i, x[rank_i]) for every site of the group in order (0.0 for a site that does
-// not contribute).  The table reads of chunk c + 1 are issued before the gathers of chunk c are consumed.
-template <int STEP, typename Use>
+// one group of sites [base, end) of one row: use(i, X[rank_i, :]) for every site of the group in order (a row of zeros for a
+// site that does not contribute).  A contributing site costs one table read and one block_load<R> of the source row; the
+// table reads of chunk c + 1 are issued before the gathers of chunk c are consumed.
+template <int STEP, int R, typename Use>
 __device__ __forceinline__ void ladder_group(uint64_t s, bool have, int base, int end, uint32_t word, uint32_t other,
-                                             const uint32_t* __restrict__ table, const double* __restrict__ v, Use use) {
-  uint32_t rkA[DSEA_LADDER_CHUNK], rkB[DSEA_LADDER_CHUNK];
-  ladder_ranks<STEP>(rkA, s, have, base, end, base, word, other, table);
-  for (int k0 = base; k0 < end; k0 += DSEA_LADDER_CHUNK) {
-    double xv[DSEA_LADDER_CHUNK];
-    ladder_gather(xv, rkA, v);
-    ladder_ranks<STEP>(rkB, s, have, k0 + DSEA_LADDER_CHUNK, end, base, word, other, table);
+                                             const uint32_t* __restrict__ table, const double* __restrict__ X, Use use) {
+  constexpr int CH = ladder_chunk<R>();
+  uint32_t rkA[CH], rkB[CH];
+  ladder_ranks<STEP, CH>(rkA, s, have, base, end, base, word, other, table);
+  for (int k0 = base; k0 < end; k0 += CH) {
+    double xv[CH][R];
 #pragma unroll
-    for (int e = 0; e < DSEA_LADDER_CHUNK; ++e) {
+    for (int e = 0; e < CH; ++e) {
+#pragma unroll
+      for (int j = 0; j < R; ++j) xv[e][j] = 0.0;
+      if (rkA[e] != DSEA_LADDER_NO_RANK) block_load<R>(xv[e], X, (int64_t)rkA[e]);
+    }
+    ladder_ranks<STEP, CH>(rkB, s, have, k0 + CH, end, base, word, other, table);
+#pragma unroll
+    for (int e = 0; e < CH; ++e) {
       if (k0 + e < end) use(k0 + e, xv[e]);        // (the same for every lane)
       rkA[e] = rkB[e];
     }
+  }
+}
+
+// the sites of the row with state st, STEP = +-1: the state's two words, the row's own entry of either table, then the low
+// group and the high group
+template <int STEP, int R, typename Use>
+__device__ __forceinline__ void ladder_sites(const LadderParams& p, uint64_t st, bool have, uint64_t lomask,
+                                             const double* __restrict__ X, Use use) {
+  const uint32_t sl = (uint32_t)(st & lomask), sh = (uint32_t)(st >> p.Llo);
+  const uint32_t own_hi = p.hi_base[sh], own_lo = p.lo_rank[sl];
+  ladder_group<STEP, R>(st, have, 0, p.Llo, sl, own_hi, p.lo_rank, X, use);
+  ladder_group<STEP, R>(st, have, p.Llo, p.L, sh, own_lo, p.hi_base, X, use);
+}
+
+// sum[j] = (S(c) X)[r, j] of the row r (row n - 1 for a thread without a row); a site that does not contribute adds a zero
+// product, so every column sees the same operations in the same order whatever R
+template <int STEP, int R>
+__device__ __forceinline__ void ladder_row(const LadderParams& p, const double (&cw)[DSEA_SECTOR_MAX_L], uint64_t lomask, int64_t r,
+                                           bool have, const double* __restrict__ X, double (&sum)[R]) {
+  const int64_t rr = have ? r : p.n - 1;
+  const uint64_t st = p.states[rr];
+  if constexpr (STEP == 0) {
+    double xr[R];
+    block_load<R>(xr, X, rr);
+    double diag = 0.0;
+    for (int i = 0; i < p.L; ++i) diag += block_signed(cw[i], (st >> i) & 1ull);
+#pragma unroll
+    for (int j = 0; j < R; ++j) sum[j] = diag * xr[j];
+  } else {
+#pragma unroll
+    for (int j = 0; j < R; ++j) sum[j] = 0.0;
+    ladder_sites<STEP, R>(p, st, have, lomask, X, [&](int i, const double (&xrow)[R]) {
+      const double w = cw[i];
+#pragma unroll
+      for (int j = 0; j < R; ++j) sum[j] = fma(w, xrow[j], sum[j]);
+    });
   }
 }
 }  // namespace
@@ -101,29 +138,24 @@ __device__ __forceinline__ void ladder_group(uint64_t s, bool have, int base, in
 template <int STEP>
 __global__ __launch_bounds__(256) void k_sector_ladder(LadderParams p, const double* __restrict__ x, double* __restrict__ y) {
   __shared__ double cw[DSEA_SECTOR_MAX_L];
-  const int L = p.L, Llo = p.Llo;
   const int64_t n = p.n;
-  for (int c = threadIdx.x; c < L; c += 256) cw[c] = p.c[c];
+  for (int c = threadIdx.x; c < p.L; c += 256) cw[c] = p.c[c];
   __syncthreads();
-  const uint64_t lomask = (1ull << Llo) - 1;
+  const uint64_t lomask = (1ull << p.Llo) - 1;
   for (int64_t row0 = (int64_t)blockIdx.x * 256; row0 < n; row0 += (int64_t)gridDim.x * 256) {
     const int64_t r = row0 + threadIdx.x;
     const bool have = r < n;
-    const uint64_t st = p.states[have ? r : n - 1];
-    double sum = 0.0;
-    if constexpr (STEP == 0) {
+    double sum[1];
+    if constexpr (STEP == 0) {   // Z(c) keeps the row it had, spelled out: docs/design/38-ladder-parts.md, 38.6
+      const uint64_t st = p.states[have ? r : n - 1];
       const double xr = x[have ? r : n - 1];
       double diag = 0.0;
-      for (int i = 0; i < L; ++i) diag += ladder_signed(cw[i], (st >> i) & 1ull);
-      sum = diag * xr;
+      for (int i = 0; i < p.L; ++i) diag += block_signed(cw[i], (st >> i) & 1ull);
+      sum[0] = diag * xr;
     } else {
-      const uint32_t sl = (uint32_t)(st & lomask), sh = (uint32_t)(st >> Llo);
-      const uint32_t own_hi = p.hi_base[sh], own_lo = p.lo_rank[sl];
-      auto use = [&](int i, double xv) { sum = fma(cw[i], xv, sum); };
-      ladder_group<STEP>(st, have, 0, Llo, sl, own_hi, p.lo_rank, x, use);
-      ladder_group<STEP>(st, have, Llo, L, sh, own_lo, p.hi_base, x, use);
+      ladder_row<STEP, 1>(p, cw, lomask, r, have, x, sum);
     }
-    if (have) y[r] = sum;
+    if (have) block_store<1>(y, r, sum);
   }
 }
 
@@ -136,13 +168,13 @@ template <int STEP>
 __global__ __launch_bounds__(256) void k_sector_ladder_forms(LadderParams p, const double* __restrict__ v1,
                                                              const double* __restrict__ v2, double* __restrict__ scratch) {
   __shared__ double accs[4][DSEA_SECTOR_MAX_L];
-  const int L = p.L, Llo = p.Llo;
+  const int L = p.L;
   const int64_t n = p.n;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   double* __restrict__ mine = accs[wv];
   for (int c = lane; c < L; c += 64) mine[c] = 0.0;       // (afterwards a wave's row is touched by its lane 0 alone)
   __syncthreads();
-  const uint64_t lomask = (1ull << Llo) - 1;
+  const uint64_t lomask = (1ull << p.Llo) - 1;
   auto add = [&](int term, double val) {
     const double tot = wave_sum(val);
     if (lane == 0) mine[term] += tot;
@@ -154,13 +186,9 @@ __global__ __launch_bounds__(256) void k_sector_ladder_forms(LadderParams p, con
     const double a = have ? v1[r] : 0.0;
     if constexpr (STEP == 0) {
       const double d = a * v2[have ? r : n - 1];
-      for (int i = 0; i < L; ++i) add(i, ladder_signed(d, (st >> i) & 1ull));
+      for (int i = 0; i < L; ++i) add(i, block_signed(d, (st >> i) & 1ull));
     } else {
-      const uint32_t sl = (uint32_t)(st & lomask), sh = (uint32_t)(st >> Llo);
-      const uint32_t own_hi = p.hi_base[sh], own_lo = p.lo_rank[sl];
-      auto use = [&](int i, double xv) { add(i, a * xv); };
-      ladder_group<STEP>(st, have, 0, Llo, sl, own_hi, p.lo_rank, v2, use);
-      ladder_group<STEP>(st, have, Llo, L, sh, own_lo, p.hi_base, v2, use);
+      ladder_sites<STEP, 1>(p, st, have, lomask, v2, [&](int i, const double (&xrow)[1]) { add(i, a * xrow[0]); });
     }
   }
   __syncthreads();
@@ -177,87 +205,10 @@ __global__ __launch_bounds__(256) void k_sector_ladder_forms_reduce(const double
 }
 
 // ---- the block forms (docs/design/35-finite-temperature-dynamics.md): the map and its column dots on blocks fp64 [n, R]
-// row-major, R in {1, 2, 4, 8} (dsea_block.h).  The row walk is that of k_sector_ladder; what changes is that a contributing
-// site costs one table read and one block_load<R> of the source row for all R columns.  The helpers are written apart from
-// the single-vector ones above (whose chunk is a macro), so that those keep their instructions.
-namespace {
-// sites in flight per thread: R * chunk doubles of gathered rows are live beside sum[R] (and acc[R] in the dots)
-template <int R>
-constexpr int ladder_block_chunk() {
-  return R <= 2 ? 8 : (R == 4 ? 4 : 2);
-}
+// row-major, R in {1, 2, 4, 8} (dsea_block.h)
 
-// ladder_ranks with the chunk as a template argument
-template <int STEP, int CH>
-__device__ __forceinline__ void ladder_block_ranks(uint32_t (&rk)[CH], uint64_t s, bool have, int k0, int end, int base, uint32_t word,
-                                                   uint32_t other, const uint32_t* __restrict__ table) {
-#pragma unroll
-  for (int e = 0; e < CH; ++e) {
-    const int i = k0 + e;
-    const bool on = have && i < end && ladder_qualifies<STEP>(s, i);
-    rk[e] = DSEA_LADDER_NO_RANK;
-    if (on) rk[e] = other + table[word ^ (1u << (i - base))];
-  }
-}
-
-// one group of sites [base, end) of one row: sum[j] = fma(cw[i], X[rank_i, j], sum[j]) for every site of the group in order
-// (X[rank_i, :] = 0 for a site that does not contribute: the single-vector kernel adds the same zero product).  The table
-// reads of chunk c + 1 are issued before the gathers of chunk c are consumed.
-template <int STEP, int R>
-__device__ __forceinline__ void ladder_block_group(uint64_t s, bool have, int base, int end, uint32_t word, uint32_t other,
-                                                   const uint32_t* __restrict__ table, const double* __restrict__ X,
-                                                   const double (&cw)[DSEA_SECTOR_MAX_L], double (&sum)[R]) {
-  constexpr int CH = ladder_block_chunk<R>();
-  uint32_t rkA[CH], rkB[CH];
-  ladder_block_ranks<STEP, CH>(rkA, s, have, base, end, base, word, other, table);
-  for (int k0 = base; k0 < end; k0 += CH) {
-    double xv[CH][R];
-#pragma unroll
-    for (int e = 0; e < CH; ++e) {
-#pragma unroll
-      for (int j = 0; j < R; ++j) xv[e][j] = 0.0;
-      if (rkA[e] != DSEA_LADDER_NO_RANK) block_load<R>(xv[e], X, (int64_t)rkA[e]);
-    }
-    ladder_block_ranks<STEP, CH>(rkB, s, have, k0 + CH, end, base, word, other, table);
-#pragma unroll
-    for (int e = 0; e < CH; ++e) {
-      if (k0 + e < end) {                          // (the same for every lane)
-        const double w = cw[k0 + e];
-#pragma unroll
-        for (int j = 0; j < R; ++j) sum[j] = fma(w, xv[e][j], sum[j]);
-      }
-      rkA[e] = rkB[e];
-    }
-  }
-}
-
-// sum[j] = (S(c) X)[r, j] of the row r (row n - 1 for a thread without a row): column j in the operations and the order of
-// k_sector_ladder on column j
-template <int STEP, int R>
-__device__ __forceinline__ void ladder_block_row(const LadderParams& p, const double (&cw)[DSEA_SECTOR_MAX_L], uint64_t lomask,
-                                                 int64_t r, bool have, const double* __restrict__ X, double (&sum)[R]) {
-  const int64_t rr = have ? r : p.n - 1;
-  const uint64_t st = p.states[rr];
-  if constexpr (STEP == 0) {
-    double xr[R];
-    block_load<R>(xr, X, rr);
-    double diag = 0.0;
-    for (int i = 0; i < p.L; ++i) diag += ladder_signed(cw[i], (st >> i) & 1ull);
-#pragma unroll
-    for (int j = 0; j < R; ++j) sum[j] = diag * xr[j];
-  } else {
-#pragma unroll
-    for (int j = 0; j < R; ++j) sum[j] = 0.0;
-    const uint32_t sl = (uint32_t)(st & lomask), sh = (uint32_t)(st >> p.Llo);
-    const uint32_t own_hi = p.hi_base[sh], own_lo = p.lo_rank[sl];
-    ladder_block_group<STEP, R>(st, have, 0, p.Llo, sl, own_hi, p.lo_rank, X, cw, sum);
-    ladder_block_group<STEP, R>(st, have, p.Llo, p.L, sh, own_lo, p.hi_base, X, cw, sum);
-  }
-}
-}  // namespace
-
-// Y = S(c) X.  The grid, the 256-row ranges and the thread past the last row as in k_sector_ladder; column j of Y equals
-// k_sector_ladder on column j of X bit for bit.
+// Y = S(c) X.  The grid, the 256-row ranges and the thread past the last row as in k_sector_ladder, which is this kernel at
+// R = 1; column j of Y equals k_sector_ladder on column j of X bit for bit.
 template <int STEP, int R>
 __global__ __launch_bounds__(256) void k_sector_ladder_block(LadderParams p, const double* __restrict__ X, double* __restrict__ Y) {
   __shared__ double cw[DSEA_SECTOR_MAX_L];
@@ -269,7 +220,7 @@ __global__ __launch_bounds__(256) void k_sector_ladder_block(LadderParams p, con
     const int64_t r = row0 + threadIdx.x;
     const bool have = r < n;
     double sum[R];
-    ladder_block_row<STEP, R>(p, cw, lomask, r, have, X, sum);
+    ladder_row<STEP, R>(p, cw, lomask, r, have, X, sum);
     if (have) block_store<R>(Y, r, sum);
   }
 }
@@ -294,7 +245,7 @@ __global__ __launch_bounds__(256) void k_sector_ladder_block_dots(LadderParams p
     const int64_t r = row0 + threadIdx.x;
     const bool have = r < n;
     double sum[R];
-    ladder_block_row<STEP, R>(p, cw, lomask, r, have, X, sum);
+    ladder_row<STEP, R>(p, cw, lomask, r, have, X, sum);
     if (have) {
       double l[R];
       block_load<R>(l, Lft, r);
@@ -313,27 +264,12 @@ bool ladder_sizes(int L, int ndown_src, int step, int64_t* n_src, int64_t* n_dst
   return sector_sizes(L, ndown_src, n_src, &n_lo, &n_hi) && sector_sizes(L, ndown_src + step, n_dst, &n_lo, &n_hi);
 }
 
-// one block per 256 rows up to the cap 2^grid_log2 (6 .. 12; 0 = 12); beyond it blocks walk row ranges
-static inline int ladder_blocks(int64_t n, int grid_log2) {
-  int64_t nblk = (n + 255) / 256;
-  const int64_t cap = (int64_t)1 << (grid_log2 == 0 ? 12 : grid_log2);
-  if (nblk > cap) nblk = cap;
-  return (int)nblk;
-}
-
-// partials per form that launch_sector_ladder_forms may write at any grid cap: the largest cap gives the most blocks
-int64_t ladder_forms_scratch_doubles(int64_t n_dst, int L) {
-  int64_t nblk = (n_dst + 255) / 256;
-  if (nblk > DSEA_MAX_TFIM_BLOCKS) nblk = DSEA_MAX_TFIM_BLOCKS;
-  return (int64_t)L * nblk;
-}
-
 // the kernel arguments (c: the weights, null for the forms); false when an argument is out of range
 static bool ladder_params(int L, int ndown_src, int step, int grid_log2, const double* c, const uint64_t* states_dst,
                           const uint32_t* lo_rank_src, const uint32_t* hi_base_src, LadderParams* p) {
   int64_t n_src, n_dst;
   if (!ladder_sizes(L, ndown_src, step, &n_src, &n_dst)) return false;
-  if (grid_log2 != 0 && (grid_log2 < 6 || grid_log2 > 12)) return false;
+  if (!ladder_grid_ok(grid_log2)) return false;
   if (!states_dst || !lo_rank_src || !hi_base_src) return false;
   p->L = L;
   p->Llo = (L + 1) / 2;
@@ -345,14 +281,20 @@ static bool ladder_params(int L, int ndown_src, int step, int grid_log2, const d
   return true;
 }
 
+// the one place that turns the run-time step of a launch into the template argument (0 for anything but +-1)
+template <class F>
+static inline void dispatch_ladder_step(int step, F&& f) {
+  dispatch_int<1, -1, 0>(step, f);
+}
+
 int launch_sector_ladder(int L, int ndown_src, int step, const double* c, const uint64_t* states_dst, const uint32_t* lo_rank_src,
                          const uint32_t* hi_base_src, const double* x, double* y, int grid_log2, hipStream_t st) {
   LadderParams p;
   if (!c || !ladder_params(L, ndown_src, step, grid_log2, c, states_dst, lo_rank_src, hi_base_src, &p)) return -1;
   const dim3 grid((unsigned)ladder_blocks(p.n, grid_log2));
-  if (step > 0) hipLaunchKernelGGL((k_sector_ladder<1>), grid, dim3(256), 0, st, p, x, y);
-  else if (step < 0) hipLaunchKernelGGL((k_sector_ladder<-1>), grid, dim3(256), 0, st, p, x, y);
-  else hipLaunchKernelGGL((k_sector_ladder<0>), grid, dim3(256), 0, st, p, x, y);
+  dispatch_ladder_step(step, [&](auto s) {
+    hipLaunchKernelGGL((k_sector_ladder<decltype(s)::value>), grid, dim3(256), 0, st, p, x, y);
+  });
   return 0;
 }
 
@@ -363,24 +305,11 @@ int launch_sector_ladder_forms(int L, int ndown_src, int step, const uint64_t* s
   if (!ladder_params(L, ndown_src, step, grid_log2, nullptr, states_dst, lo_rank_src, hi_base_src, &p)) return -1;
   const int nblk = ladder_blocks(p.n, grid_log2);
   const dim3 grid((unsigned)nblk);
-  if (step > 0) hipLaunchKernelGGL((k_sector_ladder_forms<1>), grid, dim3(256), 0, st, p, v1, v2, scratch);
-  else if (step < 0) hipLaunchKernelGGL((k_sector_ladder_forms<-1>), grid, dim3(256), 0, st, p, v1, v2, scratch);
-  else hipLaunchKernelGGL((k_sector_ladder_forms<0>), grid, dim3(256), 0, st, p, v1, v2, scratch);
+  dispatch_ladder_step(step, [&](auto s) {
+    hipLaunchKernelGGL((k_sector_ladder_forms<decltype(s)::value>), grid, dim3(256), 0, st, p, v1, v2, scratch);
+  });
   hipLaunchKernelGGL(k_sector_ladder_forms_reduce, dim3((unsigned)L), dim3(256), 0, st, scratch, nblk, out);
   return 0;
-}
-
-// partials that launch_sector_ladder_block_dots may write at any grid cap
-int64_t ladder_block_dots_scratch_doubles(int64_t n_dst, int R) {
-  int64_t nblk = (n_dst + 255) / 256;
-  if (nblk > DSEA_MAX_TFIM_BLOCKS) nblk = DSEA_MAX_TFIM_BLOCKS;
-  return (int64_t)R * nblk;
-}
-
-// the one place that turns the run-time step of a block launch into the template argument (0 for anything but +-1)
-template <class F>
-static inline void dispatch_ladder_step(int step, F&& f) {
-  dispatch_int<1, -1, 0>(step, f);
 }
 
 int launch_sector_ladder_block(int L, int ndown_src, int step, int R, const double* c, const uint64_t* states_dst,

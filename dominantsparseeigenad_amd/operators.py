@@ -934,8 +934,119 @@ def ring_momentum_weights(L, m):
 
 
 class _SectorLadderBase:
-    """What ``SpinSectorLadder`` and ``HubbardLadder`` share: a subclass sets ``L``, ``device``, ``n_src``, ``n_dst`` and ``_grid``
-    (one list for the ladder and its transpose) and provides ``T``, ``_apply_raw(c, x)`` and ``_forms_raw(v1, v2)``."""
+    """What ``SpinSectorLadder`` and ``HubbardLadder`` share (docs/design/38-ladder-parts.md): the argument checks, the
+    transpose and the whole call path into libdsea.  A subclass names its family of C entries, ``_entry`` (``dsea_sector_ladder``
+    has the entries ``dsea_sector_ladder_apply``, ``_forms``, ``_forms_scratch_doubles``, ``_block_apply``, ``_block_dots`` and
+    ``_block_dots_scratch_doubles``), and their leading integer arguments, ``_sector_args()``; its constructor checks its
+    operands (``_pair``), then sets ``step``, ``n_src``, ``n_dst`` and ``_tables`` = (states of dst, lo_rank of src, hi_base of
+    src)."""
+
+    _entry = None        # the stem of the family's C entries
+    _operand = ()        # the attributes an operand must carry, and what to say when one is missing (% (name, attr))
+    _no_operand = None
+
+    def _sector_args(self):
+        """the integers that open every C entry of the family"""
+        raise NotImplementedError
+
+    def _check_operand(self, name, op):
+        """the checks of one operand beyond its attributes (ValueError)"""
+        raise NotImplementedError
+
+    def _transpose_args(self):
+        """the constructor arguments of ``T`` after (dst, src)"""
+        return ()
+
+    def _pair(self, src, dst, _transpose):
+        """what both constructors ask of (src, dst) and keep of them; ``_grid`` is one list for the ladder and its transpose"""
+        for name, op in (("src", src), ("dst", dst)):
+            for attr in self._operand:
+                if not hasattr(op, attr):
+                    raise ValueError(self._no_operand % (name, attr))
+            self._check_operand(name, op)
+        if int(src.N) != int(dst.N):
+            raise ValueError("the two sectors must have the same number of sites, got L = %d and L = %d" % (src.N, dst.N))
+        if torch.device(src.device) != torch.device(dst.device):
+            raise ValueError("the two sectors must live on the same device, got %s and %s" % (src.device, dst.device))
+        self.src, self.dst = src, dst
+        self.L = self.N = int(src.N)
+        self.device = torch.device(src.device)
+        self._T = _transpose
+        self._grid = _transpose._grid if _transpose is not None else [0]
+
+    @property
+    def T(self):
+        """the ladder dst -> src on the same tables: ``lad.T(c, .)`` is the transpose of ``lad(c, .)``"""
+        if self._T is None:
+            self._T = type(self)(self.dst, self.src, *self._transpose_args(), _transpose=self)
+        return self._T
+
+    def _call(self, entry, *args):
+        """one C entry of the family on this ladder's sectors: ``args`` follow the sector arguments; tensors go by pointer"""
+        name = "%s_%s" % (self._entry, entry)
+        args = [c_void_p(a.data_ptr()) if torch.is_tensor(a) else a for a in args]
+        check(getattr(_lib.load(), name)(*self._sector_args(), *args), name)
+
+    def _launch(self, entry, lead, operands):
+        """``_call`` of a launching entry: ``lead`` (the width, the weights), the three tables, the operands, grid cap, stream"""
+        with torch.cuda.device(self.device):
+            self._call(entry, *lead, *self._tables, *operands, self._grid[0], engine._stream(self.device))
+
+    def _scratch(self, entry, *width):
+        """the scratch of a two-stage entry, sized by the library (``<entry>_scratch_doubles``)"""
+        need = c_int64()
+        self._call(entry + "_scratch_doubles", *width, byref(need))
+        return torch.empty(need.value, dtype=F64, device=self.device)
+
+    def _apply_raw(self, c, x):
+        c, x = engine.as_vector(c, self.L), engine.as_vector(x, self.n_src)
+        y = torch.empty(self.n_dst, dtype=F64, device=x.device)
+        self._launch("apply", (c,), (x, y))
+        return y
+
+    def _forms_raw(self, v1, v2):
+        v1, v2 = engine.as_vector(v1, self.n_dst), engine.as_vector(v2, self.n_src)
+        out = torch.empty(self.L, dtype=F64, device=v1.device)
+        self._launch("forms", (), (v1, v2, out, self._scratch("forms")))
+        return out
+
+    def apply_block(self, c, X):
+        """sum_i c_i O_i X for a device tensor X of shape (n_src, R), any R >= 1: (n_dst, R), in blocks of 8, 4, 2 and 1 columns
+        (the family's ``_block_apply`` entry).  Column j equals ``lad(c, X[:, j])`` bit for bit; what a row needs whatever the
+        column -- its state word, its table reads, the Hubbard row's division -- is done once for all columns of a block.
+        Detached, not differentiable."""
+        from .chebyshev import _aligned_piece
+        from .thermal import block_pieces
+        c = self._weights(c)
+        X = self._block(X, self.n_src, "X")
+        c = engine.as_vector(c.detach(), self.L)
+        out = []
+        for first, w in block_pieces(X.shape[1]):
+            Yp = torch.empty((self.n_dst, w), dtype=F64, device=self.device)
+            self._launch("block_apply", (w, c), (_aligned_piece(X, first, w), Yp))
+            out.append(Yp)
+        return out[0] if len(out) == 1 else torch.cat(out, dim=1)
+
+    def block_dots(self, c, Lft, X):
+        """d[j] = sum_r Lft[r, j] (sum_i c_i O_i X)[r, j] as a device tensor [R], for Lft (n_dst, R) and X (n_src, R), any R >= 1:
+        the column dots of ``Lft`` with ``apply_block(c, X)`` without the product block (the family's ``_block_dots`` entry, in
+        blocks of 8, 4, 2 and 1 columns; fixed-order sums, identical calls return identical bits).  Detached, not
+        differentiable."""
+        from .chebyshev import _aligned_piece
+        from .thermal import block_pieces
+        c = self._weights(c)
+        X = self._block(X, self.n_src, "X")
+        Lft = self._block(Lft, self.n_dst, "Lft")
+        if Lft.shape[1] != X.shape[1]:
+            raise ValueError("Lft and X must have the same number of columns, got %d and %d" % (Lft.shape[1], X.shape[1]))
+        c = engine.as_vector(c.detach(), self.L)
+        out = torch.empty(X.shape[1], dtype=F64, device=self.device)
+        for first, w in block_pieces(X.shape[1]):
+            piece = torch.empty(w, dtype=F64, device=self.device)
+            self._launch("block_dots", (w, c), (_aligned_piece(Lft, first, w), _aligned_piece(X, first, w), piece,
+                                                self._scratch("block_dots", w)))
+            out[first:first + w] = piece
+        return out
 
     def set_grid_log2(self, grid_log2):
         """log2 of the most blocks a launch uses (6..12, 0 = the default 12; measurement aid), for the ladder and ``T``"""
@@ -1001,126 +1112,31 @@ class SpinSectorLadder(_SectorLadderBase):
     ``lad.T(c, .)`` the exact transpose of ``lad(c, .)``.  ``lad.forms(v1, v2)[i] = v1^T (d lad / d c_i) v2`` for all sites in
     one pass (v1 on the destination, v2 on the source; deterministic).  Both are differentiable to any order in c and in the
     vectors: the map is bilinear and each of the two ``autograd.Function``s is the other's derivative.  ``dense(c)`` is the
-    n_dst x n_src matrix, a test aid for small sectors.  Every argument check is host arithmetic before the device is touched
-    and raises ``ValueError``."""
+    n_dst x n_src matrix, a test aid for small sectors.  ``apply_block`` and ``block_dots`` are the map and its column dots on
+    blocks of columns (dsea_sector_ladder_block_apply and dsea_sector_ladder_block_dots,
+    docs/design/35-finite-temperature-dynamics.md): a row's table reads are made once for all columns of a block.  Every
+    argument check is host arithmetic before the device is touched and raises ``ValueError``."""
+
+    _entry = "dsea_sector_ladder"
+    _operand = ("N", "ndown", "device", "_tables")
+    _no_operand = "%s carries no sector tables (no attribute %r): a SpinSectorOperator or a SpinSectorPairOperator is needed"
 
     def __init__(self, src, dst, _transpose=None):
-        for name, op in (("src", src), ("dst", dst)):
-            for attr in ("N", "ndown", "device", "_tables"):
-                if not hasattr(op, attr):
-                    raise ValueError("%s carries no sector tables (no attribute %r): a SpinSectorOperator or a "
-                                     "SpinSectorPairOperator is needed" % (name, attr))
-            _check_sector(op.N, op.ndown)
-            if len(op._tables) != 3:
-                raise ValueError("%s._tables must be (states, lo_rank, hi_base)" % name)
-        if int(src.N) != int(dst.N):
-            raise ValueError("the two sectors must have the same number of sites, got L = %d and L = %d" % (src.N, dst.N))
-        if torch.device(src.device) != torch.device(dst.device):
-            raise ValueError("the two sectors must live on the same device, got %s and %s" % (src.device, dst.device))
+        self._pair(src, dst, _transpose)
         step = int(dst.ndown) - int(src.ndown)
         if step not in (-1, 0, 1):
             raise ValueError("a ladder changes ndown by +1, 0 or -1, got %d -> %d" % (src.ndown, dst.ndown))
-        self.src, self.dst = src, dst
-        self.L = self.N = int(src.N)
         self.step = step
-        self.device = torch.device(src.device)
         self.n_src, self.n_dst = math.comb(self.L, int(src.ndown)), math.comb(self.L, int(dst.ndown))
         self._tables = (dst._tables[0], src._tables[1], src._tables[2])     # states of dst, rank tables of src: kept alive
-        self._T = _transpose
-        self._grid = _transpose._grid if _transpose is not None else [0]    # one setting for the ladder and its transpose
 
-    @property
-    def T(self):
-        """the ladder dst -> src on the same tables: ``lad.T(c, .)`` is the transpose of ``lad(c, .)``"""
-        if self._T is None:
-            self._T = SpinSectorLadder(self.dst, self.src, _transpose=self)
-        return self._T
+    def _check_operand(self, name, op):
+        _check_sector(op.N, op.ndown)
+        if len(op._tables) != 3:
+            raise ValueError("%s._tables must be (states, lo_rank, hi_base)" % name)
 
-    def _apply_raw(self, c, x):
-        c, x = engine.as_vector(c, self.L), engine.as_vector(x, self.n_src)
-        states, lo_rank, hi_base = self._tables
-        y = torch.empty(self.n_dst, dtype=F64, device=x.device)
-        with torch.cuda.device(self.device):
-            check(_lib.load().dsea_sector_ladder_apply(self.L, int(self.src.ndown), self.step, c_void_p(c.data_ptr()),
-                                                       c_void_p(states.data_ptr()), c_void_p(lo_rank.data_ptr()),
-                                                       c_void_p(hi_base.data_ptr()), c_void_p(x.data_ptr()),
-                                                       c_void_p(y.data_ptr()), self._grid[0], engine._stream(self.device)),
-                  "dsea_sector_ladder_apply")
-        return y
-
-    def _forms_raw(self, v1, v2):
-        lib = _lib.load()
-        v1, v2 = engine.as_vector(v1, self.n_dst), engine.as_vector(v2, self.n_src)
-        states, lo_rank, hi_base = self._tables
-        need = c_int64()
-        check(lib.dsea_sector_ladder_forms_scratch_doubles(self.L, int(self.src.ndown), self.step, byref(need)),
-              "dsea_sector_ladder_forms_scratch_doubles")
-        scratch = torch.empty(need.value, dtype=F64, device=v1.device)
-        out = torch.empty(self.L, dtype=F64, device=v1.device)
-        with torch.cuda.device(self.device):
-            check(lib.dsea_sector_ladder_forms(self.L, int(self.src.ndown), self.step, c_void_p(states.data_ptr()),
-                                               c_void_p(lo_rank.data_ptr()), c_void_p(hi_base.data_ptr()),
-                                               c_void_p(v1.data_ptr()), c_void_p(v2.data_ptr()), c_void_p(out.data_ptr()),
-                                               c_void_p(scratch.data_ptr()), self._grid[0], engine._stream(self.device)),
-                  "dsea_sector_ladder_forms")
-        return out
-
-    def apply_block(self, c, X):
-        """sum_i c_i O_i X for a device tensor X of shape (n_src, R), any R >= 1: (n_dst, R), in blocks of 8, 4, 2 and 1 columns
-        (dsea_sector_ladder_block_apply, docs/design/35-finite-temperature-dynamics.md).  Column j equals ``lad(c, X[:, j])``
-        bit for bit; a row's table reads are made once for all columns of a block.  Detached, not differentiable."""
-        from .chebyshev import _aligned_piece
-        from .thermal import block_pieces
-        c = self._weights(c)
-        X = self._block(X, self.n_src, "X")
-        c = engine.as_vector(c.detach(), self.L)
-        states, lo_rank, hi_base = self._tables
-        run = _lib.load().dsea_sector_ladder_block_apply
-        out = []
-        with torch.cuda.device(self.device):
-            for first, w in block_pieces(X.shape[1]):
-                Xp = _aligned_piece(X, first, w)
-                Yp = torch.empty((self.n_dst, w), dtype=F64, device=self.device)
-                check(run(self.L, int(self.src.ndown), self.step, w, c_void_p(c.data_ptr()), c_void_p(states.data_ptr()),
-                          c_void_p(lo_rank.data_ptr()), c_void_p(hi_base.data_ptr()), c_void_p(Xp.data_ptr()),
-                          c_void_p(Yp.data_ptr()), self._grid[0], engine._stream(self.device)),
-                      "dsea_sector_ladder_block_apply")
-                out.append(Yp)
-        return out[0] if len(out) == 1 else torch.cat(out, dim=1)
-
-    def block_dots(self, c, Lft, X):
-        """d[j] = sum_r Lft[r, j] (sum_i c_i O_i X)[r, j] as a device tensor [R], for Lft (n_dst, R) and X (n_src, R), any R >= 1:
-        the column dots of ``Lft`` with ``apply_block(c, X)`` without the product block (dsea_sector_ladder_block_dots, in
-        blocks of 8, 4, 2 and 1 columns; fixed-order sums, identical calls return identical bits).  Detached, not
-        differentiable."""
-        from .chebyshev import _aligned_piece
-        from .thermal import block_pieces
-        c = self._weights(c)
-        X = self._block(X, self.n_src, "X")
-        Lft = self._block(Lft, self.n_dst, "Lft")
-        if Lft.shape[1] != X.shape[1]:
-            raise ValueError("Lft and X must have the same number of columns, got %d and %d" % (Lft.shape[1], X.shape[1]))
-        c = engine.as_vector(c.detach(), self.L)
-        lib = _lib.load()
-        states, lo_rank, hi_base = self._tables
-        out = torch.empty(X.shape[1], dtype=F64, device=self.device)
-        with torch.cuda.device(self.device):
-            for first, w in block_pieces(X.shape[1]):
-                need = c_int64()
-                check(lib.dsea_sector_ladder_block_dots_scratch_doubles(self.L, int(self.src.ndown), self.step, w, byref(need)),
-                      "dsea_sector_ladder_block_dots_scratch_doubles")
-                scratch = torch.empty(need.value, dtype=F64, device=self.device)
-                Xp, Lp = _aligned_piece(X, first, w), _aligned_piece(Lft, first, w)
-                piece = torch.empty(w, dtype=F64, device=self.device)
-                check(lib.dsea_sector_ladder_block_dots(self.L, int(self.src.ndown), self.step, w, c_void_p(c.data_ptr()),
-                                                        c_void_p(states.data_ptr()), c_void_p(lo_rank.data_ptr()),
-                                                        c_void_p(hi_base.data_ptr()), c_void_p(Lp.data_ptr()),
-                                                        c_void_p(Xp.data_ptr()), c_void_p(piece.data_ptr()),
-                                                        c_void_p(scratch.data_ptr()), self._grid[0],
-                                                        engine._stream(self.device)),
-                      "dsea_sector_ladder_block_dots")
-                out[first:first + w] = piece
-        return out
+    def _sector_args(self):
+        return self.L, int(self.src.ndown), self.step
 
 
 class _LadderApply(torch.autograd.Function):
@@ -1931,20 +1947,17 @@ class HubbardLadder(_SectorLadderBase):
     ``lad(w, .)``.  ``lad.forms(v1, v2)[i] = v1^T (d lad / d w_i) v2`` for all sites in one pass (v1 on the destination, v2 on
     the source; deterministic).  Both are differentiable to any order in w and in the vectors: the map is bilinear and each of
     the two ``autograd.Function``s is the other's derivative.  ``dense(w)`` is the n_dst x n_src matrix, a test aid for small
-    sectors.  Every argument check is host arithmetic before the device is touched and raises ``ValueError``."""
+    sectors.  ``apply_block`` and ``block_dots`` are the map and its column dots on blocks of columns
+    (dsea_hubbard_ladder_block_apply and dsea_hubbard_ladder_block_dots,
+    docs/design/37-hubbard-finite-temperature-dynamics.md): a row's division, state word and table reads are made once for all
+    columns of a block.  Every argument check is host arithmetic before the device is touched and raises ``ValueError``."""
+
+    _entry = "dsea_hubbard_ladder"
+    _operand = ("N", "nup", "ndn", "device", "_up", "_dn")
+    _no_operand = "%s carries no species tables (no attribute %r): a HubbardOperator is needed"
 
     def __init__(self, src, dst, species=None, _transpose=None):
-        for name, op in (("src", src), ("dst", dst)):
-            for attr in ("N", "nup", "ndn", "device", "_up", "_dn"):
-                if not hasattr(op, attr):
-                    raise ValueError("%s carries no species tables (no attribute %r): a HubbardOperator is needed" % (name, attr))
-            _check_hubbard(op.N, op.nup, op.ndn)
-            if len(op._up) != 3 or len(op._dn) != 3:
-                raise ValueError("%s._up and %s._dn must be (states, lo_rank, hi_base)" % (name, name))
-        if int(src.N) != int(dst.N):
-            raise ValueError("the two sectors must have the same number of sites, got L = %d and L = %d" % (src.N, dst.N))
-        if torch.device(src.device) != torch.device(dst.device):
-            raise ValueError("the two sectors must live on the same device, got %s and %s" % (src.device, dst.device))
+        self._pair(src, dst, _transpose)
         if species is not None and species not in _HUBBARD_SPECIES:
             raise ValueError("species must be 'up', 'dn' or None, got %r" % (species,))
         dup, ddn = int(dst.nup) - int(src.nup), int(dst.ndn) - int(src.ndn)
@@ -1964,112 +1977,23 @@ class HubbardLadder(_SectorLadderBase):
                 raise ValueError("species=%r contradicts the sectors (%d, %d) -> (%d, %d), which move the %s species"
                                  % (species, src.nup, src.ndn, dst.nup, dst.ndn, implied))
             species = implied
-        self.src, self.dst = src, dst
-        self.L = self.N = int(src.N)
         self.species, self.step = species, step
         self._species = _HUBBARD_SPECIES[species]
-        self.device = torch.device(src.device)
         self.n_src = math.comb(self.L, int(src.nup)) * math.comb(self.L, int(src.ndn))
         self.n_dst = math.comb(self.L, int(dst.nup)) * math.comb(self.L, int(dst.ndn))
         moving_src, moving_dst = (src._up, dst._up) if species == "up" else (src._dn, dst._dn)
         self._tables = (moving_dst[0], moving_src[1], moving_src[2])    # states of dst, rank tables of src: kept alive
-        self._T = _transpose
-        self._grid = _transpose._grid if _transpose is not None else [0]    # one setting for the ladder and its transpose
 
-    @property
-    def T(self):
-        """the ladder dst -> src on the same tables: ``lad.T(w, .)`` is the transpose of ``lad(w, .)``"""
-        if self._T is None:
-            self._T = HubbardLadder(self.dst, self.src, self.species, _transpose=self)
-        return self._T
+    def _check_operand(self, name, op):
+        _check_hubbard(op.N, op.nup, op.ndn)
+        if len(op._up) != 3 or len(op._dn) != 3:
+            raise ValueError("%s._up and %s._dn must be (states, lo_rank, hi_base)" % (name, name))
+
+    def _transpose_args(self):
+        return (self.species,)
 
     def _sector_args(self):
         return self.L, int(self.src.nup), int(self.src.ndn), self._species, self.step
-
-    def _apply_raw(self, w, x):
-        w, x = engine.as_vector(w, self.L), engine.as_vector(x, self.n_src)
-        states, lo_rank, hi_base = self._tables
-        y = torch.empty(self.n_dst, dtype=F64, device=x.device)
-        with torch.cuda.device(self.device):
-            check(_lib.load().dsea_hubbard_ladder_apply(*self._sector_args(), c_void_p(w.data_ptr()), c_void_p(states.data_ptr()),
-                                                        c_void_p(lo_rank.data_ptr()), c_void_p(hi_base.data_ptr()),
-                                                        c_void_p(x.data_ptr()), c_void_p(y.data_ptr()), self._grid[0],
-                                                        engine._stream(self.device)), "dsea_hubbard_ladder_apply")
-        return y
-
-    def _forms_raw(self, v1, v2):
-        lib = _lib.load()
-        v1, v2 = engine.as_vector(v1, self.n_dst), engine.as_vector(v2, self.n_src)
-        states, lo_rank, hi_base = self._tables
-        need = c_int64()
-        check(lib.dsea_hubbard_ladder_forms_scratch_doubles(*self._sector_args(), byref(need)),
-              "dsea_hubbard_ladder_forms_scratch_doubles")
-        scratch = torch.empty(need.value, dtype=F64, device=v1.device)
-        out = torch.empty(self.L, dtype=F64, device=v1.device)
-        with torch.cuda.device(self.device):
-            check(lib.dsea_hubbard_ladder_forms(*self._sector_args(), c_void_p(states.data_ptr()), c_void_p(lo_rank.data_ptr()),
-                                                c_void_p(hi_base.data_ptr()), c_void_p(v1.data_ptr()), c_void_p(v2.data_ptr()),
-                                                c_void_p(out.data_ptr()), c_void_p(scratch.data_ptr()), self._grid[0],
-                                                engine._stream(self.device)), "dsea_hubbard_ladder_forms")
-        return out
-
-    def apply_block(self, w, X):
-        """sum_i w_i O_i X for a device tensor X of shape (n_src, R), any R >= 1: (n_dst, R), in blocks of 8, 4, 2 and 1 columns
-        (dsea_hubbard_ladder_block_apply, docs/design/37-hubbard-finite-temperature-dynamics.md).  Column j equals
-        ``lad(w, X[:, j])`` bit for bit; a row's division, state word and table reads are made once for all columns of a block.
-        Detached, not differentiable."""
-        from .chebyshev import _aligned_piece
-        from .thermal import block_pieces
-        w = self._weights(w)
-        X = self._block(X, self.n_src, "X")
-        w = engine.as_vector(w.detach(), self.L)
-        states, lo_rank, hi_base = self._tables
-        run = _lib.load().dsea_hubbard_ladder_block_apply
-        out = []
-        with torch.cuda.device(self.device):
-            for first, width in block_pieces(X.shape[1]):
-                Xp = _aligned_piece(X, first, width)
-                Yp = torch.empty((self.n_dst, width), dtype=F64, device=self.device)
-                check(run(*self._sector_args(), width, c_void_p(w.data_ptr()), c_void_p(states.data_ptr()),
-                          c_void_p(lo_rank.data_ptr()), c_void_p(hi_base.data_ptr()), c_void_p(Xp.data_ptr()),
-                          c_void_p(Yp.data_ptr()), self._grid[0], engine._stream(self.device)),
-                      "dsea_hubbard_ladder_block_apply")
-                out.append(Yp)
-        return out[0] if len(out) == 1 else torch.cat(out, dim=1)
-
-    def block_dots(self, w, Lft, X):
-        """d[j] = sum_r Lft[r, j] (sum_i w_i O_i X)[r, j] as a device tensor [R], for Lft (n_dst, R) and X (n_src, R), any R >= 1:
-        the column dots of ``Lft`` with ``apply_block(w, X)`` without the product block (dsea_hubbard_ladder_block_dots, in
-        blocks of 8, 4, 2 and 1 columns; fixed-order sums, identical calls return identical bits).  Detached, not
-        differentiable."""
-        from .chebyshev import _aligned_piece
-        from .thermal import block_pieces
-        w = self._weights(w)
-        X = self._block(X, self.n_src, "X")
-        Lft = self._block(Lft, self.n_dst, "Lft")
-        if Lft.shape[1] != X.shape[1]:
-            raise ValueError("Lft and X must have the same number of columns, got %d and %d" % (Lft.shape[1], X.shape[1]))
-        w = engine.as_vector(w.detach(), self.L)
-        lib = _lib.load()
-        states, lo_rank, hi_base = self._tables
-        out = torch.empty(X.shape[1], dtype=F64, device=self.device)
-        with torch.cuda.device(self.device):
-            for first, width in block_pieces(X.shape[1]):
-                need = c_int64()
-                check(lib.dsea_hubbard_ladder_block_dots_scratch_doubles(*self._sector_args(), width, byref(need)),
-                      "dsea_hubbard_ladder_block_dots_scratch_doubles")
-                scratch = torch.empty(need.value, dtype=F64, device=self.device)
-                Xp, Lp = _aligned_piece(X, first, width), _aligned_piece(Lft, first, width)
-                piece = torch.empty(width, dtype=F64, device=self.device)
-                check(lib.dsea_hubbard_ladder_block_dots(*self._sector_args(), width, c_void_p(w.data_ptr()),
-                                                         c_void_p(states.data_ptr()), c_void_p(lo_rank.data_ptr()),
-                                                         c_void_p(hi_base.data_ptr()), c_void_p(Lp.data_ptr()),
-                                                         c_void_p(Xp.data_ptr()), c_void_p(piece.data_ptr()),
-                                                         c_void_p(scratch.data_ptr()), self._grid[0],
-                                                         engine._stream(self.device)),
-                      "dsea_hubbard_ladder_block_dots")
-                out[first:first + width] = piece
-        return out
 
 
 def one_body_density_matrix(op, psi, species, target=None):

@@ -1,7 +1,8 @@
 """Source invariants of the host layer of libdsea (read from the sources: no build, no GPU).  One HIP error path: the
 slot behind dsea_last_hip_error() is written by one function, and every hipGetLastError() of the two host files goes
 through it or is discarded on purpose.  One CG polling loop, and one predicate for the fused Lanczos tail.  The launchers: one
-dispatch rule per kernel family and each grid rule once.  The kernels: each defined in one file and launched from that file."""
+dispatch rule per kernel family and each grid rule once.  The kernels: each defined in one file and launched from that file.  The ladder maps:
+one host rule set for both families and one site walk in the sector file."""
 import glob
 import os
 import re
@@ -158,3 +159,75 @@ def test_each_kernel_is_defined_in_one_file_and_launched_from_that_file():
             if k in defined and defined[k] != [name]:
                 strays.append((name, k))
     assert not strays, strays
+
+
+# ---- the ladder maps (docs/design/38-ladder-parts.md): one host rule set for both families, one site walk per file ------
+LADDER_FILES = ("dsea_ladder.hip", "dsea_hubbard_ladder.hip")
+
+
+def enclosing_one_liner(text, needle):
+    """the name of the one-line function `... name(...) { ... needle ... }` that holds the needle"""
+    line = [ln for ln in code(text).splitlines() if needle in ln]
+    assert len(line) == 1, line
+    return re.match(r"(?:static |inline )*[\w:<>*&]+\s+(\w+)\(", line[0]).group(1)
+
+
+def test_the_ladder_grid_cap_range_is_tested_once():
+    hits = {name: len(re.findall(r"grid_log2\s*(?:>=|<)\s*6\b", code(text))) for name, text in sources().items()}
+    assert sum(hits.values()) == 1, {k: v for k, v in hits.items() if v}
+    assert enclosing_one_liner(sources()["dsea_internal.h"], "grid_log2 >= 6") == "ladder_grid_ok"
+
+
+def test_the_ladder_partial_count_is_stated_once():
+    """The scratch of the site forms and of the column dots: blocks of 256 rows, capped by DSEA_MAX_TFIM_BLOCKS, times the
+    terms.  Neither ladder file nor the C entries repeat it."""
+    src = sources()
+    files = LADDER_FILES + ("dsea_capi.hip", "dsea_internal.h")
+    rules = []
+    for name in files:
+        text = code(src[name])
+        for fn, a, b in function_spans(text):
+            if "+ 255) / 256" in text[a:b] and "DSEA_MAX_TFIM_BLOCKS" in text[a:b]:
+                rules.append((name, fn))
+    assert rules == [("dsea_internal.h", "ladder_partials")], rules
+    for name in LADDER_FILES + ("dsea_capi.hip",):
+        assert "DSEA_MAX_TFIM_BLOCKS" not in code(src[name]), name
+    # one grid rule too: the cap 2^grid_log2 is applied in one function, and no ladder file divides rows by 256 itself
+    shifts = [(name, fn) for name in files for fn in enclosing_functions(code(src[name]), "<< (grid_log2")]
+    assert shifts == [("dsea_internal.h", "ladder_blocks")], shifts
+    for name in LADDER_FILES:
+        assert "/ 256" not in host_code(src[name]), name
+
+
+def test_each_single_vector_ladder_kernel_has_one_launch_expression():
+    src = {name: code(text) for name, text in sources().items()}
+    for family in ("k_sector_ladder<", "k_sector_ladder_forms<", "k_hubbard_ladder<", "k_hubbard_ladder_forms<"):
+        hits = {name: text.count(family) for name, text in src.items() if family in text}
+        assert list(hits.values()) == [1], (family, hits)
+    # and the Hubbard (species, step) pair is picked through dispatch_int, not through a hand-written chain
+    text = src["dsea_hubbard_ladder.hip"]
+    spans = {name: text[a:b] for name, a, b in function_spans(text)}
+    assert spans["hubbard_ladder_dispatch"].count("dispatch_int<") == 2 and "integral_constant" not in text
+
+
+def test_the_sector_ladder_has_one_site_walk():
+    """The chunk is a template argument and the block helpers are the only helpers: no macro chunk, no second set of
+    functions, no sign helper beside block_signed -- in either ladder file."""
+    src = sources()
+    text = src["dsea_ladder.hip"]
+    assert "DSEA_LADDER_CHUNK" not in text
+    assert not re.findall(r"\bladder_block_\w*", text)
+    helpers = [name for name, _, _ in device_spans(code(text)) if name.startswith("ladder_")]
+    assert sorted(helpers) == ["ladder_group", "ladder_qualifies", "ladder_ranks", "ladder_row", "ladder_sites"], helpers
+    assert len(re.findall(r"\bint ladder_chunk\(\)", text)) == 1
+    # what remains twice: the diagonal row of Z(c), in ladder_row and spelled out in k_sector_ladder at STEP = 0, whose shared
+    # form missed the speed bar of the design note (38.6).  Every walk of the sites goes through ladder_sites, from ladder_row
+    # and from the forms kernel.
+    spans = {re.search(r"\b(?!__launch_bounds__)(\w+)\(", code(text)[a:b]).group(1): code(text)[a:b]    # (a kernel by its own name)
+             for _, a, b in device_spans(code(text))}
+    assert len(spans) == 5 + 5, sorted(spans)      # five helpers, five kernels
+    assert sorted(name for name, body in spans.items() if "diag +=" in body) == ["k_sector_ladder", "ladder_row"]
+    assert sorted(name for name, body in spans.items() if "ladder_sites<" in body) == ["k_sector_ladder_forms", "ladder_row"]
+    assert sorted(name for name, body in spans.items() if "ladder_group<" in body) == ["ladder_sites"]
+    for name in LADDER_FILES:
+        assert not re.findall(r"\bh?ladder_signed\b", src[name]) and "block_signed(" in src[name], name

@@ -293,3 +293,29 @@ def test_value_errors_that_need_no_device():
         lad.forms(x, x)                                     # v1 lives on the destination
     with pytest.raises(ValueError):
         lad(torch.zeros(8, dtype=torch.float64), x)         # host tensors: the map is a device kernel, there is no fallback
+
+
+def test_the_call_path_is_written_once_in_the_base():
+    """docs/design/38-ladder-parts.md: the two public classes carry no call path of their own, only the stem of their C entries
+    and the integers that open them -- as many as include/dsea.h (through _lib._SIGNATURES) declares before the first pointer."""
+    from ctypes import c_int
+
+    from dominantsparseeigenad_amd import _lib
+    from dominantsparseeigenad_amd.operators import HubbardLadder, _SectorLadderBase
+
+    shared = ("_apply_raw", "_forms_raw", "apply_block", "block_dots", "T")
+    for name in shared:
+        assert name in _SectorLadderBase.__dict__, name
+        for cls in (SpinSectorLadder, HubbardLadder):
+            assert name not in cls.__dict__, (cls.__name__, name)
+    cpu = torch.device("cpu")
+    hub = [types.SimpleNamespace(N=6, nup=nup, ndn=2, device=cpu, _up=(None,) * 3, _dn=(None,) * 3) for nup in (3, 4)]
+    for lad in (SpinSectorLadder(carrier(8, 4), carrier(8, 5)), HubbardLadder(*hub)):
+        args = lad._sector_args()
+        assert all(type(a) is int for a in args), args
+        assert type(lad.T) is type(lad) and lad.T._sector_args()[-1] == -args[-1] and lad.T.T is lad
+        for entry, extra in (("apply", 0), ("forms", 0), ("forms_scratch_doubles", 0), ("block_apply", 1), ("block_dots", 1),
+                             ("block_dots_scratch_doubles", 1)):                # (the block entries take the width next)
+            argtypes = _lib._SIGNATURES["%s_%s" % (lad._entry, entry)][1]
+            k = len(args) + extra
+            assert argtypes[:k] == [c_int] * k and argtypes[k] is not c_int, (lad._entry, entry)

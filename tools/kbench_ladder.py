@@ -5,6 +5,8 @@ two events, median (min - max) of five rounds), in one process:
     k_sector_ladder<+1>                        sigma^-(c) x, random weights
     k_sector_ladder_forms<+1> + reduce         all L site forms
     k_spmv_sector of the destination sector    the Heisenberg mat-vec that a spectral function applies k times
+    k_sector_ladder<-1>, <0> and k_sector_ladder_forms<-1>, <0> + reduce: the transposed ladder 13 -> 12 and Z(c) on ndown 12
+    (docs/design/38-ladder-parts.md), each checked against its forms like the first pair
 
 REPORTED ONLY, there is no bar: a spectral function applies the ladder once and the Hamiltonian k times.  GB/s on ALGORITHMIC
 bytes: 8 n_dst (states) + 8 n_src (x) + 8 n_dst (y) for the ladder, 8 n_dst + 8 n_dst + 8 n_src for the forms, 3 * 8 n_dst for
@@ -103,6 +105,25 @@ def main():
                 gathers_per_row=float(ndown + 1)),
             row("k_sector_ladder_forms<+1> + reduce (%d forms)" % L, tf, 8 * (2 * dst.n + src.n)),
             row("k_spmv_sector of the destination (%d bonds)" % nb, tm, 3 * 8 * dst.n)]
+    # the other two steps on the same tables: sigma^+(c) back from ndown + 1, and Z(c) within ndown
+    for step, a, b in ((-1, dst, src), (0, src, src)):
+        other = lad.T if step < 0 else SpinSectorLadder(src, src)
+        tabs = [_ptr(t) for t in other._tables]
+        _lib.check(lib.dsea_sector_ladder_forms_scratch_doubles(L, a.ndown, step, byref(cnt)), "scratch")
+        assert cnt.value <= scratch.numel()
+        xs = torch.randn(a.n, dtype=F64, device=dev, generator=gen)
+        vs = torch.randn(b.n, dtype=F64, device=dev, generator=gen)
+        ys = torch.empty(b.n, dtype=F64, device=dev)
+        apply_s = lambda: lib.dsea_sector_ladder_apply(L, a.ndown, step, _ptr(c), *tabs, _ptr(xs), _ptr(ys), 0, st)  # noqa: E731
+        forms_s = lambda: lib.dsea_sector_ladder_forms(L, a.ndown, step, *tabs, _ptr(vs), _ptr(xs), _ptr(out), _ptr(scratch),  # noqa: E731
+                                                       0, st)
+        assert apply_s() == 0 and forms_s() == 0
+        agree_s = abs(float(vs @ ys) - float(c @ out)) / float(vs.norm() * ys.norm())
+        assert agree_s < 1e-12, (step, agree_s)
+        rows.append(row("k_sector_ladder<%+d> (ndown %d -> %d)" % (step, a.ndown, b.ndown), timed(apply_s, args.reps, args.rounds),
+                        8 * (2 * b.n + a.n)))
+        rows.append(row("k_sector_ladder_forms<%+d> + reduce (%d forms)" % (step, L), timed(forms_s, reps2, args.rounds),
+                        8 * (2 * b.n + a.n)))
     rec = {"L": L, "ndown_src": ndown, "ndown_dst": ndown + 1, "n_src": src.n, "n_dst": dst.n, "bonds": nb, "reps": args.reps,
            "rounds": args.rounds, "device": torch.cuda.get_device_name(0), "agreement": agree, "kernels": rows,
            "ladder_over_matvec": rows[0]["us"] / rows[2]["us"], "forms_over_matvec": rows[1]["us"] / rows[2]["us"]}
