@@ -11,8 +11,10 @@ empty; users import sub-modules by name):
                                         Bipartition (reduced density matrices and entanglement entropies of their vectors)
                                         SpinSectorLadder (sigma^-, sigma^+ and Z maps between magnetisation sectors)
                                         HubbardLadder (c+, c and n maps between Hubbard sectors), one_body_density_matrix
+                                        HubbardCurrent (the bond current map of a Hubbard sector)
     dominantsparseeigenad_amd.spectral  lanczos_measure, SpectralMeasure, dynamical_structure_factor,
-                                        hubbard_spectral_function, kpm_measure, kpm_structure_factor (re-exported here)
+                                        hubbard_spectral_function, kpm_measure, kpm_structure_factor, optical_conductivity,
+                                        OpticalResponse (re-exported here)
     dominantsparseeigenad_amd.thermal   block_lanczos_measures, sector_trace_measure, ThermalEnsemble, spin_thermodynamics,
                                         GrandCanonicalEnsemble, hubbard_thermodynamics, thermal_correlations,
                                         thermal_dynamics, ThermalDynamics, hubbard_thermal_dynamics, HubbardThermalDynamics, sector_density_of_states, spin_density_of_states, hubbard_density_of_states (finite
@@ -31,7 +33,7 @@ __version__ = "0.1.0"
 def __getattr__(name):
     # the spectral functions under the package's own name, resolved on first use (the module imports torch and the engine)
     if name in ("spectral", "lanczos_measure", "SpectralMeasure", "dynamical_structure_factor",
-                "hubbard_spectral_function", "kpm_measure", "kpm_structure_factor"):
+                "hubbard_spectral_function", "kpm_measure", "kpm_structure_factor", "optical_conductivity", "OpticalResponse"):
         import importlib
         mod = importlib.import_module(__name__ + ".spectral")
         return mod if name == "spectral" else getattr(mod, name)

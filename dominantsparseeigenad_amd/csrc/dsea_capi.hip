@@ -2259,6 +2259,26 @@ int dsea_op_hubbard_block_moments(dsea_op_t op, int R, int M, double centre, dou
   return check_launch();
 }
 
+int dsea_op_hubbard_current_apply(dsea_op_t op, int R, const double* weights_dev, const double* X, double* Y, void* stream) {
+  REQUIRE(op && op->d.kind == OP_HUBBARD && block_width_ok(R) && weights_dev && X && Y && X != Y, DSEA_ERR_ARG);
+  REQUIRE(R == 1 || (aligned16(X) && aligned16(Y)), DSEA_ERR_ALIGN);
+  if (launch_hubbard_current(op->d, R, weights_dev, X, Y, static_cast<hipStream_t>(stream)) < 0) return DSEA_ERR_UNSUPPORTED;
+  return check_launch();
+}
+
+int dsea_op_hubbard_current_forms_scratch_doubles(int L, int nup, int ndn, int nb, int64_t* out) {
+  int64_t n, n_up, n_dn;
+  REQUIRE(out && hubbard_sizes(L, nup, ndn, &n, &n_up, &n_dn) && nb >= 1 && nb <= DSEA_LATTICE_MAX_BONDS, DSEA_ERR_ARG);
+  *out = ladder_partials(n, 2 * nb);
+  return DSEA_OK;
+}
+
+int dsea_op_hubbard_current_forms(dsea_op_t op, const double* v1, const double* v2, double* out, double* scratch, void* stream) {
+  REQUIRE(op && op->d.kind == OP_HUBBARD && v1 && v2 && out && scratch, DSEA_ERR_ARG);
+  if (launch_hubbard_current_forms(op->d, v1, v2, out, scratch, static_cast<hipStream_t>(stream)) != 0) return DSEA_ERR_UNSUPPORTED;
+  return check_launch();
+}
+
 // what the four launching entries of the Hubbard ladder refuse with DSEA_ERR_ARG besides their own operands: a species, a
 // step or a pair of sectors that hubbard_ladder_sizes refuses, a grid cap that ladder_grid_ok refuses, a null table.  The
 // entries that read the weights add them, the block entries a width outside {1, 2, 4, 8}.

@@ -647,6 +647,13 @@ int launch_hubbard_block_chebyshev(const OpDesc& op, int R, int A, int M, double
                                    const double* X, double* U, double* V, double* ACC, hipStream_t st);
 int launch_hubbard_block_moments(const OpDesc& op, int R, int M, double centre, double halfwidth, const double* X, const double* Y,
                                  double* U, double* V, double* MU, double* scratch, hipStream_t st);
+// dsea_hubbard_current.hip (the bond current map K(w) on the sector of an OP_HUBBARD descriptor,
+// docs/design/39-hubbard-current.md): Y = K(w) X for a block fp64 [n, R] row-major, R in {1, 2, 4, 8}, with w = [w_up(nb),
+// w_dn(nb)] on the device (column j is the same bits at every R; the callers check R), and the 2 nb forms v1^T K_{s t} v2 into
+// out through per-block partials in the caller's scratch (ladder_partials(n, 2 nb) doubles).  The couplings of the descriptor are
+// not read.  -1 when the descriptor is out of range.
+int launch_hubbard_current(const OpDesc& op, int R, const double* w, const double* X, double* Y, hipStream_t st);
+int launch_hubbard_current_forms(const OpDesc& op, const double* v1, const double* v2, double* out, double* scratch, hipStream_t st);
 // dsea_block_lanczos.hip (the basis-free block Lanczos recurrence for any operator; the device parts the block kernels share are
 // in dsea_block.h, docs/design/32-block-kernel-parts.md): the start and k steps with the per-column break record on nblk blocks
 // of 256 rows, three launches per step, nothing read back.  The mat-vec of a step is the caller's step(q, w, state, first, PA),

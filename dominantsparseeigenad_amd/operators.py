@@ -1890,6 +1890,10 @@ class HubbardOperator(_CouplingsOperator):
         """the site-weighted c+ / c / n maps of one species from this sector into the sector of ``dst`` (``HubbardLadder``)"""
         return HubbardLadder(self, dst, species)
 
+    def current(self):
+        """the bond current map K(w) of this sector, on this operator's tables, bonds and grid tuning (``HubbardCurrent``)"""
+        return HubbardCurrent(self)
+
     def to_csr(self, layout="sell", col16="auto", values="auto"):
         """The matrix as an explicit device CSR operand: the diagonal, and one entry per (row, species, distinct bond mask that
         moves a particle of that species in the row); bonds with equal masks are summed.  Built on the device with index
@@ -1925,6 +1929,166 @@ class HubbardOperator(_CouplingsOperator):
                 c_all.append(partner * n_dn + rd[moved] if up else ru[moved] * n_dn + partner)
                 v_all.append(amp * (1 - 2 * (par & 1)).to(F64))
         return _csr_from_coo(r_all, c_all, v_all, n, layout, col16, values)
+
+
+# ------------------------------------------------------------------------------------------ bond current of a Hubbard sector
+class HubbardCurrent:
+    """The bond-weighted current map of the sector of a ``HubbardOperator``, matrix-free (docs/design/39-hubbard-current.md):
+
+        K(w) = sum_t sum_s w[s, t] (c+_{a s} c_{b s} - c+_{b s} c_{a s}),      (a, b) = op.bonds[t] in the caller's orientation
+
+    real and antisymmetric in the state order of the operator; the current operator is J = i K(w).  Reversing a bond flips the
+    sign of its term, a repeated bond counts each time.  ``w`` is a real tensor of shape (2, nb), species 0 = up and 1 = dn; a
+    (nb,) vector is used for both species (the charge current; ``torch.stack([w, -w])`` is the spin current).  The object works
+    on the operator's sector, tables, bond list and grid tuning (``op.set_grid_log2``) and allocates no tables of its own; the
+    operator's couplings are not read.
+
+    ``cur(w, x)`` is K(w) x, differentiable to any order in w and in x: the map is bilinear and each of the two
+    ``autograd.Function``s is the other's derivative.  ``cur.forms(v1, v2)[s, t] = v1^T K_{s t} v2``, the bond-current matrix
+    elements of all 2 nb unit-weight maps in one pass (deterministic: fixed-order sums, no atomics).  There is no second object
+    for the transpose: K(w)^T = -K(w) = K(-w), so ``cur.T`` would be ``-cur`` and ``x . K(w) y = -y . K(w) x``.
+    ``apply_block(w, X)`` is the map on a block of columns (detached); ``dense(w)`` the n x n matrix, a test aid for small
+    sectors.  Every argument check is host arithmetic before the device is touched and raises ``ValueError``."""
+
+    _operand = ("N", "nup", "ndn", "nb", "n", "device", "bonds", "handle")
+
+    def __init__(self, op):
+        for attr in self._operand:
+            if not hasattr(op, attr):
+                raise ValueError("op carries no Hubbard sector (no attribute %r): a HubbardOperator is needed" % attr)
+        _check_hubbard(op.N, op.nup, op.ndn)
+        self.op = op
+        self.L = self.N = int(op.N)
+        self.nb = int(op.nb)
+        self.n = int(op.n)
+        self.device = torch.device(op.device)
+
+    @property
+    def bonds(self):
+        """the operator's bond list: the orientation (a, b) of bond t is the sign convention of w[:, t]"""
+        return self.op.bonds
+
+    def _weights(self, w):
+        """the weights as a real float64 (2, nb) tensor on the device; the graph of a tensor input is kept"""
+        if not torch.is_tensor(w):
+            w = torch.as_tensor(w, dtype=F64)
+        if w.is_complex():
+            raise ValueError("the bond weights must be real: apply the real and the imaginary part one after the other")
+        if tuple(w.shape) not in ((self.nb,), (2, self.nb)):
+            raise ValueError("expected bond weights of shape (2, %d) or (%d,), got %r" % (self.nb, self.nb, tuple(w.shape)))
+        if w.dtype != F64 or w.device != self.device:
+            w = w.to(device=self.device, dtype=F64)
+        return torch.stack([w, w]) if w.dim() == 1 else w
+
+    def _vector(self, v, what):
+        if not torch.is_tensor(v) or v.dim() != 1 or v.numel() != self.n:
+            raise ValueError("%s must be a vector of %d elements, got %s"
+                             % (what, self.n, tuple(v.shape) if torch.is_tensor(v) else type(v)))
+        if v.device != self.device:
+            raise ValueError("%s must live on %s, got %s" % (what, self.device, v.device))
+        if v.is_complex():
+            raise ValueError("%s must be real: apply the map to the real and the imaginary part one after the other" % what)
+        return v
+
+    def _block(self, X, what):
+        if not torch.is_tensor(X) or X.dim() != 2 or X.shape[0] != self.n or X.shape[1] < 1:
+            raise ValueError("%s must be a tensor of shape (%d, R) with R >= 1, got %r"
+                             % (what, self.n, tuple(X.shape) if torch.is_tensor(X) else type(X).__name__))
+        if X.device != self.device:
+            raise ValueError("%s must live on %s, got %s" % (what, self.device, X.device))
+        if X.is_complex():
+            raise ValueError("%s must be real: the real and the imaginary part are columns of one real block" % what)
+        return X.detach().to(F64)
+
+    def _launch_apply(self, w, R, X, Y):
+        with torch.cuda.device(self.device):
+            check(_lib.load().dsea_op_hubbard_current_apply(self.op.handle, R, c_void_p(w.data_ptr()), c_void_p(X.data_ptr()),
+                                                            c_void_p(Y.data_ptr()), engine._stream(self.device)),
+                  "dsea_op_hubbard_current_apply")
+
+    def _apply_raw(self, w, x):
+        w, x = engine.as_vector(w.reshape(-1), 2 * self.nb), engine.as_vector(x, self.n)
+        y = torch.empty(self.n, dtype=F64, device=self.device)
+        self._launch_apply(w, 1, x, y)
+        return y
+
+    def _forms_raw(self, v1, v2):
+        lib = _lib.load()
+        v1, v2 = engine.as_vector(v1, self.n), engine.as_vector(v2, self.n)
+        need = c_int64()
+        check(lib.dsea_op_hubbard_current_forms_scratch_doubles(self.N, int(self.op.nup), int(self.op.ndn), self.nb, byref(need)),
+              "dsea_op_hubbard_current_forms_scratch_doubles")
+        scratch = torch.empty(need.value, dtype=F64, device=self.device)
+        out = torch.empty((2, self.nb), dtype=F64, device=self.device)
+        with torch.cuda.device(self.device):
+            check(lib.dsea_op_hubbard_current_forms(self.op.handle, c_void_p(v1.data_ptr()), c_void_p(v2.data_ptr()),
+                                                    c_void_p(out.data_ptr()), c_void_p(scratch.data_ptr()),
+                                                    engine._stream(self.device)), "dsea_op_hubbard_current_forms")
+        return out
+
+    def __call__(self, w, x):
+        """the vector K(w) x, differentiable in w and in x"""
+        return _CurrentApply.apply(self._weights(w), self._vector(x, "x"), self)
+
+    def forms(self, v1, v2):
+        """out[s, t] = v1^T K_{s t} v2 for every species and bond, shape (2, nb); differentiable.  ``forms(v, v)`` is 0."""
+        return _CurrentForms.apply(self._vector(v1, "v1"), self._vector(v2, "v2"), self)
+
+    def apply_block(self, w, X):
+        """K(w) X for a device tensor X of shape (n, R), any R >= 1, in blocks of 8, 4, 2 and 1 columns
+        (dsea_op_hubbard_current_apply).  Column j equals ``cur(w, X[:, j])`` bit for bit; a row's division, state words and
+        table reads are made once for all columns of a block.  Detached, not differentiable."""
+        from .chebyshev import _aligned_piece
+        from .thermal import block_pieces
+        w = engine.as_vector(self._weights(w).detach().reshape(-1), 2 * self.nb)
+        X = self._block(X, "X")
+        out = []
+        for first, width in block_pieces(X.shape[1]):
+            Yp = torch.empty((self.n, width), dtype=F64, device=self.device)
+            self._launch_apply(w, width, _aligned_piece(X, first, width), Yp)
+            out.append(Yp)
+        return out[0] if len(out) == 1 else torch.cat(out, dim=1)
+
+    def dense(self, w):
+        """the n x n matrix of ``cur(w, .)``, by applying the map to the columns of the identity (small sectors)"""
+        return self.apply_block(w, torch.eye(self.n, dtype=F64, device=self.device))
+
+
+class _CurrentApply(torch.autograd.Function):
+    """y = K(w) x.  Bilinear and antisymmetric: with the cotangent gy, w-bar = forms(gy, x) and x-bar = K(w)^T gy = -K(w) gy --
+    both re-entrant."""
+
+    @staticmethod
+    def forward(ctx, w, x, cur):
+        ctx.cur = cur
+        ctx.save_for_backward(w, x)
+        return cur._apply_raw(w.detach(), x.detach())
+
+    @staticmethod
+    def backward(ctx, gy):
+        w, x = ctx.saved_tensors
+        gw = _CurrentForms.apply(gy, x, ctx.cur) if ctx.needs_input_grad[0] else None
+        gx = -_CurrentApply.apply(w, gy, ctx.cur) if ctx.needs_input_grad[1] else None
+        return gw, gx, None
+
+
+class _CurrentForms(torch.autograd.Function):
+    """out[s, t] = v1^T K_{s t} v2, shape (2, nb).  K is linear in the weights, so with the cotangent G as weights
+    v1-bar = K(G) v2 and v2-bar = K(G)^T v1 = -K(G) v1."""
+
+    @staticmethod
+    def forward(ctx, v1, v2, cur):
+        ctx.cur = cur
+        ctx.save_for_backward(v1, v2)
+        return cur._forms_raw(v1.detach(), v2.detach())
+
+    @staticmethod
+    def backward(ctx, G):
+        v1, v2 = ctx.saved_tensors
+        G = G.reshape(2, ctx.cur.nb)
+        g1 = _CurrentApply.apply(G, v2, ctx.cur) if ctx.needs_input_grad[0] else None
+        g2 = -_CurrentApply.apply(G, v1, ctx.cur) if ctx.needs_input_grad[1] else None
+        return g1, g2, None
 
 
 # ------------------------------------------------------------------------------------------ c / c+ between two Hubbard sectors

@@ -284,3 +284,90 @@ def kpm_structure_factor(op0, psi0, E0, weights, channel, M=256, target=None, bo
     if bounds is None:
         bounds = spectral_bounds(target)
     return ChebyshevMeasure(chebyshev_moments(target, Phi, M, bounds).sum(dim=1), bounds).shifted(float(E0))
+
+
+class OpticalResponse:
+    """What ``optical_conductivity`` returns: plain host numbers, not differentiable (docs/design/39-hubbard-current.md).
+
+        measure          the ``SpectralMeasure`` of K(w) psi0 in omega = E_n - E0: sum_j w_j delta(omega - theta_j)
+        diamagnetic      K_d = sum_t t_t d_t^2 <c+_a c_b + h.c.>_t summed over the species
+        inverse_moment   I_-1 = sum_{theta_j > floor} w_j / theta_j
+        dropped_weight   the weight of the poles at or below ``floor``, which I_-1 leaves out (a degenerate ground level, or
+                         a current that does not leave the ground state)
+        stiffness        K_d - 2 I_-1 = d^2 E0 / d phi^2 under the Peierls twist t_t -> t_t exp(i phi d_t)
+
+    Convention (no volume factor, e = hbar = 1): sigma(omega) = pi stiffness delta(omega) + sigma_reg(omega) on the whole axis,
+    so the Drude weight in the usual convention is pi * stiffness, and
+
+        sigma_reg(omega) = pi sum_j (w_j / theta_j) delta(omega - theta_j)        for omega > 0,
+
+    ``regular(omega, eta)`` with every delta a Lorentzian of half width eta.  Then int_0^inf sigma_reg = pi I_-1 and the f-sum
+    rule reads  pi stiffness / 2 + pi I_-1 = pi K_d / 2  (``f_sum()`` returns the two sides)."""
+
+    def __init__(self, measure, diamagnetic, floor=1e-9):
+        self.measure = measure
+        self.diamagnetic = float(diamagnetic)
+        self.floor = float(floor)
+        keep = measure.poles > self.floor
+        self._poles = measure.poles[keep]
+        self._strengths = measure.weights[keep] / self._poles
+        self.inverse_moment = float(self._strengths.sum())
+        self.dropped_weight = float(measure.weights[~keep].sum())
+        self.stiffness = self.diamagnetic - 2.0 * self.inverse_moment
+
+    def regular(self, omega, eta):
+        """sigma_reg(omega) = pi sum_j (w_j / theta_j) eta / (pi ((omega - theta_j)^2 + eta^2)) over the poles above the floor,
+        for a real tensor (or number) omega; a host float64 tensor of the shape of omega"""
+        omega = torch.as_tensor(omega, dtype=F64).detach().cpu()
+        eta = float(eta)
+        if not eta > 0.0:
+            raise ValueError("regular needs eta > 0, got %r" % eta)
+        diff = omega.unsqueeze(-1) - self._poles
+        return (self._strengths * eta / (diff * diff + eta * eta)).sum(dim=-1)
+
+    def f_sum(self):
+        """(pi stiffness / 2 + pi I_-1, pi K_d / 2): the two sides of the f-sum rule"""
+        return math.pi * self.stiffness / 2.0 + math.pi * self.inverse_moment, math.pi * self.diamagnetic / 2.0
+
+    def __repr__(self):
+        return ("OpticalResponse(K_d = %.10g, I_-1 = %.10g, stiffness = %.10g, dropped_weight = %.3g, %d poles)"
+                % (self.diamagnetic, self.inverse_moment, self.stiffness, self.dropped_weight, len(self.measure)))
+
+
+def optical_conductivity(op0, psi0, E0, displacements, kind="charge", k=200, basis_free=False, floor=1e-9):
+    """The optical response of the eigenstate (psi0, E0) of the ``HubbardOperator`` ``op0`` to a uniform field, as an
+    ``OpticalResponse`` (docs/design/39-hubbard-current.md): the regular part of sigma(omega), its f-sum rule and Kohn's
+    stiffness from ONE application of the bond current map (``HubbardCurrent``), one Lanczos measure in the same sector and the
+    bond kinetic energies of ``op0.Hadjoint_to_couplingsadjoint``.
+
+    ``displacements``: a real (nb,) vector d_t, the projection of r_b - r_a of bond t = (a, b) of ``op0.bonds`` on the field
+    direction.  On a periodic cluster it must be the MINIMUM IMAGE (the bond (L - 1, 0) of a ring has d = +1, not 1 - L): that
+    is the caller's duty, the function cannot know the geometry.  The current weights are w[s, t] = t_t d_t for
+    ``kind="charge"`` and w[up] = t_t d_t, w[dn] = -t_t d_t for ``kind="spin"``, with the hoppings t_t read from
+    ``op0.couplings``; the paramagnetic current is J = i K(w) and the measure is that of K(w) psi0, ``k`` Lanczos steps
+    (``lanczos_measure``), or the basis-free recurrence of ``thermal.block_lanczos_measures`` with ``basis_free=True``.  Poles at
+    or below ``floor`` are left out of the inverse moment and reported as ``dropped_weight``: with a degenerate ground level
+    the stiffness of this formula is not defined.  Plain numbers: not differentiable."""
+    from .operators import HubbardCurrent, HubbardOperator
+    if not isinstance(op0, HubbardOperator):
+        raise ValueError("optical_conductivity works on a HubbardOperator, got %s" % type(op0).__name__)
+    if kind not in ("charge", "spin"):
+        raise ValueError("kind must be 'charge' or 'spin', got %r" % (kind,))
+    d = torch.as_tensor(displacements)
+    if d.is_complex() or d.dim() != 1 or d.numel() != op0.nb:
+        raise ValueError("displacements must be a real vector of %d elements (one per bond), got shape %r"
+                         % (op0.nb, tuple(d.shape)))
+    d = d.detach().to(device=op0.device, dtype=F64)
+    psi0 = psi0.detach()
+    hop = op0.couplings.detach()[:op0.nb]
+    wt = hop * d
+    cur = HubbardCurrent(op0)
+    phi = cur(torch.stack([wt, wt if kind == "charge" else -wt]), psi0).detach()
+    if basis_free:
+        from .thermal import block_lanczos_measures
+        measure = block_lanczos_measures(op0, phi.reshape(-1, 1), k)[0]
+    else:
+        measure = lanczos_measure(op0, phi, k)
+    kinetic = op0.Hadjoint_to_couplingsadjoint(psi0, psi0).detach()[:op0.nb]       # dE0/dt_t = -<c+_a c_b + h.c.>
+    diamagnetic = -float((hop * d * d * kinetic).sum())
+    return OpticalResponse(measure.shifted(float(E0)), diamagnetic, floor)

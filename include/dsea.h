@@ -1148,6 +1148,28 @@ int dsea_hubbard_ladder_block_dots(int L, int nup_src, int ndn_src, int species,
                                    const double *Lft /* [n_dst,R] */, const double *X /* [n_src,R] */, double *out_dev /* [R] */,
                                    double *scratch, int grid_log2, void *stream);
 
+/* ------------------------------------------------------------------ Hubbard bond current map (docs/design/39-hubbard-current.md)
+ * The bond-weighted, real antisymmetric map K(w) = sum_t sum_s w_{s t} (c+_{a s} c_{b s} - c+_{b s} c_{a s}) on the sector of
+ * an operator of dsea_op_create_hubbard, (a, b) = bond t in the orientation given at creation; the current operator is J = i K(w).
+ * It works on the operator's sector, tables, bond list and grid cap (dsea_op_set_tuning) and does not read its couplings.
+ * Reversing a bond flips its sign, a repeated bond counts each time, K(w)^T = -K(w).  weights_dev: fp64 [2 nb] on the device, the
+ * up weights then the down weights, READ THROUGH THE POINTER ON EVERY LAUNCH.
+ * dsea_op_hubbard_current_apply: Y = K(w) X for a block fp64 [n, R] row-major (element (r, j) at r * R + j), R in {1, 2, 4, 8};
+ * blocks with R >= 2 must be 16-byte aligned (DSEA_ERR_ALIGN otherwise; the argument checks come first).  Every product is
+ * exact (the signs go into the sign bit of the weight) and column j of Y is the same bits at every R.
+ * dsea_op_hubbard_current_forms: out[s * nb + t] = v1^T K_{s t} v2 for all 2 nb unit-weight bond maps (s = 0 up, 1 dn) in one
+ * pass: the adjoint of the map in its weights.  Wave and block sums in fixed order into per-block partials in `scratch`, then
+ * one block per form: no floating-point atomics, repeated calls return identical bits.  `scratch`: caller-owned,
+ * dsea_op_hubbard_current_forms_scratch_doubles = 2 nb * min(4096, ceil(n / 256)) doubles (enough for every grid cap).
+ * Nothing is allocated, read back or synchronised.  Refused by host arithmetic before any device work (DSEA_ERR_ARG): an
+ * operator of another kind; R outside {1, 2, 4, 8}; X == Y; a null op, weights_dev, X, Y, v1, v2, out, scratch; in the query a
+ * sector that dsea_hubbard_sizes refuses or nb outside 1 .. DSEA_LATTICE_MAX_BONDS. */
+int dsea_op_hubbard_current_apply(dsea_op_t op, int R, const double *weights_dev /* [2 nb]: up then dn */,
+                                  const double *X /* [n,R] */, double *Y /* [n,R] */, void *stream);
+int dsea_op_hubbard_current_forms_scratch_doubles(int L, int nup, int ndn, int nb, int64_t *out);
+int dsea_op_hubbard_current_forms(dsea_op_t op, const double *v1, const double *v2, double *out /* [2 nb] */,
+                                  double *scratch, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
