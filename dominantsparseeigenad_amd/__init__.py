@@ -17,7 +17,7 @@ empty; users import sub-modules by name):
                                         OpticalResponse (re-exported here)
     dominantsparseeigenad_amd.thermal   block_lanczos_measures, sector_trace_measure, ThermalEnsemble, spin_thermodynamics,
                                         GrandCanonicalEnsemble, hubbard_thermodynamics, thermal_correlations,
-                                        thermal_dynamics, ThermalDynamics, hubbard_thermal_dynamics, HubbardThermalDynamics, sector_density_of_states, spin_density_of_states, hubbard_density_of_states (finite
+                                        thermal_dynamics, ThermalDynamics, hubbard_thermal_dynamics, HubbardThermalDynamics, hubbard_thermal_conductivity, ThermalOpticalResponse, sector_density_of_states, spin_density_of_states, hubbard_density_of_states (finite
                                         temperature; re-exported here)
     dominantsparseeigenad_amd.chebyshev chebyshev_coefficients, exp_order, spectral_bounds, chebyshev_apply, expm_block,
                                         time_evolve (f(H) X without a basis), chebyshev_moments, jackson_kernel,
@@ -40,7 +40,8 @@ def __getattr__(name):
     if name in ("thermal", "block_lanczos_measures", "sector_trace_measure", "ThermalEnsemble", "spin_thermodynamics",
                 "GrandCanonicalEnsemble", "hubbard_thermodynamics", "thermal_correlations", "sector_density_of_states",
                 "spin_density_of_states", "hubbard_density_of_states", "thermal_dynamics", "ThermalDynamics",
-                "hubbard_thermal_dynamics", "HubbardThermalDynamics"):
+                "hubbard_thermal_dynamics", "HubbardThermalDynamics", "hubbard_thermal_conductivity",
+                "ThermalOpticalResponse"):
         import importlib
         mod = importlib.import_module(__name__ + ".thermal")
         return mod if name == "thermal" else getattr(mod, name)

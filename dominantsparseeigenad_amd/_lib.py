@@ -149,6 +149,8 @@ _SIGNATURES = {
     "dsea_op_hubbard_current_apply": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dsea_op_hubbard_current_forms_scratch_doubles": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_int64)]),
     "dsea_op_hubbard_current_forms": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dsea_op_hubbard_current_block_dots_scratch_doubles": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_int64)]),
+    "dsea_op_hubbard_current_block_dots": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dsea_hubbard_sizes": (c_int,[c_int, c_int, c_int, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)]),
     "dsea_op_create_hubbard": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_int32), c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_void_p, c_void_p, POINTER(c_void_p)]),

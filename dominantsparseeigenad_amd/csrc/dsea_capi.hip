@@ -2279,6 +2279,22 @@ int dsea_op_hubbard_current_forms(dsea_op_t op, const double* v1, const double* 
   return check_launch();
 }
 
+int dsea_op_hubbard_current_block_dots_scratch_doubles(int L, int nup, int ndn, int R, int64_t* out) {
+  int64_t n, n_up, n_dn;
+  REQUIRE(out && hubbard_sizes(L, nup, ndn, &n, &n_up, &n_dn) && block_width_ok(R), DSEA_ERR_ARG);
+  *out = ladder_partials(n, R);
+  return DSEA_OK;
+}
+
+int dsea_op_hubbard_current_block_dots(dsea_op_t op, int R, const double* weights_dev, const double* Lft, const double* X,
+                                       double* out_dev, double* scratch, void* stream) {
+  REQUIRE(op && op->d.kind == OP_HUBBARD && block_width_ok(R) && weights_dev && Lft && X && out_dev && scratch, DSEA_ERR_ARG);
+  REQUIRE(R == 1 || (aligned16(Lft) && aligned16(X)), DSEA_ERR_ALIGN);
+  if (launch_hubbard_current_block_dots(op->d, R, weights_dev, Lft, X, out_dev, scratch, static_cast<hipStream_t>(stream)) != 0)
+    return DSEA_ERR_UNSUPPORTED;
+  return check_launch();
+}
+
 // what the four launching entries of the Hubbard ladder refuse with DSEA_ERR_ARG besides their own operands: a species, a
 // step or a pair of sectors that hubbard_ladder_sizes refuses, a grid cap that ladder_grid_ok refuses, a null table.  The
 // entries that read the weights add them, the block entries a width outside {1, 2, 4, 8}.

@@ -1,6 +1,6 @@
 // dsea_hubbard_current.hip -- the bond current map of the Hubbard sector of dsea_hubbard.hip (docs/design/39-hubbard-current.md):
-// the kernel k_hubbard_current<R>, the parameter adjoint k_hubbard_current_forms (+ k_hubbard_current_forms_reduce), and their
-// launchers.
+// the kernel k_hubbard_current<R>, the parameter adjoint k_hubbard_current_forms (+ k_hubbard_current_forms_reduce), the column
+// dots k_hubbard_current_block_dots<R> (docs/design/40-finite-temperature-conductivity.md), and their launchers.
 //
 //   K(w) = sum_t sum_s w_{s t} (c+_{a s} c_{b s} - c+_{b s} c_{a s}),   (a, b) = bond t in the caller's orientation,   J = i K(w)
 // real and antisymmetric on the sector (L, nup, ndn) of the operator, in its state order and on its tables.  With the notation
@@ -176,6 +176,72 @@ __global__ __launch_bounds__(256) void k_hubbard_current(HubbardCurrentParams p,
   }
 }
 
+// The column dots d[j] = sum_r Lft[r, j] (K(w) X)[r, j] without the product block (docs/design/40-finite-temperature-conductivity.md):
+// the row walk of k_hubbard_current<R>, written again here so that kernel keeps its instructions -- the same staging, chunks,
+// look-ahead and fma chain, so sum[j] is the bits that kernel stores.  The row of Lft is read after the last chunk's gathers are
+// consumed; one accumulator per column and thread over the row ranges the block walks (a thread without a row adds nothing), then
+// block_partials into scratch[j * gridDim.x + block].  k_hubbard_current_forms_reduce with R blocks closes them.  No atomics.
+template <int R>
+__global__ __launch_bounds__(256) void k_hubbard_current_block_dots(HubbardCurrentParams p, const double* __restrict__ Lft,
+                                                                    const double* __restrict__ x, double* __restrict__ scratch) {
+  __shared__ double wp[2 * DSEA_LATTICE_MAX_BONDS];
+  __shared__ uint64_t bm[DSEA_LATTICE_MAX_BONDS];
+  __shared__ uint16_t tb[DSEA_LATTICE_MAX_BONDS];
+  __shared__ double sm[R][4];
+  constexpr int CH = HcurChunk<R>::value;
+  constexpr int HOPS = 2 * CH;
+  const int nb = p.nb;
+  const int64_t n = p.n;
+  for (int c = threadIdx.x; c < 2 * nb; c += 256) wp[c] = p.w[c];
+  hcur_stage_bonds(p, tb, bm);
+  __syncthreads();
+  const double* __restrict__ wu = wp;
+  const double* __restrict__ wd = wp + nb;
+  double acc[R];
+#pragma unroll
+  for (int j = 0; j < R; ++j) acc[j] = 0.0;
+  for (int64_t row0 = (int64_t)blockIdx.x * 256; row0 < n; row0 += (int64_t)gridDim.x * 256) {
+    const int64_t r = row0 + threadIdx.x;
+    const bool have = r < n;                       // (a thread past the last row reads row n - 1 and adds nothing)
+    const uint32_t rr = (uint32_t)(have ? r : n - 1);
+    const uint32_t ru = rr / p.n_dn, rd = rr - ru * p.n_dn;
+    const uint64_t u = p.up_states[ru], d = p.dn_states[rd];
+    uint32_t hi[HOPS], lo[HOPS];
+    uint32_t on = hcur_lookups<CH>(hi, lo, u, d, have, 0, p, tb);
+    double sum[R];
+#pragma unroll
+    for (int j = 0; j < R; ++j) sum[j] = 0.0;
+    for (int k0 = 0; k0 < nb; k0 += CH) {
+      uint32_t rw[HOPS];
+      double xv[HOPS][R];
+      hcur_rows<CH>(rw, on, hi, lo, ru, rd, p.n_dn);
+      hcur_gather<R, HOPS>(xv, rw, x);
+      on = hcur_lookups<CH>(hi, lo, u, d, have, k0 + CH, p, tb);
+#pragma unroll
+      for (int e = 0; e < CH; ++e) {
+        if (k0 + e < nb) {
+          const uint32_t w = tb[k0 + e];
+          const uint64_t between = bm[k0 + e];
+          const double tu = block_signed(wu[k0 + e], hcur_negative(u, w, between));
+          const double td = block_signed(wd[k0 + e], hcur_negative(d, w, between));
+#pragma unroll
+          for (int j = 0; j < R; ++j) {
+            sum[j] = fma(tu, xv[2 * e][j], sum[j]);
+            sum[j] = fma(td, xv[2 * e + 1][j], sum[j]);
+          }
+        }
+      }
+    }
+    if (have) {
+      double l[R];
+      block_load<R>(l, Lft, r);
+#pragma unroll
+      for (int j = 0; j < R; ++j) acc[j] = fma(l[j], sum[j], acc[j]);
+    }
+  }
+  block_partials<R>(acc, sm, scratch);
+}
+
 // The parameter adjoint: out[s nb + t] = v1^T K_{s t} v2 for all 2 nb unit-weight bond maps (s = 0 up, 1 dn) in one pass over v1
 // and v2:
 //   up, t: sum_r v1[r] o_t(u) sgn_t(u) v2[up partner]          dn, t: sum_r v1[r] o_t(d) sgn_t(d) v2[dn partner]
@@ -281,6 +347,19 @@ int launch_hubbard_current_forms(const OpDesc& op, const double* v1, const doubl
   const int nblk = block_blocks(op);
   klaunch(nullptr, k_hubbard_current_forms, nblk, 256, 0, st, p, v1, v2, scratch);
   klaunch(nullptr, k_hubbard_current_forms_reduce, 2 * p.nb, 256, 0, st, scratch, nblk, out);
+  return 0;
+}
+
+// block_blocks(op) partials per column: at most ladder_partials(n, R) doubles of scratch at any grid cap; the caller has checked R
+int launch_hubbard_current_block_dots(const OpDesc& op, int R, const double* w, const double* Lft, const double* X, double* out,
+                                      double* scratch, hipStream_t st) {
+  HubbardCurrentParams p;
+  if (!w || !hubbard_current_params(op, w, &p)) return -1;
+  const int nblk = block_blocks(op);
+  dispatch_block_width(R, [&](auto r) {
+    klaunch(nullptr, k_hubbard_current_block_dots<decltype(r)::value>, nblk, 256, 0, st, p, Lft, X, scratch);
+  });
+  klaunch(nullptr, k_hubbard_current_forms_reduce, R, 256, 0, st, scratch, nblk, out);
   return 0;
 }
 

@@ -654,6 +654,11 @@ int launch_hubbard_block_moments(const OpDesc& op, int R, int M, double centre, 
 // not read.  -1 when the descriptor is out of range.
 int launch_hubbard_current(const OpDesc& op, int R, const double* w, const double* X, double* Y, hipStream_t st);
 int launch_hubbard_current_forms(const OpDesc& op, const double* v1, const double* v2, double* out, double* scratch, hipStream_t st);
+// The column dots (docs/design/40-finite-temperature-conductivity.md): out[j] = sum_r Lft[r, j] (K(w) X)[r, j] through per-block
+// partials in the caller's scratch (ladder_partials(n, R) doubles), without the product block; Lft == X is allowed.  0, or -1
+// when the descriptor is out of range; the caller has checked R.
+int launch_hubbard_current_block_dots(const OpDesc& op, int R, const double* w, const double* Lft, const double* X, double* out,
+                                      double* scratch, hipStream_t st);
 // dsea_block_lanczos.hip (the basis-free block Lanczos recurrence for any operator; the device parts the block kernels share are
 // in dsea_block.h, docs/design/32-block-kernel-parts.md): the start and k steps with the per-column break record on nblk blocks
 // of 256 rows, three launches per step, nothing read back.  The mat-vec of a step is the caller's step(q, w, state, first, PA),

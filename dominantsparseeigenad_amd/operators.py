@@ -2049,6 +2049,37 @@ class HubbardCurrent:
             out.append(Yp)
         return out[0] if len(out) == 1 else torch.cat(out, dim=1)
 
+    def block_dots(self, w, Lft, X):
+        """d[j] = sum_r Lft[r, j] (K(w) X)[r, j] as a device tensor [R], for Lft and X of shape (n, R), any R >= 1: the column
+        dots of ``Lft`` with ``apply_block(w, X)`` without the product block (dsea_op_hubbard_current_block_dots,
+        docs/design/40-finite-temperature-conductivity.md; in blocks of 8, 4, 2 and 1 columns; fixed-order sums, identical calls
+        return identical bits).  ``Lft`` may be ``X``: the dots are then 0 up to rounding.  Detached, not differentiable."""
+        from .chebyshev import _aligned_piece
+        from .thermal import block_pieces
+        w = self._weights(w)
+        X = self._block(X, "X")
+        Lft = self._block(Lft, "Lft")
+        if Lft.shape[1] != X.shape[1]:
+            raise ValueError("Lft and X must have the same number of columns, got %d and %d" % (Lft.shape[1], X.shape[1]))
+        w = engine.as_vector(w.detach().reshape(-1), 2 * self.nb)
+        lib = _lib.load()
+        out = torch.empty(X.shape[1], dtype=F64, device=self.device)
+        for first, width in block_pieces(X.shape[1]):
+            need = c_int64()
+            check(lib.dsea_op_hubbard_current_block_dots_scratch_doubles(self.N, int(self.op.nup), int(self.op.ndn), width,
+                                                                         byref(need)),
+                  "dsea_op_hubbard_current_block_dots_scratch_doubles")
+            scratch = torch.empty(need.value, dtype=F64, device=self.device)
+            piece = torch.empty(width, dtype=F64, device=self.device)
+            Lp, Xp = _aligned_piece(Lft, first, width), _aligned_piece(X, first, width)
+            with torch.cuda.device(self.device):
+                check(lib.dsea_op_hubbard_current_block_dots(self.op.handle, width, c_void_p(w.data_ptr()), c_void_p(Lp.data_ptr()),
+                                                             c_void_p(Xp.data_ptr()), c_void_p(piece.data_ptr()),
+                                                             c_void_p(scratch.data_ptr()), engine._stream(self.device)),
+                      "dsea_op_hubbard_current_block_dots")
+            out[first:first + width] = piece
+        return out
+
     def dense(self, w):
         """the n x n matrix of ``cur(w, .)``, by applying the map to the columns of the identity (small sectors)"""
         return self.apply_block(w, torch.eye(self.n, dtype=F64, device=self.device))

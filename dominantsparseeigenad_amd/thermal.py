@@ -28,6 +28,10 @@ through the three-term recurrence at once as one [n, R] block, on the block mat-
     hubbard_thermal_dynamics(L, bonds, couplings, weights, channel, betas, mus, dt, steps, ...)   the same for the Hubbard model
                                                        and A = sum_i w_i c_{i s}, c+_{i s}, n_i or 2 S^z_i at every (beta, mu): the
                                                        one-particle A(k, omega; T) (docs/design/37-hubbard-finite-temperature-dynamics.md)
+    hubbard_thermal_conductivity(L, bonds, couplings, displacements, betas, mus, dt, steps, ...)   <J(t) J> and the diamagnetic
+                                                       term K_d of the Hubbard model at every (beta, mu): sigma_reg(omega; T), its
+                                                       weight and the thermodynamic stiffness, the block current map and its
+                                                       column dots in between (docs/design/40-finite-temperature-conductivity.md)
 
 Plain host float64 numbers: nothing here is differentiable.
 """
@@ -1094,3 +1098,228 @@ def hubbard_thermal_dynamics(L, bonds, couplings, weights, channel, betas, mus, 
     prob = torch.exp(logw - logXi)
     correlation = sum(prob[s][:, :, None] * out[s][1][:, None, :] for s in range(len(out)))
     return HubbardThermalDynamics(betas, mus, times, logXi, correlation)
+
+
+# ------------------------------------------------------------------------------------------ finite-temperature conductivity
+class ThermalOpticalResponse:
+    """What ``hubbard_thermal_conductivity`` returns (docs/design/40-finite-temperature-conductivity.md), host tensors:
+    ``betas`` [B], ``mus`` [M], ``times`` [K + 1] with t_k = k dt, ``logXi`` [B, M], ``correlation`` [B, M, K + 1] (complex128),
+    C(t_k; beta, mu) = tr[e^{-beta (H - mu N)} K^T(t_k) K] / Xi = <J(t_k) J> for the current J = i K(w), and ``diamagnetic``
+    [B, M], K_d = <sum_t t_t d_t^2 sum_s (c+_{a s} c_{b s} + h.c.)>.  No volume factor, e = hbar = 1.  Plain numbers: not
+    differentiable."""
+
+    def __init__(self, betas, mus, times, logXi, correlation, diamagnetic):
+        self.betas, self.mus, self.times, self.logXi = betas, mus, times, logXi
+        self.correlation, self.diamagnetic = correlation, diamagnetic
+
+    def static(self):
+        """C(0).real [B, M]: the equal-time value <K^T K> = <J J>"""
+        return self.correlation[:, :, 0].real.clone()
+
+    def spectrum(self, omega, eta):
+        """S_eta(omega) [B, M, len omega]: the Gaussian-windowed transform of ``ThermalDynamics.spectrum`` of C at every
+        (beta, mu), (1 / 2 pi) int dt e^{i omega t} C(t) e^{-(eta t)^2 / 2}: a pair of levels with E_m - E_n = eps becomes a Gaussian
+        of width ``eta`` at omega = eps.  THE CALLER picks dt and K: eta t_K >= 8, so that the window has decayed where the record
+        ends, and pi / dt well above the band width, so that the trapezoid sum does not alias."""
+        omega = torch.as_tensor(omega, dtype=F64).detach().cpu().reshape(-1)
+        B, M, K1 = self.correlation.shape
+        return _windowed_spectrum(self.times, self.correlation.reshape(B * M, K1), omega, eta).reshape(B, M, -1)
+
+    def regular(self, omega, eta):
+        """sigma_reg(omega) [B, M, len omega] = pi g_beta(omega) S_eta(omega), g_beta(omega) = (1 - e^{-beta omega}) / omega (beta at
+        omega = 0, 0 at beta = 0), even in omega.  Pairs of levels with E_m = E_n carry the weight beta p_n |K_mn|^2 at omega = 0:
+        the part of the Drude weight above the stiffness.  It is NOT separated: the broadened ``regular`` contains it as a
+        Gaussian of width ``eta`` around omega = 0, and so do ``weight`` and ``stiffness``."""
+        omega = torch.as_tensor(omega, dtype=F64).detach().cpu().reshape(-1)
+        x = self.betas[:, None] * omega[None, :]                                        # [B, W]
+        safe = torch.where(omega == 0, torch.ones_like(omega), omega)
+        g = torch.where(omega[None, :] == 0, self.betas[:, None].expand_as(x), -torch.expm1(-x) / safe[None, :])
+        return math.pi * g[:, None, :] * self.spectrum(omega, eta)
+
+    def weight(self, omega, eta):
+        """[B, M]: the trapezoid sum of ``regular`` over the caller's uniform ascending grid ``omega`` (at least two points),
+        int sigma_reg d omega = pi X.  THE CALLER picks the grid: a spacing well below ``eta`` and a range that covers the band of
+        excitations on both sides of omega = 0 by several ``eta`` AND NO MORE: at omega < 0 g_beta = (e^{beta |omega|} - 1) / |omega|
+        multiplies S, which is e^{-beta |omega|} small there, and with it the rounding of the transform (about 1e-16 C(0)); a grid
+        that reaches beta |omega| = 37 has lost every digit."""
+        omega = torch.as_tensor(omega, dtype=F64).detach().cpu().reshape(-1)
+        if omega.numel() < 2:
+            raise ValueError("weight needs a grid of at least two frequencies")
+        step = omega[1:] - omega[:-1]
+        h = float(step[0])
+        if not (h > 0 and bool(((step - h).abs() <= 1e-9 * abs(h)).all())):
+            raise ValueError("weight needs a uniform ascending grid of frequencies")
+        sigma = self.regular(omega, eta)
+        return h * (sigma.sum(dim=-1) - 0.5 * (sigma[..., 0] + sigma[..., -1]))
+
+    def stiffness(self, omega, eta):
+        """[B, M]: K_d - weight / pi, the second derivative d^2 F / d phi^2 of the free energy F = -ln Xi / beta at fixed mu
+        under the Peierls twist t_t -> t_t e^{i phi d_t} (the f-sum rule: pi K_d = pi stiffness + int sigma_reg), with the grid
+        duties of ``weight``"""
+        return self.diamagnetic - self.weight(omega, eta) / math.pi
+
+
+def _current_weights(w, nb):
+    """host float64 (2, nb) from a (2, nb) tensor or a (nb,) vector used for both species"""
+    w = torch.as_tensor(w, dtype=F64).detach().cpu()
+    if tuple(w.shape) == (nb,):
+        w = torch.stack([w, w])
+    if tuple(w.shape) != (2, nb):
+        raise ValueError("expected bond weights of shape (2, %d) or (%d,), got %r" % (nb, nb, tuple(w.shape)))
+    return w
+
+
+def _one_species_current_matrix(L, bonds, w, count):
+    """the host matrix of sum_t w_t (c+_a c_b - c+_b c_a) of one species with ``count`` particles on ``sector_states``: the row
+    of a word with differing bits at a_t and b_t holds w_t o_t sgn_t at the column of the word with both flipped (o_t = +1 if
+    bit a_t is set, else -1; sgn_t the parity of the particles strictly between).  An empty or full species: 0."""
+    from .operators import sector_states
+    states = sector_states(L, count)
+    rank = {word: r for r, word in enumerate(states)}
+    K = torch.zeros((len(states), len(states)), dtype=F64)
+    w = w.tolist()
+    for t, (a, b) in enumerate(bonds):
+        lo, hi = min(a, b), max(a, b)
+        between = ((1 << hi) - 1) & ~((1 << (lo + 1)) - 1)
+        for r, word in enumerate(states):
+            if ((word >> a) ^ (word >> b)) & 1:
+                o = 1.0 if (word >> a) & 1 else -1.0
+                sgn = -1.0 if bin(word & between).count("1") & 1 else 1.0
+                K[r, rank[word ^ ((1 << a) | (1 << b))]] += w[t] * o * sgn
+    return K
+
+
+def _dense_hubbard_current_matrix(L, nup, ndn, bonds, w):
+    """the n x n host matrix of K(w) on the sector (nup, ndn), rows r = ru * n_dn + rd on ``operators.sector_states`` of both
+    species (edge sectors included): K_up(w_up) x 1 + 1 x K_dn(w_dn), each factor with the sign o_t sgn_t of
+    docs/design/39-hubbard-current.md section 39.2; an empty or full species contributes 0.  Equal to -K^T bit for bit."""
+    w = _current_weights(w, len(bonds))
+    n_up, n_dn = math.comb(L, nup), math.comb(L, ndn)
+    return (torch.kron(_one_species_current_matrix(L, bonds, w[0], nup), torch.eye(n_dn, dtype=F64))
+            + torch.kron(torch.eye(n_up, dtype=F64), _one_species_current_matrix(L, bonds, w[1], ndn)))
+
+
+def _dense_hubbard_diamagnetic_matrix(L, nup, ndn, bonds, td2):
+    """the n x n host matrix of T_d = sum_t td2_t sum_s (c+_{a s} c_{b s} + h.c.) on the rows of ``_dense_hubbard_current_matrix``:
+    T_up x 1 + 1 x T_dn, each factor ``one_species_matrix`` with the couplings [-td2, 0, 0, 0] (V = U = eps = 0, so that
+    Hamiltonian is T_d exactly); both species frozen: 0"""
+    nb = len(bonds)
+    c_d = torch.cat([-torch.as_tensor(td2, dtype=F64).detach().cpu(), torch.zeros(nb + 2 * L, dtype=F64)])
+    n_up, n_dn = math.comb(L, nup), math.comb(L, ndn)
+    T_up = one_species_matrix(L, bonds, c_d, nup, False)
+    T_dn = one_species_matrix(L, bonds, c_d, ndn, False)
+    return torch.kron(T_up, torch.eye(n_dn, dtype=F64)) + torch.kron(torch.eye(n_up, dtype=F64), T_dn)
+
+
+def _tpq_diamagnetic(op, td2, betas, R, seed, tol):
+    """K_d [B] of a sampled sector: a pass over ``_tpq_states`` with the seed and the bounds of ``_tpq_block_dynamics`` (hence
+    the same states); at every beta column j gives -sum_t td2_t Hadjoint_to_couplingsadjoint(phi_j, phi_j)[t] (the bond kinetic
+    energies: dH / dt_t = -(hop_t + h.c.)), weighted by the column weights w_j like ``energy`` in ``_tpq_sector_correlations``"""
+    from .chebyshev import spectral_bounds
+    nb = td2.numel()
+    rows = []
+    for Phi, _, _, w, _ in _tpq_states(op, betas, R, seed, tol, spectral_bounds(op, seed=seed)):
+        cols = []
+        for j in range(R):
+            phi = Phi[:, j].contiguous()
+            cols.append(-(td2 * op.Hadjoint_to_couplingsadjoint(phi, phi).detach()[:nb].cpu()).sum())
+        rows.append((w * torch.stack(cols)).sum() / w.sum())
+    return torch.stack(rows)
+
+
+def hubbard_thermal_conductivity(L, bonds, couplings, displacements, betas, mus, dt, steps, kind="charge", R=8, seed=0,
+                                 dense_below=256, sectors=None, edge_dense_max=4096, tol=1e-15, device=None):
+    """The finite-temperature optical response of the Hubbard model of ``hubbard_thermodynamics`` (parameter order [t(nb), V(nb),
+    U(L), eps(L)]) to a uniform field (docs/design/40-finite-temperature-conductivity.md): a ``ThermalOpticalResponse`` with
+
+        C(t_k; beta, mu) = (1 / Xi) sum_s e^{beta mu N_s} tr_s[ e^{-beta H} e^{i H t_k} K^T e^{-i H t_k} K ] = <J(t_k) J>,   t_k = k dt
+        K_d(beta, mu)    = < sum_t t_t d_t^2 sum_s (c+_{a s} c_{b s} + h.c.) >
+
+    at the ascending inverse temperatures ``betas`` >= 0 and the chemical potentials ``mus``, for the current J = i K(w) of
+    ``HubbardCurrent`` with w = t_t d_t on both species (``kind="charge"``) or +t_t d_t on up and -t_t d_t on dn
+    (``kind="spin"``), the hoppings t_t read from ``couplings[:nb]``.  ``displacements``: a real (nb,) vector d_t, the projection
+    of r_b - r_a of bond t on the field direction, on a periodic cluster the MINIMUM IMAGE -- the caller's duty, as in
+    ``spectral.optical_conductivity``.  From the result, sigma_reg(omega) = pi g_beta(omega) S(omega) (``regular``), its integral
+    (``weight``) and d^2 F / d phi^2 = K_d - weight / pi (``stiffness``).
+
+    ``sectors`` lists the pairs (nup, ndn), default all (L + 1)^2; K keeps both counts, so every sector maps to itself, and
+    every mu comes from one sweep, combined by a log-sum-exp of log weight + beta mu N.  An edge sector (a species empty or
+    full, which ``HubbardOperator`` refuses) and a bulk sector of at most ``dense_below`` rows are exact on the host: the
+    spectrum from ``one_species_matrix`` or from ``apply_block`` on identity columns, K and T_d from ``operators.sector_states``
+    with the fermion signs.  An edge sector above ``edge_dense_max`` rows raises ``ValueError`` before any sector is computed.
+    A larger bulk sector is sampled by the R thermal pure quantum states of ``thermal_correlations`` (start vectors
+    ``normal_vector(n, seed + j)``): a_0 = K |beta, j> by ``HubbardCurrent.apply_block``, both stepped by ``chebyshev.time_evolve``,
+    C_j(t_k) = <K b_k,j | a_k,j> by ``HubbardCurrent.block_dots`` on the (re | im) blocks, and K_d from the bond kinetic energies
+    of the same states in a second pass.  The error of a sampled sector is the sampling error of R vectors; it is not
+    estimated.  Plain numbers: not differentiable."""
+    from .operators import HubbardCurrent, HubbardOperator
+    what = "hubbard_thermal_conductivity"
+    if kind not in ("charge", "spin"):
+        raise ValueError("kind must be 'charge' or 'spin', got %r" % (kind,))
+    L, bonds, c, sectors, device = _hubbard_model(what, L, bonds, couplings, sectors, edge_dense_max, device)
+    nb = len(bonds)
+    d = torch.as_tensor(displacements)
+    if d.is_complex() or d.dim() != 1 or d.numel() != nb:
+        raise ValueError("displacements must be a real vector of %d elements (one per bond), got shape %r" % (nb, tuple(d.shape)))
+    d = d.detach().cpu().to(F64)
+    if not bool(torch.isfinite(d).all()):
+        raise ValueError("displacements must be finite")
+    betas = torch.as_tensor(betas, dtype=F64).detach().cpu().reshape(-1)
+    if betas.numel() < 1 or not bool(torch.isfinite(betas).all()) or bool((betas < 0).any()) or bool((betas[1:] < betas[:-1]).any()):
+        raise ValueError("betas must be finite, >= 0 and ascending")
+    mus = torch.as_tensor(mus, dtype=F64).detach().cpu().reshape(-1)
+    if mus.numel() < 1 or not bool(torch.isfinite(mus).all()):
+        raise ValueError("mus must be at least one finite chemical potential")
+    dt, steps, R = float(dt), int(steps), int(R)
+    if not (dt > 0 and math.isfinite(dt)):
+        raise ValueError("%s needs a finite dt > 0, got %r" % (what, dt))
+    if steps < 0:
+        raise ValueError("%s needs steps >= 0, got %d" % (what, steps))
+    if R < 1:
+        raise ValueError("%s needs R >= 1" % what)
+    times = dt * torch.arange(steps + 1, dtype=F64)
+    host = c.cpu()
+    hop = host[:nb]
+    wt = hop * d
+    w = torch.stack([wt, wt if kind == "charge" else -wt])
+    td2 = hop * d * d
+    is_edge = lambda pair: pair[0] in (0, L) or pair[1] in (0, L)              # noqa: E731
+    rows = lambda pair: math.comb(L, pair[0]) * math.comb(L, pair[1])           # noqa: E731
+    on_device = [None]
+    out = []
+    for pair in sectors:
+        nup, ndn = pair
+        if is_edge(pair) or rows(pair) <= int(dense_below):
+            if nup in (0, L) and ndn in (0, L):
+                spec = (one_species_matrix(L, bonds, host, nup, ndn == L).reshape(1), torch.ones((1, 1), dtype=F64))
+            elif is_edge(pair):
+                count, frozen = (ndn, nup) if nup in (0, L) else (nup, ndn)
+                spec = torch.linalg.eigh(one_species_matrix(L, bonds, host, count, frozen == L))
+            else:
+                if on_device[0] is None:
+                    on_device[0] = c.to(device)
+                op = HubbardOperator(L, bonds, on_device[0], nup, ndn, device)
+                spec = torch.linalg.eigh(_dense_sector_matrix(op))
+                del op
+            logweight, C = _dense_pair_dynamics(spec, spec, [_dense_hubbard_current_matrix(L, nup, ndn, bonds, w)], betas, times)
+            theta, V = spec
+            kinetic = torch.einsum("rn,rs,sn->n", V, _dense_hubbard_diamagnetic_matrix(L, nup, ndn, bonds, td2), V)
+            prob = torch.exp(-betas[:, None] * theta[None, :] - logweight[:, None])
+            out.append((logweight, C, prob @ kinetic))
+        else:
+            if on_device[0] is None:
+                on_device[0] = c.to(device)
+            op = HubbardOperator(L, bonds, on_device[0], nup, ndn, device)
+            cur = HubbardCurrent(op)
+            logweight, C = _tpq_block_dynamics(op, op, cur.apply_block, lambda w_, Lft, X: cur.block_dots(w_, Lft, X).cpu(),
+                                               [w.to(device)], betas, dt, steps, R, seed, tol)
+            out.append((logweight, C, _tpq_diamagnetic(op, td2, betas, R, seed, tol)))
+            del cur, op
+    logw = torch.stack([p[0] for p in out])                                 # [sectors, B]
+    N = torch.tensor([float(a + b) for a, b in sectors], dtype=F64)
+    logw = logw[:, :, None] + betas[None, :, None] * mus[None, None, :] * N[:, None, None]      # [sectors, B, M]
+    logXi = torch.logsumexp(logw, dim=0)
+    prob = torch.exp(logw - logXi)
+    correlation = sum(prob[s][:, :, None] * out[s][1][:, None, :] for s in range(len(out)))
+    diamagnetic = sum(prob[s] * out[s][2][:, None] for s in range(len(out)))
+    return ThermalOpticalResponse(betas, mus, times, logXi, correlation, diamagnetic)

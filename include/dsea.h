@@ -1170,6 +1170,23 @@ int dsea_op_hubbard_current_forms_scratch_doubles(int L, int nup, int ndn, int n
 int dsea_op_hubbard_current_forms(dsea_op_t op, const double *v1, const double *v2, double *out /* [2 nb] */,
                                   double *scratch, void *stream);
 
+/* ------------------------------------------------------------------ Hubbard current column dots (docs/design/40-finite-temperature-conductivity.md)
+ * out_dev[j] = sum_r Lft[r, j] (K(w) X)[r, j] for the R columns of two blocks fp64 [n, R] row-major of the operator's sector, K(w)
+ * the map of the section above with the same weights_dev [2 nb], without the product block K X: the rows of K X are formed as
+ * dsea_op_hubbard_current_apply forms them (the same bits) and multiplied into the row of Lft at once.  Wave and block sums in
+ * fixed order into per-block partials in `scratch`, then one block per column: no floating-point atomics, repeated calls return
+ * identical bits, and column j of an R = 8 call equals the R = 1 call on that column bit for bit.  Lft == X is allowed (both are
+ * only read; the result is then 0 up to rounding, K being antisymmetric).  `scratch`: caller-owned,
+ * dsea_op_hubbard_current_block_dots_scratch_doubles = R * min(4096, ceil(n / 256)) doubles (enough for every grid cap).
+ * Nothing is allocated, read back or synchronised.  Refused by host arithmetic before any device work (DSEA_ERR_ARG): an
+ * operator of another kind; R outside {1, 2, 4, 8}; a null op, weights_dev, Lft, X, out_dev or scratch; in the query a sector
+ * that dsea_hubbard_sizes refuses, R outside {1, 2, 4, 8} or a null out.  With R >= 2, Lft and X must be 16-byte aligned
+ * (DSEA_ERR_ALIGN otherwise; the argument checks come first). */
+int dsea_op_hubbard_current_block_dots_scratch_doubles(int L, int nup, int ndn, int R, int64_t *out);
+int dsea_op_hubbard_current_block_dots(dsea_op_t op, int R, const double *weights_dev /* [2 nb]: up then dn */,
+                                       const double *Lft /* [n,R] */, const double *X /* [n,R] */, double *out_dev /* [R] */,
+                                       double *scratch, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
