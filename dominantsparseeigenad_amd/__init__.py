@@ -12,8 +12,10 @@ empty; users import sub-modules by name):
                                         SpinSectorLadder (sigma^-, sigma^+ and Z maps between magnetisation sectors)
                                         HubbardLadder (c+, c and n maps between Hubbard sectors), one_body_density_matrix
                                         HubbardCurrent (the bond current map of a Hubbard sector)
+                                        HubbardPairLadder (pair and spin-flip maps between Hubbard sectors), pair_correlations,
+                                        onsite_pairing, bond_pairing, total_spin
     dominantsparseeigenad_amd.spectral  lanczos_measure, SpectralMeasure, dynamical_structure_factor,
-                                        hubbard_spectral_function, kpm_measure, kpm_structure_factor, optical_conductivity,
+                                        hubbard_spectral_function, hubbard_pair_spectral_function, kpm_measure, kpm_structure_factor, optical_conductivity,
                                         OpticalResponse (re-exported here)
     dominantsparseeigenad_amd.thermal   block_lanczos_measures, sector_trace_measure, ThermalEnsemble, spin_thermodynamics,
                                         GrandCanonicalEnsemble, hubbard_thermodynamics, thermal_correlations,
@@ -33,7 +35,7 @@ __version__ = "0.1.0"
 def __getattr__(name):
     # the spectral functions under the package's own name, resolved on first use (the module imports torch and the engine)
     if name in ("spectral", "lanczos_measure", "SpectralMeasure", "dynamical_structure_factor",
-                "hubbard_spectral_function", "kpm_measure", "kpm_structure_factor", "optical_conductivity", "OpticalResponse"):
+                "hubbard_spectral_function", "hubbard_pair_spectral_function", "kpm_measure", "kpm_structure_factor", "optical_conductivity", "OpticalResponse"):
         import importlib
         mod = importlib.import_module(__name__ + ".spectral")
         return mod if name == "spectral" else getattr(mod, name)

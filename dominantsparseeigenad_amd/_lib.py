@@ -128,6 +128,11 @@ _SIGNATURES = {
     "dsea_hubbard_ladder_block_dots_scratch_doubles": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_int64)]),
     "dsea_hubbard_ladder_block_dots": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                                c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "dsea_hubbard_pair_apply": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "dsea_hubbard_pair_forms_scratch_doubles": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_int64)]),
+    "dsea_hubbard_pair_forms": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "dsea_op_sector_block_apply": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "dsea_op_sector_block_lanczos_scratch_doubles": (c_int, [c_int, c_int, c_int, POINTER(c_int64)]),
     "dsea_op_sector_block_lanczos": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -2379,4 +2379,50 @@ int dsea_hubbard_ladder_block_dots(int L, int nup_src, int ndn_src, int species,
   return check_launch();
 }
 
+// what the two launching entries of the Hubbard pair map refuse with DSEA_ERR_ARG besides their own operands: steps, an order
+// or a pair of sectors that hubbard_pair_sizes refuses, a grid cap that ladder_grid_ok refuses, a null table
+static inline bool hubbard_pair_args_ok(int L, int nup_src, int ndn_src, int step_up, int step_dn, int order, int grid_log2,
+                                        const void* const tables[6]) {
+  int64_t n_src, n_dst, n_dn_src, n_dn_dst;
+  bool ok = hubbard_pair_sizes(L, nup_src, ndn_src, step_up, step_dn, order, &n_src, &n_dst, &n_dn_src, &n_dn_dst) &&
+            ladder_grid_ok(grid_log2);
+  for (int t = 0; t < 6; ++t) ok = ok && tables[t];
+  return ok;
+}
+
+int dsea_hubbard_pair_apply(int L, int nup_src, int ndn_src, int step_up, int step_dn, int order, const double* weights_dev,
+                            const int64_t* up_states_dst, const int32_t* up_lo_rank_src, const int32_t* up_hi_base_src,
+                            const int64_t* dn_states_dst, const int32_t* dn_lo_rank_src, const int32_t* dn_hi_base_src,
+                            const double* x, double* y, int grid_log2, void* stream) {
+  const void* const tables[6] = {up_states_dst, up_lo_rank_src, up_hi_base_src, dn_states_dst, dn_lo_rank_src, dn_hi_base_src};
+  REQUIRE(hubbard_pair_args_ok(L, nup_src, ndn_src, step_up, step_dn, order, grid_log2, tables) && weights_dev && x && y &&
+              x != y,
+          DSEA_ERR_ARG);
+  if (launch_hubbard_pair(L, nup_src, ndn_src, step_up, step_dn, order, weights_dev, tables, x, y, grid_log2,
+                          static_cast<hipStream_t>(stream)) != 0)
+    return DSEA_ERR_ARG;
+  return check_launch();
+}
+
+int dsea_hubbard_pair_forms_scratch_doubles(int L, int nup_src, int ndn_src, int step_up, int step_dn, int order, int64_t* out) {
+  int64_t n_src, n_dst, n_dn_src, n_dn_dst;
+  REQUIRE(out && hubbard_pair_sizes(L, nup_src, ndn_src, step_up, step_dn, order, &n_src, &n_dst, &n_dn_src, &n_dn_dst),
+          DSEA_ERR_ARG);
+  *out = ladder_partials(n_dst, L * L);
+  return DSEA_OK;
+}
+
+int dsea_hubbard_pair_forms(int L, int nup_src, int ndn_src, int step_up, int step_dn, int order, const int64_t* up_states_dst,
+                            const int32_t* up_lo_rank_src, const int32_t* up_hi_base_src, const int64_t* dn_states_dst,
+                            const int32_t* dn_lo_rank_src, const int32_t* dn_hi_base_src, const double* v1, const double* v2,
+                            double* out, double* scratch, int grid_log2, void* stream) {
+  const void* const tables[6] = {up_states_dst, up_lo_rank_src, up_hi_base_src, dn_states_dst, dn_lo_rank_src, dn_hi_base_src};
+  REQUIRE(hubbard_pair_args_ok(L, nup_src, ndn_src, step_up, step_dn, order, grid_log2, tables) && v1 && v2 && out && scratch,
+          DSEA_ERR_ARG);
+  if (launch_hubbard_pair_forms(L, nup_src, ndn_src, step_up, step_dn, order, tables, v1, v2, out, scratch, grid_log2,
+                                static_cast<hipStream_t>(stream)) != 0)
+    return DSEA_ERR_ARG;
+  return check_launch();
+}
+
 }  // extern "C"

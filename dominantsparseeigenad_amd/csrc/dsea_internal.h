@@ -606,6 +606,21 @@ int launch_hubbard_ladder_block_dots(int L, int nup_src, int ndn_src, int specie
                                      const uint64_t* states_dst, const uint32_t* lo_rank_src, const uint32_t* hi_base_src,
                                      const double* Lft, const double* X, double* out, double* scratch, int grid_log2,
                                      hipStream_t st);
+// dsea_hubbard_pair.hip (linear maps that move one particle of each species between two Hubbard sectors,
+// docs/design/41-hubbard-pair-ladder.md): sum_ij W_ij A_{i up} B_{j dn} (order 0; order 1 is the down operator left, the negative)
+// from (L, nup_src, ndn_src) to (nup_src + step_up, ndn_src + step_dn), A, B = c+ for a step of +1 and c for -1, as a gather
+// over the destination rows; W fp64 [L, L] on the device.  tables: for the up and then for the down species, the state table at
+// its destination count and lo_rank, hi_base at its source count.  The L^2 site-pair forms v1^T (dP/dW_ij) v2 go into out
+// through per-block partials in the caller's scratch (ladder_partials(n_dst, L * L) doubles).  The grid rules are those of the
+// ladder files above.  hubbard_pair_sizes is false, and the launchers return -1, for a step that is not +-1, an order outside
+// {0, 1}, a sector outside the limits of hubbard_sizes, a grid_log2 that ladder_grid_ok refuses, or a null table.
+bool hubbard_pair_sizes(int L, int nup_src, int ndn_src, int step_up, int step_dn, int order, int64_t* n_src, int64_t* n_dst,
+                        int64_t* n_dn_src, int64_t* n_dn_dst);
+int launch_hubbard_pair(int L, int nup_src, int ndn_src, int step_up, int step_dn, int order, const double* W,
+                        const void* const tables[6], const double* x, double* y, int grid_log2, hipStream_t st);
+int launch_hubbard_pair_forms(int L, int nup_src, int ndn_src, int step_up, int step_dn, int order,
+                              const void* const tables[6], const double* v1, const double* v2, double* out, double* scratch,
+                              int grid_log2, hipStream_t st);
 // dsea_sector_block.hip (the bond-list sector Hamiltonian on a block of R vectors, docs/design/27-finite-temperature.md): a block is
 // fp64 [n, R] row-major, R in {1, 2, 4, 8}.  launch_sector_block_apply: Y = H X (column j bit for bit the single-vector mat-vec).
 // launch_sector_block_lanczos: block_lanczos_drive (below) with the file's Lanczos-step kernel as the mat-vec.  The launchers

@@ -2210,6 +2210,219 @@ def one_body_density_matrix(op, psi, species, target=None):
     return C @ C.T
 
 
+# ------------------------------------------------------------------------------------------ pair and spin-flip maps between two Hubbard sectors
+_PAIR_ORDERS = {"up_left": 0, "dn_left": 1}
+
+
+class _NotOffered:
+    """a method of the base class that a subclass does not have (its C entries do not exist): reading it is an AttributeError"""
+
+    def __set_name__(self, owner, name):
+        self._what = "%s has no %s" % (owner.__name__, name)
+
+    def __get__(self, obj, owner=None):
+        raise AttributeError(self._what)
+
+
+class HubbardPairLadder(_SectorLadderBase):
+    """The maps that move one particle of EACH species between two particle-number sectors of the Hubbard space of the same L
+    sites in one pass, matrix-free (docs/design/41-hubbard-pair-ladder.md).  ``src`` and ``dst`` are ``HubbardOperator`` objects
+    (anything that carries the species tables, as for ``HubbardLadder``) with the same L on the same device and
+    (dst.nup - src.nup, dst.ndn - src.ndn) one of (+-1, +-1).  With A = c+ where the up count grows and c where it shrinks, B
+    likewise for the down species, and a real weight matrix W (L, L) -- an (L,) vector means its diagonal --
+
+        order="up_left":  lad(W, x) = sum_ij W_ij A_{i up} B_{j dn} x        order="dn_left":  sum_ij W_ij B_{j dn} A_{i up} x
+
+    (the second is the negative of the first) as a vector of the destination sector, fermion signs of the ordering convention of
+    ``HubbardOperator`` included.  (+1, +1) is the pair creation field, (-1, -1) pair annihilation, (+1, -1) and (-1, +1) the
+    spin flips c+_{i up} c_{j dn} and c_{i up} c+_{j dn}.  ``lad.T`` is the map dst -> src with the other order on the same tables
+    and ``lad.T(W, .)`` the exact transpose of ``lad(W, .)``: the transpose of sum W_ij c+_{i up} c+_{j dn} is sum W_ij c_{j dn}
+    c_{i up}.  ``lad.forms(v1, v2)[i, j] = v1^T (d lad / d W_ij) v2`` for all L^2 site pairs in one pass (v1 on the destination, v2
+    on the source; deterministic).  Both are differentiable to any order in W and in the vectors: the map is bilinear and each of
+    the two ``autograd.Function``s is the other's derivative.  ``dense(W)`` is the n_dst x n_src matrix, a test aid for small
+    sectors.  There are no block forms.  Every argument check is host arithmetic before the device is touched and raises
+    ``ValueError``."""
+
+    _entry = "dsea_hubbard_pair"
+    _operand = HubbardLadder._operand
+    _no_operand = HubbardLadder._no_operand
+    apply_block = _NotOffered()
+    block_dots = _NotOffered()
+
+    def __init__(self, src, dst, order="up_left", _transpose=None):
+        self._pair(src, dst, _transpose)
+        if order not in _PAIR_ORDERS:
+            raise ValueError("order must be 'up_left' or 'dn_left', got %r" % (order,))
+        dup, ddn = int(dst.nup) - int(src.nup), int(dst.ndn) - int(src.ndn)
+        if dup not in (-1, 1) or ddn not in (-1, 1):
+            raise ValueError("a pair map changes the count of each species by +1 or -1, got (nup, ndn) = (%d, %d) -> (%d, %d)"
+                             % (src.nup, src.ndn, dst.nup, dst.ndn))
+        self.order, self.steps = order, (dup, ddn)
+        self.n_src = math.comb(self.L, int(src.nup)) * math.comb(self.L, int(src.ndn))
+        self.n_dst = math.comb(self.L, int(dst.nup)) * math.comb(self.L, int(dst.ndn))
+        # per species: states of dst, rank tables of src -- kept alive
+        self._tables = (dst._up[0], src._up[1], src._up[2], dst._dn[0], src._dn[1], src._dn[2])
+
+    _check_operand = HubbardLadder._check_operand
+
+    def _transpose_args(self):
+        return ("dn_left" if self.order == "up_left" else "up_left",)
+
+    def _sector_args(self):
+        return self.L, int(self.src.nup), int(self.src.ndn), self.steps[0], self.steps[1], _PAIR_ORDERS[self.order]
+
+    def _weights(self, W):
+        if not torch.is_tensor(W):
+            W = torch.as_tensor(W, dtype=F64)
+        if W.is_complex():
+            raise ValueError("the pair weights must be real: apply the real and the imaginary part one after the other")
+        if W.dim() == 1 and W.numel() == self.L:
+            W = torch.diag(W)
+        if tuple(W.shape) != (self.L, self.L):
+            raise ValueError("expected pair weights of shape (%d, %d) or (%d,), got %r" % (self.L, self.L, self.L, tuple(W.shape)))
+        if W.dtype != F64 or W.device != self.device:
+            W = W.to(device=self.device, dtype=F64)
+        return W
+
+    def _apply_raw(self, W, x):
+        W, x = engine.as_vector(W.reshape(-1), self.L * self.L), engine.as_vector(x, self.n_src)
+        y = torch.empty(self.n_dst, dtype=F64, device=x.device)
+        self._launch("apply", (W,), (x, y))
+        return y
+
+    def _forms_raw(self, v1, v2):
+        v1, v2 = engine.as_vector(v1, self.n_dst), engine.as_vector(v2, self.n_src)
+        out = torch.empty((self.L, self.L), dtype=F64, device=v1.device)
+        self._launch("forms", (), (v1, v2, out, self._scratch("forms")))
+        return out
+
+    def __call__(self, W, x):
+        """the vector sum_ij W_ij O_ij x of the destination sector, differentiable in W and in x"""
+        return _PairApply.apply(self._weights(W), self._vector(x, self.n_src, "x"), self)
+
+    def forms(self, v1, v2):
+        """out[i, j] = v1^T O_ij v2 for every site pair, shape (L, L): v1 on the destination, v2 on the source; differentiable"""
+        return _PairForms.apply(self._vector(v1, self.n_dst, "v1"), self._vector(v2, self.n_src, "v2"), self)
+
+
+class _PairApply(torch.autograd.Function):
+    """y = P(W) x.  Bilinear: with the cotangent gy, W-bar = forms(gy, x) and x-bar = P(W)^T gy, the transposed map on the same
+    tables -- both re-entrant."""
+
+    @staticmethod
+    def forward(ctx, W, x, lad):
+        ctx.lad = lad
+        ctx.save_for_backward(W, x)
+        return lad._apply_raw(W.detach(), x.detach())
+
+    @staticmethod
+    def backward(ctx, gy):
+        W, x = ctx.saved_tensors
+        gW = _PairForms.apply(gy, x, ctx.lad) if ctx.needs_input_grad[0] else None
+        gx = _PairApply.apply(W, gy, ctx.lad.T) if ctx.needs_input_grad[1] else None
+        return gW, gx, None
+
+
+class _PairForms(torch.autograd.Function):
+    """out[i, j] = v1^T (dP/dW_ij) v2, shape (L, L).  P is linear in the weights, so with the cotangent G as weights
+    v1-bar = P(G) v2 and v2-bar = P(G)^T v1."""
+
+    @staticmethod
+    def forward(ctx, v1, v2, lad):
+        ctx.lad = lad
+        ctx.save_for_backward(v1, v2)
+        return lad._forms_raw(v1.detach(), v2.detach())
+
+    @staticmethod
+    def backward(ctx, G):
+        v1, v2 = ctx.saved_tensors
+        g1 = _PairApply.apply(G, v2, ctx.lad) if ctx.needs_input_grad[0] else None
+        g2 = _PairApply.apply(G, v1, ctx.lad.T) if ctx.needs_input_grad[1] else None
+        return g1, g2, None
+
+
+def onsite_pairing(L, signs=None):
+    """the (L, L) weights of the on-site pair field sum_i s_i c+_{i up} c+_{i dn}: diag(signs), the identity for ``signs=None``
+    (s-wave); signs = (-1)^i on a bipartite lattice is the eta pair.  A float64 host tensor (pure torch, no device)."""
+    L = int(L)
+    if L < 1:
+        raise ValueError("onsite_pairing needs L >= 1")
+    if signs is None:
+        return torch.eye(L, dtype=F64)
+    s = torch.as_tensor(signs, dtype=F64)
+    if tuple(s.shape) != (L,):
+        raise ValueError("expected %d signs, got shape %r" % (L, tuple(s.shape)))
+    return torch.diag(s)
+
+
+def bond_pairing(L, bonds, amplitudes):
+    """the (L, L) weights of the singlet pair field sum_t amp_t (c+_{a up} c+_{b dn} + c+_{b up} c+_{a dn}) / sqrt(2) over the
+    bonds t = (a, b): W_ab = W_ba = amp_t / sqrt(2), summed over bonds that name the same pair.  Equal amplitudes give the
+    extended-s field, +1 on the x bonds and -1 on the y bonds of a square lattice the d-wave field.  Differentiable in
+    ``amplitudes``; on their device (pure torch)."""
+    L = int(L)
+    bonds = [(int(a), int(b)) for a, b in bonds]
+    for a, b in bonds:
+        if not (0 <= a < L and 0 <= b < L) or a == b:
+            raise ValueError("a bond joins two different sites of 0 .. %d, got (%d, %d)" % (L - 1, a, b))
+    amp = torch.as_tensor(amplitudes)
+    if amp.is_complex() or tuple(amp.shape) != (len(bonds),):
+        raise ValueError("expected %d real amplitudes (one per bond), got shape %r" % (len(bonds), tuple(amp.shape)))
+    amp = amp.to(F64) / math.sqrt(2.0)
+    a = torch.tensor([a for a, _ in bonds] + [b for _, b in bonds], dtype=torch.int64, device=amp.device)
+    b = torch.tensor([b for _, b in bonds] + [a for a, _ in bonds], dtype=torch.int64, device=amp.device)
+    return torch.zeros((L, L), dtype=F64, device=amp.device).index_put((a, b), torch.cat([amp, amp]), accumulate=True)
+
+
+def _hubbard_target(op, nup, ndn):
+    """the sector (nup, ndn) on the bonds of ``op`` with zero couplings: a carrier of tables"""
+    _check_hubbard(op.N, nup, ndn)
+    return HubbardOperator(op.N, op.bonds, torch.zeros(op.nparam, dtype=F64, device=op.device), nup, ndn, op.device)
+
+
+def pair_correlations(op, psi, pairings, target=None):
+    """P[a, b] = <psi| Delta+(W_a) Delta(W_b) |psi> for the pair fields Delta(W) = sum_ij W_ij c_{j dn} c_{i up}, the transpose of
+    Delta+(W) = sum_ij W_ij c+_{i up} c+_{j dn}, of the real (M, L, L) tensor ``pairings`` (``onsite_pairing``, ``bond_pairing``):
+    the Gram matrix of the M vectors Delta(W_b) psi, shape (M, M), from M applications of one ``HubbardPairLadder``.
+    Differentiable in psi (hence through ``DominantSparseSymeig``) and in the pairings.  ``target`` carries the tables of the
+    sector (nup - 1, ndn - 1); ``None`` builds them."""
+    if not torch.is_tensor(pairings):
+        pairings = torch.as_tensor(pairings, dtype=F64)
+    if pairings.dim() != 3 or tuple(pairings.shape[1:]) != (int(op.N), int(op.N)) or pairings.shape[0] < 1:
+        raise ValueError("pairings must have shape (M, %d, %d) with M >= 1, got %r" % (op.N, op.N, tuple(pairings.shape)))
+    if target is None:
+        target = _hubbard_target(op, op.nup - 1, op.ndn - 1)
+    lad = HubbardPairLadder(op, target, "dn_left")
+    if lad.steps != (-1, -1):
+        raise ValueError("pair_correlations needs a target with one particle of each species less than op")
+    C = torch.stack([lad(pairings[a], psi) for a in range(pairings.shape[0])])
+    return C @ C.T
+
+
+def total_spin(op, psi, target=None):
+    """<psi| S^2 |psi> of a vector of the Hubbard sector of ``op``, a 0-dim tensor differentiable in psi: with S^z = (nup - ndn)
+    / 2 and S^+ = sum_i c+_{i up} c_{i dn}, S^2 = S^- S^+ + S^z (S^z + 1) = |S^+ psi|^2 + S^z (S^z + 1).  S^+ psi lives in
+    (nup + 1, ndn - 1); when that sector is outside the library's limits (ndn = 1 or nup = L - 1) the other side serves: S^2 =
+    |S^- psi|^2 + S^z (S^z - 1) in (nup - 1, ndn + 1).  ``target`` carries the tables of either sector; ``None`` builds them.
+    ``ValueError`` when neither sector exists (nup = ndn = 1 at L = 2)."""
+    L, nup, ndn = int(op.N), int(op.nup), int(op.ndn)
+    sz = 0.5 * (nup - ndn)
+    plus_ok = ndn - 1 >= 1 and nup + 1 <= L - 1
+    minus_ok = nup - 1 >= 1 and ndn + 1 <= L - 1
+    if target is None:
+        if not plus_ok and not minus_ok:
+            raise ValueError("total_spin: neither (nup + 1, ndn - 1) nor (nup - 1, ndn + 1) is a sector of 1 .. L - 1 particles per "
+                             "species for L = %d, (nup, ndn) = (%d, %d)" % (L, nup, ndn))
+        target = _hubbard_target(op, nup + 1, ndn - 1) if plus_ok else _hubbard_target(op, nup - 1, ndn + 1)
+    raising = (int(target.nup), int(target.ndn)) == (nup + 1, ndn - 1)
+    if not raising and (int(target.nup), int(target.ndn)) != (nup - 1, ndn + 1):
+        raise ValueError("total_spin needs a target at (nup + 1, ndn - 1) or (nup - 1, ndn + 1), got (%d, %d)"
+                         % (target.nup, target.ndn))
+    lad = HubbardPairLadder(op, target, "up_left" if raising else "dn_left")
+    phi = lad(torch.ones(L, dtype=F64, device=lad.device), psi)
+    return phi.dot(phi) + (sz * (sz + 1.0) if raising else sz * (sz - 1.0))
+
+
 # ------------------------------------------------------------------------------------------ stencil
 class Stencil3Operator:
     """H v = coef (-2 v + v_{+1} + v_{-1}) + V o v, Dirichlet ends (reference examples/schrodinger1D.py:18-27

@@ -251,6 +251,58 @@ def hubbard_spectral_function(op0, psi0, E0, weights, channel, k=200, target=Non
     return total.shifted(float(E0))
 
 
+_HUBBARD_PAIR_CHANNELS = {"pair_add": ((1, 1), "up_left"), "pair_remove": ((-1, -1), "dn_left"), "s_plus": ((1, -1), "up_left"),
+                          "s_minus": ((-1, 1), "dn_left")}
+
+
+def _pair_weight_parts(weights):
+    """the real pair weights whose measures add up, each a matrix (L, L) or a vector (L,) (its diagonal): [W] for real weights,
+    [re, im] for a (re, im) pair or a complex tensor"""
+    if isinstance(weights, (tuple, list)) and len(weights) == 2 and all(torch.is_tensor(w) and w.dim() >= 1 for w in weights):
+        return [w.to(F64) for w in weights]
+    t = torch.as_tensor(weights)
+    if t.is_complex():
+        return [t.real.to(F64), t.imag.to(F64)]
+    return [t.to(F64)]
+
+
+def hubbard_pair_spectral_function(op0, psi0, E0, weights, channel, k=200, target=None, basis_free=False):
+    """The spectral measure of O psi0 as a function of the excitation energy E - E0, for the eigenstate (psi0, E0) of the
+    ``HubbardOperator`` ``op0`` and an operator that moves one particle of each species (``HubbardPairLadder``,
+    docs/design/41-hubbard-pair-ladder.md)
+
+        channel "pair_add":     O = Delta+(W) = sum_ij W_ij c+_{i up} c+_{j dn}     (lands in (nup + 1, ndn + 1))
+        channel "pair_remove":  O = Delta(W)  = sum_ij W_ij c_{j dn} c_{i up}       (lands in (nup - 1, ndn - 1))
+        channel "s_plus":       O = sum_ij W_ij c+_{i up} c_{j dn}                  (S^+(q) for diagonal W; (nup + 1, ndn - 1))
+        channel "s_minus":      O = sum_ij W_ij c+_{j dn} c_{i up}                  (its transpose; (nup - 1, ndn + 1))
+
+    ``weights``: a real matrix (L, L), a real vector (L,) for a diagonal one (``ring_momentum_weights``), a ``(re, im)`` pair of
+    either, or a complex tensor.  For complex weights the result is the sum of the measures of the real and of the imaginary
+    part: H is real symmetric, so the cross terms cancel.  ``target`` is the Hamiltonian of the destination sector; ``None``
+    builds it from the bonds and couplings of ``op0`` at the new particle numbers, on new tables.  ``k`` Lanczos steps per real
+    vector; ``basis_free=True`` runs the parts as one block through ``thermal.block_lanczos_measures``.  Plain numbers: not
+    differentiable."""
+    from .operators import HubbardOperator, HubbardPairLadder
+    if channel not in _HUBBARD_PAIR_CHANNELS:
+        raise ValueError("channel must be one of %s, got %r" % (", ".join(repr(c) for c in _HUBBARD_PAIR_CHANNELS), channel))
+    (su, sd), order = _HUBBARD_PAIR_CHANNELS[channel]
+    if target is None:
+        target = HubbardOperator(op0.N, op0.bonds, op0.couplings.detach(), op0.nup + su, op0.ndn + sd, op0.device)
+    lad = HubbardPairLadder(op0, target, order)
+    if lad.steps != (su, sd):
+        raise ValueError("channel %r needs a target at (nup, ndn) = (%d, %d), got (%d, %d)"
+                         % (channel, op0.nup + su, op0.ndn + sd, target.nup, target.ndn))
+    psi0 = psi0.detach()
+    parts = [lad(W, psi0).detach() for W in _pair_weight_parts(weights)]
+    if basis_free:
+        from .thermal import block_lanczos_measures
+        measures = block_lanczos_measures(target, torch.stack(parts, dim=1), k)
+    else:
+        measures = [lanczos_measure(target, phi, k) for phi in parts]
+    total = measures[0] if len(measures) == 1 else measures[0] + measures[1]
+    return total.shifted(float(E0))
+
+
 def kpm_measure(op, phi, M, bounds=None):
     """The ``chebyshev.ChebyshevMeasure`` of the vector ``phi`` under ``op``: its M moments mu_m = <phi| T_m((H - centre) / h)
     |phi> from ceil(M / 2) mat-vecs without a basis (``chebyshev.chebyshev_moments``; docs/design/33-chebyshev-moments.md), the

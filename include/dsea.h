@@ -990,6 +990,38 @@ int dsea_hubbard_ladder_forms(int L, int nup_src, int ndn_src, int species, int 
                               const int32_t *lo_rank_src, const int32_t *hi_base_src, const double *v1, const double *v2,
                               double *out, double *scratch, int grid_log2, void *stream);
 
+/* ------------------------------------------------------------------ Hubbard pair maps (docs/design/41-hubbard-pair-ladder.md)
+ * Linear maps from the Hubbard sector (L, nup_src, ndn_src) to (nup_src + step_up, ndn_src + step_dn), step_up and step_dn each
+ * +1 or -1: one particle of EACH species moves in one pass.  Conventions and row order of dsea_op_create_hubbard.  With A = c+
+ * for step_up = +1 and c for -1, B likewise for step_dn, and weights_dev fp64 [L, L] row-major on the device, READ THROUGH THE
+ * POINTER ON EVERY LAUNCH: order 0 is sum_ij W_ij A_{i up} B_{j dn}, order 1 is sum_ij W_ij B_{j dn} A_{i up} (its negative).  With
+ * (u', d') the words of a row of the destination, below_i = (1 << i) - 1, par = popcount & 1:
+ *     y[ru' n_dn_dst + rd'] = g sum_{i qualifies in u'} sum_{j qualifies in d'} W_ij (-1)^par(u' & below_i) (-1)^par(d' & below_j)
+ *                               x[rank_up_src(u' ^ (1 << i)) n_dn_src + rank_dn_src(d' ^ (1 << j))]
+ * A site qualifies when its bit is set in the destination word for a step of +1 and clear for -1; g = (-1)^(nup_src + order).
+ * The terms are added i ascending outer, j ascending inner.  The map (-step_up, -step_dn, 1 - order) from the destination to
+ * the source is the exact transpose.  A gather over the destination rows (no atomics).  The six tables
+ * (dsea_sector_build_tables): for the up species and then for the down species, the state table at its DESTINATION count and
+ * lo_rank, hi_base at its SOURCE count.  x fp64 [n_src], y fp64 [n_dst].  grid_log2: log2 of the most blocks of a launch,
+ * 6 .. 12, 0 = the default 12.  The library allocates nothing.  Refused by host arithmetic before any device work
+ * (DSEA_ERR_ARG): a step that is not +1 or -1; order outside {0, 1}; the source or the destination outside the limits of
+ * dsea_hubbard_sizes; grid_log2 outside {0, 6 .. 12}; a null pointer; x == y. */
+int dsea_hubbard_pair_apply(int L, int nup_src, int ndn_src, int step_up, int step_dn, int order /* 0 up left, 1 dn left */,
+                            const double *weights_dev, const int64_t *up_states_dst, const int32_t *up_lo_rank_src,
+                            const int32_t *up_hi_base_src, const int64_t *dn_states_dst, const int32_t *dn_lo_rank_src,
+                            const int32_t *dn_hi_base_src, const double *x, double *y, int grid_log2 /* 0 = default */,
+                            void *stream);
+/* dsea_hubbard_pair_forms: out [L, L] on the device, out[i * L + j] = v1^T (dP/dW_ij) v2 for every site pair in one pass, v1 fp64
+ * [n_dst] on the destination and v2 fp64 [n_src] on the source.  Wave and block reductions in fixed order into per-block
+ * partials in `scratch`, then one block per form: no floating-point atomics, repeated calls return identical bits.  `scratch`:
+ * caller-owned, dsea_hubbard_pair_forms_scratch_doubles = L * L * min(4096, ceil(n_dst / 256)) doubles (enough for every grid
+ * cap).  The same argument checks as dsea_hubbard_pair_apply. */
+int dsea_hubbard_pair_forms_scratch_doubles(int L, int nup_src, int ndn_src, int step_up, int step_dn, int order, int64_t *out);
+int dsea_hubbard_pair_forms(int L, int nup_src, int ndn_src, int step_up, int step_dn, int order, const int64_t *up_states_dst,
+                            const int32_t *up_lo_rank_src, const int32_t *up_hi_base_src, const int64_t *dn_states_dst,
+                            const int32_t *dn_lo_rank_src, const int32_t *dn_hi_base_src, const double *v1, const double *v2,
+                            double *out, double *scratch, int grid_log2, void *stream);
+
 /* ------------------------------------------------------------------ block sector mat-vec, block Lanczos (docs/design/27-finite-temperature.md)
  * The operator of dsea_op_create_sector applied to R vectors at once, and the basis-free Lanczos recurrence on it.  A block is fp64
  * [n, R] row-major (element (r, j) at r * R + j), 16-byte aligned (DSEA_ERR_ALIGN otherwise), R in {1, 2, 4, 8}.  The library
