@@ -75,12 +75,12 @@ def apply(L, couplings, x):
     return y + diag * x
 
 
-def forms(L, v1, v2):
+def forms(L, v1, v2, dtype=np.float64):
     """out[t] = v1^T (dH/dp_t) v2, shape (5, L)"""
-    v1, v2 = np.asarray(v1, dtype=np.float64), np.asarray(v2, dtype=np.float64)
+    v1, v2 = np.asarray(v1, dtype=dtype), np.asarray(v2, dtype=dtype)
     s = np.arange(1 << L, dtype=np.int64)
-    z = _z(L, s)
-    out = np.zeros((5, L))
+    z = [zi.astype(dtype) for zi in _z(L, s)]
+    out = np.zeros((5, L), dtype=dtype)
     for b in range(L):
         zz = z[b] * z[(b + 1) % L]
         flipped = v2[s ^ _mask(L, b)]

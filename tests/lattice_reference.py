@@ -82,13 +82,13 @@ def apply(L, bonds, p, x):
     return y + diag * x
 
 
-def forms(L, bonds, v1, v2):
+def forms(L, bonds, v1, v2, dtype=np.float64):
     """out[t] = v1^T (dH/dp_t) v2, shape (3 nb + 2 L,)"""
-    v1, v2 = np.asarray(v1, dtype=np.float64), np.asarray(v2, dtype=np.float64)
+    v1, v2 = np.asarray(v1, dtype=dtype), np.asarray(v2, dtype=dtype)
     nb = len(bonds)
     s = np.arange(1 << L, dtype=np.int64)
-    z = _z(L, s)
-    out = np.zeros(nparam(L, bonds))
+    z = [zi.astype(dtype) for zi in _z(L, s)]
+    out = np.zeros(nparam(L, bonds), dtype=dtype)
     for t, (a, b) in enumerate(bonds):
         zz = z[a] * z[b]
         flipped = v2[s ^ ((1 << a) | (1 << b))]

@@ -119,6 +119,65 @@ def tfim_apply(L, L_local, row_offset, g, diag_scale):
     return apply
 
 
+# ---- XYZ spins: the chain and the bond list ------------------------------------------------------------------------------
+def xor_gather(x, mask):
+    """x[s ^ mask] for every row s: one block swap per set bit of the mask (as ``flip_sum``; no index array)"""
+    j = 0
+    while mask >> j:
+        if (mask >> j) & 1:
+            x = x.reshape(-1, 2, 1 << j)[:, ::-1, :].reshape(-1)
+        j += 1
+    return x
+
+
+def site_bits(L):
+    """bits[i][s] = bit i of the row index s, as int8"""
+    s = np.arange(1 << L, dtype=np.int64)
+    return [((s >> i) & 1).astype(np.int8) for i in range(L)]
+
+
+def lattice_apply(L, bonds, p):
+    """y[s] = (sum_t Jz_t zz_t + sum_i hz_i z_i) x[s] + sum_i hx_i x[s ^ (1 << i)] + sum_t (Jx_t - Jy_t zz_t) x[s ^ m_t]
+    (include/dsea.h dsea_op_create_lattice; p = [Jx(nb), Jy(nb), Jz(nb), hx(L), hz(L)]).  The magnitude of an off-diagonal
+    coefficient is |Jx_t| + |Jy_t|.  Vectorised over the rows: a term costs a few passes over the vector."""
+    nb = len(bonds)
+    p = np.asarray(p, dtype=np.float64).reshape(3 * nb + 2 * L)
+    jx, jy, jz, hx, hz = p[:nb], p[nb:2 * nb], p[2 * nb:3 * nb], p[3 * nb:3 * nb + L], p[3 * nb + L:]
+    bits = site_bits(L)
+
+    def apply(x, dtype):
+        xd = np.asarray(x, dtype=dtype)
+        x64 = np.abs(np.asarray(x, dtype=np.float64))
+        diag = np.zeros(1 << L, dtype=dtype)
+        ax = np.zeros(1 << L, dtype=dtype)
+        sc = (np.sum(np.abs(jz)) + np.sum(np.abs(hz))) * x64
+        for i in range(L):
+            diag += dtype(hz[i]) * (1 - 2 * bits[i]).astype(dtype)
+            ax += dtype(hx[i]) * xor_gather(xd, 1 << i)
+            sc += abs(hx[i]) * xor_gather(x64, 1 << i)
+        for t, (a, b) in enumerate(bonds):
+            zz = (1 - 2 * (bits[a] ^ bits[b])).astype(dtype)
+            m = (1 << a) | (1 << b)
+            diag += dtype(jz[t]) * zz
+            ax += (dtype(jx[t]) - dtype(jy[t]) * zz) * xor_gather(xd, m)
+            sc += (abs(jx[t]) + abs(jy[t])) * xor_gather(x64, m)
+        return ax + diag * xd, sc
+
+    return apply
+
+
+def chain_bonds(L):
+    """bond b joins sites b and (b + 1) mod L (at L = 2 both bonds join sites 0 and 1, and both count)"""
+    return [(b, (b + 1) % L) for b in range(L)]
+
+
+def chain_apply(L, c):
+    """the periodic chain of include/dsea.h dsea_op_create_chain, couplings (5, L) in rows Jx, Jy, Jz, hx, hz: the bond list
+    operator on ``chain_bonds``"""
+    c = np.asarray(c, dtype=np.float64).reshape(5, L)
+    return lattice_apply(L, chain_bonds(L), np.concatenate((c[0], c[1], c[2], c[3], c[4])))
+
+
 # ---- CSR / SELL --------------------------------------------------------------------------------------------------------
 def row_sums(rowptr, terms):
     """sum of each row's terms, in the order they are stored (empty rows: 0)"""
